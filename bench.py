@@ -10,6 +10,10 @@ Workload (BASELINE.json configs[1]): config/multimodal_context.yml -- PoseGenera
 iteration (3 G forwards, 1 G backward, 3 D forwards, D backward passes, both Adam steps), batch 128 clips of 34 frames x 27
 dims per GPU, 36 267 audio samples per clip, synthetic data (V = 20 000 words, 1 370 speakers), random-init weights, fp32.
 A "step" is one full iteration; inputs are resident in HBM before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the steps and prints the line.  --full adds everything that takes runs of its own: the per-kernel
+rooflines, the CPU baselines and (default training line) the `secondary` block of the other BASELINE configurations.
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import importlib
@@ -172,6 +176,52 @@ def finish(line, dist_on):
         _REAL_STDOUT = None
     if line is not None:
         print(line, flush=True)
+
+
+DUMP_BUDGET = 60 * 10 ** 6          # array bytes over all files --dump-outputs writes (under 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name -> tensor / number) as path/<name>.npy, float32 tensors as float32, everything else as float64.  The
+    budget is shared smallest array first; an array larger than what is left for it is replaced by a fixed, seeded sample of its entries
+    (flattened, ascending indices, the same in every run), so that two builds can be compared entry for entry.  Inputs, weights and
+    random draws are seeded, and the training modes start the last timed step from the state captured at setup (timed_steps): what
+    is written is a function of the arguments, up to the order of float-atomic sums."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64)
+    left = DUMP_BUDGET
+    for i, name in enumerate(sorted(host, key=lambda n: host[n].nbytes)):
+        a = host[name]
+        cap = left // (len(host) - i) // a.itemsize
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
+def timed_steps(step, n, fence, reset=None):
+    """`step` n times under the clock: (seconds, what the last call returned).  `fence` synchronises (and, across ranks, barriers).
+    reset (--dump-outputs): called OUTSIDE the clock just before the last step -- it puts the training state back to the seeded state
+    captured at setup, so that the last step, whose outputs are written, computes from the same state and inputs in every run (the
+    steps before it chain state whose rounding differences -- float-atomic combines are not ordered -- grow step by step)."""
+    dt, out = 0.0, None
+    fence()
+    t0 = time.perf_counter()
+    for i in range(n):
+        if reset is not None and i == n - 1:
+            fence()
+            dt += time.perf_counter() - t0
+            reset()
+            fence()
+            t0 = time.perf_counter()
+        out = step()
+    fence()
+    return dt + time.perf_counter() - t0, out
 
 
 def time_kernel(fn, iters=50, warm=5):
@@ -345,9 +395,11 @@ def cpu_baseline(batch, seed=1234, warm=2, max_steps=5, budget_s=60.0):
                       f"fp32 ATen kernels, {dt:.2f} s/iter"}
 
 
-def measure_decode(pkg, args, G, device, batch, steps, warmup, *, graph=True, world=1, rank=0, cpu=True, cpu_budget_s=15.0):
+def measure_decode(pkg, args, G, device, batch, steps, warmup, *, graph=True, world=1, rank=0, cpu=True, cpu_budget_s=15.0, full=True,
+                   dump=None):
     """Inference path (synthesize.py:82-160): every step is one 34-frame window for `batch` utterances in lock-step
-    (seed hand-over + cross-fade on device, hipGraph replay).  Replicas only under --gpus N: no collective.  Returns the JSON line's dict."""
+    (seed hand-over + cross-fade on device, hipGraph replay).  Replicas only under --gpus N: no collective.  Returns the JSON line's dict.
+    full: + the dominant kernel's roofline and (cpu) the CPU baseline.  dump: directory for the last window's poses (rank 0)."""
     syn = importlib.import_module(PKG + ".synthesize")
     args.motion_resampling_framerate = 15
     dec = syn.WindowDecoder(args, G, batch, device, graph=graph)
@@ -377,9 +429,11 @@ def measure_decode(pkg, args, G, device, batch, steps, warmup, *, graph=True, wo
     assert bool(torch.isfinite(out).all())
     if rank != 0:
         return None
+    if dump is not None:
+        dump_outputs(dump, {"poses": out})
     fps = world * batch * T * steps / dt
-    extra = {"roofline": decode_kernel_roofline(pkg, device, batch)}
-    if world == 1 and cpu:
+    extra = {"roofline": decode_kernel_roofline(pkg, device, batch)} if full else {}
+    if world == 1 and cpu and full:
         extra["cpu_baseline"] = cpu_baseline_decode(batch, budget_s=cpu_budget_s)
     return {
         **extra,
@@ -395,14 +449,16 @@ def measure_decode(pkg, args, G, device, batch, steps, warmup, *, graph=True, wo
 
 
 def decode_bench(pkg, a, args, G, device, world, rank):
-    d = measure_decode(pkg, args, G, device, a.batch, a.steps, a.warmup, graph=not a.no_graph, world=world, rank=rank, cpu=not a.no_cpu_baseline)
+    d = measure_decode(pkg, args, G, device, a.batch, a.steps, a.warmup, graph=not a.no_graph, world=world, rank=rank, cpu=not a.no_cpu_baseline,
+                       full=a.full, dump=a.dump_outputs)
     finish(json.dumps(d) if d is not None else None, world > 1)
 
 
-def measure_ae(pkg, args, device, batch, steps, warmup, *, graph=True, world=1, rank=0, cpu=True, cpu_budget_s=10.0):
+def measure_ae(pkg, args, device, batch, steps, warmup, *, graph=True, world=1, rank=0, cpu=True, cpu_budget_s=10.0, full=True, dump=None):
     """FGD autoencoder training (BASELINE.json configs[4], train_feature_extractor.py:54-97): one step = one Adam iteration
     of the pose-mode EmbeddingNet on `batch` synthetic clips.  1.04 M MAC/clip forward: launch/latency bound, clips/s only.
-    Replicas only under --gpus N.  Returns the JSON line's dict."""
+    Replicas only under --gpus N.  Returns the JSON line's dict.  full: + (cpu) the CPU baseline.  dump: directory for the last step's
+    loss and the parameters after it (rank 0)."""
     fgd = importlib.import_module(PKG + ".fgd")
     torch.manual_seed(0)
     net = pkg.EmbeddingNet(args, D, T, None, None, None, mode="pose").to(device)
@@ -410,6 +466,16 @@ def measure_ae(pkg, args, device, batch, steps, warmup, *, graph=True, world=1, 
     tr = fgd.AutoencoderTrainer(net)
     g = torch.Generator().manual_seed(4321 + rank)
     poses = (0.1 * torch.randn(batch, T, D, generator=g)).to(device)
+
+    def state():          # everything a step reads and writes: weights, gradients, Adam moments and counter, BatchNorm buffers
+        sl = net.engine.slab.ensure()
+        return [sl.flat, sl.grad, sl.m, sl.v, sl.step] + [b for _, b in net.named_buffers()]
+    snap = [t.detach().clone() for t in state()] if dump is not None else None
+
+    def reset():
+        with torch.no_grad():
+            for t, c in zip(state(), snap):
+                t.copy_(c)
     cg = None
     if graph:
         side = torch.cuda.Stream(); side.wait_stream(torch.cuda.current_stream())
@@ -424,16 +490,12 @@ def measure_ae(pkg, args, device, batch, steps, warmup, *, graph=True, world=1, 
     step = cg.replay if cg is not None else (lambda: tr.train_iter(poses))
     for _ in range(max(warmup, 1)):
         step()
-    torch.cuda.synchronize()
-    if world > 1:
-        torch.distributed.barrier()
-    t0 = time.perf_counter()
-    for _ in range(steps):
-        r = step()
-    torch.cuda.synchronize()
-    if world > 1:
-        torch.distributed.barrier()
-    dt = time.perf_counter() - t0
+
+    def fence():
+        torch.cuda.synchronize()
+        if world > 1:
+            torch.distributed.barrier()
+    dt, r = timed_steps(step, steps, fence, reset if dump is not None else None)
     if world > 1:
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
@@ -442,8 +504,10 @@ def measure_ae(pkg, args, device, batch, steps, warmup, *, graph=True, world=1, 
     assert lv == lv and lv < 1e6
     if rank != 0:
         return None
+    if dump is not None:
+        dump_outputs(dump, {"loss": lv, "grads": net.engine.slab.grad, "params": net.engine.slab.flat})
     extra = {}
-    if world == 1 and cpu:
+    if world == 1 and cpu and full:
         extra["cpu_baseline"] = cpu_baseline_ae(batch, budget_s=cpu_budget_s)
     fused = getattr(tr, "_plan", None) is not None
     return {
@@ -464,7 +528,8 @@ def measure_ae(pkg, args, device, batch, steps, warmup, *, graph=True, world=1, 
 
 
 def ae_bench(pkg, a, args, device, world, rank):
-    d = measure_ae(pkg, args, device, a.batch, a.steps, a.warmup, graph=not a.no_graph, world=world, rank=rank, cpu=not a.no_cpu_baseline)
+    d = measure_ae(pkg, args, device, a.batch, a.steps, a.warmup, graph=not a.no_graph, world=world, rank=rank, cpu=not a.no_cpu_baseline,
+                   full=a.full, dump=a.dump_outputs)
     finish(json.dumps(d) if d is not None else None, world > 1)
 
 
@@ -488,7 +553,7 @@ def step_roofline(clips_per_s_per_gpu, epoch, dtype):
 
 
 def secondary_lines(pkg, a, device, cpu_train):
-    """Short runs of the other BASELINE.json configurations, appended to the default single-GPU line so that the driver's one command times
+    """Short runs of the other BASELINE.json configurations, appended to the --full single-GPU line so that one command times
     them too: configs[1] as written ("training bf16": the plain-bf16 operand tier), configs[3] (synthesis windows at 128
     utterances and at the reference's own single utterance), configs[4] (autoencoder training).  Each carries its own ms_per_step, roofline
     and cpu_baseline; everything here runs AFTER the headline's timed region."""
@@ -541,11 +606,11 @@ def secondary_lines(pkg, a, device, cpu_train):
     def decode(batch, steps, budget):
         args, G, _ = build(pkg, device, seed=0)
         G.eval()
-        return measure_decode(pkg, args, G, device, batch, steps, 10, cpu=cpu_train is not None, cpu_budget_s=budget)
+        return measure_decode(pkg, args, G, device, batch, steps, 10, cpu=cpu_train is not None, cpu_budget_s=budget, full=True)
     guarded("decode_b128", lambda: decode(128, 60, 3.0))
     guarded("decode_b1", lambda: decode(1, 100, 2.0))
     # ---- configs[4]: FGD autoencoder training
-    guarded("ae_train", lambda: measure_ae(pkg, make_args(), device, 128, 200, 20, cpu=cpu_train is not None, cpu_budget_s=3.0))
+    guarded("ae_train", lambda: measure_ae(pkg, make_args(), device, 128, 200, 20, cpu=cpu_train is not None, cpu_budget_s=3.0, full=True))
     try:
         pkg.ops.check_async_errors()
     except Exception as e:
@@ -590,10 +655,17 @@ def main():
                          "per-sample assembly of SpeechMotionDataset.__getitem__ + collate runs on the device (never the headline value)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the short runs of the other BASELINE configurations that the default single-GPU line appends (`secondary`)")
+                    help="skip the short runs of the other BASELINE configurations that the --full single-GPU line appends (`secondary`)")
     ap.add_argument("--force-ddp", action="store_true", help="run the data-parallel code path (graph segments + RCCL) even with one rank")
     ap.add_argument("--deterministic", action="store_true",
                     help="tg_set_deterministic(1): fixed-order combines everywhere, bit-reproducible runs (cost line for DESIGN.md; never the headline value)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-kernel rooflines, the CPU baselines and, on the default single-GPU training "
+                         "line, the `secondary` block (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (training: the losses "
+                         "and both models' gradients; decode: the window's poses; ae: the loss, gradients and parameters), at most 64 MB "
+                         "in all.  Training modes: the last timed step then starts from the seeded state of setup (restored outside the clock)")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -645,6 +717,7 @@ def main():
     if grad_sync is not None:
         ddp.broadcast_parameters([trainer.G.slab.ensure(), trainer.D.slab.ensure()])
     text, audio, poses, vid = synthetic_batch(a.batch, 1234 + rank, device)
+    snap = trainer.snapshot() if a.dump_outputs is not None else None         # the seeded starting state (timed_steps)
 
     ddp_info = None
     if a.no_graph:
@@ -699,18 +772,19 @@ def main():
         if world > 1:
             torch.distributed.barrier()
         torch.cuda.synchronize()
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        losses = step()
-    fence()
-    dt = time.perf_counter() - t0
+    dt, losses = timed_steps(step, a.steps, fence, (lambda: trainer.restore(snap)) if snap is not None else None)
     if world > 1:
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(tmax, op=torch.distributed.ReduceOp.MAX)
         dt = float(tmax.item())
     loss_dict = losses.to_dict()
     assert all(v == v and abs(v) < 1e6 for v in loss_dict.values()), loss_dict     # finite
+    if rank == 0 and a.dump_outputs is not None:
+        # the losses the last step returned and the gradients it computed (identical on every rank).  Not the parameters its Adam steps
+        # left: a parameter whose true gradient is zero (a bias feeding a train-mode BatchNorm) gets a rounding-noise gradient, which Adam's
+        # first step turns into a move of +-lr -- its sign is not reproducible from run to run
+        dump_outputs(a.dump_outputs, {**{"losses_" + k: v for k, v in loss_dict.items()},
+                                      "generator_grads": trainer.G.slab.grad, "discriminator_grads": trainer.D.slab.grad})
 
     line = None
     if rank == 0:
@@ -731,12 +805,13 @@ def main():
         if ddp_info is not None:
             out["ddp"] = {"ranks": ddp_info["ranks"], "collectives": ddp_info["collectives"],
                           "rejected": [f"{m}: {w}" for m, w in ddp_info["rejected"]]}
-        out["roofline"] = dominant_kernel_roofline(pkg, device, a.batch)
-        out["roofline_hbm"] = hbm_kernel_roofline(pkg, device)
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full:
+            out["roofline"] = dominant_kernel_roofline(pkg, device, a.batch)
+            out["roofline_hbm"] = hbm_kernel_roofline(pkg, device)
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.batch, seed=1234 + rank)
         plain = (world == 1 and grad_sync is None and a.dtype == "f32" and a.epoch > 10 and not (a.no_graph or a.host_input or a.host_records or a.deterministic))
-        if plain and not a.no_secondary and not a.no_cpu_baseline:
+        if a.full and plain and not a.no_secondary and not a.no_cpu_baseline:
             del step
             try:
                 out["secondary"] = secondary_lines(pkg, a, device, out.get("cpu_baseline"))

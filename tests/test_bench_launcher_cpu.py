@@ -37,6 +37,7 @@ def test_bench_cli_becomes_launcher_without_world_size(tmp_path):
     with a message (not start ranks).  The ranks it starts here have no GPU, so they fail loudly -- what is checked is that the parent
     launched them, relayed the failure as a non-zero exit code and made no GPU call itself."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")         # no GPU for the ranks, on a GPU machine too
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0

@@ -5,7 +5,7 @@ tag=${1:-r3}
 out=gpurun_out
 mkdir -p $out
 export TMPDIR=/tmp
-python3 bench.py --steps 100 --warmup 20 --no-cpu-baseline ${BENCH_ARGS:-} > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full --steps 100 --warmup 20 --no-cpu-baseline ${BENCH_ARGS:-} > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 head -c 330 $out/${tag}_bench.json; echo
 rm -rf /tmp/prof_$tag
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$tag -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-} > $out/${tag}_prof.log 2>&1
