@@ -15,6 +15,12 @@ using namespace tg;
 constexpr int GC_UNITS = 32;          // hidden units per workgroup
 constexpr int GC_HX = 320;            // largest H: 10 workgroups per cluster
 constexpr int GC_FLAG_STRIDE = 16;    // flag words per cluster (one 64-byte line)
+constexpr int GC_MAX_CLUSTERS = 256;  // 2 * n_bt clusters of cw >= 1 workgroups, at most 256 workgroups
+// The flag block has room for the largest plan whatever B is: the row chunks of one call share a workspace (ops.gru_cluster_chunks), and
+// chunks of different tilings (B = 385 forward: 224 rows at mt = 2, 14 clusters, then 161 at mt = 1, 22) would otherwise put one launch's
+// exchange buffer over flag lines of another.  Flag words are never zeroed: a line holding h or gradient planes could satisfy a wait
+// before its member has published.  (257 lines = 16 KB, against 1.7 MB of exchange buffer at B = 224, H = 300.)
+constexpr int64_t GC_FLAG_WORDS = (int64_t)(GC_MAX_CLUSTERS + 1) * GC_FLAG_STRIDE;
 
 
 // the kernels' launchers (gru_cluster_x3.hip)
@@ -56,13 +62,12 @@ extern "C" int32_t tg_gru_cluster_supported(int32_t B, int32_t H) {
     return 2 * n_bt * cw <= (cus < 256 ? cus : 256) && cw <= GC_FLAG_STRIDE;
 }
 
-// workspace: [flag block: 2*n_bt clusters x 16 words + 16 words (timeout word first) ...] [exchange buffer 2 dirs x 2 slots]
+// workspace: [16 words (timeout word first) ... | flag block: GC_MAX_CLUSTERS lines x 16 words] [exchange buffer 2 dirs x 2 slots]
 extern "C" int64_t tg_gru_cluster_ws_bytes(int32_t B, int32_t H) {
     int mt, n_bt, cw;
     cluster_plan(B, H, &mt, &n_bt, &cw);
-    const int64_t flag_words = (int64_t)(2 * n_bt + 1) * GC_FLAG_STRIDE;
     const int64_t b_pad = (int64_t)n_bt * 16 * mt;
-    return flag_words * 4 + tg_gru_x3_fwd_exchange_bytes((int)b_pad, cw);
+    return GC_FLAG_WORDS * 4 + tg_gru_x3_fwd_exchange_bytes((int)b_pad, cw);
 }
 
 // (always 1 since the f32-MFMA kernels went; kept so that callers built against ABI <= 5 keep working)
@@ -92,14 +97,13 @@ extern "C" int tg_gru_forward_cluster_rows(const float* gi, int64_t gi_dir_strid
                "tg_gru_forward_cluster: operands must be 16-byte aligned");
     int mt, n_bt, cw;
     cluster_plan(B, H, &mt, &n_bt, &cw);
-    const int64_t flag_words = (int64_t)(2 * n_bt + 1) * GC_FLAG_STRIDE;
     hipStream_t s = (hipStream_t)stream;
     // The first 16 words (the timeout marker and its diagnostics) are sticky until the host reads and clears them
     // (ops.check_async_errors), so a timeout in any launch that shares this workspace survives the launches after it.  The flag
     // words behind them are numbered by generation and never zeroed (gru_cluster_x3.hip).
     unsigned* tmo = (unsigned*)ws;
     unsigned* flags = tmo + GC_FLAG_STRIDE;
-    float* hx = (float*)(tmo + flag_words);
+    float* hx = (float*)(tmo + GC_FLAG_WORDS);
     const int b_pad = n_bt * 16 * mt;
     return tg_gru_x3_fwd_launch(mt, gi, (long)gi_dir_stride, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, y, save, (long)save_dir_stride, drop_mask, y_drop, hx,
                                 flags, tmo, B, T, H, n_bt, cw, b_pad, save_row0, save_rows, s);
@@ -122,8 +126,7 @@ extern "C" int32_t tg_gru_cluster_bwd_supported(int32_t B, int32_t H) {
 extern "C" int64_t tg_gru_cluster_bwd_ws_bytes(int32_t B, int32_t H) {
     int n_bt, cw;
     cluster_plan_bwd(B, H, &n_bt, &cw);
-    const int64_t flag_words = (int64_t)(2 * n_bt + 1) * GC_FLAG_STRIDE;
-    return flag_words * 4 + tg_gru_x3_bwd_exchange_bytes(n_bt * 16, cw);
+    return GC_FLAG_WORDS * 4 + tg_gru_x3_bwd_exchange_bytes(n_bt * 16, cw);
 }
 
 extern "C" int tg_gru_backward_cluster_stats(const float* dy, const float* dy_mask, const float* y, const float* save, int64_t save_dir_stride,
@@ -142,11 +145,10 @@ extern "C" int tg_gru_backward_cluster_stats(const float* dy, const float* dy_ma
                "tg_gru_backward_cluster_stats: operands must be 16-byte aligned");
     int n_bt, cw;
     cluster_plan_bwd(B, H, &n_bt, &cw);
-    const int64_t flag_words = (int64_t)(2 * n_bt + 1) * GC_FLAG_STRIDE;
     hipStream_t s = (hipStream_t)stream;
     unsigned* tmo = (unsigned*)ws;              // sticky timeout block: cleared by the host only (see the forward entry point)
     unsigned* flags = tmo + GC_FLAG_STRIDE;
-    float* gx = (float*)(tmo + flag_words);
+    float* gx = (float*)(tmo + GC_FLAG_WORDS);
     return tg_gru_x3_bwd_launch(dy, dy_mask, y, save, (long)save_dir_stride, w_hh_t_fwd, w_hh_t_rev, dgi, dgh, (long)dg_dir_stride, gx, flags, tmo, B, T, H,
                                 n_bt, cw, n_bt * 16, gi_rowmax, (long)rowmax_dir_stride, gi_colmax, gh_colmax, s);
 }

@@ -289,3 +289,54 @@ def dataset_samples(g):
                     {"vid": str(g[f"raw{i}/vid"]), "start_frame_no": int(aux[0]), "end_frame_no": int(aux[1]), "start_time": float(aux[2]),
                      "end_time": float(aux[3])}])
     return out
+
+
+def gru_forward_fp64(gi, w_hh, b_hh):
+    """torch.nn.GRU's recurrence (bidirectional, batch_first; multimodal_context_net.py:155) restated in fp64 from the input projections
+    gi [2, B, T, 3H] and the recurrent parameters w_hh / b_hh ((fwd, rev) pairs of [3H, H] / [3H]), on gi's device.
+    -> y [B, T, 2H] and the taped gates in the kernels' `save` layout [2, B, T, 4H] = (r, z, n, W_hn h + b_hn) per step, both float64."""
+    _, B, T, H3 = gi.shape
+    H = H3 // 3
+    f64 = dict(dtype=torch.float64, device=gi.device)
+    y, save = torch.empty(B, T, 2 * H, **f64), torch.empty(2, B, T, 4 * H, **f64)
+    for d in range(2):
+        W, b, g = w_hh[d].double(), b_hh[d].double(), gi[d].double()
+        h = torch.zeros(B, H, **f64)
+        for t in (range(T) if d == 0 else range(T - 1, -1, -1)):
+            gh = h @ W.t() + b
+            r = torch.sigmoid(g[:, t, :H] + gh[:, :H])
+            z = torch.sigmoid(g[:, t, H:2 * H] + gh[:, H:2 * H])
+            n = torch.tanh(g[:, t, 2 * H:] + r * gh[:, 2 * H:])
+            h = (1 - z) * n + z * h
+            y[:, t, d * H:(d + 1) * H] = h
+            save[d, :, t] = torch.cat([r, z, n, gh[:, 2 * H:]], 1)
+    return y, save
+
+
+def gru_backward_fp64(dy, y, save, w_hh):
+    """Backward through time of the recurrence above, restated in fp64 from a taped forward -- y [B, T, 2H] and save [2, B, T, 4H] as the
+    kernels leave them (pass the kernel's OWN tape to measure a backward kernel apart from the forward's error) -- for dy [B, T, 2H].
+    -> (dgi, dgh), float64 [2, B, T, 3H]: the gradients of gi and of gh = W_hh h + b_hh per step (nn.GRU backward)."""
+    B, T, H2 = y.shape
+    H = H2 // 2
+    f64 = dict(dtype=torch.float64, device=y.device)
+    r_gi, r_gh = [], []
+    for d in range(2):
+        W = w_hh[d].double()
+        yd, s, dyd = y[..., d * H:(d + 1) * H].double(), save[d].double(), dy[..., d * H:(d + 1) * H].double()
+        dh = torch.zeros(B, H, **f64)
+        a, c = torch.zeros(B, T, 3 * H, **f64), torch.zeros(B, T, 3 * H, **f64)
+        for t in (range(T - 1, -1, -1) if d == 0 else range(T)):
+            tp = t - 1 if d == 0 else t + 1
+            hp = yd[:, tp] if 0 <= tp < T else torch.zeros(B, H, **f64)
+            r, z, n, hn = s[:, t, :H], s[:, t, H:2 * H], s[:, t, 2 * H:3 * H], s[:, t, 3 * H:]
+            dht = dyd[:, t] + dh
+            dn = dht * (1 - z) * (1 - n * n)
+            dz = dht * (hp - n) * z * (1 - z)
+            dr = dn * hn * r * (1 - r)
+            a[:, t] = torch.cat([dr, dz, dn], 1)
+            c[:, t] = torch.cat([dr, dz, dn * r], 1)
+            dh = dht * z + c[:, t] @ W
+        r_gi.append(a)
+        r_gh.append(c)
+    return torch.stack(r_gi), torch.stack(r_gh)

@@ -5,6 +5,7 @@ import math
 import pytest
 import torch
 import torch.nn.functional as F
+from harness import gru_backward_fp64
 
 pytestmark = pytest.mark.gpu
 
@@ -1585,24 +1586,7 @@ def test_gru_backward_cluster_fp16x2_on_rows_of_very_different_scale(pkg, dev):
         ops.check_async_errors()
         assert ops.gru_cluster_chunks(B, H, bwd=True) is not None     # the cluster kernel is what ran
         # fp64 restatement from the taped gates (sv = r, z, n, W_hn h + b_hn per step)
-        r_gi, r_gh = [], []
-        for d in range(2):
-            W = w[d].double()
-            yd, s, dyd = y[..., d * H:(d + 1) * H].double(), sv[d].double(), dy[..., d * H:(d + 1) * H].double()
-            dh = torch.zeros(B, H, dtype=torch.float64, device=dev)
-            a, c = torch.zeros(B, T, 3 * H, dtype=torch.float64, device=dev), torch.zeros(B, T, 3 * H, dtype=torch.float64, device=dev)
-            for t in (range(T - 1, -1, -1) if d == 0 else range(T)):
-                tp = t - 1 if d == 0 else t + 1
-                hp = yd[:, tp] if 0 <= tp < T else torch.zeros(B, H, dtype=torch.float64, device=dev)
-                r, z, n, hn = s[:, t, :H], s[:, t, H:2 * H], s[:, t, 2 * H:3 * H], s[:, t, 3 * H:]
-                dht = dyd[:, t] + dh
-                dn = dht * (1 - z) * (1 - n * n)
-                dz = dht * (hp - n) * z * (1 - z)
-                dr = dn * hn * r * (1 - r)
-                a[:, t] = torch.cat([dr, dz, dn], 1); c[:, t] = torch.cat([dr, dz, dn * r], 1)
-                dh = dht * z + c[:, t] @ W
-            r_gi.append(a); r_gh.append(c)
-        r_gi, r_gh = torch.stack(r_gi), torch.stack(r_gh)
+        r_gi, r_gh = gru_backward_fp64(dy, y, sv, w)
         assert bool(torch.isfinite(dgi).all()) and bool(torch.isfinite(dgh).all())
         rowmax = r_gi.abs().amax(dim=(0, 2, 3)).view(1, B, 1, 1)
         live = (rowmax > 0).expand_as(r_gi)
