@@ -137,9 +137,21 @@ SIGNATURES = {
     "tg_ae_loss": [P, P, I32, I32, I32, P, P, P],
     "tg_counter_inc": [P, P],
     "tg_adam_step": [P, P, P, P, I64, F32, F32, F32, F32, P, P],
+    "tg_conv2d_fwd": [P, I32, P, P, P] + [I32] * 12 + [P],
+    "tg_conv2d_dgrad": [P, P, P, I32] + [I32] * 12 + [P],
+    "tg_conv2d_wgrad_ws_bytes": [I32] * 12 + [P],
+    "tg_conv2d_wgrad": [P, P, I32, P, I32, P, I64] + [I32] * 12 + [P],
+    "tg_s2g_rows_interp": [P, P, I32, I32, I32, I32, I32, I32, P],
+    "tg_s2g_rows_interp_bwd": [P, P, I32, I32, I32, I32, I32, I32, P],
+    "tg_s2g_up_add": [P, P, P, I32, I32, I32, I32, P],
+    "tg_s2g_up_add_bwd": [P, P, I32, I32, I32, I32, I32, P],
+    "tg_s2g_diff": [P, P, I32, I32, I32, P],
+    "tg_s2g_diff_bwd": [P, P, I32, I32, I32, I32, P],
+    "tg_s2g_mse_const": [P, I64, F32, F32, P, P, P],
+    "tg_s2g_l1_grad": [P, P, P, I64, P],
 }
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 _lib = None
 
 

@@ -36,7 +36,7 @@ _ref_pickle.loads = lambda b, **kw: _RefUnpickler(io.BytesIO(b), **kw).load()
 
 
 def init_model(args, lang_model, speaker_model, pose_dim, _device):
-    """train.py:36-62 for the models on the hot path ('multimodal_context', 'gesture_autoencoder')."""
+    """train.py:36-62 for the models on the hot path ('multimodal_context', 'gesture_autoencoder') and the Speech2Gesture baseline."""
     generator = discriminator = loss_fn = None
     if args.model == "multimodal_context":
         generator = PoseGenerator(args, n_words=lang_model.n_words, word_embed_size=args.wordembed_dim,
@@ -46,6 +46,11 @@ def init_model(args, lang_model, speaker_model, pose_dim, _device):
     elif args.model == "gesture_autoencoder":
         generator = EmbeddingNet(args, pose_dim, args.n_poses, lang_model.n_words, args.wordembed_dim,
                                  lang_model.word_embedding_weights, mode="pose").to(_device)
+    elif args.model == "speech2gesture":
+        from .speech2gesture import Discriminator, Generator
+        generator = Generator(n_poses=args.n_poses, pose_dim=pose_dim, n_pre_poses=args.n_pre_poses).to(_device)
+        discriminator = Discriminator(pose_dim).to(_device)
+        loss_fn = torch.nn.L1Loss()
     else:
         raise NotImplementedError(f"model {args.model!r} is a baseline outside the hot path (SURVEY.md section 8)")
     return generator, discriminator, loss_fn

@@ -394,6 +394,37 @@ def conv_dgrad(dy, w, L_in, *, stride=1, out=None, accumulate=False):
     return dx
 
 
+def same_pad(L, kw, stride):
+    """TF "SAME" padding of Conv1d_tf / Conv2d_tf along one axis: (output length, left pad, right pad).  out = ceil(L / stride), total =
+    max(0, (out - 1) * stride + kw - L); the odd extra zero goes right (bottom)."""
+    out = (L + stride - 1) // stride
+    total = max(0, (out - 1) * stride + kw - L)
+    return out, total // 2, total - total // 2
+
+
+def conv_dgrad_padded(dy, w, L_in, *, stride=1, pad=0, out=None, accumulate=False):
+    """Input gradient of Conv1d(stride, left zero padding `pad`, any right padding, dilation 1).  dy: (B, Lout, Co) view; w: (Co, Ci, kw).
+    Input positions p = stride * u + r (phase r) receive the kernel taps j = j0 + stride * t, j0 = (r + pad) % stride, from the output rows
+    q = u + (r + pad - j0) / stride - t: one tap window with that shift per phase over dgrad_pack's phase-j0 weights (zero taps outside dy)."""
+    B, Lo, Co = dy.shape
+    _, Ci, kw = w.shape
+    J = (kw + stride - 1) // stride
+    packed = dgrad_pack(w, stride)
+    if out is not None:
+        assert tuple(out.shape) == (B, L_in, Ci) and out.is_contiguous()
+    dx = out if out is not None else empty(B, L_in, Ci, like=w)
+    probs = []
+    for r in range(stride):
+        nq = (L_in - r + stride - 1) // stride
+        if nq <= 0:
+            continue
+        j0 = (r + pad) % stride
+        probs.append(dict(A=Win.taps(dy, J, shift=(r + pad - j0) // stride, dil=-1, rows_out=nq), W=packed[j0], bias=None, out=dx[:, r:, :],
+                          c_batch_stride=dx.stride(0), c_row_stride=stride * Ci, c_rows_out=nq, accumulate=bool(accumulate and out is not None)))
+    ops.gemm_nt_group(probs)
+    return dx
+
+
 def conv_transpose_fwd(x, w, b, *, out=None):
     """ConvTranspose1d(stride 1, no padding).  x: (B, L, Ci); w: (Ci, Co, kw) -> (B, L + kw - 1, Co).
     Same arithmetic as conv_dgrad with the roles of the channel axes swapped."""

@@ -1574,3 +1574,95 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, step_dev):
     n = _same(p, g, m, v)
     assert step_dev.is_cuda and step_dev.dtype == torch.int32
     call("tg_adam_step", _p(p), _p(g), _p(m), _p(v), n, float(lr), float(beta1), float(beta2), float(eps), _p(step_dev), _stream())
+
+
+# ------------------------------------------------------------------------------------------------- Speech2Gesture (csrc/conv2d.hip)
+def _geom2d(B, H, W, Ci, Co, kh, kw, stride, pad_top, pad_left, Ho, Wo):
+    return [int(v) for v in (B, H, W, Ci, Co, kh, kw, stride, pad_top, pad_left, Ho, Wo)]
+
+
+def _x2d(x):
+    if x.dtype not in (torch.float32, torch.float16) or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("conv2d input: contiguous fp32 or fp16 CUDA tensor (B, H, W, Ci)")
+    return int(x.dtype == torch.float16)
+
+
+def conv2d_fwd(x, w, bias, y, *, stride, pad_top, pad_left):
+    """y (B, Ho, Wo, Co) = conv2d(x (B, H, W, Ci) channel-last, w [Co][Ci][kh][kw]) + bias."""
+    B, H, W, Ci = x.shape
+    _, Ho, Wo, Co = y.shape
+    kh, kw = w.shape[2], w.shape[3]
+    assert tuple(w.shape) == (Co, Ci, kh, kw) and tuple(y.shape[:1]) == (B,)
+    call("tg_conv2d_fwd", _p(x), _x2d(x), _p(_flat(w, "w")), _p(bias), _p(_flat(y, "y")),
+         *_geom2d(B, H, W, Ci, Co, kh, kw, stride, pad_top, pad_left, Ho, Wo), _stream())
+    return y
+
+
+def conv2d_dgrad(dy, w, dx, *, stride, pad_top, pad_left, accumulate=False):
+    B, H, W, Ci = dx.shape
+    _, Ho, Wo, Co = dy.shape
+    kh, kw = w.shape[2], w.shape[3]
+    assert tuple(w.shape) == (Co, Ci, kh, kw)
+    call("tg_conv2d_dgrad", _p(_flat(dy, "dy")), _p(_flat(w, "w")), _p(_flat(dx, "dx")), int(accumulate),
+         *_geom2d(B, H, W, Ci, Co, kh, kw, stride, pad_top, pad_left, Ho, Wo), _stream())
+    return dx
+
+
+def conv2d_wgrad(dy, x, dw, *, stride, pad_top, pad_left, accumulate=False):
+    """dw [Co][Ci][kh][kw] (+)= weight gradient (split K, fixed-order fp64 combine: bitwise repeatable)."""
+    B, H, W, Ci = x.shape
+    _, Ho, Wo, Co = dy.shape
+    kh, kw = dw.shape[2], dw.shape[3]
+    g = _geom2d(B, H, W, Ci, Co, kh, kw, stride, pad_top, pad_left, Ho, Wo)
+    nbytes = C.c_int64(0)
+    call("tg_conv2d_wgrad_ws_bytes", *g, C.cast(C.pointer(nbytes), C.c_void_p))
+    ws = torch.empty((nbytes.value + 3) // 4, device=dy.device, dtype=torch.float32)
+    call("tg_conv2d_wgrad", _p(_flat(dy, "dy")), _p(x), _x2d(x), _p(_flat(dw, "dw")), int(accumulate), _p(ws), ws.numel() * 4, *g, _stream())
+    return dw
+
+
+def s2g_rows_interp(x, y, col):
+    B, Hin, Win_, Cc = x.shape
+    call("tg_s2g_rows_interp", _p(_flat(x, "x")), _p(_flat(y, "y")), B, Hin, Win_, int(col), Cc, y.shape[1], _stream())
+    return y
+
+
+def s2g_rows_interp_bwd(dy, dx, col):
+    B, Hin, Win_, Cc = dx.shape
+    call("tg_s2g_rows_interp_bwd", _p(_flat(dy, "dy")), _p(_flat(dx, "dx")), B, Hin, Win_, int(col), Cc, dy.shape[1], _stream())
+    return dx
+
+
+def s2g_up_add(x, skip, y):
+    B, Lx, Cc = x.shape
+    call("tg_s2g_up_add", _p(_flat(x, "x")), _p(_flat(skip, "skip")), _p(_flat(y, "y")), B, Lx, skip.shape[1], Cc, _stream())
+    return y
+
+
+def s2g_up_add_bwd(dy, dx, accumulate=False):
+    B, Lx, Cc = dx.shape
+    call("tg_s2g_up_add_bwd", _p(_flat(dy, "dy")), _p(_flat(dx, "dx")), B, Lx, dy.shape[1], Cc, int(accumulate), _stream())
+    return dx
+
+
+def s2g_diff(x, y):
+    B, T, Cc = x.shape
+    call("tg_s2g_diff", _p(_flat(x, "x")), _p(_flat(y, "y")), B, T, Cc, _stream())
+    return y
+
+
+def s2g_diff_bwd(dy, dx, accumulate=False):
+    B, T, Cc = dx.shape
+    call("tg_s2g_diff_bwd", _p(_flat(dy, "dy")), _p(_flat(dx, "dx")), B, T, Cc, int(accumulate), _stream())
+    return dx
+
+
+def s2g_mse_const(x, target, loss, dx=None, scale=1.0):
+    """loss[0] = mean((x - target)^2); dx = scale * d loss / dx (when given)."""
+    call("tg_s2g_mse_const", _p(_flat(x, "x")), x.numel(), float(target), float(scale), _p(_flat(loss, "loss")),
+         _p(_flat(dx, "dx")) if dx is not None else None, _stream())
+    return loss
+
+
+def s2g_l1_grad(a, b, d):
+    call("tg_s2g_l1_grad", _p(a), _p(b), _p(d), _same(a, b, d), _stream()); return d

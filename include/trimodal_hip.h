@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TG_ABI_VERSION 8
+#define TG_ABI_VERSION 9
 
 int tg_version(void);
 
@@ -692,6 +692,42 @@ int tg_ae_train_step(const tg_ae_step_args* args, void* stream);
 int tg_counter_inc(int32_t* counter, void* stream);
 int tg_adam_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                  float eps, const int32_t* step_dev, void* stream);
+
+/* ---- Speech2Gesture baseline (ABI 9; model/speech2gesture.py, train_eval/train_speech2gesture.py) ------------------------------------------
+ * 2-D convolution as an implicit GEMM (csrc/conv2d.hip): activations channel-last (B, H, W, C) fp32 -- x may be fp16 (x_half = 1: the
+ * spectrogram as the loader delivers it) in the forward and weight-gradient calls --, weights in nn.Conv2d's layout [Co][Ci][kh][kw].
+ * Geometry: output Ho x Wo, stride 1 or 2 in both axes, explicit top / left zero padding (pad_top < kh, pad_left < kw); bottom / right zeros
+ * come from the bounds, so TF "SAME" (the odd extra zero bottom / right) is pad_top = total / 2 with Ho = ceil(H / stride).  bf16 x 3
+ * operand split, fp32-accurate; math mode 1: plain bf16 operands. */
+/* y (B, Ho, Wo, Co) = conv(x) + bias (bias may be NULL). */
+int tg_conv2d_fwd(const void* x, int32_t x_half, const float* w, const float* bias, float* y, int32_t B, int32_t H, int32_t W, int32_t Ci,
+                  int32_t Co, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, void* stream);
+/* dx (B, H, W, Ci) (+)= input gradient of dy (B, Ho, Wo, Co). */
+int tg_conv2d_dgrad(const float* dy, const float* w, float* dx, int32_t accumulate, int32_t B, int32_t H, int32_t W, int32_t Ci, int32_t Co,
+                    int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left, int32_t Ho, int32_t Wo, void* stream);
+/* workspace of tg_conv2d_wgrad for this geometry, in bytes (*bytes). */
+int tg_conv2d_wgrad_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t Ci, int32_t Co, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top,
+                             int32_t pad_left, int32_t Ho, int32_t Wo, int64_t* bytes);
+/* dw [Co][Ci][kh][kw] (+)= weight gradient: split-K partials in ws, combined in a fixed order in fp64 (bitwise repeatable in every mode).
+ * The bias gradient is tg_colsum over dy. */
+int tg_conv2d_wgrad(const float* dy, const void* x, int32_t x_half, float* dw, int32_t accumulate, float* ws, int64_t ws_bytes, int32_t B,
+                    int32_t H, int32_t W, int32_t Ci, int32_t Co, int32_t kh, int32_t kw, int32_t stride, int32_t pad_top, int32_t pad_left,
+                    int32_t Ho, int32_t Wo, void* stream);
+/* make_1d: Upsample((Hout, 1), bilinear, align_corners=False) of x (B, Hin, Win, C) where only column `col` contributes (weight 1):
+ * y (B, Hout, C), rows by torch's half-pixel rule clamped at the edges.  The backward WRITES dx (B, Hin, Win, C), zeros off column col. */
+int tg_s2g_rows_interp(const float* x, float* y, int32_t B, int32_t Hin, int32_t Win, int32_t col, int32_t C, int32_t Hout, void* stream);
+int tg_s2g_rows_interp_bwd(const float* dy, float* dx, int32_t B, int32_t Hin, int32_t Win, int32_t col, int32_t C, int32_t Hout, void* stream);
+/* UnetUp: y[b, t] = x[b, t / 2] + skip[b, t], t < Ls <= 2 Lx (repeat_interleave x 2, crop, add); backward dx[b, l] (+)= dy[b, 2l] + dy[b, 2l + 1]
+ * (the skip's gradient is dy itself). */
+int tg_s2g_up_add(const float* x, const float* skip, float* y, int32_t B, int32_t Lx, int32_t Ls, int32_t C, void* stream);
+int tg_s2g_up_add_bwd(const float* dy, float* dx, int32_t B, int32_t Lx, int32_t Ls, int32_t C, int32_t accumulate, void* stream);
+/* first difference over time: y[b, t] = x[b, t + 1] - x[b, t] (B, T - 1, C); backward dx (B, T, C) (+)=. */
+int tg_s2g_diff(const float* x, float* y, int32_t B, int32_t T, int32_t C, void* stream);
+int tg_s2g_diff_bwd(const float* dy, float* dx, int32_t B, int32_t T, int32_t C, int32_t accumulate, void* stream);
+/* LSGAN term: loss[0] = mean((x - target)^2) over n values (one workgroup, fp64 sums in a fixed order); dx (may be NULL) = scale 2 (x - target) / n. */
+int tg_s2g_mse_const(const float* x, int64_t n, float target, float scale, float* loss, float* dx, void* stream);
+/* gradient of mean |a - b| (tg_l1_mean): d = sign(a - b) / n. */
+int tg_s2g_l1_grad(const float* a, const float* b, float* d, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }
