@@ -149,9 +149,11 @@ SIGNATURES = {
     "tg_s2g_diff_bwd": [P, P, I32, I32, I32, I32, P],
     "tg_s2g_mse_const": [P, I64, F32, F32, P, P, P],
     "tg_s2g_l1_grad": [P, P, P, I64, P],
+    "tg_logmel_query": [I32, I32, P],
+    "tg_logmel": [P, I64, I32, I32, I32, P, I64, P, I64, P, I32, P],
 }
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 _lib = None
 
 

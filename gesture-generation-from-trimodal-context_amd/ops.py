@@ -1666,3 +1666,38 @@ def s2g_mse_const(x, target, loss, dx=None, scale=1.0):
 
 def s2g_l1_grad(a, b, d):
     call("tg_s2g_l1_grad", _p(a), _p(b), _p(d), _same(a, b, d), _stream()); return d
+
+
+# ------------------------------------------------------------------------------------------------- log-mel spectrogram (csrc/logmel.hip)
+LOGMEL_PAD_MODES = {"reflect": 0, "constant": 1}
+
+
+def logmel_query(N, L):
+    """(frames F = 1 + L // 512, floats of the constant table, bytes of workspace) of tg_logmel for N clips of L samples."""
+    sizes = (C.c_int64 * 3)()
+    call("tg_logmel_query", int(N), int(L), C.cast(sizes, C.c_void_p))
+    return int(sizes[0]), int(sizes[1]), int(sizes[2])
+
+
+def logmel(audio, out, ws, *, pad_mode="reflect", tables=None):
+    """out (N, 128, F) fp32 or fp16 = log-mel spectrogram in dB of audio (N, L) fp32 at 16 kHz (rows may be strided); ws: fp32 scratch of
+    logmel_query's size; tables: melspec.device_tables (taken from there when None)."""
+    _f32(audio, "audio"); _flat(ws, "ws")
+    if pad_mode not in LOGMEL_PAD_MODES:
+        raise ValueError(f"logmel: pad_mode {pad_mode!r}, expected one of {sorted(LOGMEL_PAD_MODES)}")
+    if audio.dim() != 2 or audio.stride(1) != 1 or (audio.shape[0] > 1 and audio.stride(0) < audio.shape[1]):
+        raise ValueError(f"logmel: audio must be (N, L) with unit sample stride, got {tuple(audio.shape)} strides {audio.stride()}")
+    N, L = audio.shape
+    if tables is None:
+        from . import melspec
+        tables = melspec.device_tables(audio.device)
+    _flat(tables, "tables")
+    F, tab_floats, ws_bytes = logmel_query(N, L)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype in (torch.float16, torch.float32) and out.is_contiguous()
+            and tuple(out.shape) == (N, 128, F)):
+        raise ValueError(f"logmel: out must be a contiguous CUDA fp16 / fp32 tensor of shape {(N, 128, F)}")
+    if (N - 1) * audio.stride(0) + L > _room(audio) or tables.numel() < tab_floats or ws.numel() * 4 < ws_bytes:
+        raise ValueError("logmel: audio view, table or workspace too small (logmel_query)")
+    call("tg_logmel", _p(audio), audio.stride(0), N, L, LOGMEL_PAD_MODES[pad_mode], _p(tables), tables.numel(), _p(ws), ws.numel() * 4, _p(out),
+         int(out.dtype == torch.float16), _stream())
+    return out

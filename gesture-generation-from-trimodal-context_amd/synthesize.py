@@ -1,10 +1,14 @@
-"""Long-utterance synthesis: the multimodal branch of scripts/synthesize.py:generate_gestures (:36-209).
+"""Long-utterance synthesis: the multimodal_context and speech2gesture branches of scripts/synthesize.py:generate_gestures (:36-209).
 
 An utterance is cut into 34-frame windows with a 30-frame stride; window i is seeded with the last 4 output frames of window
 i-1 (:122-124) and its first 4 frames are cross-faded with them (:145-153).  Here the windows stay on the GPU: the seed
 hand-over and the cross-fade are device ops (tg_window_blend), the host sees the result once at the end.  Many utterances run in
 lock-step as one batch (the only serial dependency is window i-1 -> i of the same utterance), and with fixed shapes the
 per-window forward is captured into a hipGraph (WindowDecoder).
+
+With args.model == 'speech2gesture' the same window loop feeds the Speech2Gesture generator (:42-44,52-56,65,86-93,137-138): one log-mel
+spectrogram per utterance made on the device (melspec.extract_melspectrogram), one 70-frame slice per window, pose_decoder(in_spec,
+pre_seq_partial); seed hand-over, cross-fade and fade-out as above.  The joint_embedding and seq2seq branches are not implemented.
 
 TTS / Gentle alignment / LMDB front-ends of the reference script are network services and out of scope; `words` is the
 reference's word list [[word, start_s, end_s], ...].
@@ -15,7 +19,8 @@ import random
 import numpy as np
 import torch
 
-from . import ops, layers as L
+from . import melspec, ops, layers as L
+from .speech2gesture import spectrogram_length
 
 
 def words_in_time_range(word_list, start_time, end_time):
@@ -133,12 +138,86 @@ class WindowDecoder:
         return self.out
 
 
+def spec_slice_length(n_poses=34, fps=15, sr=16000):
+    """synthesize.py:65: spectrogram frames fed per window, int(round(unit_time * sr / 512)): 71 for 34 poses at 15 fps -- one more than
+    speech2gesture.spectrogram_length's 70 the generator was trained on; its 2-D convolutions reduce both widths to the same 7 columns."""
+    return int(round(n_poses / fps * sr / melspec.HOP))
+
+
+def spec_window_start(i, clip_length, n_mels=melspec.N_MELS, n_poses=34, n_pre_poses=4, fps=15):
+    """First spectrogram frame of window i, synthesize.py:90 AS WRITTEN: floor(start_time / clip_length * spectrogram.shape[0]).
+    shape[0] of the (mels, frames) spectrogram is the MEL count (128), not the frame count, so the slice does not follow the audio's
+    time axis the way the audio slice of :96 does.  That is the reference's behaviour and its checkpoints were evaluated with it, so it is
+    reproduced here, not corrected."""
+    stride_time = (n_poses - n_pre_poses) / fps
+    return math.floor(i * stride_time / clip_length * n_mels)
+
+
+def end_padding_samples(args, n_samples, audio_sr=16000):
+    """Zero samples the reference appends to the last window's audio (synthesize.py:96-102): what fade_out counts back from."""
+    n_win = num_windows(n_samples / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate)
+    stride_time = (args.n_poses - args.n_pre_poses) / args.motion_resampling_framerate
+    a0 = math.floor((n_win - 1) * stride_time / (n_samples / audio_sr) * n_samples)
+    return max(0, int(args.n_poses / args.motion_resampling_framerate * audio_sr) - (n_samples - a0))
+
+
+def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode):
+    """The speech2gesture branch for several utterances in lock-step; same return value as generate_gestures_batch."""
+    if audio_sr != melspec.SR:
+        raise ValueError(f"speech2gesture synthesis: audio_sr = {audio_sr}; the spectrogram is defined for {melspec.SR} Hz audio")
+    dev = next(pose_decoder.parameters()).device
+    B, T, n_pre, fps = len(audios), args.n_poses, args.n_pre_poses, args.motion_resampling_framerate
+    stride, width, need = T - n_pre, spec_slice_length(T, fps), spectrogram_length(T, fps)
+    n_win = [num_windows(len(a) / audio_sr, T, n_pre, fps) for a in audios]
+    starts = [[spec_window_start(i, len(a) / audio_sr, melspec.N_MELS, T, n_pre, fps) for i in range(n)] for a, n in zip(audios, n_win)]
+    for a, st in zip(audios, starts):
+        got = min(width, melspec.n_frames(len(a)) - st[-1])
+        if got < need:
+            # the reference would run a narrower network here (make_1d from another width); nothing pins that, so it is refused, not padded
+            raise ValueError(f"speech2gesture synthesis: utterance of {len(a)} samples ({len(a) / audio_sr:.3f} s) leaves {got} spectrogram frames "
+                             f"for its last window, the generator needs {need}; the minimum is {(melspec.N_MELS + need - 2) * melspec.HOP} samples "
+                             f"({(melspec.N_MELS + need - 2) * melspec.HOP / audio_sr:.3f} s)")
+    # one spectrogram per utterance, on the device, once
+    specs = [melspec.extract_melspectrogram(np.asarray(a, dtype=np.float32), melspec.SR, pad_mode=spec_pad_mode, device=dev) for a in audios]
+    D = pose_decoder.final_out.out_channels
+    pre = torch.zeros(B, n_pre, D, device=dev)
+    if seed_seqs is not None:                                                   # synthesize.py:46-50
+        pre.copy_(torch.as_tensor(np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]), dtype=torch.float32))
+    tail = torch.zeros(B, n_pre, D, device=dev)
+    total = torch.zeros(B, max(n_win) * stride + n_pre, D, device=dev)
+    was_training = pose_decoder.training
+    pose_decoder.eval()
+    try:
+        with torch.no_grad():
+            for i in range(max(n_win)):
+                a0 = [st[min(i, len(st) - 1)] for st in starts]                 # finished utterances idle on their last window
+                pieces = [specs[b][:, a0[b]:a0[b] + width] for b in range(B)]   # :90-92 (a slice at the spectrogram's end is one frame short)
+                out = torch.empty(B, T, D, device=dev)
+                for w in sorted({p.shape[1] for p in pieces}):
+                    idx = [b for b in range(B) if pieces[b].shape[1] == w]
+                    out[idx] = pose_decoder(torch.stack([pieces[b] for b in idx]), pre[idx])     # (b, T, D), synthesize.py:138
+                if i > 0:
+                    ops.window_blend(tail, out)                                 # :145-153
+                tail.copy_(out[:, T - n_pre:, :])
+                pre = tail.clone()                                              # :122-126
+                for b in range(B):
+                    if i < n_win[b]:                                            # an idling utterance's frames are not written
+                        total[b, i * stride:i * stride + T, :].copy_(out[b])
+    finally:
+        pose_decoder.train(was_training)
+    res = total.cpu().numpy()
+    return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
+
+
 def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, vids=None, seed_seqs=None, audio_sr=16000,
-                            graph=True, _draws=None):
+                            graph=True, _draws=None, spec_pad_mode="reflect"):
     """Lock-step synthesis of several utterances.  Returns a list of (n_i * 30 + 4, D) numpy arrays (mean-subtracted direction
     vectors, like the reference's return value without fade-out).  vids: one speaker id per utterance, or None / a falsy entry to
     draw it like the reference (synthesize.py:67-74; ignored unless args.z_type == 'speaker').  _draws (parity tests): per window,
-    the (B, 16) eps / z to replay instead of the device RNG."""
+    the (B, 16) eps / z to replay instead of the device RNG.  args.model == 'speech2gesture': lang_model, words_list, vids, graph are unused
+    (the model sees the spectrogram only; no capture), spec_pad_mode is melspec.extract_melspectrogram's pad_mode."""
+    if getattr(args, "model", "multimodal_context") == "speech2gesture":
+        return _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode)
     dev = next(pose_decoder.parameters()).device
     B = len(audios)
     n_win = [num_windows(len(a) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate) for a in audios]
@@ -187,12 +266,14 @@ def fade_out_to_mean(out_dir_vec, end_padding_samples, args, audio_sr=16000):
 
 
 def generate_gestures(args, pose_decoder, lang_model, audio, words, audio_sr=16000, vid=None, seed_seq=None, fade_out=False,
-                      _draws=None):
-    """Single-utterance API of the reference (synthesize.py:36-209, multimodal_context model)."""
+                      _draws=None, spec_pad_mode="reflect"):
+    """Single-utterance API of the reference (synthesize.py:36-209, multimodal_context and speech2gesture models)."""
     out = generate_gestures_batch(args, pose_decoder, lang_model, [audio], [words], [vid], None if seed_seq is None else [seed_seq],
-                                  audio_sr, graph=True, _draws=_draws)[0]
+                                  audio_sr, graph=True, _draws=_draws, spec_pad_mode=spec_pad_mode)[0]
     if not fade_out:
         return out
+    if getattr(args, "model", "multimodal_context") == "speech2gesture":
+        return fade_out_to_mean(out, end_padding_samples(args, len(audio), audio_sr), args, audio_sr)
     n_win = num_windows(len(audio) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate)
     _, _, end_padding = window_inputs(args, lang_model, audio, words, n_win - 1, audio_sr)
     return fade_out_to_mean(out, end_padding, args, audio_sr)

@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TG_ABI_VERSION 9
+#define TG_ABI_VERSION 10
 
 int tg_version(void);
 
@@ -728,6 +728,20 @@ int tg_s2g_diff_bwd(const float* dy, float* dx, int32_t B, int32_t T, int32_t C,
 int tg_s2g_mse_const(const float* x, int64_t n, float target, float scale, float* loss, float* dx, void* stream);
 /* gradient of mean |a - b| (tg_l1_mean): d = sign(a - b) / n. */
 int tg_s2g_l1_grad(const float* a, const float* b, float* d, int64_t n, void* stream);
+
+/* ---- log-mel spectrogram (ABI 10; utils/data_utils.py:34-38 extract_melspectrogram: librosa.feature.melspectrogram(n_fft = 1024, hop_length = 512,
+ * power = 2) with 128 Slaney mels over 0 .. 8 kHz, power_to_db(ref = np.max), the fp16 cast) for N clips of L samples at 16 kHz in two launches
+ * (csrc/logmel.hip).  Frames: center = True, F = 1 + L / 512, frame t = samples 512 t - 512 .. 512 t + 511 of the clip, the boundary read by index
+ * arithmetic -- pad_mode 0: reflected (L >= 513), 1: zeros.  Periodic Hann window, |rfft|^2 over 513 bins, mel filters gathered in bin order,
+ * db = 10 log10(max(M, 1e-10)) - 10 log10(max(max M, 1e-10)) with the maximum over the whole clip, floored at -80.  No atomics: bitwise repeatable.
+ * tg_logmel_query: sizes[0] = F, sizes[1] = floats of the constant table, sizes[2] = bytes of workspace for (N, L).
+ * tables (device, sizes[1] floats, built by the caller in fp64 and rounded once): [0, 1024) exp(-2 pi i k / 1024), k < 512, as (re, im) pairs;
+ * [1024, 2048) the window; [2048, 5120) filter weights [24][128] (weight j of filter i at j * 128 + i, zero past the filter's last bin);
+ * [5120, 5248) every filter's first bin as a float.  audio: clip n at audio + n * audio_stride.  out: (N, 128, F), fp32 or (out_half = 1) fp16 = the
+ * round-to-nearest-even cast of the fp32 result.  ws: sizes[2] bytes of scratch, no initialisation needed. */
+int tg_logmel_query(int32_t N, int32_t L, int64_t* sizes);
+int tg_logmel(const float* audio, int64_t audio_stride, int32_t N, int32_t L, int32_t pad_mode, const float* tables, int64_t table_floats, void* ws,
+              int64_t ws_bytes, void* out, int32_t out_half, void* stream);
 
 #ifdef __cplusplus
 }
