@@ -266,15 +266,17 @@ __global__ __launch_bounds__(256) void conv2d_wgrad_reduce_kernel(const float* _
 
 // ---- small ops of the Speech2Gesture generator / discriminator ---------------------------------------------------------------------
 
-// torch's bilinear source row (align_corners=False, size given): src = max(0, (t + 0.5) Hin / Hout - 0.5), rows h0 / h1, weight of h1
+// torch's bilinear source row (align_corners=False, size given): src = max(0, (t + 0.5) Hin / Hout - 0.5), rows h0 / h1, weight of h1.
+// In integers, src = ((2 t + 1) Hin - Hout) / (2 Hout): the row is exact and the weight is rounded once.  (In fp32 the weight carries the
+// rounding of Hin / Hout times src, 1.7e-6 of the output at 34 -> 14.)
 __device__ __forceinline__ void interp_src(int t, int Hin, int Hout, int& h0, int& h1, float& l1) {
-    const float scale = (float)Hin / (float)Hout;
-    float src = ((float)t + 0.5f) * scale - 0.5f;
-    src = src < 0.f ? 0.f : src;
-    h0 = (int)src;
-    if (h0 > Hin - 1) h0 = Hin - 1;
+    const long den = 2L * Hout;
+    long num = (2L * t + 1) * Hin - Hout;
+    num = num < 0 ? 0 : num;
+    const long q = num / den;
+    h0 = q > Hin - 1 ? Hin - 1 : (int)q;
     h1 = h0 + 1 < Hin ? h0 + 1 : h0;
-    l1 = src - (float)h0;
+    l1 = (float)(num - q * den) / (float)den;
 }
 
 // y[b, t, c] = (1 - l) x[b, h0, col, c] + l x[b, h1, col, c]     x (B, Hin, Win, C), y (B, Hout, C)

@@ -1587,12 +1587,20 @@ def _x2d(x):
     return int(x.dtype == torch.float16)
 
 
+def _conv2d_fits(what, H, W, kh, kw, stride, pad_top, pad_left, Ho, Wo):
+    """The output (Ho, Wo) must be one the (H, W) input can give: the last output's window starts inside the input (c2_check's rule)."""
+    if Ho < 1 or Wo < 1 or (Ho - 1) * int(stride) - int(pad_top) >= H or (Wo - 1) * int(stride) - int(pad_left) >= W:
+        raise ValueError(f"{what}: output {Ho} x {Wo} does not fit a {H} x {W} input (k {kh} x {kw}, stride {stride}, pads {pad_top}, {pad_left})")
+
+
 def conv2d_fwd(x, w, bias, y, *, stride, pad_top, pad_left):
     """y (B, Ho, Wo, Co) = conv2d(x (B, H, W, Ci) channel-last, w [Co][Ci][kh][kw]) + bias."""
     B, H, W, Ci = x.shape
     _, Ho, Wo, Co = y.shape
     kh, kw = w.shape[2], w.shape[3]
     assert tuple(w.shape) == (Co, Ci, kh, kw) and tuple(y.shape[:1]) == (B,)
+    assert bias is None or tuple(bias.shape) == (Co,)
+    _conv2d_fits("conv2d_fwd", H, W, kh, kw, stride, pad_top, pad_left, Ho, Wo)
     call("tg_conv2d_fwd", _p(x), _x2d(x), _p(_flat(w, "w")), _p(bias), _p(_flat(y, "y")),
          *_geom2d(B, H, W, Ci, Co, kh, kw, stride, pad_top, pad_left, Ho, Wo), _stream())
     return y
@@ -1602,7 +1610,8 @@ def conv2d_dgrad(dy, w, dx, *, stride, pad_top, pad_left, accumulate=False):
     B, H, W, Ci = dx.shape
     _, Ho, Wo, Co = dy.shape
     kh, kw = w.shape[2], w.shape[3]
-    assert tuple(w.shape) == (Co, Ci, kh, kw)
+    assert tuple(w.shape) == (Co, Ci, kh, kw) and dy.shape[0] == dx.shape[0]
+    _conv2d_fits("conv2d_dgrad", H, W, kh, kw, stride, pad_top, pad_left, Ho, Wo)
     call("tg_conv2d_dgrad", _p(_flat(dy, "dy")), _p(_flat(w, "w")), _p(_flat(dx, "dx")), int(accumulate),
          *_geom2d(B, H, W, Ci, Co, kh, kw, stride, pad_top, pad_left, Ho, Wo), _stream())
     return dx
@@ -1612,7 +1621,10 @@ def conv2d_wgrad(dy, x, dw, *, stride, pad_top, pad_left, accumulate=False):
     """dw [Co][Ci][kh][kw] (+)= weight gradient (split K, fixed-order fp64 combine: bitwise repeatable)."""
     B, H, W, Ci = x.shape
     _, Ho, Wo, Co = dy.shape
+    assert dw.dim() == 4
     kh, kw = dw.shape[2], dw.shape[3]
+    assert dy.shape[0] == x.shape[0] and tuple(dw.shape) == (Co, Ci, kh, kw)
+    _conv2d_fits("conv2d_wgrad", H, W, kh, kw, stride, pad_top, pad_left, Ho, Wo)
     g = _geom2d(B, H, W, Ci, Co, kh, kw, stride, pad_top, pad_left, Ho, Wo)
     nbytes = C.c_int64(0)
     call("tg_conv2d_wgrad_ws_bytes", *g, C.cast(C.pointer(nbytes), C.c_void_p))

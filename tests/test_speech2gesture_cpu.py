@@ -71,3 +71,46 @@ def test_spectrogram_length(pkg):
     from importlib import import_module
     s2g = import_module(pkg.__name__ + ".speech2gesture")
     assert s2g.spectrogram_length(34, 15) == 70
+
+
+def test_conv2d_wrappers_refuse_mismatched_tensors(pkg):
+    """ops.conv2d_fwd / _dgrad / _wgrad take the batch and channel counts from one tensor: a second tensor that disagrees must raise in
+    Python (before the device checks, so CPU tensors show it) instead of letting the kernel read past its end."""
+    import torch
+    ops = pkg.ops
+    B, H, W, Ci, Co, kh, kw, s, pt, pl, Ho, Wo = 2, 10, 12, 3, 5, 3, 2, 2, 1, 0, 5, 6
+    kw_ = dict(stride=s, pad_top=pt, pad_left=pl)
+    x, y, w = torch.zeros(B, H, W, Ci), torch.zeros(B, Ho, Wo, Co), torch.zeros(Co, Ci, kh, kw)
+    # batch counts
+    with pytest.raises(AssertionError):
+        ops.conv2d_fwd(x, w, None, torch.zeros(B + 1, Ho, Wo, Co), **kw_)
+    with pytest.raises(AssertionError):
+        ops.conv2d_dgrad(torch.zeros(B + 1, Ho, Wo, Co), w, x, **kw_)
+    with pytest.raises(AssertionError):
+        ops.conv2d_dgrad(y, w, torch.zeros(B - 1, H, W, Ci), **kw_)
+    with pytest.raises(AssertionError):
+        ops.conv2d_wgrad(torch.zeros(B + 1, Ho, Wo, Co), x, w, **kw_)
+    # channel counts and the weight gradient's shape
+    with pytest.raises(AssertionError):
+        ops.conv2d_fwd(x, w, torch.zeros(Co + 1), y, **kw_)
+    for bad in ((Co + 1, Ci, kh, kw), (Co, Ci + 1, kh, kw), (Ci, Co, kh, kw), (Co, Ci, kh * kw)):
+        with pytest.raises(AssertionError):
+            ops.conv2d_wgrad(y, x, torch.zeros(bad), **kw_)
+    with pytest.raises(AssertionError):
+        ops.conv2d_dgrad(y, torch.zeros(Co, Ci + 1, kh, kw), x, **kw_)
+    # spatial sizes: an output whose last window starts past the input, along either axis, and an empty one
+    for Ho_, Wo_ in ((Ho + 2, Wo), (Ho, Wo + 1), (0, Wo)):
+        y_ = torch.zeros(B, Ho_, Wo_, Co)
+        with pytest.raises(ValueError, match="does not fit"):
+            ops.conv2d_fwd(x, w, None, y_, **kw_)
+        with pytest.raises(ValueError, match="does not fit"):
+            ops.conv2d_dgrad(y_, w, x, **kw_)
+        with pytest.raises(ValueError, match="does not fit"):
+            ops.conv2d_wgrad(y_, x, w, **kw_)
+    # the consistent call gets past all of these and stops at the device check
+    with pytest.raises((TypeError, ValueError), match="CUDA"):
+        ops.conv2d_fwd(x, w, None, y, **kw_)
+    with pytest.raises((TypeError, ValueError), match="CUDA"):
+        ops.conv2d_dgrad(y, w, x, **kw_)
+    with pytest.raises((TypeError, ValueError), match="CUDA"):
+        ops.conv2d_wgrad(y, x, w, **kw_)
