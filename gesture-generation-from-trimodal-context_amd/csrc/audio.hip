@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void wav_apply_kernel(WavGeom g, const float* 
             const bool ok = 16 * tt + 4 * i + (l >> 4) < g.T1;
             const float xh = (x[i] - mu) * rs;                 // association of bn_apply_kernel
             const float z = xh * ga + be;
-            const bool pos = z >= 0.f;
+            const bool pos = z > 0.f;                          // the gate bit follows act'(0) = slope (csrc/norm.hip's backward kernels); y is the same either way
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pos ? z : z * slope), y_rsrc, (unsigned)((16 * tt * WV_CO + 64 * i + l) * 4), 0, 0);
             const unsigned long long word = __ballot(ok && pos);
             mine = l == i ? word : mine;

@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
         for (long r = (long)blockIdx.x * rpi + rsub; r < rows; r += (long)gridDim.x * rpi) {
             const float xh = (x[r * C + c] - mu) * rs;
             const float z = xh * ga + be;
-            const float dz = dy[r * C + c] * (z >= 0.f ? 1.f : slope);
+            const float dz = dy[r * C + c] * (z > 0.f ? 1.f : slope);
             s += dz;
             sx += (double)dz * xh;
         }
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         const float rs = rstd[c], ga = gamma[c];
         const float xh = (x[e] - mean[c]) * rs;
         const float z = xh * ga + beta[c];
-        const float dz = dy[e] * (z >= 0.f ? 1.f : slope);
+        const float dz = dy[e] * (z > 0.f ? 1.f : slope);
         // the two batch means are subtracted in fp64: rounding them to fp32 first would shift every element of the
         // channel by the same amount, and the next layer's weight-gradient sum over ~1e6 rows amplifies that coherently
         const double m1 = ws[c] * inv_n, m2 = ws[C + c] * inv_n;
@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const float* __r
         for (int q = 0; q < 4; ++q) {
             const float xh = (xv[q] - mu[q]) * rs[q];
             const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z >= 0.f ? 1.f : slope);
+            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
             s[q] += dz;
             sx[q] += (double)dz * xh;
         }
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const float* __re
         for (int q = 0; q < 4; ++q) {
             const float xh = (xv[q] - mu[q]) * rs[q];
             const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z >= 0.f ? 1.f : slope);
+            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
             o[q] = (float)((double)(ga[q] * rs[q]) * ((double)dz - m1[q] - (double)xh * m2[q]));     // fp64 means: see bn_bwd_apply_kernel
         }
         dx4[i] = o;
@@ -358,7 +358,7 @@ __global__ __launch_bounds__(BN_SMALL_THREADS) void bn_small_bwd_kernel(
         for (int q = 0; q < 4; ++q) {
             const float xh = (xv[q] - mu[q]) * rs[q];
             const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z >= 0.f ? 1.f : slope);
+            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
             s[q] += dz;
             sx[q] += (double)dz * xh;
         }
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(BN_SMALL_THREADS) void bn_small_bwd_kernel(
         for (int q = 0; q < 4; ++q) {
             const float xh = (xv[q] - mu[q]) * rs[q];
             const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z >= 0.f ? 1.f : slope);
+            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
             o[q] = (float)((double)(ga[q] * rs[q]) * ((double)dz - m1[q] - (double)xh * m2[q]));
         }
         dx4[i] = o;
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(256) void bn2_partial_kernel(const float* __restric
             for (int q = 0; q < 4; ++q) {
                 const float xh = (xv[q] - mu[q]) * rs[q];
                 const float z = xh * ga[q] + be[q];
-                const float dz = dv[q] * (z >= 0.f ? 1.f : slope);
+                const float dz = dv[q] * (z > 0.f ? 1.f : slope);
                 s[q] += dz;
                 ss[q] += (double)dz * xh;
             }
@@ -598,7 +598,7 @@ __global__ __launch_bounds__(256) void bn2_bwd_apply_kernel(const float* __restr
         for (int q = 0; q < 4; ++q) {
             const float xh = (xv[q] - mu[q]) * rs[q];
             const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z >= 0.f ? 1.f : slope);
+            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
             o[q] = (float)((double)(ga[q] * rs[q]) * ((double)dz - m1[q] - (double)xh * m2[q]));     // fp64 means: see bn_bwd_apply_kernel
         }
         dx4[i] = o;

@@ -468,20 +468,26 @@ def _eval_stats(running_mean, running_var, mean, rstd):
     return frozen(("bn_eval", running_mean.data_ptr(), running_var.data_ptr()), make)
 
 
+def _a16(*ts):
+    """True when every tensor starts on a 16-byte boundary (what the 16-byte BatchNorm kernels require of x, y, dy and dx)."""
+    return all(t.data_ptr() % 16 == 0 for t in ts)
+
+
 def bn_fwd(x, gamma, beta, running_mean, running_var, nbt, *, training, groups=1, act_slope=1.0, out=None, repeats=1):
-    """x: (..., C) contiguous channel-last.  Returns (y, BNState)."""
+    """x: (..., C) contiguous channel-last.  Returns (y, BNState).  A contiguous x or out that does not start on a 16-byte boundary (a slab
+    slice at an odd float offset) takes the streaming kernels, whose scalar forms exist for that input."""
     Cc = x.shape[-1]
     x2 = x.view(-1, Cc)
     st = BNState()
     g = groups if training else 1
     st.mean, st.rstd = empty(g, Cc, like=x), empty(g, Cc, like=x)
     st.groups, st.x, st.slope = g, x, act_slope
-    if training and x2.shape[0] % g == 0 and ops.bn2_supported(x2.shape[0] // g, Cc, g) and x2.is_contiguous():
-        y = torch.empty_like(x) if out is None else out
+    y = torch.empty_like(x) if out is None else out
+    a16 = _a16(x2, y)
+    if training and a16 and x2.shape[0] % g == 0 and ops.bn2_supported(x2.shape[0] // g, Cc, g) and x2.is_contiguous():
         ops.bn2_train(x2, y.view(-1, Cc), g, st.mean, st.rstd, running_mean, running_var, nbt, gamma, beta, act_slope, repeats=repeats)
         return y, st
-    if training and ops.bn_fused_supported(x2.shape[0], Cc, g):
-        y = torch.empty_like(x) if out is None else out
+    if training and a16 and ops.bn_fused_supported(x2.shape[0], Cc, g):
         ops.bn_train_fused(x2, y.view(-1, Cc), g, st.mean, st.rstd, running_mean, running_var, nbt, gamma, beta, act_slope, repeats=repeats)
         return y, st
     if training:
@@ -489,23 +495,24 @@ def bn_fwd(x, gamma, beta, running_mean, running_var, nbt, *, training, groups=1
         ops.bn_train_stats(x2, g, ws, st.mean, st.rstd, running_mean, running_var, nbt, repeats=repeats)
     else:
         st.mean, st.rstd = _eval_stats(running_mean, running_var, st.mean, st.rstd)
-    y = torch.empty_like(x) if out is None else out
     ops.bn_apply(x2, y.view(-1, Cc), g, st.mean, st.rstd, gamma, beta, act_slope)
     return y, st
 
 
-def bn_bwd(dy, st, gamma, beta, dgamma, dbeta, *, g0=0, ng=1, row0=0):
+def bn_bwd(dy, st, gamma, beta, dgamma, dbeta, *, g0=0, ng=1, row0=0, out=None):
     """Backward of act(BN(x)) for `ng` consecutive statistics groups starting at group g0.  dy: (nb, ..., C) holds
-    exactly those groups' batch rows; the matching rows of the taped input start at batch index row0."""
+    exactly those groups' batch rows; the matching rows of the taped input start at batch index row0.  dgamma / dbeta are added to.
+    out: a contiguous tensor of dy's shape that receives dx (default: a new one)."""
     Cc = dy.shape[-1]
     nb = dy.shape[0]
     assert nb % ng == 0
     per = nb // ng
     dy = dy.contiguous()
-    dx = torch.empty_like(dy)
+    dx = torch.empty_like(dy) if out is None else out
+    assert dx.shape == dy.shape and dx.is_contiguous()
     rpg = dy[0].numel() // Cc * per
     x_all = st.x[row0:row0 + nb]
-    if ops.bn2_supported(rpg, Cc, ng) and x_all.is_contiguous():
+    if ops.bn2_supported(rpg, Cc, ng) and x_all.is_contiguous() and _a16(dy, x_all, dx):
         # every group of the call in one pair of launches
         ops.bn2_backward(dy.view(-1, Cc), x_all.reshape(-1, Cc), dx.view(-1, Cc), ng, st.mean[g0:g0 + ng], st.rstd[g0:g0 + ng], gamma, beta, st.slope,
                          dgamma, dbeta)

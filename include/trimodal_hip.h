@@ -426,7 +426,7 @@ int tg_out_mlp_param_grads(const float* P, const float* s, const float* w1, cons
  * audio: B clips of L samples, `audio_stride` floats apart; w [16][15], bias [16]; T1 = (L + 2 pad - 15) / stride + 1 output frames.
  * ws: scratch of tg_wav_front_ws_doubles() doubles (no initialisation needed); fstat: tg_wav_front_fstat_doubles() doubles written by
  * _stats and read by _backward (sums of the forward pass); gate: tg_wav_front_gate_words(B, T1) 64-bit words written by _apply
- * (one bit per output element: pre-activation >= 0) and read by _backward. */
+ * (one bit per output element: pre-activation > 0, so act'(0) = act_slope as in tg_bn_backward) and read by _backward. */
 int64_t tg_wav_front_ws_doubles(void);
 int64_t tg_wav_front_fstat_doubles(void);
 int64_t tg_wav_front_gate_words(int32_t B, int32_t T1);
