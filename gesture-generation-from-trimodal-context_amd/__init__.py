@@ -10,7 +10,8 @@ from .optim import FusedAdam  # noqa: F401
 from .train_gan import GanTrainer, GraphedGanStep, StepLosses  # noqa: F401
 from .vocab import Vocab  # noqa: F401
 from .melspec import extract_melspectrogram  # noqa: F401
-from . import checkpoint, config, data, ddp, eval_metrics, fgd, layers, melspec, ops, synthesize  # noqa: F401,E402  (hip.fgd, hip.config, ... as INTEGRATION.md uses them)
+from .preprocess import DataPreprocessor, calculate_data_mean, resample_pose_seq  # noqa: F401
+from . import checkpoint, config, data, ddp, eval_metrics, fgd, layers, melspec, ops, preprocess, synthesize  # noqa: F401,E402  (hip.fgd, hip.config, ... as INTEGRATION.md uses them)
 
 __all__ = ["PoseGenerator", "ConvDiscriminator", "EmbeddingNet", "FusedAdam", "GanTrainer", "GraphedGanStep", "StepLosses",
-           "Vocab", "extract_melspectrogram"]
+           "Vocab", "extract_melspectrogram", "DataPreprocessor", "calculate_data_mean", "resample_pose_seq"]

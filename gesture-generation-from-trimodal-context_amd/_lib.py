@@ -151,9 +151,14 @@ SIGNATURES = {
     "tg_s2g_l1_grad": [P, P, P, I64, P],
     "tg_logmel_query": [I32, I32, P],
     "tg_logmel": [P, I64, I32, I32, I32, P, I64, P, I64, P, I32, P],
+    "tg_pose_resample": [P, I64, I32, P, I64, I32, P, I64, P],
+    "tg_clip_windows": [P, I64, I32, P, I64, I32, I32, P, I64, P, P, P, P, P],
+    "tg_clip_slices": [P, I64, I32, I32, P, I64, I32, I32, P, P],
+    "tg_motion_stats_query": [I64, P],
+    "tg_motion_stats": [P, I64, I32, P, I64, P, P],
 }
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 _lib = None
 
 

@@ -1713,3 +1713,87 @@ def logmel(audio, out, ws, *, pad_mode="reflect", tables=None):
     call("tg_logmel", _p(audio), audio.stride(0), N, L, LOGMEL_PAD_MODES[pad_mode], _p(tables), tables.numel(), _p(ws), ws.numel() * 4, _p(out),
          int(out.dtype == torch.float16), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ training samples from raw clips (csrc/preprocess.hip)
+PP_CLIP_WORDS, PP_SLICE_WORDS, PP_CONSTS, PP_STATS = 5, 4, 61, 6
+
+
+def _pp_tensor(t, name, dtypes):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and t.is_contiguous()):
+        raise ValueError(f"{name}: expected a contiguous CUDA tensor of dtype {' / '.join(str(d) for d in dtypes)}, got "
+                         f"{type(t).__name__} {getattr(t, 'dtype', None)} {getattr(t, 'device', None)}")
+    return t
+
+
+def _pp_frames(t, name):
+    _pp_tensor(t, name, (torch.float32, torch.float16))
+    if t.dim() != 2 or t.shape[1] != 30 or t.shape[0] < 1:
+        raise ValueError(f"{name}: expected (frames >= 1, 30), got {tuple(t.shape)}")
+    return t
+
+
+def pose_resample(src, clip_table, dst):
+    """dst (dst_rows, 30) = every clip of src (src_rows, 30) fp32 / fp16 resampled as utils/data_utils.py:46-56 does; clip_table: int64
+    (n_clips, 5) = [src_row0, n, dst_row0, m, bits of the double step] per clip, in increasing dst_row0 (tg_pose_resample)."""
+    _pp_frames(src, "src"); _pp_frames(dst, "dst")
+    _pp_tensor(clip_table, "clip_table", (torch.int64,))
+    if dst.dtype != src.dtype or clip_table.dim() != 2 or clip_table.shape[1] != PP_CLIP_WORDS or clip_table.shape[0] < 1:
+        raise ValueError(f"pose_resample: dst must have src's dtype and clip_table must be (n_clips >= 1, {PP_CLIP_WORDS}) int64")
+    call("tg_pose_resample", _p(src), src.shape[0], int(src.dtype == torch.float16), _p(clip_table), clip_table.numel() * 8, clip_table.shape[0],
+         _p(dst), dst.shape[0], _stream())
+    return dst
+
+
+def clip_windows(skel, win_row0, n_poses, consts, poses, vec, stats, verdict):
+    """Windows of n_poses frames of skel (rows, 30) starting at the rows of win_row0 (W,) int64: poses (W, n_poses, 30) in skel's dtype,
+    vec (W, n_poses, 27) fp32, stats (W, 6) fp32, verdict (W,) int32 (tg_clip_windows); consts: 61 doubles = mean_pose, mean_dir_vec and the
+    four thresholds."""
+    _pp_frames(skel, "skel")
+    _pp_tensor(win_row0, "win_row0", (torch.int64,)); _pp_tensor(consts, "consts", (torch.float64,))
+    W, n_poses = win_row0.numel(), int(n_poses)
+    if W < 1 or n_poses < 1 or consts.numel() < PP_CONSTS:
+        raise ValueError(f"clip_windows: {W} windows of {n_poses} frames, {consts.numel()} constants ({PP_CONSTS} needed)")
+    for t, name, dt, shape in ((poses, "poses", skel.dtype, (W, n_poses, 30)), (vec, "vec", torch.float32, (W, n_poses, 27)),
+                               (stats, "stats", torch.float32, (W, PP_STATS)), (verdict, "verdict", torch.int32, (W,))):
+        _pp_tensor(t, name, (dt,))
+        if tuple(t.shape) != shape:
+            raise ValueError(f"clip_windows: {name} must have shape {shape}, got {tuple(t.shape)}")
+    call("tg_clip_windows", _p(skel), skel.shape[0], int(skel.dtype == torch.float16), _p(win_row0), W * 8, W, n_poses, _p(consts), consts.numel() * 8,
+         _p(poses), _p(vec), _p(stats), _p(verdict), _stream())
+    return poses, vec, stats, verdict
+
+
+def clip_slices(src, table, rows, length, dst):
+    """dst (W, rows, length) = per window `length` elements of every row of a signal inside the flat buffer src (fp32 or fp16), read past the
+    end by np.pad(mode='symmetric') index arithmetic; table: int64 (W, 4) = [base, L, row_stride, start] in elements (tg_clip_slices)."""
+    _pp_tensor(src, "src", (torch.float32, torch.float16)); _pp_tensor(dst, "dst", (src.dtype,))
+    _pp_tensor(table, "table", (torch.int64,))
+    if table.dim() != 2 or table.shape[1] != PP_SLICE_WORDS or table.shape[0] < 1 or tuple(dst.shape) != (table.shape[0], int(rows), int(length)):
+        raise ValueError(f"clip_slices: table must be (W >= 1, {PP_SLICE_WORDS}) int64 and dst (W, {rows}, {length}), got {tuple(table.shape)}, {tuple(dst.shape)}")
+    call("tg_clip_slices", _p(src), src.numel(), src.element_size(), int(rows), _p(table), table.numel() * 8, table.shape[0], int(length), _p(dst),
+         _stream())
+    return dst
+
+
+def motion_stats_query(n_rows):
+    """(workgroups, bytes of workspace) of tg_motion_stats over n_rows frames."""
+    sizes = (C.c_int64 * 2)()
+    call("tg_motion_stats_query", int(n_rows), C.cast(sizes, C.c_void_p))
+    return int(sizes[0]), int(sizes[1])
+
+
+def motion_stats(skel, out=None, ws=None):
+    """out (66,) fp64 = mean pose (30), mean unit bone vector (27), mean bone length (9) over the frames of skel (rows, 30)
+    (calculate_motion_stats.py:33-44; tg_motion_stats)."""
+    _pp_frames(skel, "skel")
+    _, ws_bytes = motion_stats_query(skel.shape[0])
+    if ws is None:
+        ws = torch.empty(ws_bytes // 8, device=skel.device, dtype=torch.float64)
+    if out is None:
+        out = torch.empty(66, device=skel.device, dtype=torch.float64)
+    _pp_tensor(ws, "ws", (torch.float64,)); _pp_tensor(out, "out", (torch.float64,))
+    if ws.numel() * 8 < ws_bytes or out.numel() < 66:
+        raise ValueError("motion_stats: workspace or output too small (motion_stats_query)")
+    call("tg_motion_stats", _p(skel), skel.shape[0], int(skel.dtype == torch.float16), _p(ws), ws.numel() * 8, _p(out), _stream())
+    return out

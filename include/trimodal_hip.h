@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define TG_ABI_VERSION 10
+#define TG_ABI_VERSION 11
 
 int tg_version(void);
 
@@ -742,6 +742,46 @@ int tg_s2g_l1_grad(const float* a, const float* b, float* d, int64_t n, void* st
 int tg_logmel_query(int32_t N, int32_t L, int64_t* sizes);
 int tg_logmel(const float* audio, int64_t audio_stride, int32_t N, int32_t L, int32_t pad_mode, const float* tables, int64_t table_floats, void* ws,
               int64_t ws_bytes, void* out, int32_t out_half, void* stream);
+
+/* ---- training samples from raw clips (ABI 11; data_loader/data_preprocessor.py:66-170, data_loader/motion_preprocessor.py:32-87,
+ * utils/data_utils.py:46-56, data_loader/calculate_motion_stats.py:33-44; csrc/preprocess.hip).  A BATCH is many clips packed into one device buffer
+ * and described by device-resident tables of 8-byte words (the host builds them and ships them with one copy per batch); one call covers the whole
+ * batch.  Skeleton frames are 30 values (10 joints x 3), fp32 or (half = 1) fp16.  Doubles travel in the tables, never as arguments.  No atomics,
+ * fixed reduction orders, fp64 accumulators: bitwise repeatable.  The host cannot inspect the tables, so the kernels check every table entry against
+ * the extents given here and skip an entry that points outside (nothing is read or written there).
+ *
+ * tg_pose_resample -- resample_pose_seq (data_utils.py:46-56).  clips: n_clips records {int64 src_row0, int64 n, int64 dst_row0, int64 m, double step},
+ * in increasing dst_row0: clip c owns frames src_row0 .. src_row0 + n - 1 of src (src_rows frames) and writes m = len(np.arange(0, n, step)) frames from
+ * dst_row0 on (dst_rows frames in all), step = n / (duration * fps).  Output frame k is interp1d(kind = 'linear', fill_value = 'extrapolate') at
+ * x = k * step, formed in fp64: segment hi = clip(ceil(x), 1, n - 1), lo = hi - 1, y = (y[hi] - y[lo]) * (x - lo) + y[lo] with the difference taken
+ * in the input dtype (as numpy subtracts the arrays) and everything after it in fp64; x > n - 1 (an up-sampled clip) extrapolates along the last
+ * segment.  The result is rounded once to the input dtype.  n = 1 copies the frame.
+ *
+ * tg_clip_windows -- window w = frames win_row0[w] .. + n_poses - 1 of skel (int64 table; the host adds the clip's first row and start_idx).
+ * consts: 61 doubles = mean_pose[30], mean_dir_vec[27], thresholds {0.02, 30, 20, 0.0014} (pose difference, max / mean spine angle in degrees,
+ * wrist variance).  Outputs: poses (n_windows, n_poses, 30) in the input dtype, the slice; vec (n_windows, n_poses, 27) fp32 = the nine unit vectors
+ * of dir_vec_pairs (a zero-length bone gives zeros, sklearn.preprocessing.normalize) minus mean_dir_vec, formed in fp64 and rounded once;
+ * stats (n_windows, 6) fp32 = mean |x - mean_pose|, max and mean over frames of arccos(clip(u . (0, -1, 0), -1, 1)) in degrees with u the unit vector
+ * joint 1 - joint 0, the summed population variance of joint 6 and of joint 9 over the window, the count of non-finite inputs;
+ * verdict (n_windows) int32 = 0 PASS, 1 "pose" (stats[0] < th0), 2 "spine angle" (stats[1] > th1 or stats[2] > th2), 3 "motion" (both variances < th3),
+ * the first failing check in that order, decided on the fp64 values; -1: the table entry lies outside skel.
+ *
+ * tg_clip_slices -- window w copies `len` elements per row of a signal of `rows` rows: table records {int64 base, int64 L, int64 row_stride,
+ * int64 start} (element units; row r of the signal begins at src + base + r * row_stride and holds L elements).  Element j of row r is index
+ * start + j, read past the end as np.pad(mode = 'symmetric') does: q = (start + j) mod 2 L, q >= L -> 2 L - 1 - q (any padding length).  dst
+ * (n_windows, rows, len).  elem_bytes 4 serves raw audio (rows = 1), 2 the fp16 spectrogram (rows = 128, slices along time).  Bit-exact.
+ *
+ * tg_motion_stats -- calculate_data_mean (calculate_motion_stats.py:33-44) over n_rows frames: out[0..30) the mean pose, [30, 57) the mean unit bone
+ * vector, [57, 66) the mean bone length, doubles; fp64 partial sums per workgroup in ws (tg_motion_stats_query: sizes[0] = workgroups,
+ * sizes[1] = bytes of ws), added in workgroup order by a second launch.  Batches are combined by the caller, weighted by their frame counts. */
+int tg_pose_resample(const void* src, int64_t src_rows, int32_t half, const void* clips, int64_t clip_bytes, int32_t n_clips, void* dst,
+                     int64_t dst_rows, void* stream);
+int tg_clip_windows(const void* skel, int64_t skel_rows, int32_t half, const void* win_row0, int64_t table_bytes, int32_t n_windows, int32_t n_poses,
+                    const void* consts, int64_t const_bytes, void* poses, float* vec, float* stats, int32_t* verdict, void* stream);
+int tg_clip_slices(const void* src, int64_t src_elems, int32_t elem_bytes, int32_t rows, const void* table, int64_t table_bytes, int32_t n_windows,
+                   int32_t len, void* dst, void* stream);
+int tg_motion_stats_query(int64_t n_rows, int64_t* sizes);
+int tg_motion_stats(const void* skel, int64_t n_rows, int32_t half, void* ws, int64_t ws_bytes, void* out, void* stream);
 
 #ifdef __cplusplus
 }
