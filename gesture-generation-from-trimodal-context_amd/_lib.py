@@ -156,6 +156,8 @@ SIGNATURES = {
     "tg_clip_slices": [P, I64, I32, I32, P, I64, I32, I32, P, P],
     "tg_motion_stats_query": [I64, P],
     "tg_motion_stats": [P, I64, I32, P, I64, P, P],
+    "tg_h36m_normalize": [P, I64, I32, P, P],
+    "tg_h36m_samples": [P, I64, P, I64, I32, I32, I32, P, I64, P, I64, P, U32, U32, F32, F32, F32, P, P, P, P],
 }
 
 ABI_VERSION = 11

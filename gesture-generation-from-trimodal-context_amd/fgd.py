@@ -1,6 +1,9 @@
-"""Frechet Gesture Distance on the HIP autoencoder (model/embedding_space_evaluator.py:15-156) and the autoencoder's
-training step (train_feature_extractor.py:54-97).  Feature extraction runs on the GPU; the 32x32 statistics are fp64
+"""Frechet Gesture Distance on the HIP autoencoder (model/embedding_space_evaluator.py:15-156), the autoencoder's
+training step (train_feature_extractor.py:54-97) and its training loop (:118-194).  Feature extraction runs on the GPU; the 32x32 statistics are fp64
 host maths exactly as in the reference (numpy mean / cov(rowvar=False) / matrix square root)."""
+import os
+import time
+
 import numpy as np
 import torch
 
@@ -165,6 +168,62 @@ def train_iter(args, epoch, target_data, net, optim):
     E.backward(res["tape"], d_recon)
     optim.step()
     return {"loss": float(loss)}
+
+
+def train_autoencoder(args, train_set, val_set, save_dir=None, log=print, generator=None):
+    """scripts/train_feature_extractor.py:118-194 (`main` after the datasets are built) over `h36m.Human36M` datasets: per epoch the
+    validation loss (`evaluate_testset` over val_set.batches(args.batch_size, shuffle=False), drop_last as there), the best-so-far
+    bookkeeping, the checkpoint {'args', 'epoch', 'pose_dim', 'gen_dict'} as <save_dir>/<args.name>_checkpoint_best.bin whenever the validation
+    loss improves (save_dir defaults to args.model_save_path; `EmbeddingSpaceEvaluator(args, path, None, device)` loads it), then one pass of
+    `train_iter` over train_set.batches(args.batch_size, shuffle=True) with the reference's status line five times per epoch.
+    Returns (best (val_loss, epoch), history): history[e] = {'epoch', 'val_loss', 'train_loss' (sample-weighted mean over the epoch),
+    'samples_per_s' (whole epoch, batches built and consumed)}.  Sample videos (:159-161) are not rendered.  `generator`: an already built
+    pose-mode EmbeddingNet to train instead of a fresh one."""
+    from .checkpoint import save_checkpoint
+    from .modules import EmbeddingNet
+    pose_dim = 27                                                          # 9 x 3 (:119)
+    device = train_set.device
+    save_dir = args.model_save_path if save_dir is None else save_dir
+    start = time.time()
+    best_val_loss = (1e+10, 0)                                             # value, epoch
+    batch_size = int(args.batch_size)
+    n_train = train_set.n_batches(batch_size)
+    if n_train < 1 or val_set.n_batches(batch_size) < 1:
+        raise ValueError(f"train_autoencoder: {len(train_set)} training and {len(val_set)} validation samples give no full batch of {batch_size}")
+    print_interval = max(int(n_train / 5), 1)
+    if generator is None:
+        generator = EmbeddingNet(args, pose_dim, args.n_poses, None, None, None, mode="pose").to(device)
+    gen_optimizer = FusedAdam(generator.engine, lr=args.learning_rate, betas=(0.5, 0.999))
+    history = []
+    for epoch in range(args.epochs):
+        val_loss = evaluate_testset(val_set.batches(batch_size, shuffle=False), generator)["loss"]
+        is_best = val_loss < best_val_loss[0]
+        if is_best:
+            log("  *** BEST VALIDATION LOSS: {:.3f}".format(val_loss))
+            best_val_loss = (val_loss, epoch)
+            if save_dir is not None:
+                os.makedirs(save_dir, exist_ok=True)
+                save_checkpoint({"args": args, "epoch": epoch, "pose_dim": pose_dim, "gen_dict": generator.state_dict()},
+                                "{}/{}_checkpoint_best.bin".format(save_dir, args.name))
+        else:
+            log("  best validation loss so far: {:.3f} at EPOCH {}".format(best_val_loss[0], best_val_loss[1]))
+        epoch_start = iter_start_time = time.time()
+        total, count, meter, meter_n = 0.0, 0, 0.0, 0
+        for iter_idx, (target_pose, target_vec) in enumerate(train_set.batches(batch_size, shuffle=True), 0):
+            n = target_vec.size(0)
+            loss = train_iter(args, epoch, target_vec, generator, gen_optimizer)["loss"]
+            total, count, meter, meter_n = total + loss * n, count + n, meter + loss * n, meter_n + n
+            if (iter_idx + 1) % print_interval == 0:
+                elapsed = time.time() - start
+                log("EP {} ({:3d}) | {:>8s}, {:.0f} samples/s | loss: {:.3f}, ".format(
+                    epoch, iter_idx + 1, "{:d}m {:d}s".format(int(elapsed // 60), int(elapsed % 60)), n / max(time.time() - iter_start_time, 1e-9),
+                    meter / meter_n))
+                meter, meter_n = 0.0, 0
+            iter_start_time = time.time()
+        torch.cuda.synchronize(device)
+        history.append({"epoch": epoch, "val_loss": val_loss, "train_loss": total / count,
+                        "samples_per_s": count / max(time.time() - epoch_start, 1e-9)})
+    return best_val_loss, history
 
 
 class AutoencoderTrainer:

@@ -1797,3 +1797,54 @@ def motion_stats(skel, out=None, ws=None):
         raise ValueError("motion_stats: workspace or output too small (motion_stats_query)")
     call("tg_motion_stats", _p(skel), skel.shape[0], int(skel.dtype == torch.float16), _p(ws), ws.numel() * 8, _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------ autoencoder batches from Human3.6M positions (csrc/h36m.hip)
+H36M_MIN_JOINTS = 28
+
+
+def h36m_normalize(positions, out=None):
+    """out (rows, 30) fp32 = every frame of positions (rows, J >= 28, 3) fp32 normalised and frontalised as Human36M.normalize does
+    (data_loader/h36m_loader.py:37-38, :69-90; tg_h36m_normalize)."""
+    _pp_tensor(positions, "positions", (torch.float32,))
+    if positions.dim() != 3 or positions.shape[2] != 3 or positions.shape[1] < H36M_MIN_JOINTS or positions.shape[0] < 1:
+        raise ValueError(f"h36m_normalize: positions must be (rows >= 1, J >= {H36M_MIN_JOINTS}, 3), got {tuple(positions.shape)}")
+    if out is None:
+        out = torch.empty(positions.shape[0], 30, device=positions.device, dtype=torch.float32)
+    _pp_tensor(out, "out", (torch.float32,))
+    if tuple(out.shape) != (positions.shape[0], 30):
+        raise ValueError(f"h36m_normalize: out must be ({positions.shape[0]}, 30), got {tuple(out.shape)}")
+    call("tg_h36m_normalize", _p(positions), positions.shape[0], positions.shape[1], _p(out), _stream())
+    return out
+
+
+def h36m_samples(skel, win_row0, n_poses, frame_stride, mean_dir_vec, poses, vec, flag, noise=None, rng=None):
+    """Windows of n_poses frames, frame_stride rows apart, of skel (rows, 30) fp32 from the rows of win_row0 (W,) int64: poses (W, n_poses, 30)
+    fp32 = joints rebuilt from the unit bone vectors (plus noise), vec (W, n_poses, 27) fp32 = their direction vectors minus mean_dir_vec
+    (27 doubles), flag (W,) int32 = 0, or -1 for a table entry outside skel (tg_h36m_samples; h36m_loader.py:44-64).  noise: (W, n_poses, 30)
+    fp64, the additive values; or rng = (state, noise_site, select_site, p_large, std_large, std_small): drawn in the launch."""
+    _pp_frames(skel, "skel")
+    if skel.dtype != torch.float32:
+        raise ValueError("h36m_samples: skel must be float32")
+    _pp_tensor(win_row0, "win_row0", (torch.int64,)); _pp_tensor(mean_dir_vec, "mean_dir_vec", (torch.float64,))
+    W, n_poses, frame_stride = win_row0.numel(), int(n_poses), int(frame_stride)
+    if W < 1 or n_poses < 1 or frame_stride < 1 or mean_dir_vec.numel() < 27:
+        raise ValueError(f"h36m_samples: {W} windows of {n_poses} frames, stride {frame_stride}, {mean_dir_vec.numel()} mean values (27 needed)")
+    for t, name, dt, shape in ((poses, "poses", torch.float32, (W, n_poses, 30)), (vec, "vec", torch.float32, (W, n_poses, 27)),
+                               (flag, "flag", torch.int32, (W,))):
+        _pp_tensor(t, name, (dt,))
+        if tuple(t.shape) != shape:
+            raise ValueError(f"h36m_samples: {name} must have shape {shape}, got {tuple(t.shape)}")
+    if noise is not None and rng is not None:
+        raise ValueError("h36m_samples: noise and rng are both given")
+    if noise is not None:
+        _pp_tensor(noise, "noise", (torch.float64,))
+        if tuple(noise.shape) != (W, n_poses, 30):
+            raise ValueError(f"h36m_samples: noise must have shape {(W, n_poses, 30)}, got {tuple(noise.shape)}")
+    state, noise_site, select_site, p_large, std_large, std_small = rng if rng is not None else (None, 0, 0, 0.0, 0.0, 0.0)
+    if state is not None:
+        _i64(state, "rng_state")
+    call("tg_h36m_samples", _p(skel), skel.shape[0], _p(win_row0), W * 8, W, n_poses, frame_stride, _p(mean_dir_vec), mean_dir_vec.numel() * 8,
+         _p(noise), noise.numel() * 8 if noise is not None else 0, _p(state), int(noise_site), int(select_site), float(p_large), float(std_large),
+         float(std_small), _p(poses), _p(vec), _p(flag), _stream())
+    return poses, vec, flag

@@ -783,6 +783,40 @@ int tg_clip_slices(const void* src, int64_t src_elems, int32_t elem_bytes, int32
 int tg_motion_stats_query(int64_t n_rows, int64_t* sizes);
 int tg_motion_stats(const void* skel, int64_t n_rows, int32_t half, void* ws, int64_t ws_bytes, void* out, void* stream);
 
+/* ---- autoencoder batches from raw Human3.6M positions (added under ABI 11; data_loader/h36m_loader.py:16-17, :37-42, :44-64, :69-106,
+ * utils/data_utils.py:77-120; csrc/h36m.hip).  The conventions of the block above: actions packed into one device buffer, windows described by a
+ * device-resident int64 table, one call per stage and batch, fp64 per-thread arithmetic without fused multiply-adds, no atomics, bitwise repeatable;
+ * every table entry is checked against the extents given here, an entry that points outside is skipped and flagged.
+ *
+ * tg_h36m_normalize -- Human36M.normalize per frame.  positions: (rows, n_joints, 3) fp32, n_joints >= 28 (32 in data_3d_h36m.npz); out: (rows, 30)
+ * fp32, the packed skeleton format of the block above, row r from frame r.  Per frame: the twelve target_joints {1, 6, 12, 13, 14, 15, 17, 18, 19, 25,
+ * 26, 27} are gathered; gathered joint 2 is subtracted from all twelve in fp32; (x, y, z) becomes (x, -z, y) (:73-75); with hip = joint 1 - joint 0
+ * (fp32), angle = pi - atan2(hip_z, hip_x) in fp64; deg = angle * (180 / pi); 0 < deg < 180 keeps the angle, 180 < deg < 360 subtracts
+ * 360 * (pi / 180), anything else (exactly 0, 180 or 360 degrees) is left alone (:81-84, strict inequalities); with a = cos(angle / 2) and
+ * c = -sin(angle / 2) the matrix of :93-106 about (0, 1, 0) is {{aa - cc, 0, -2 ac}, {0, aa + cc, 0}, {2 ac, 0, aa - cc}}; every joint becomes the
+ * row vector joint @ matrix, the fp32 operands converted to fp64, the three products added left to right, the sum rounded once to fp32; joints 0 and 1
+ * are dropped.
+ *
+ * tg_h36m_samples -- Human36M.__getitem__ for n_windows windows.  Window w is rows win_row0[w] + k * frame_stride, k < n_poses, of skel (skel_rows, 30)
+ * (the reference: n_poses 34, frame_stride 2).  Per frame, in fp64: the nine bone differences of dir_vec_pairs, each taken in fp32 (numpy subtracts
+ * the fp32 arrays); unit vectors d / sqrt(dx dx + dy dy + dz dz), a zero-length bone gives zeros; the joints rebuilt from the bone lengths {0.26, 0.18,
+ * 0.14, 0.22, 0.36, 0.33, 0.22, 0.36, 0.33} with the root at the origin (parent + length * unit, multiply then add); the additive noise on all 30
+ * coordinates, if any; the nine unit vectors again, now from fp64 differences; minus mean_dir_vec (27 doubles in device memory, mean_bytes >= 216).
+ * Outputs: poses (n_windows, n_poses, 30) fp32 = the rebuilt (noisy) joints, vec (n_windows, n_poses, 27) fp32, each rounded once;
+ * flag (n_windows) int32 = 0, or -1 where the window does not lie inside skel: nothing is read, poses and vec of that window are not written.
+ * Noise: (a) noise == NULL and rng_state == NULL: none.  (b) noise: (n_windows, n_poses, 30) doubles (noise_bytes >= that), the final additive
+ * values.  (c) rng_state (device uint64[2], see "randomness" above; never together with noise): drawn in the same launch, nothing stored -- the value
+ * for window slot i (its index in win_row0) and coordinate e < n_poses * 30 is (double)z * (double)std_i, z being the float that
+ * tg_normal(out, n, rng_state, noise_site) would write at index i * n_poses * 30 + e, and std_i = std_large where
+ * tg_dropout_mask(mask, n, p_large, rng_state, select_site) would write 0 at index i (probability p_large), std_small otherwise.  Both draws are pure
+ * functions of (state, site, index): they do not depend on the length n of the call they are compared with (any n > index, vectorised or not).
+ * 0 <= p_large < 1 as for tg_dropout_mask.  The reference's values (:50-56): p_large 0.2, std_large sqrt(0.002), std_small sqrt(0.0001). */
+int tg_h36m_normalize(const float* positions, int64_t rows, int32_t n_joints, float* out, void* stream);
+int tg_h36m_samples(const float* skel, int64_t skel_rows, const void* win_row0, int64_t table_bytes, int32_t n_windows, int32_t n_poses,
+                    int32_t frame_stride, const void* mean_dir_vec, int64_t mean_bytes, const void* noise, int64_t noise_bytes, const uint64_t* rng_state,
+                    uint32_t noise_site, uint32_t select_site, float p_large, float std_large, float std_small, float* poses, float* vec, int32_t* flag,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
