@@ -33,6 +33,7 @@ def main():
     ap.add_argument("--n-words", type=int, default=2000)
     ap.add_argument("--n-speakers", type=int, default=200)
     ap.add_argument("--out", default="")
+    ap.add_argument("--device-fgd", action="store_true", help="FGD statistics on the device (fgd.DeviceEmbeddingSpaceEvaluator): no host read per validation batch")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     args = importlib.import_module(hip.__name__ + ".config").load_config("multimodal_context", name="synthetic", pose_dim=27)
@@ -49,7 +50,7 @@ def main():
     generator, discriminator, _ = ckpt.init_model(args, lang, spk, args.pose_dim, dev)              # train.py:36-62
     trainer = hip.GanTrainer(generator, discriminator, args)
     ae = hip.EmbeddingNet(args, args.pose_dim, args.n_poses, None, None, None, mode="pose").to(dev)  # stands in for the trained FGD net
-    evaluator = fgd.EmbeddingSpaceEvaluator.from_net(ae, args.n_pre_poses)
+    evaluator = (fgd.DeviceEmbeddingSpaceEvaluator if a.device_fgd else fgd.EmbeddingSpaceEvaluator).from_net(ae, args.n_pre_poses)
     args.mean_dir_vec = np.zeros(27, dtype=np.float32)
     val_loader = torch.utils.data.DataLoader(val_set, batch_size=a.batch, collate_fn=data.collate_reference)
 

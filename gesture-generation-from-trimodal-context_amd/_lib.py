@@ -158,6 +158,11 @@ SIGNATURES = {
     "tg_motion_stats": [P, I64, I32, P, I64, P, P],
     "tg_h36m_normalize": [P, I64, I32, P, P],
     "tg_h36m_samples": [P, I64, P, I64, I32, I32, I32, P, I64, P, I64, P, U32, U32, F32, F32, F32, P, P, P, P],
+    "tg_fgd_state_doubles": [I32, P],
+    "tg_fgd_reset": [P, I32, P],
+    "tg_fgd_push": [P, P, P, I32, I32, P, P, P],
+    "tg_fgd_scores": [P, I32, P, P],
+    "tg_fgd_from_stats": [P, P, P, P, I32, P, P],
 }
 
 ABI_VERSION = 11

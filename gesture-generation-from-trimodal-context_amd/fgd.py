@@ -1,6 +1,8 @@
 """Frechet Gesture Distance on the HIP autoencoder (model/embedding_space_evaluator.py:15-156), the autoencoder's
 training step (train_feature_extractor.py:54-97) and its training loop (:118-194).  Feature extraction runs on the GPU; the 32x32 statistics are fp64
-host maths exactly as in the reference (numpy mean / cov(rowvar=False) / matrix square root)."""
+host maths exactly as in the reference (numpy mean / cov(rowvar=False) / matrix square root) in EmbeddingSpaceEvaluator / fgd_scores /
+frechet_distance, and fp64 device maths (streaming moments, Jacobi finish: csrc/fgd.hip) in DeviceEmbeddingSpaceEvaluator / fgd_scores_device /
+frechet_distance_device."""
 import os
 import time
 
@@ -104,6 +106,88 @@ class EmbeddingSpaceEvaluator:
 
     def get_scores(self):
         return fgd_scores(np.vstack(self.generated_feat_list), np.vstack(self.real_feat_list))
+
+
+class DeviceEmbeddingSpaceEvaluator(EmbeddingSpaceEvaluator):
+    """EmbeddingSpaceEvaluator with the statistics on the device (csrc/fgd.hip): push_samples adds the batch to fp64 streaming moments with one
+    tg_fgd_push and reads nothing back, get_scores is one finish launch and one host read.  Storage does not grow with the validation set.  Same
+    constructor, from_net and from_checkpoint.  The score is the symmetric formulation sum sqrt(eig(S1^1/2 S2 S1^1/2)) in fp64 with fp64 means
+    (DESIGN.md): it never goes complex, so neither the eps-offset retry nor the 1e10 sentinel of fgd_scores exists here."""
+
+    FEAT_DIM = 32
+
+    def reset(self):
+        dev = next(self.net.parameters()).device
+        if getattr(self, "_state", None) is None or self._state.device != dev:
+            self._state = ops.fgd_new_state(self.FEAT_DIM, dev)
+            self._out = torch.empty(ops.FGD_OUT_DOUBLES, device=dev, dtype=torch.float64)
+        ops.fgd_reset(self._state, self.FEAT_DIM)
+        self._pushes, self._rows, self._last = 0, 0, None
+
+    def get_no_of_samples(self):
+        """Pushes so far, as EmbeddingSpaceEvaluator counts them (the length of its feature list); kept on the host, nothing is read back."""
+        return self._pushes
+
+    def push_samples(self, context_text, context_spec, generated_poses, real_poses):
+        eng = self.net.engine
+        with torch.no_grad():
+            r = eng.forward(real_poses.float(), training=False)
+            g = eng.forward(generated_poses.float(), training=False)
+            err = torch.empty(2, device=real_poses.device)
+            ops.l1_mean(real_poses.float().contiguous(), r["recon"], err[0:1])
+            ops.l1_mean(generated_poses.float().contiguous(), g["recon"], err[1:2])
+            ops.fgd_push(self._state, r["feat"], g["feat"], err[0:1], err[1:2])
+        self._pushes, self._rows, self._last = self._pushes + 1, self._rows + int(real_poses.shape[0]), None
+
+    def _finish(self):
+        if self._rows < 2:
+            raise ValueError(f"DeviceEmbeddingSpaceEvaluator: {self._rows} rows pushed, a covariance needs at least two")
+        if self._last is None:
+            ops.fgd_scores(self._state, self.FEAT_DIM, self._out)
+            self._last = dict(zip(ops.FGD_OUT, self._out.tolist()))          # the one host read
+            if int(self._last["status"]) & ops.FGD_STATUS_SWEEP_CAP:
+                raise RuntimeError("DeviceEmbeddingSpaceEvaluator: the Jacobi solve reached its sweep cap (non-finite features?)")
+        return self._last
+
+    def get_scores(self):
+        s = self._finish()
+        return s["fgd"], s["feat_dist"]
+
+    @property
+    def recon_err_diff(self):
+        """Mean over pushes of (reconstruction L1 of the generated batch - that of the real batch); the host evaluator keeps the list."""
+        return self._finish()["recon_err_diff"]
+
+
+def _fgd_result(out):
+    s = dict(zip(ops.FGD_OUT, out.tolist()))
+    if int(s["status"]) & ops.FGD_STATUS_FEW_ROWS:
+        raise ValueError("fgd: fewer than two rows per set")
+    if int(s["status"]) & ops.FGD_STATUS_SWEEP_CAP:
+        raise RuntimeError("fgd: the Jacobi solve reached its sweep cap (non-finite input?)")
+    return s
+
+
+def fgd_scores_device(generated_feats, real_feats, details=False):
+    """fgd_scores for device tensors (N, D <= 32) of any row count: (FGD, mean L1 distance of paired latents) from one push and one finish;
+    details=True returns the whole named output (ops.FGD_OUT) instead."""
+    g, r = generated_feats.float().contiguous(), real_feats.float().contiguous()
+    if r.dim() != 2 or g.shape != r.shape or not 1 <= r.shape[1] <= ops.FGD_MAX_DIM or g.device != r.device:
+        raise ValueError(f"fgd_scores_device: two (N, D <= {ops.FGD_MAX_DIM}) tensors of one shape on one device expected, got "
+                         f"{tuple(g.shape)} on {g.device} and {tuple(r.shape)} on {r.device}")
+    state = ops.fgd_new_state(r.shape[1], r.device)
+    ops.fgd_push(state, r, g)
+    s = _fgd_result(ops.fgd_scores(state, r.shape[1]))
+    return s if details else (s["fgd"], s["feat_dist"])
+
+
+def frechet_distance_device(mu1, sigma1, mu2, sigma2, details=False):
+    """frechet_distance for moments on the device (converted to fp64; host arrays are copied over): the symmetric finish of tg_fgd_from_stats."""
+    dev = next((t.device for t in (mu1, sigma1, mu2, sigma2) if isinstance(t, torch.Tensor) and t.is_cuda), torch.device("cuda"))
+    m1, s1, m2, s2 = (torch.as_tensor(np.asarray(t) if not isinstance(t, torch.Tensor) else t).to(device=dev, dtype=torch.float64).contiguous()
+                      for t in (mu1, sigma1, mu2, sigma2))
+    s = _fgd_result(ops.fgd_from_stats(m1.reshape(-1), s1, m2.reshape(-1), s2))
+    return s if details else s["fgd"]
 
 
 def eval_embed(in_text, in_audio, pre_poses, target_poses, net, mode=None):

@@ -1848,3 +1848,84 @@ def h36m_samples(skel, win_row0, n_poses, frame_stride, mean_dir_vec, poses, vec
          _p(noise), noise.numel() * 8 if noise is not None else 0, _p(state), int(noise_site), int(select_site), float(p_large), float(std_large),
          float(std_small), _p(poses), _p(vec), _p(flag), _stream())
     return poses, vec, flag
+
+
+# ------------------------------------------------------------------------------------------------ Frechet gesture distance on the device (csrc/fgd.hip)
+FGD_MAX_DIM = 32
+FGD_OUT_DOUBLES = 16                                     # TG_FGD_OUT_DOUBLES; slots 0 .. 10 are used
+FGD_OUT = ("fgd", "feat_dist", "n", "recon_err_diff", "tr1", "tr2", "d2", "sum_sqrt", "sweeps1", "sweeps2", "status")
+FGD_STATUS_SWEEP_CAP, FGD_STATUS_FEW_ROWS = 1, 2
+
+
+def fgd_state_doubles(D):
+    """Doubles of one evaluator's state buffer for feature width D (tg_fgd_state_doubles)."""
+    n = C.c_int64(0)
+    call("tg_fgd_state_doubles", int(D), C.cast(C.pointer(n), C.c_void_p))
+    return int(n.value)
+
+
+def _fgd_state(state, D):
+    _pp_tensor(state, "state", (torch.float64,))
+    if not 1 <= int(D) <= FGD_MAX_DIM:
+        raise ValueError(f"fgd: feature width D = {D} outside 1 .. {FGD_MAX_DIM}")
+    if state.numel() < fgd_state_doubles(D):
+        raise ValueError(f"fgd: state of {state.numel()} doubles, {fgd_state_doubles(D)} needed for D = {D}")
+    return state
+
+
+def fgd_new_state(D, device):
+    """A zeroed state buffer for feature width D (the workspace too, so that whole buffers of identical runs compare equal)."""
+    return fgd_reset(torch.zeros(fgd_state_doubles(D), device=device, dtype=torch.float64), D)
+
+
+def fgd_reset(state, D):
+    call("tg_fgd_reset", _p(_fgd_state(state, D)), int(D), _stream()); return state
+
+
+def fgd_push(state, real_feat, gen_feat, recon_err_real=None, recon_err_fake=None):
+    """Adds the paired rows of real_feat / gen_feat (B, D) fp32 to the streaming moments in `state`; recon_err_*: device fp32 scalars or None
+    (tg_fgd_push).  No host read."""
+    _pp_tensor(real_feat, "real_feat", (torch.float32,)); _pp_tensor(gen_feat, "gen_feat", (torch.float32,))
+    if real_feat.dim() != 2 or real_feat.shape != gen_feat.shape:
+        raise ValueError(f"fgd_push: features must be two (B, D) tensors of one shape, got {tuple(real_feat.shape)} and {tuple(gen_feat.shape)}")
+    B, D = real_feat.shape
+    if B < 1 or not 1 <= D <= FGD_MAX_DIM:
+        raise ValueError(f"fgd_push: features must be (B >= 1, 1 <= D <= {FGD_MAX_DIM}), got {tuple(real_feat.shape)}")
+    for e in (recon_err_real, recon_err_fake):
+        if e is not None and (_pp_tensor(e, "recon_err", (torch.float32,)).numel() != 1):
+            raise ValueError("fgd_push: a reconstruction error must be one float32 element")
+    _fgd_state(state, D)
+    for t, name in ((real_feat, "real_feat"), (gen_feat, "gen_feat"), (recon_err_real, "recon_err_real"), (recon_err_fake, "recon_err_fake")):
+        if t is not None and t.device != state.device:
+            raise ValueError(f"fgd_push: {name} is on {t.device}, the state on {state.device}")
+    call("tg_fgd_push", _p(_fgd_state(state, D)), _p(real_feat), _p(gen_feat), B, D, _p(recon_err_real), _p(recon_err_fake), _stream())
+    return state
+
+
+def fgd_scores(state, D, out=None):
+    """out (16,) fp64 on the device, slots named by FGD_OUT (tg_fgd_scores): one launch, no host read."""
+    if out is None:
+        out = torch.empty(FGD_OUT_DOUBLES, device=state.device, dtype=torch.float64)
+    _pp_tensor(out, "out", (torch.float64,))
+    if out.numel() < FGD_OUT_DOUBLES:
+        raise ValueError(f"fgd_scores: out needs {FGD_OUT_DOUBLES} doubles")
+    call("tg_fgd_scores", _p(_fgd_state(state, D)), int(D), _p(out), _stream())
+    return out
+
+
+def fgd_from_stats(mu1, sigma1, mu2, sigma2, out=None):
+    """The same finish for given fp64 device moments mu (D,), sigma (D, D) (tg_fgd_from_stats)."""
+    for t, name in ((mu1, "mu1"), (sigma1, "sigma1"), (mu2, "mu2"), (sigma2, "sigma2")):
+        _pp_tensor(t, name, (torch.float64,))
+    D = mu1.numel()
+    if not 1 <= D <= FGD_MAX_DIM or len({t.device for t in (mu1, sigma1, mu2, sigma2)}) != 1:
+        raise ValueError(f"fgd_from_stats: D = {D} must be 1 .. {FGD_MAX_DIM} and all moments on one device")
+    if mu2.numel() != D or tuple(sigma1.shape) != (D, D) or tuple(sigma2.shape) != (D, D):
+        raise ValueError(f"fgd_from_stats: mu (D,) and sigma (D, D) expected, got {tuple(mu1.shape)} {tuple(sigma1.shape)} {tuple(mu2.shape)} {tuple(sigma2.shape)}")
+    if out is None:
+        out = torch.empty(FGD_OUT_DOUBLES, device=mu1.device, dtype=torch.float64)
+    _pp_tensor(out, "out", (torch.float64,))
+    if out.numel() < FGD_OUT_DOUBLES:
+        raise ValueError(f"fgd_from_stats: out needs {FGD_OUT_DOUBLES} doubles")
+    call("tg_fgd_from_stats", _p(mu1), _p(sigma1), _p(mu2), _p(sigma2), D, _p(out), _stream())
+    return out

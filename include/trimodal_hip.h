@@ -817,6 +817,38 @@ int tg_h36m_samples(const float* skel, int64_t skel_rows, const void* win_row0, 
                     uint32_t noise_site, uint32_t select_site, float p_large, float std_large, float std_small, float* poses, float* vec, int32_t* flag,
                     void* stream);
 
+/* ---- Frechet gesture distance on the device (added under ABI 11 -- new symbols only, nothing existing changes, so the version stays; model/embedding_space_evaluator.py:74-156; csrc/fgd.hip).  The score is evaluated
+ * in the symmetric formulation Tr sqrt(S1 S2) = sum sqrt(eig(S1^1/2 S2 S1^1/2)) in fp64: always real and finite, so the reference's eps-offset retry
+ * (:139-144) and its imaginary-component branch (:147-151) cannot occur; the means are fp64 where the reference's are fp32.
+ *
+ * State: one caller-owned buffer of tg_fgd_state_doubles(D) doubles per evaluator (1 <= D <= 32; the size comes back through *doubles, the return
+ * value is the status like everywhere else).  Layout: [0] first-push flag, [1] pushes, [2] sum over pushes of (recon_err_fake - recon_err_real),
+ * [3] sum over rows of sum_j |real - generated|, [4, 4 + D) the pivot K = the mean of the first pushed real batch (formed on the device inside that
+ * push); then for the real set and for the generated set {n, sum (x - K) [D], sum (x - K)(x - K)^T [D][D]}; the rest is the push workspace.  The
+ * pivot keeps features far from zero from cancelling in S - s s^T / n.  States whose pivots agree are additive.
+ *
+ * tg_fgd_reset -- zeroes the state (not the workspace).
+ * tg_fgd_push  -- real_feat, gen_feat: (B, D) fp32 row-major, paired rows; recon_err_real / recon_err_fake: device fp32 scalars, either may be NULL
+ *   (that term is then skipped).  fp64 accumulation; rows are spread over up to 16 workgroups of 256 rows each (more rows: they stride), partial
+ *   sums go to the workspace and a second launch adds them to the state in workgroup order.  No floating-point atomics: two identical runs leave
+ *   bit-identical states.  The inputs must not overlap the state.
+ * tg_fgd_scores -- one workgroup.  mu and cov (ddof = 1) of both sets from the shifted sums, symmetrised; cyclic Jacobi (round-robin parallel
+ *   ordering: the D / 2 disjoint rotations of a step together) on S1 = the generated set's covariance, R = S1^1/2 with negative eigenvalues clamped
+ *   to 0; M = R S2 R symmetrised, Jacobi again for its eigenvalues l.  A solve stops when the off-diagonal Frobenius norm is <= 2^-52 ||A||_F, or
+ *   after 30 sweeps.  out (TG_FGD_OUT_DOUBLES doubles, 11 used): [0] fgd = ||mu1 - mu2||^2 + tr S1 + tr S2 - 2 sum sqrt(max(l, 0)),
+ *   [1] feat_dist = mean over rows of sum_j |real - generated|, [2] n (rows per set), [3] mean over pushes of (recon_err_fake - recon_err_real),
+ *   [4] tr S1, [5] tr S2, [6] ||mu1 - mu2||^2, [7] sum sqrt l, [8] / [9] the sweeps of the two solves, [10] status: bit 0 a solve reached the sweep
+ *   cap, bit 1 n < 2 (then [0] and [4 .. 9] are NaN).
+ * tg_fgd_from_stats -- the same finish for given fp64 moments (mu [D], S [D][D] row-major, device memory): frechet_distance on the device; out[1],
+ *   out[2], out[3] are 0. */
+#define TG_FGD_OUT_DOUBLES 16
+int tg_fgd_state_doubles(int32_t D, int64_t* doubles);
+int tg_fgd_reset(void* state, int32_t D, void* stream);
+int tg_fgd_push(void* state, const float* real_feat, const float* gen_feat, int32_t B, int32_t D, const float* recon_err_real,
+                const float* recon_err_fake, void* stream);
+int tg_fgd_scores(const void* state, int32_t D, double* out, void* stream);
+int tg_fgd_from_stats(const double* mu1, const double* S1, const double* mu2, const double* S2, int32_t D, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
