@@ -12,7 +12,8 @@ from .vocab import Vocab  # noqa: F401
 from .melspec import extract_melspectrogram  # noqa: F401
 from .preprocess import DataPreprocessor, calculate_data_mean, resample_pose_seq  # noqa: F401
 from .h36m import Human36M  # noqa: F401
-from . import checkpoint, config, data, ddp, eval_metrics, fgd, h36m, layers, melspec, ops, preprocess, synthesize  # noqa: F401,E402  (hip.fgd, hip.config, ... as INTEGRATION.md uses them)
+from .rnn import GRU, EncoderRNN  # noqa: F401
+from . import checkpoint, config, data, ddp, eval_metrics, fgd, h36m, layers, melspec, ops, preprocess, rnn, synthesize  # noqa: F401,E402  (hip.fgd, hip.config, ... as INTEGRATION.md uses them)
 
 __all__ = ["PoseGenerator", "ConvDiscriminator", "EmbeddingNet", "FusedAdam", "GanTrainer", "GraphedGanStep", "StepLosses",
-           "Vocab", "extract_melspectrogram", "DataPreprocessor", "calculate_data_mean", "resample_pose_seq", "Human36M"]
+           "Vocab", "extract_melspectrogram", "DataPreprocessor", "calculate_data_mean", "resample_pose_seq", "Human36M", "GRU", "EncoderRNN"]

@@ -163,6 +163,9 @@ SIGNATURES = {
     "tg_fgd_push": [P, P, P, I32, I32, P, P, P],
     "tg_fgd_scores": [P, I32, P, P],
     "tg_fgd_from_stats": [P, P, P, P, I32, P, P],
+    "tg_gru_seq_supported": [I32, I32, I32, I32, P],
+    "tg_gru_seq_forward": [P] * 11 + [I32, I32, I32, I32, P],
+    "tg_gru_seq_backward": [P] * 10 + [I32, I32, I32, I32, P],
 }
 
 ABI_VERSION = 11

@@ -862,3 +862,93 @@ def gru_stack_bwd(dy, tape, P, G, prefix, n_layers, *, b0=0, nb=None, need_dx=Tr
     if fork is None:
         fk.join()
     return dy
+
+
+# ----------------------------------------------------------------------------------------------- general GRU stack (csrc/gru_seq.hip)
+class GRUSeqTape:
+    __slots__ = ("x", "save", "masks", "lengths", "B", "T", "H", "D")
+
+
+def _gru_name(prefix, name):
+    return f"{prefix}.{name}" if prefix else name
+
+
+def gru_seq_stack_fwd(x, P, prefix, n_layers, H, D, *, lengths=None, h0=None, p_drop=0.0, training=False, rng=None, save=False, inject=None,
+                      tag="g"):
+    """torch.nn.GRU(batch_first=True) over n_layers layers of D directions.  x: (B, T, Kin) contiguous, finite at padded positions; P: name ->
+    parameter tensor (weight_ih_l{k}, weight_hh_l{k}, bias_ih_l{k}, bias_hh_l{k}, with `_reverse` at D = 2) under `prefix`; lengths: per-row
+    lengths as ops.gru_seq_forward takes them; h0: (n_layers * D, B, H) or None.  Inter-layer dropout as in gru_stack_fwd: masks injectable
+    as f"{tag}.gru.drop{l}", none after the last layer.
+    Returns (y_last (B, T, D*H), h_n (n_layers * D, B, H) layer-major / direction-minor, tape or None, flag word of device lengths or None)."""
+    B, T, _ = x.shape
+    sfxs = ("", "_reverse")[:D]
+    ldev, flag = ops.gru_seq_lengths(lengths, B, T, x.device)      # validated / uploaded once for all layers
+    tape = GRUSeqTape()
+    tape.x, tape.save, tape.masks = [], [], []
+    tape.lengths, tape.B, tape.T, tape.H, tape.D = ldev, B, T, H, D
+    h_n = empty(n_layers * D, B, H, like=x)
+    if h0 is not None:
+        assert tuple(h0.shape) == (n_layers * D, B, H) and h0.is_contiguous()
+    cur = x
+    for l in range(n_layers):
+        Kin = cur.shape[2]
+        gi = empty(D, B, T, 3 * H, like=x)
+        a_win = Win.plain(cur.view(B * T, Kin))
+        ops.gemm_nt_group([dict(A=a_win, W=P[_gru_name(prefix, f"weight_ih_l{l}{s}")], bias=P[_gru_name(prefix, f"bias_ih_l{l}{s}")],
+                                out=gi[d].view(B * T, 3 * H)) for d, s in enumerate(sfxs)])
+        y = empty(B, T, D * H, like=x)
+        sv = empty(D, B, T, 5 * H, like=x) if save else None
+        whh = tuple(P[_gru_name(prefix, f"weight_hh_l{l}{s}")] for s in sfxs)
+        bhh = tuple(P[_gru_name(prefix, f"bias_hh_l{l}{s}")] for s in sfxs)
+        ops.gru_seq_forward(gi, whh, bhh, y, h_n[l * D:(l + 1) * D], sv, lengths=ldev, h0=None if h0 is None else h0[l * D:(l + 1) * D], flag=flag)
+        tape.x.append(cur); tape.save.append(sv)
+        mask = None
+        name = f"{tag}.gru.drop{l}"
+        if training and l < n_layers - 1:
+            if inject is not None and name in inject:
+                mask = inject[name].contiguous()
+                cur = ops.mul(y, mask, torch.empty_like(y))
+            elif p_drop > 0:
+                cur, mask = ops.dropout_apply(y, p_drop, rng.state, rng.site(name))
+            else:
+                cur = y
+        else:
+            cur = y
+        tape.masks.append(mask)
+    return cur, h_n, (tape if save else None), flag
+
+
+def gru_seq_stack_bwd(dy, dh_n, tape, P, G, prefix, n_layers, *, need_dx=True, need_dh0=False):
+    """Backward of gru_seq_stack_fwd.  dy: (B, T, D*H) gradient of the last layer's output or None; dh_n: (n_layers * D, B, H) gradient of h_n or
+    None.  ACCUMULATES the parameter gradients into G[name] and returns (dx (B, T, Kin0) or None, dh0 (n_layers * D, B, H) or None).  dgi / dgh
+    come out of the recurrence as exact zeros at padded positions, so the weight, bias and input gradients below need no mask."""
+    B, T, H, D = tape.B, tape.T, tape.H, tape.D
+    sfxs = ("", "_reverse")[:D]
+    if dy is None:
+        dy = ops.zeros(B, T, D * H, device=tape.x[0].device)
+    dh0 = empty(n_layers * D, B, H, like=dy) if need_dh0 else None
+    dx = None
+    for l in range(n_layers - 1, -1, -1):
+        if tape.masks[l] is not None:
+            dy = ops.mul(dy.contiguous(), tape.masks[l], torch.empty_like(dy))
+        wt = tuple(transpose2d(P[_gru_name(prefix, f"weight_hh_l{l}{s}")]) for s in sfxs)
+        dgi, dgh = empty(D, B, T, 3 * H, like=dy), empty(D, B, T, 3 * H, like=dy)
+        ops.gru_seq_backward(dy.contiguous(), tape.save[l], wt, dgi, dgh, lengths=tape.lengths,
+                             dh_n=None if dh_n is None else dh_n[l * D:(l + 1) * D], dh0=None if dh0 is None else dh0[l * D:(l + 1) * D])
+        x_l = tape.x[l]
+        Kin = x_l.shape[2]
+        probs = []
+        for d, s in enumerate(sfxs):
+            probs.append(dict(dY=dgi[d].view(B * T, 3 * H), A=Win.plain(x_l.view(B * T, Kin)), dW=G[_gru_name(prefix, f"weight_ih_l{l}{s}")],
+                              dbias=G[_gru_name(prefix, f"bias_ih_l{l}{s}")]))
+            # h_prev of every step is the fifth block of the tape (h0 at a row's first step, zeros at padded positions)
+            probs.append(dict(dY=dgh[d].view(B * T, 3 * H), A=Win.plain(tape.save[l][d].view(B * T, 5 * H)[:, 4 * H:]),
+                              dW=G[_gru_name(prefix, f"weight_hh_l{l}{s}")], dbias=G[_gru_name(prefix, f"bias_hh_l{l}{s}")]))
+        ops.gemm_tn_group(probs)
+        dx = None
+        if need_dx or l > 0:
+            dx = empty(B * T, Kin, like=dy)
+            for d, s in enumerate(sfxs):
+                ops.gemm_nt(Win.plain(dgi[d].view(B * T, 3 * H)), transpose2d(P[_gru_name(prefix, f"weight_ih_l{l}{s}")]), None, dx, accumulate=(d == 1))
+            dy = dx.view(B, T, Kin)
+    return (dx.view(B, T, -1) if dx is not None else None), dh0

@@ -849,6 +849,94 @@ def gru_backward(dy, y, save, w_hh_t, dgi, dgh, dh_scratch, *, b0=0, nb=None, dy
          _p(dgi), _p(dgh), nb * T * 3 * H, _p(dh_scratch), nb, T, H, _stream())
 
 
+# ------------------------------------------------------------------------------------------------- general GRU recurrence (csrc/gru_seq.hip)
+GRU_SEQ_ENVELOPE = "D in {1, 2}, B >= 1, T >= 1, H % 4 == 0, 8 <= H <= 320"
+
+
+def gru_seq_supported(B, T, H, D):
+    """True when tg_gru_seq_forward / tg_gru_seq_backward take the shape (GRU_SEQ_ENVELOPE)."""
+    if min(int(B), int(T), int(H), int(D)) < 1:
+        return False
+    out = C.c_int32(0)
+    call("tg_gru_seq_supported", int(B), int(T), int(H), int(D), C.cast(C.byref(out), C.c_void_p))
+    return bool(out.value)
+
+
+def gru_seq_lengths(lengths, B, T, device, flag=None, want_flag=True):
+    """(device int64 [B] or None, flag or None).  A list or a CPU tensor is validated here (ValueError) and uploaded: no flag is needed.  A
+    device tensor is passed through with a zeroed int32 flag word that the kernel sets for an entry outside [1, T] (ops.gru_seq_check)."""
+    if lengths is None:
+        return None, None
+    if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+        if lengths.dtype != torch.int64 or not lengths.is_contiguous() or lengths.numel() != B:
+            raise ValueError(f"gru_seq: device lengths must be a contiguous int64 tensor of {B} entries")
+        if flag is not None and not (flag.is_cuda and flag.dtype == torch.int32 and flag.numel() >= 1):
+            raise TypeError("gru_seq: flag must be a CUDA int32 tensor")
+        return lengths, (flag if (flag is not None or not want_flag) else zeros(1, device=lengths.device, dtype=torch.int32))
+    vals = [int(v) for v in (lengths.tolist() if isinstance(lengths, torch.Tensor) else lengths)]
+    if len(vals) != B:
+        raise ValueError(f"gru_seq: {len(vals)} lengths for a batch of {B} rows")
+    bad = [(i, v) for i, v in enumerate(vals) if not 1 <= v <= T]
+    if bad:
+        raise ValueError(f"gru_seq: lengths must lie in [1, T = {T}]; (row, length) {bad[:4]}")
+    return torch.tensor(vals, dtype=torch.int64).to(device), None
+
+
+def gru_seq_check(flag):
+    """Raise if a gru_seq launch that was given this flag word met a device length outside [1, T] (synchronises); clears the word."""
+    if flag is not None and int(flag.item()) != 0:
+        zero_(flag)
+        raise RuntimeError("gru_seq: a device lengths entry was outside [1, T]; its rows were skipped (y = 0, h_n = h0)")
+
+
+def _gru_seq_dims(gi, w, b):
+    _flat(gi, "gi")
+    D, B, T, H3 = gi.shape
+    H = H3 // 3
+    assert H3 == 3 * H and len(w) == D and (b is None or len(b) == D)
+    if not gru_seq_supported(B, T, H, D):
+        raise ValueError(f"gru_seq: (B, T, H, D) = {(B, T, H, D)} is outside the kernel envelope {GRU_SEQ_ENVELOPE}")
+    return D, B, T, H
+
+
+def gru_seq_forward(gi, w_hh, b_hh, y, h_n, save, lengths=None, h0=None, flag=None):
+    """nn.GRU recurrence of one layer.  gi: [D, B, T, 3H] contiguous (D = 1 or 2); w_hh / b_hh: one tensor per direction; y: [B, T, D*H];
+    h_n: [D, B, H]; save: [D, B, T, 5H] (r, z, n, W_hn h + b_hn, h_prev) or None; lengths: list / CPU tensor (validated here) or a device int64
+    tensor (checked by the kernel); h0: [D, B, H] or None (zeros); flag: the int32 word a device `lengths` reports into (a zeroed one is made
+    when it is not given).  Returns that flag word (ops.gru_seq_check), None for host lengths."""
+    D, B, T, H = _gru_seq_dims(gi, w_hh, b_hh)
+    _flat(y, "y"); _flat(h_n, "h_n")
+    assert tuple(y.shape) == (B, T, D * H) and tuple(h_n.shape) == (D, B, H)
+    for w, b in zip(w_hh, b_hh):
+        _flat(w, "w_hh"); _flat(b, "b_hh"); assert tuple(w.shape) == (3 * H, H) and b.numel() == 3 * H
+    if save is not None:
+        _flat(save, "save"); assert tuple(save.shape) == (D, B, T, 5 * H)
+    if h0 is not None:
+        _flat(h0, "h0"); assert tuple(h0.shape) == (D, B, H)
+    ldev, flag = gru_seq_lengths(lengths, B, T, gi.device, flag)
+    call("tg_gru_seq_forward", _p(gi), _p(w_hh[0]), _p(w_hh[-1]), _p(b_hh[0]), _p(b_hh[-1]), _p(h0), _p(ldev), _p(y), _p(h_n), _p(save), _p(flag),
+         B, T, H, D, _stream())
+    return flag
+
+
+def gru_seq_backward(dy, save, w_hh_t, dgi, dgh, lengths=None, dh_n=None, dh0=None):
+    """Backward through time of gru_seq_forward.  dy: [B, T, D*H]; save: the forward's tape [D, B, T, 5H]; w_hh_t: per direction [H, 3H];
+    dgi / dgh: [D, B, T, 3H] (exact zeros at t >= length); lengths as in the forward; dh_n: [D, B, H] or None; dh0: [D, B, H] or None (not
+    wanted)."""
+    D, B, T, H = _gru_seq_dims(dgi, w_hh_t, None)
+    _flat(dy, "dy"); _flat(save, "save"); _flat(dgh, "dgh")
+    assert tuple(dy.shape) == (B, T, D * H) and tuple(save.shape) == (D, B, T, 5 * H) and tuple(dgh.shape) == tuple(dgi.shape)
+    for w in w_hh_t:
+        _flat(w, "w_hh_t"); assert tuple(w.shape) == (H, 3 * H)
+    for t_, name in ((dh_n, "dh_n"), (dh0, "dh0")):
+        if t_ is not None:
+            _flat(t_, name); assert tuple(t_.shape) == (D, B, H)
+    ldev, _ = gru_seq_lengths(lengths, B, T, dy.device, want_flag=False)      # (the forward reported bad entries; the backward skips the same rows)
+    scratch = torch.empty(2 * D * B * H, device=dy.device, dtype=torch.float32)
+    call("tg_gru_seq_backward", _p(dy), _p(dh_n), _p(save), _p(w_hh_t[0]), _p(w_hh_t[-1]), _p(ldev), _p(dgi), _p(dgh), _p(dh0), _p(scratch),
+         B, T, H, D, _stream())
+
+
 # ------------------------------------------------------------------------------------------------- BatchNorm
 def bn_train_stats(x2d, groups, ws, mean, rstd, running_mean, running_var, nbt, eps=1e-5, momentum=0.1, repeats=1):
     _flat(x2d, "x"); rows, Cc = x2d.shape

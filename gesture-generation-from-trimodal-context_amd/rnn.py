@@ -1,0 +1,163 @@
+"""torch.nn.GRU-shaped modules on the general HIP recurrence (csrc/gru_seq.hip): per-row lengths, an initial state, the final state, one
+direction or two.
+
+`GRU` has torch.nn.GRU's constructor, parameter names, shapes and initialisation (state dicts load strictly both ways) and takes a padded
+tensor or a PackedSequence; `EncoderRNN` is the Seq2Seq text encoder of the reference (model/seq2seq_net.py:14-56) on top of it.  All
+arithmetic runs in libtrimodal_hip.so (layers.gru_seq_stack_fwd / gru_seq_stack_bwd); torch is plumbing -- parameter containers, the
+packing / unpacking index shuffles and the autograd bridge.  Shapes outside the kernel envelope raise: there is no torch fallback.
+"""
+import torch
+import torch.nn as nn
+from torch.nn.utils.rnn import PackedSequence, pack_padded_sequence, pad_packed_sequence
+
+from . import layers as L
+from . import ops
+
+
+class _GRUFn(torch.autograd.Function):
+    """The stack's hand-written backward behind torch.autograd (as modules._Bridge, with the parameters as inputs so that their gradients
+    reach any optimiser the ordinary way)."""
+
+    @staticmethod
+    def forward(ctx, cfg, x, hx, *params):
+        names, n_layers, H, D, lengths, p_drop, training, rng, inject, save = cfg
+        P = dict(zip(names, params))
+        y, h_n, tape, _ = L.gru_seq_stack_fwd(x, P, "", n_layers, H, D, lengths=lengths, h0=hx, p_drop=p_drop, training=training, rng=rng,
+                                              save=save, inject=inject)
+        ctx.set_materialize_grads(False)
+        ctx.tape, ctx.names, ctx.n_layers, ctx.P = tape, names, n_layers, P
+        return y, h_n
+
+    @staticmethod
+    def backward(ctx, dy, dh_n):
+        assert ctx.tape is not None, "GRU: the forward ran without saving its tape"
+        G = {n: ops.zeros_like(ctx.P[n]) for n in ctx.names}
+        dx, dh0 = L.gru_seq_stack_bwd(None if dy is None else dy.contiguous(), None if dh_n is None else dh_n.contiguous(), ctx.tape, ctx.P, G,
+                                      "", ctx.n_layers, need_dx=ctx.needs_input_grad[1], need_dh0=ctx.needs_input_grad[2])
+        return (None, dx, dh0) + tuple(G[n] if ctx.needs_input_grad[3 + i] else None for i, n in enumerate(ctx.names))
+
+
+class GRU(nn.Module):
+    """torch.nn.GRU on the HIP recurrence.  forward(input, hx=None) -> (output, h_n) for a padded tensor ((T, B, K), or (B, T, K) with
+    batch_first) or a PackedSequence (sorted or not); float32 on the GPU.  Train-mode inter-layer dropout draws from the module's own
+    counter RNG (`seed`); parity tests queue injected masks {f"g.gru.drop{l}": (B, T, D*H)} in `_replay_draws`."""
+
+    def __init__(self, input_size, hidden_size, num_layers=1, bias=True, batch_first=False, dropout=0.0, bidirectional=False, seed=0):
+        super().__init__()
+        if not bias:
+            raise NotImplementedError("GRU(bias=False) is not implemented on the HIP path")
+        self.input_size, self.hidden_size, self.num_layers = int(input_size), int(hidden_size), int(num_layers)
+        self.bias, self.batch_first, self.dropout, self.bidirectional = True, bool(batch_first), float(dropout), bool(bidirectional)
+        self.seed = int(seed)
+        # torch's own module gives the names, shapes and default initialisation; only its parameters are kept
+        proto = nn.GRU(input_size, hidden_size, num_layers, bias=True, batch_first=batch_first, dropout=dropout, bidirectional=bidirectional)
+        self._names = []
+        for name, p in proto.named_parameters():
+            self.register_parameter(name, nn.Parameter(p.detach().clone()))
+            self._names.append(name)
+        self._rng = None
+        self._replay_draws = []
+
+    def extra_repr(self):
+        return (f"{self.input_size}, {self.hidden_size}, num_layers={self.num_layers}, batch_first={self.batch_first}, dropout={self.dropout}, "
+                f"bidirectional={self.bidirectional}")
+
+    def flatten_parameters(self):
+        """No-op (the reference calls it under DataParallel)."""
+
+    def run_batch_first(self, x, lengths=None, hx=None):
+        """The stack on x (B, T, K) float32 contiguous on the GPU; lengths: None, a list / CPU tensor, or a device int64 tensor; hx
+        (num_layers * D, B, H).  Returns (y (B, T, D*H) with zeros at t >= length, h_n)."""
+        D, H = (2 if self.bidirectional else 1), self.hidden_size
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[2] == self.input_size):
+            raise TypeError(f"GRU: expected a CUDA float32 input with {self.input_size} features in 3 dimensions, got "
+                            f"{getattr(x, 'dtype', None)} {getattr(x, 'device', None)} {tuple(getattr(x, 'shape', ()))}")
+        B, T = x.shape[0], x.shape[1]
+        if B < 1 or T < 1 or not ops.gru_seq_supported(B, T, H, D):
+            raise ValueError(f"GRU: (B, T, H, D) = {(B, T, H, D)} is outside the HIP kernel envelope {ops.GRU_SEQ_ENVELOPE}; there is no torch fallback")
+        if hx is not None:
+            if tuple(hx.shape) != (self.num_layers * D, B, H):
+                raise ValueError(f"GRU: hx must have shape {(self.num_layers * D, B, H)}, got {tuple(hx.shape)}")
+            hx = hx.float().contiguous()
+        params = [getattr(self, n) for n in self._names]
+        training = self.training and self.num_layers > 1
+        inject = self._replay_draws.pop(0) if (training and self._replay_draws) else None
+        rng = None
+        if training and self.dropout > 0 and inject is None:
+            if self._rng is None:
+                from .engine import DeviceRNG
+                self._rng = DeviceRNG(self.seed, x.device)
+            self._rng.advance()
+            rng = self._rng
+        save = torch.is_grad_enabled() and (x.requires_grad or (hx is not None and hx.requires_grad) or any(p.requires_grad for p in params))
+        cfg = (tuple(self._names), self.num_layers, H, D, lengths, self.dropout, training, rng, inject, save)
+        return _GRUFn.apply(cfg, x.contiguous(), hx, *params)
+
+    def forward(self, input, hx=None):
+        if isinstance(input, PackedSequence):
+            x, lens = pad_packed_sequence(input, batch_first=True)         # original batch order, as hx and h_n are
+            y, h_n = self.run_batch_first(x.contiguous(), lens, hx)
+            ys, ls = (y, lens) if input.sorted_indices is None else (y.index_select(0, input.sorted_indices), lens[input.sorted_indices.cpu()])
+            data = pack_padded_sequence(ys, ls, batch_first=True, enforce_sorted=True).data
+            return PackedSequence(data, input.batch_sizes, input.sorted_indices, input.unsorted_indices), h_n
+        if input.dim() != 3:
+            raise ValueError("GRU: unbatched (2-D) input is not implemented on the HIP path")
+        x = input if self.batch_first else input.transpose(0, 1)
+        y, h_n = self.run_batch_first(x.contiguous(), None, hx)
+        return (y if self.batch_first else y.transpose(0, 1)), h_n
+
+
+class _EmbedFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, idx):
+        out = torch.empty(*idx.shape, table.shape[1], device=table.device, dtype=torch.float32)
+        ops.embed_gather(table, idx, out)
+        ctx.idx, ctx.shape = idx, tuple(table.shape)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        dtable = ops.zeros(*ctx.shape, device=dout.device)
+        ops.embed_scatter_add(dout.contiguous(), ctx.idx, dtable)
+        return dtable, None
+
+
+class _SumHalvesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y):
+        o = torch.empty(*y.shape[:-1], y.shape[-1] // 2, device=y.device, dtype=torch.float32)
+        return ops.add_halves(y, o)
+
+    @staticmethod
+    def backward(ctx, d_o):
+        dy = torch.empty(*d_o.shape[:-1], 2 * d_o.shape[-1], device=d_o.device, dtype=torch.float32)
+        return ops.dup_halves(d_o.contiguous(), dy)
+
+
+class EncoderRNN(nn.Module):
+    """The Seq2Seq text encoder (model/seq2seq_net.py:14-56): embedding -> packed bidirectional GRU -> the two directions summed.
+    forward(input_seqs (T, B) int64, input_lengths, hidden=None) -> (outputs (max length, B, H), hidden (2 * n_layers, B, H)); the lengths
+    need not be sorted."""
+
+    def __init__(self, input_size, embed_size, hidden_size, n_layers=1, dropout=0.5, pre_trained_embedding=None):
+        super().__init__()
+        self.input_size, self.hidden_size, self.embed_size, self.n_layers, self.dropout = input_size, hidden_size, embed_size, n_layers, dropout
+        if pre_trained_embedding is not None:
+            assert pre_trained_embedding.shape[0] == input_size and pre_trained_embedding.shape[1] == embed_size
+            self.embedding = nn.Embedding.from_pretrained(torch.as_tensor(pre_trained_embedding, dtype=torch.float32), freeze=False)
+        else:
+            self.embedding = nn.Embedding(input_size, embed_size)       # parameter container: its forward is never called
+        self.gru = GRU(embed_size, hidden_size, n_layers, dropout=dropout, bidirectional=True)
+        self.do_flatten_parameters = False
+
+    def forward(self, input_seqs, input_lengths, hidden=None):
+        if not (input_seqs.is_cuda and input_seqs.dtype == torch.int64 and input_seqs.dim() == 2):
+            raise TypeError("EncoderRNN: input_seqs must be a CUDA int64 tensor of shape (T, B)")
+        lens = [int(v) for v in (input_lengths.tolist() if isinstance(input_lengths, torch.Tensor) else input_lengths)]
+        T = max(lens) if lens else 0
+        if not 1 <= T <= input_seqs.shape[0]:
+            raise ValueError(f"EncoderRNN: lengths up to {T} for {input_seqs.shape[0]} steps")
+        idx = input_seqs[:T].t().contiguous()                            # (B, T): the kernels are batch-first
+        embedded = _EmbedFn.apply(self.embedding.weight, idx)
+        y, hidden = self.gru.run_batch_first(embedded, lens, hidden)
+        return _SumHalvesFn.apply(y).transpose(0, 1), hidden

@@ -849,6 +849,33 @@ int tg_fgd_push(void* state, const float* real_feat, const float* gen_feat, int3
 int tg_fgd_scores(const void* state, int32_t D, double* out, void* stream);
 int tg_fgd_from_stats(const double* mu1, const double* S1, const double* mu2, const double* S2, int32_t D, double* out, void* stream);
 
+/* ---- General GRU recurrence (csrc/gru_seq.hip): nn.GRU semantics for ONE layer with D = 1 or 2 directions, per-row lengths, an initial state
+ * and the final state -- what pack_padded_sequence -> nn.GRU -> pad_packed_sequence computes (seq2seq_net.py:51-56), and a GRU started from
+ * a given hidden state (seq2seq_net.py:181, embedding_net.py:251-253).  One launch per time step; no workgroup waits on another.
+ *   gi      [D][B][T][3H]  input projections with b_ih added; gi[:, b, t] at t >= lengths[b] is never read
+ *   w_hh_*  [3H][H], b_hh_* [3H] per direction (the _rev pair is ignored, and may be NULL, at D = 1)
+ *   h0      [D][B][H] or NULL (zeros)
+ *   lengths [B] int64 in DEVICE memory or NULL (every row has T steps); valid entries are 1 .. T in any order.  An entry outside that range
+ *           skips the row (y = 0, h_n = h0, dgi = dgh = 0, dh0 = dh_n) and sets *flag = 1 (flag: one int32 word zeroed by the caller, or
+ *           NULL); nothing outside the row's own positions is read or written.
+ *   y       [B][T][D*H]    direction d in columns [d*H, (d+1)*H); EXACTLY 0 at t >= lengths[b].  The forward direction runs t = 0 .. len-1, the
+ *           reverse direction STARTS at t = len-1 and runs down to 0.
+ *   h_n     [D][B][H]      the last state of each direction: y[b, len-1, :H] and y[b, 0, H:], bit for bit
+ *   save    [D][B][T][5H]  the tape r, z, n, W_hn h + b_hn, h_prev (h_prev: the state the step started from, h0 at a row's first step), zeros
+ *           at t >= lengths[b]; NULL for a forward without a backward.  dW_hh = dgh^T @ save[..., 4H:5H].
+ * Backward: dy [B][T][D*H] (never read at t >= lengths[b]), dh_n [D][B][H] or NULL, w_hh_t_* the TRANSPOSED recurrent weights [H][3H];
+ * dgi, dgh [D][B][T][3H] as tg_gru_backward gives them, EXACTLY 0 at t >= lengths[b]; dh0 [D][B][H] or NULL (not wanted);
+ * dh_scratch: 2*D*B*H floats.
+ * Envelope: D in {1, 2}, B >= 1, T >= 1, H % 4 == 0, 8 <= H <= 320 (and ceil(B/32) * ceil(H/16) * D workgroups fit an int32).  Outside it
+ * the entries return non-zero, set tg_last_error and launch nothing; tg_gru_seq_supported writes 1 / 0 for a shape of positive sizes. */
+int tg_gru_seq_supported(int32_t B, int32_t T, int32_t H, int32_t D, int32_t* supported);
+int tg_gru_seq_forward(const float* gi, const float* w_hh_fwd, const float* w_hh_rev, const float* b_hh_fwd, const float* b_hh_rev,
+                       const float* h0, const void* lengths, float* y, float* h_n, float* save, int32_t* flag, int32_t B, int32_t T,
+                       int32_t H, int32_t D, void* stream);
+int tg_gru_seq_backward(const float* dy, const float* dh_n, const float* save, const float* w_hh_t_fwd, const float* w_hh_t_rev,
+                        const void* lengths, float* dgi, float* dgh, float* dh0, float* dh_scratch, int32_t B, int32_t T, int32_t H,
+                        int32_t D, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
