@@ -7,27 +7,16 @@
 //  * Step s of the forward handles, for batch row b of length len_b, position t = s (forward direction) or t = len_b - 1 - s (reverse
 //    direction, which therefore STARTS at the row's last valid position).  Rows with s >= len_b are idle in the product (their A rows are
 //    zero) and write the exact zero of the padded position t = s instead -- y, and the tape, come out fully written without a fill pass.
-//  * The recurrent product runs on v_mfma_f32_16x16x4_f32 (true fp32 operands and accumulators) exactly as in gru.hip: a workgroup owns
-//    [32 batch rows] x [16 hidden units, three gates], 8 waves = 2 row tiles x 4 K slices, partial sums meet in LDS.
+//  * The recurrent product runs on v_mfma_f32_16x16x4_f32 (true fp32 operands and accumulators); workgroup tiling, product and cell: gru_step.hpp.
 //  * Tape [D][B][T][5H]: r, z, n, W_hn h + b_hn, h_prev.  h_prev (the state the step started from: h0 at a row's first step) is taped so
 //    that the backward and the W_hh weight gradient (dgh^T @ h_prev) need neither y, h0 nor the row's length to find it.
 //  * The backward runs the steps in the opposite order on the same per-row clock (step s handles forward step k = len_b - 1 - s); one extra
 //    step (k = -1) forms dh0 when it is asked for.  dgi / dgh are written as exact zeros at t >= len_b.
 //  * lengths outside [1, T]: the row is skipped (y = 0, h_n = h0, dgi = dgh = 0, dh0 = dh_n) and the caller's flag word is set; nothing is
 //    read or written outside the row's own [T] positions.
-#include "common.hpp"
+#include "gru_step.hpp"    // the workgroup tiling, the product and the cell (shared with gru.hip)
 
 namespace tg {
-
-constexpr int GS_MT = 2;   // 16-row tiles per workgroup
-constexpr int GS_KS = 4;   // K slices per workgroup
-constexpr int GS_PF = 5;   // K fragments in flight per wave (covers H <= 320 in one batch of loads)
-constexpr int GS_THREADS = 64 * GS_MT * GS_KS;
-
-__device__ __forceinline__ f32x4 gs_ld4(const float* p, bool ok) {
-    f32x4 z = {0.f, 0.f, 0.f, 0.f};
-    return ok ? *reinterpret_cast<const f32x4*>(p) : z;
-}
 
 // effective length of row b: len_b, or 0 (the row is skipped) when the table entry is outside [1, T]
 __device__ __forceinline__ int gs_len(const long long* __restrict__ lengths, int b, int T) {
@@ -36,26 +25,18 @@ __device__ __forceinline__ int gs_len(const long long* __restrict__ lengths, int
     return (L < 1 || L > T) ? 0 : (int)L;
 }
 
-__global__ __launch_bounds__(GS_THREADS) void gru_seq_fwd_step_kernel(
+__global__ __launch_bounds__(GRU_THREADS) void gru_seq_fwd_step_kernel(
     const float* __restrict__ gi, long gi_ds, const float* __restrict__ whh0, const float* __restrict__ whh1,
     const float* __restrict__ bhh0, const float* __restrict__ bhh1, const float* __restrict__ h0, const long long* __restrict__ lengths,
     float* __restrict__ Y, float* __restrict__ hn_out, float* __restrict__ save, long save_ds, int* __restrict__ flag,
     int B, int T, int H, int D, int step, int n_jt, int n_bt) {
-    __shared__ float red[GS_KS][GS_MT][3][4][64];
-    const int lid = xcd_chunked_id(blockIdx.x, gridDim.x);
-    const int bt = lid % n_bt, jt = (lid / n_bt) % n_jt;
-    const int dir = lid / (n_bt * n_jt);
-    const float* whh = dir ? whh1 : whh0;
+    __shared__ float red[GRU_KS][GRU_MT][3][4][64];
+    const StepTile t = step_tile(n_jt, n_bt);
+    const int dir = t.dir, erow = t.erow, ej = t.ej;
     const float* bhh = dir ? bhh1 : bhh0;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int mt = wave % GS_MT, ks = wave / GS_MT;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int j0 = jt * 16, b0 = bt * (GS_MT * 16);
     const long DH = (long)D * H;
 
-    // gate epilogue ownership: wave (mt, ks) finalises accumulator row i = ks of m-tile mt; its operands go out first
-    const int erow = b0 + mt * 16 + kq * 4 + ks;
-    const int ej = j0 + r16;
+    // the gate epilogue's operands go out first
     const bool e_ok = erow < B && ej < H;
     const int eL = erow < B ? gs_len(lengths, erow, T) : 0;
     const bool act = e_ok && step < eL;
@@ -70,46 +51,14 @@ __global__ __launch_bounds__(GS_THREADS) void gru_seq_fwd_step_kernel(
         else if (h0) hp = h0[((long)dir * B + erow) * H + ej];
     }
 
-    f32x4 acc[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (step > 0 || h0) {                 // (launch-uniform: the first step of a zero initial state has no product)
-        const int b = b0 + mt * 16 + r16;
-        const int bL = b < B ? gs_len(lengths, b, T) : 0;
-        const bool b_ok = step < bL;      // idle and skipped rows feed zeros
-        const int bprev = dir ? bL - step : step - 1;       // the position the row's previous step wrote (step > 0)
-        const float* hrow = !b_ok ? Y : (step > 0 ? Y + ((long)b * T + bprev) * DH + dir * H : h0 + ((long)dir * B + b) * H);
-        const int j = j0 + r16;
-        const bool j_ok = j < H;
-        const float* wrow[3];
-#pragma unroll
-        for (int g = 0; g < 3; ++g) wrow[g] = whh + (long)(g * H + (j_ok ? j : 0)) * H;
-        for (int kbase = ks * 16; kbase < H; kbase += GS_KS * 16 * GS_PF) {
-            f32x4 a[GS_PF], w[3][GS_PF];
-#pragma unroll
-            for (int p = 0; p < GS_PF; ++p) {
-                const int k = kbase + p * (GS_KS * 16) + 4 * kq;
-                const bool inb = k < H;   // H % 4 == 0 (checked on the host)
-                a[p] = gs_ld4(hrow + k, b_ok && inb);
-#pragma unroll
-                for (int g = 0; g < 3; ++g) w[g][p] = gs_ld4(wrow[g] + k, j_ok && inb);
-            }
-#pragma unroll
-            for (int p = 0; p < GS_PF; ++p) {
-                if (kbase + p * (GS_KS * 16) < H) {      // wave-uniform
-#pragma unroll
-                    for (int v = 0; v < 4; ++v)
-#pragma unroll
-                        for (int g = 0; g < 3; ++g) acc[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[p][v], w[g][p][v], acc[g], 0, 0, 0);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int g = 0; g < 3; ++g)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) red[ks][mt][g][i][lane] = acc[g][i];
-    __syncthreads();
+    const int b = t.brow;
+    const int bL = b < B ? gs_len(lengths, b, T) : 0;
+    const bool b_ok = step < bL;          // idle and skipped rows feed zeros
+    const int bprev = dir ? bL - step : step - 1;           // the position the row's previous step wrote (step > 0)
+    const float* hrow = !b_ok ? Y : (step > 0 ? Y + ((long)b * T + bprev) * DH + dir * H : h0 + ((long)dir * B + b) * H);
+    float gh[3];
+    // (launch-uniform: the first step of a zero initial state has no product)
+    step_product_fwd(step > 0 || h0, hrow, b_ok, dir ? whh1 : whh0, H, t, red, gh);
     if (!e_ok) return;
     if (!act) {
         // step >= len: position t = step of this row is padding -- exact zeros in y and in the tape
@@ -124,53 +73,33 @@ __global__ __launch_bounds__(GS_THREADS) void gru_seq_fwd_step_kernel(
         }
         return;
     }
-    float gh[3];
-#pragma unroll
-    for (int g = 0; g < 3; ++g) {
-        float s = red[0][mt][g][ks][lane];
-#pragma unroll
-        for (int q = 1; q < GS_KS; ++q) s += red[q][mt][g][ks][lane];
-        gh[g] = s;
-    }
-    const float hn = gh[2] + bh_n;
-    const float r = gate_sigmoid(gi_r + gh[0] + bh_r);
-    const float z = gate_sigmoid(gi_z + gh[1] + bh_z);
-    const float n = gate_tanh(gi_n + r * hn);
-    const float h = (1.f - z) * n + z * hp;
-    Y[((long)erow * T + tau) * DH + dir * H + ej] = h;
-    if (step == eL - 1) hn_out[((long)dir * B + erow) * H + ej] = h;
+    const GruCell c = gru_cell_fwd(gi_r, gi_z, gi_n, gh, bh_r, bh_z, bh_n, hp);
+    Y[((long)erow * T + tau) * DH + dir * H + ej] = c.h;
+    if (step == eL - 1) hn_out[((long)dir * B + erow) * H + ej] = c.h;
     if (save) {
         float* sp = save + dir * save_ds + ((long)erow * T + tau) * (5 * H);
-        sp[ej] = r; sp[H + ej] = z; sp[2 * H + ej] = n; sp[3 * H + ej] = hn; sp[4 * H + ej] = hp;
+        sp[ej] = c.r; sp[H + ej] = c.z; sp[2 * H + ej] = c.n; sp[3 * H + ej] = c.hn; sp[4 * H + ej] = hp;
     }
 }
 
 // Backward step s: forward step k = len_b - 1 - s of every row, i.e. position tau = len_b - 1 - s (forward direction) or s (reverse).  With
 // the gate gradients dgh of the step that consumed h_tau (k + 1, written by the previous launch, at position tau_next):
 //     dh_tau = dy_tau + dh_next * z_next + dgh_next @ W_hh        (W_hh passed transposed: [H][3H]);   at s = 0: dy_tau + dh_n
-//     dn = dh (1-z)(1-n^2),  dz = dh (h_prev - n) z (1-z),  dr = dn * hn * r (1-r),  dgi = [dr, dz, dn],  dgh = [dr, dz, dn * r]
+//     dgi = [dr, dz, dn],  dgh = [dr, dz, dn * r]                 (gru_cell_bwd)
 // k = -1 (s = len_b; launched only when dh0 is asked for): dh0 = dh_next * z_next + dgh_next @ W_hh of the row's first step.
 // s >= len_b: exact zeros into dgi / dgh at the padded position t = s.
-__global__ __launch_bounds__(GS_THREADS) void gru_seq_bwd_step_kernel(
+__global__ __launch_bounds__(GRU_THREADS) void gru_seq_bwd_step_kernel(
     const float* __restrict__ dY, const float* __restrict__ dhn, const float* __restrict__ save, long save_ds,
     const float* __restrict__ wt0, const float* __restrict__ wt1, const long long* __restrict__ lengths, float* __restrict__ dgi,
     float* __restrict__ dgh, long dg_ds, float* __restrict__ dhbuf, float* __restrict__ dh0, int B, int T, int H, int D, int step,
     int n_jt, int n_bt) {
-    __shared__ float red[GS_KS][GS_MT][4][64];
-    const int lid = xcd_chunked_id(blockIdx.x, gridDim.x);
-    const int bt = lid % n_bt, jt = (lid / n_bt) % n_jt;
-    const int dir = lid / (n_bt * n_jt);
-    const float* wt = dir ? wt1 : wt0;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int mt = wave % GS_MT, ks = wave / GS_MT;
-    const int r16 = lane & 15, kq = lane >> 4;
-    const int j0 = jt * 16, b0 = bt * (GS_MT * 16);
+    __shared__ float red[GRU_KS][GRU_MT][4][64];
+    const StepTile t = step_tile(n_jt, n_bt);
+    const int dir = t.dir, erow = t.erow, ej = t.ej;
     const int H3 = 3 * H;
     const long DH = (long)D * H;
     const bool has_next = step > 0;       // (launch-uniform; a row with step <= len_b then has a consumer step)
 
-    const int erow = b0 + mt * 16 + kq * 4 + ks;
-    const int ej = j0 + r16;
     const bool e_ok = erow < B && ej < H;
     const int eL = erow < B ? gs_len(lengths, erow, T) : 0;
     const bool act = e_ok && step < eL;
@@ -195,66 +124,30 @@ __global__ __launch_bounds__(GS_THREADS) void gru_seq_bwd_step_kernel(
         }
     }
 
-    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    if (has_next) {
-        const int b = b0 + mt * 16 + r16;
-        const int bL = b < B ? gs_len(lengths, b, T) : 0;
-        const bool b_ok = step <= bL;     // rows past their first step (and skipped rows: bL = 0 < step) feed zeros
-        const int bnext = dir ? step - 1 : bL - step;
-        const float* arow = dgh + dir * dg_ds + ((long)(b_ok ? b : 0) * T + (b_ok ? bnext : 0)) * H3;
-        const int j = j0 + r16;
-        const bool j_ok = j < H;
-        const float* wrow = wt + (long)(j_ok ? j : 0) * H3;
-        for (int kbase = ks * 16; kbase < H3; kbase += GS_KS * 16 * GS_PF) {
-            f32x4 a[GS_PF], w[GS_PF];
-#pragma unroll
-            for (int p = 0; p < GS_PF; ++p) {
-                const int k = kbase + p * (GS_KS * 16) + 4 * kq;
-                const bool inb = k < H3;
-                a[p] = gs_ld4(arow + k, b_ok && inb);
-                w[p] = gs_ld4(wrow + k, j_ok && inb);
-            }
-#pragma unroll
-            for (int p = 0; p < GS_PF; ++p) {
-                if (kbase + p * (GS_KS * 16) < H3) {
-                    // two accumulators: the dependent-accumulator latency of v_mfma_f32_16x16x4_f32 exceeds its issue interval
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[p][0], w[p][0], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[p][1], w[p][1], acc1, 0, 0, 0);
-                    acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[p][2], w[p][2], acc0, 0, 0, 0);
-                    acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[p][3], w[p][3], acc1, 0, 0, 0);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) red[ks][mt][i][lane] = acc0[i] + acc1[i];
-    __syncthreads();
+    const int b = t.brow;
+    const int bL = b < B ? gs_len(lengths, b, T) : 0;
+    const bool b_ok = step <= bL;         // rows past their first step (and skipped rows: bL = 0 < step) feed zeros
+    const int bnext = dir ? step - 1 : bL - step;
+    const float* arow = dgh + dir * dg_ds + ((long)(b_ok ? b : 0) * T + (b_ok ? bnext : 0)) * H3;
+    const float s = step_product_bwd(has_next, arow, b_ok, dir ? wt1 : wt0, H, t, red);
     if (!e_ok) return;
-    float carry = dh_next * z_next;       // what flows into h_tau from the step that consumed it (or from dh_n)
-    if (has_next) {
-        float s = red[0][mt][ks][lane];
-#pragma unroll
-        for (int q = 1; q < GS_KS; ++q) s += red[q][mt][ks][lane];
-        carry += s;
+    float carry;                          // what flows into h_tau from the step that consumed it (or from dh_n)
+    {
+        // the product is rounded before the sum joins it (no FMA): the value this kernel has always formed, stated so that it does not
+        // depend on whether the compiler sees the two in one basic block
+#pragma clang fp contract(off)
+        carry = dh_next * z_next;
+        if (has_next) carry += s;
     }
+    const long pos = dir * dg_ds + ((long)erow * T + (act ? tau : step)) * H3 + ej;    // an idle row: t = step is padding
     if (!act) {
         if (first && dh0) dh0[((long)dir * B + erow) * H + ej] = carry;
-        if (step < T) {                   // t = step is padding for this row
-            float* gi_o = dgi + dir * dg_ds + ((long)erow * T + step) * H3;
-            float* gh_o = dgh + dir * dg_ds + ((long)erow * T + step) * H3;
-            gi_o[ej] = 0.f; gi_o[H + ej] = 0.f; gi_o[2 * H + ej] = 0.f;
-            gh_o[ej] = 0.f; gh_o[H + ej] = 0.f; gh_o[2 * H + ej] = 0.f;
-        }
+        if (step < T) store_gate_grads(dgi + pos, dgh + pos, H, 0.f, 0.f, 0.f, 0.f);
         return;
     }
     const float dh = dy + carry;
-    const float dn = dh * (1.f - z) * (1.f - n * n);
-    const float dz = dh * (hp - n) * z * (1.f - z);
-    const float dr = dn * hn * r * (1.f - r);
-    float* gi_o = dgi + dir * dg_ds + ((long)erow * T + tau) * H3;
-    float* gh_o = dgh + dir * dg_ds + ((long)erow * T + tau) * H3;
-    gi_o[ej] = dr; gi_o[H + ej] = dz; gi_o[2 * H + ej] = dn;
-    gh_o[ej] = dr; gh_o[H + ej] = dz; gh_o[2 * H + ej] = dn * r;
+    const GruCellGrad g = gru_cell_bwd(dh, r, z, n, hn, hp);
+    store_gate_grads(dgi + pos, dgh + pos, H, g.dr, g.dz, g.dn, g.dn * r);
     dh_w[(long)erow * H + ej] = dh;
 }
 
@@ -285,12 +178,11 @@ extern "C" int tg_gru_seq_forward(const float* gi, const float* w_hh_fwd, const 
     TG_REQUIRE(aligned16(w_hh_fwd) && aligned16(w_hh_rev) && aligned16(y) && aligned16(h0), "tg_gru_seq_forward: w_hh / y / h0 must be 16-byte aligned");
     TG_REQUIRE(!lengths || (reinterpret_cast<uintptr_t>(lengths) & 7u) == 0, "tg_gru_seq_forward: lengths must be 8-byte aligned (int64)");
     hipStream_t s = (hipStream_t)stream;
-    const int n_jt = cdiv(H, 16), n_bt = cdiv(B, GS_MT * 16);
-    dim3 grid(n_jt * n_bt * D);
+    const StepGrid g = step_grid(B, H, D);
     const long gi_ds = (long)B * T * 3 * H, save_ds = (long)B * T * 5 * H;
     for (int step = 0; step < T; ++step)
-        hipLaunchKernelGGL(gru_seq_fwd_step_kernel, grid, dim3(GS_THREADS), 0, s, gi, gi_ds, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, h0,
-                           (const long long*)lengths, y, h_n, save, save_ds, (int*)flag, B, T, H, D, step, n_jt, n_bt);
+        hipLaunchKernelGGL(gru_seq_fwd_step_kernel, g.grid, dim3(GRU_THREADS), 0, s, gi, gi_ds, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, h0,
+                           (const long long*)lengths, y, h_n, save, save_ds, (int*)flag, B, T, H, D, step, g.n_jt, g.n_bt);
     return check_launch("tg_gru_seq_forward");
 }
 
@@ -302,12 +194,11 @@ extern "C" int tg_gru_seq_backward(const float* dy, const float* dh_n, const flo
     TG_REQUIRE(aligned16(w_hh_t_fwd) && aligned16(w_hh_t_rev) && aligned16(dgh), "tg_gru_seq_backward: w_hh_t / dgh must be 16-byte aligned");
     TG_REQUIRE(!lengths || (reinterpret_cast<uintptr_t>(lengths) & 7u) == 0, "tg_gru_seq_backward: lengths must be 8-byte aligned (int64)");
     hipStream_t s = (hipStream_t)stream;
-    const int n_jt = cdiv(H, 16), n_bt = cdiv(B, GS_MT * 16);
-    dim3 grid(n_jt * n_bt * D);
+    const StepGrid g = step_grid(B, H, D);
     const long save_ds = (long)B * T * 5 * H, dg_ds = (long)B * T * 3 * H;
     const int steps = dh0 ? T + 1 : T;    // the extra step forms dh0 of the rows of full length (shorter rows form theirs on the way)
     for (int step = 0; step < steps; ++step)
-        hipLaunchKernelGGL(gru_seq_bwd_step_kernel, grid, dim3(GS_THREADS), 0, s, dy, dh_n, save, save_ds, w_hh_t_fwd, w_hh_t_rev,
-                           (const long long*)lengths, dgi, dgh, dg_ds, dh_scratch, dh0, B, T, H, D, step, n_jt, n_bt);
+        hipLaunchKernelGGL(gru_seq_bwd_step_kernel, g.grid, dim3(GRU_THREADS), 0, s, dy, dh_n, save, save_ds, w_hh_t_fwd, w_hh_t_rev,
+                           (const long long*)lengths, dgi, dgh, dg_ds, dh_scratch, dh0, B, T, H, D, step, g.n_jt, g.n_bt);
     return check_launch("tg_gru_seq_backward");
 }

@@ -747,6 +747,11 @@ def check_async_errors():
                                f"workgroup {info[2]}, flag words seen {info[4:14]}; results are invalid")
 
 
+def _at(t_, c0, row_floats):
+    """Pointer to batch row c0 of a float32 operand with row_floats floats per batch row (NULL for an absent operand)."""
+    return C.c_void_p(0) if t_ is None else C.c_void_p(t_.data_ptr() + 4 * c0 * row_floats)
+
+
 def gru_fused_dropout(B, H, bwd=False):
     """True when the recurrence kernel that will run for (B, H) applies the inter-layer dropout itself (drop_mask / dy_mask)."""
     # H = 64 only.  The cluster kernels accept drop_mask / y_drop / dy_mask too (C-ABI; tests call them directly), but measured on the generator
@@ -767,10 +772,10 @@ def gru_forward(gi, w_hh, b_hh, y, save, drop_mask=None, y_drop=None, save_rows=
         _flat(w, "w_hh"); _flat(b, "b_hh"); assert tuple(w.shape) == (3 * H, H) and b.numel() == 3 * H
     if save is not None:
         _flat(save, "save"); assert tuple(save.shape) == (2, B, T, 4 * H)
+    if drop_mask is not None:
+        _flat(drop_mask, "drop_mask"); _flat(y_drop, "y_drop")
+        assert tuple(drop_mask.shape) == tuple(y.shape) == tuple(y_drop.shape)
     if H == 64:
-        if drop_mask is not None:
-            _flat(drop_mask, "drop_mask"); _flat(y_drop, "y_drop")
-            assert tuple(drop_mask.shape) == tuple(y.shape) == tuple(y_drop.shape)
         call("tg_gru_h64_forward", _p(gi), B * T * H3, _p(w_hh[0]), _p(w_hh[1]), _p(b_hh[0]), _p(b_hh[1]), _p(y), _p(save),
              B * T * 4 * H, _p(drop_mask), _p(y_drop), B, T, _stream())
         return y
@@ -781,19 +786,15 @@ def gru_forward(gi, w_hh, b_hh, y, save, drop_mask=None, y_drop=None, save_rows=
         return y
     chunks = gru_cluster_chunks(B, H) if (GRU_CLUSTER and H > 64) else None
     if chunks is not None:
-        if drop_mask is not None:
-            _flat(drop_mask, "drop_mask"); _flat(y_drop, "y_drop")
-            assert tuple(drop_mask.shape) == tuple(y.shape) == tuple(y_drop.shape)
         r0, rn = (0, B) if save_rows is None else (int(save_rows[0]), int(save_rows[1]))
         assert 0 <= r0 and rn >= 0 and r0 + rn <= B
         ws = _gru_cluster_ws(gi.device, chunks[0][1], H)         # (the first chunk is the largest)
-        at = lambda t_, c0, row_floats: C.c_void_p(0) if t_ is None else C.c_void_p(t_.data_ptr() + 4 * c0 * row_floats)
         for c0, cn in chunks:
             # rows [c0, c0 + cn) of every operand; the direction strides stay those of the whole batch.  Gates are saved for the part of
             # [r0, r0 + rn) that falls into the chunk
             s0, s1 = max(r0, c0), min(r0 + rn, c0 + cn)
-            call("tg_gru_forward_cluster_rows", at(gi, c0, T * H3), B * T * H3, _p(w_hh[0]), _p(w_hh[1]), _p(b_hh[0]), _p(b_hh[1]), at(y, c0, T * 2 * H),
-                 at(save, c0, T * 4 * H), B * T * 4 * H, at(drop_mask, c0, T * 2 * H), at(y_drop, c0, T * 2 * H), C.c_void_p(ws.data_ptr()), ws.numel() * 4,
+            call("tg_gru_forward_cluster_rows", _at(gi, c0, T * H3), B * T * H3, _p(w_hh[0]), _p(w_hh[1]), _p(b_hh[0]), _p(b_hh[1]), _at(y, c0, T * 2 * H),
+                 _at(save, c0, T * 4 * H), B * T * 4 * H, _at(drop_mask, c0, T * 2 * H), _at(y_drop, c0, T * 2 * H), C.c_void_p(ws.data_ptr()), ws.numel() * 4,
                  cn, T, H, max(0, s0 - c0), max(0, s1 - s0), _stream())
         return y
     assert drop_mask is None and y_drop is None, "fused dropout: H = 64 or the cluster kernels only"
@@ -818,31 +819,28 @@ def gru_backward(dy, y, save, w_hh_t, dgi, dgh, dh_scratch, *, b0=0, nb=None, dy
     for w in w_hh_t:
         _flat(w, "w_hh_t"); assert tuple(w.shape) == (H, 3 * H)
     ys, ss = y[b0:b0 + nb], save[:, b0:b0 + nb]
+    if dy_mask is not None:
+        _flat(dy_mask, "dy_mask"); assert tuple(dy_mask.shape) == tuple(dy.shape)
     if H == 64:
-        if dy_mask is not None:
-            _flat(dy_mask, "dy_mask"); assert tuple(dy_mask.shape) == tuple(dy.shape)
         call("tg_gru_h64_backward", _p(dy), _p(dy_mask), _p(ys), C.c_void_p(ss.data_ptr()), B * T * 4 * H, _p(w_hh_t[0]), _p(w_hh_t[1]),
              _p(dgi), _p(dgh), nb * T * 3 * H, nb, T, _stream())
         return
     chunks = gru_cluster_chunks(nb, H, bwd=True) if (GRU_CLUSTER and H > 64) else None
     if chunks is not None:
-        if dy_mask is not None:
-            _flat(dy_mask, "dy_mask"); assert tuple(dy_mask.shape) == tuple(dy.shape)
         ws = _gru_cluster_ws(dy.device, chunks[0][1], H, bwd=True)
-        at = lambda t_, c0, row_floats: C.c_void_p(0) if t_ is None else C.c_void_p(t_.data_ptr() + 4 * c0 * row_floats)
         if stats is not None:
             rm, ci, ch = stats
             _flat(rm, "gi_rowmax"); _flat(ci, "gi_colmax"); _flat(ch, "gh_colmax")
             assert tuple(rm.shape) == (2, nb) and tuple(ci.shape) == (2, 3 * H) == tuple(ch.shape)
         for c0, cn in chunks:                                    # (row chunks of one workspace, as in gru_forward)
             if stats is None:
-                call("tg_gru_backward_cluster", at(dy, c0, T * 2 * H), at(dy_mask, c0, T * 2 * H), at(ys, c0, T * 2 * H), at(ss, c0, T * 4 * H), B * T * 4 * H,
-                     _p(w_hh_t[0]), _p(w_hh_t[1]), at(dgi, c0, T * 3 * H), at(dgh, c0, T * 3 * H), nb * T * 3 * H, C.c_void_p(ws.data_ptr()), ws.numel() * 4,
+                call("tg_gru_backward_cluster", _at(dy, c0, T * 2 * H), _at(dy_mask, c0, T * 2 * H), _at(ys, c0, T * 2 * H), _at(ss, c0, T * 4 * H), B * T * 4 * H,
+                     _p(w_hh_t[0]), _p(w_hh_t[1]), _at(dgi, c0, T * 3 * H), _at(dgh, c0, T * 3 * H), nb * T * 3 * H, C.c_void_p(ws.data_ptr()), ws.numel() * 4,
                      cn, T, H, _stream())
             else:
-                call("tg_gru_backward_cluster_stats", at(dy, c0, T * 2 * H), at(dy_mask, c0, T * 2 * H), at(ys, c0, T * 2 * H), at(ss, c0, T * 4 * H),
-                     B * T * 4 * H, _p(w_hh_t[0]), _p(w_hh_t[1]), at(dgi, c0, T * 3 * H), at(dgh, c0, T * 3 * H), nb * T * 3 * H,
-                     C.c_void_p(ws.data_ptr()), ws.numel() * 4, cn, T, H, at(stats[0], c0, 1), nb, _p(stats[1]), _p(stats[2]), _stream())
+                call("tg_gru_backward_cluster_stats", _at(dy, c0, T * 2 * H), _at(dy_mask, c0, T * 2 * H), _at(ys, c0, T * 2 * H), _at(ss, c0, T * 4 * H),
+                     B * T * 4 * H, _p(w_hh_t[0]), _p(w_hh_t[1]), _at(dgi, c0, T * 3 * H), _at(dgh, c0, T * 3 * H), nb * T * 3 * H,
+                     C.c_void_p(ws.data_ptr()), ws.numel() * 4, cn, T, H, _at(stats[0], c0, 1), nb, _p(stats[1]), _p(stats[2]), _stream())
         return stats is not None
     assert dy_mask is None, "fused dropout backward: H = 64 or the cluster kernels only"
     call("tg_gru_backward", _p(dy), _p(ys), C.c_void_p(ss.data_ptr()), B * T * 4 * H, _p(w_hh_t[0]), _p(w_hh_t[1]),

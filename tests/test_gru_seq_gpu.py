@@ -21,6 +21,7 @@ pytestmark = pytest.mark.gpu
 
 FWD_ABS = 5e-6
 BWD_ROW = 1e-6
+HN_REL = 1e-5           # W_hn h + b_hn relative to its max (test_gru_envelope_gpu.py)
 NAN = float("nan")
 
 #        H   D  B   T   h0     dh_n   lengths
@@ -220,6 +221,57 @@ def test_bad_device_lengths_skip_their_rows_and_set_the_flag(pkg, dev, D):
     ops.gru_seq_check(o["flag"])                   # cleared by the check
     with pytest.raises(ValueError):                # the same lengths given on the host never reach the device
         _run(ops, dev, c, lengths=bad)
+
+
+@pytest.mark.parametrize("H,B,T", [(36, 33, 3), (320, 5, 2)])
+def test_full_length_rows_agree_with_the_per_step_path_of_gru_forward(pkg, dev, H, B, T):
+    """The step kernels of csrc/gru.hip and csrc/gru_seq.hip share one product and one cell (csrc/gru_step.hpp); on two directions, full
+    lengths and no h0 / dh_n / dh0 they differ in nothing but the tape's fifth block.  Their outputs are pinned to each other with the gates
+    of test_gru_envelope_gpu.py, not with equality: the compiler contracts the shared expressions differently in the two kernels
+    (gru.hip forms h = (1 - z) n + z h_prev with two products and a sum and dh with one FMA, gru_seq.hip the other way round), and each
+    entry point keeps the bits it had before the body was shared.  Measured on the MI355X, largest differences over both cases: y 1.2e-7,
+    r / z / n 1.8e-7, W_hn h + b_hn 9.7e-8 of its max, dgi 1.8e-7 and dgh 9.1e-8 of the row's largest |dgi|.
+    (36, 33, 3): a partial last hidden tile, K slices that run out at different fragments, a second batch tile of one row, a step without
+    the product and steps with it.  (320, 5, 2): every fragment in flight is live and the K range is exactly full."""
+    ops = pkg.ops
+    c = _case(H, 2, B, T, False, False, "full")
+    gi, dy = c["gi"].to(dev), c["dy"].to(dev)
+    w, b = [x.to(dev) for x in c["w"]], [x.to(dev) for x in c["b"]]
+    wt = [x.t().contiguous() for x in w]
+    full = lambda *shape: torch.full(shape, NAN, device=dev)
+    g = dict(y=full(B, T, 2 * H), save=full(2, B, T, 4 * H), dgi=full(2, B, T, 3 * H), dgh=full(2, B, T, 3 * H))
+    prev = ops.GRU_CLUSTER, ops.GRU_VEC
+    ops.GRU_CLUSTER, ops.GRU_VEC = False, False          # the per-step launches of csrc/gru.hip
+    try:
+        ops.gru_forward(gi, w, b, g["y"], g["save"])
+        ops.gru_backward(dy, g["y"], g["save"], wt, g["dgi"], g["dgh"], torch.zeros(4 * B * H, device=dev))
+    finally:
+        ops.GRU_CLUSTER, ops.GRU_VEC = prev
+    s = dict(y=full(B, T, 2 * H), h_n=full(2, B, H), save=full(2, B, T, 5 * H), dgi=full(2, B, T, 3 * H), dgh=full(2, B, T, 3 * H))
+    ops.gru_seq_forward(gi, w, b, s["y"], s["h_n"], s["save"])
+    ops.gru_seq_backward(dy, s["save"], wt, s["dgi"], s["dgh"])
+    torch.cuda.synchronize()
+    for k, v in list(g.items()) + list(s.items()):
+        assert bool(torch.isfinite(v).all()), f"{k} has unwritten (NaN) or non-finite elements"
+    dist = lambda a_, b_: float((a_.double() - b_.double()).abs().max())
+    e_y = dist(s["y"], g["y"])
+    e_g = dist(s["save"][..., :3 * H], g["save"][..., :3 * H])
+    e_hn = dist(s["save"][..., 3 * H:4 * H], g["save"][..., 3 * H:]) / float(g["save"][..., 3 * H:].abs().max())
+    rowmax = g["dgi"].double().abs().amax(dim=(0, 2, 3)).view(1, B, 1, 1)
+    live = (rowmax > 0).expand_as(g["dgi"])
+    e_gi = float((((s["dgi"].double() - g["dgi"].double()).abs() / rowmax.clamp_min(1e-300))[live]).max())
+    e_gh = float((((s["dgh"].double() - g["dgh"].double()).abs() / rowmax.clamp_min(1e-300))[live]).max())
+    print(f"gru_seq against gru (H, B, T) = {(H, B, T)}: y {e_y:.2e}  r,z,n {e_g:.2e}  hn rel {e_hn:.2e}  dgi {e_gi:.2e}  dgh {e_gh:.2e}")
+    assert e_y <= FWD_ABS and e_g <= FWD_ABS and e_hn <= HN_REL, (e_y, e_g, e_hn)
+    assert e_gi <= BWD_ROW and e_gh <= BWD_ROW, (e_gi, e_gh)
+    dead = (rowmax == 0).view(B)                         # (the middle row of dy carries no gradient)
+    assert bool(dead.any()) and float(s["dgi"][:, dead].abs().max()) == 0.0 and float(s["dgh"][:, dead].abs().max()) == 0.0
+    # what gru_seq states about its own y holds as values: the taped h_prev is the previous step's y (zeros at a direction's first step),
+    # h_n the y of its last step
+    h_prev = torch.zeros(2, B, T, H, device=dev)
+    h_prev[0, :, 1:], h_prev[1, :, :-1] = s["y"][:, :-1, :H], s["y"][:, 1:, H:]
+    assert torch.equal(s["save"][..., 4 * H:], h_prev)
+    assert torch.equal(s["h_n"][0], s["y"][:, T - 1, :H]) and torch.equal(s["h_n"][1], s["y"][:, 0, H:])
 
 
 # ------------------------------------------------------------------------------------------------------------------ modules
