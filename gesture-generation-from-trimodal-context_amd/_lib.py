@@ -166,6 +166,13 @@ SIGNATURES = {
     "tg_gru_seq_supported": [I32, I32, I32, I32, P],
     "tg_gru_seq_forward": [P] * 11 + [I32, I32, I32, I32, P],
     "tg_gru_seq_backward": [P] * 10 + [I32, I32, I32, I32, P],
+    "tg_attn_step_supported": [I32, I32, I32, P],
+    "tg_attn_step_forward": [P, P, P, P, P, P, I64, I32, I32, I32, P],
+    "tg_attn_step_backward": [P, I64] + [P] * 9 + [I32, I32, I32, P],
+    "tg_seq2seq_loss": [P, P, I32, I32, I32, F32, F32, F32, P, P, P, P],
+    "tg_sumsq_accumulate": [P, I64, P, P, P],
+    "tg_clip_scale": [P, F32, P, P],
+    "tg_scale_by": [P, I64, P, P],
 }
 
 ABI_VERSION = 11

@@ -433,6 +433,100 @@ __global__ __launch_bounds__(1024) void d_head_step_kernel(const float* __restri
     }
 }
 
+// ---- Seq2Seq custom_loss (train_eval/train_seq2seq.py:6-33) forward + d_output.  output, target [B][T][P]:
+//   w_reg mean((o - t)^2) + w_cont sum_n |o[:, n] - o[:, n-1]| / numel - w_var sum_{b,p} ||o[b, :, p]||_2 / numel     (the norm runs over TIME)
+// Stage 1: one workgroup per batch row, thread p walks the T frames of column (b, p) twice (sums, then gradient) with fp64 sums; the row's
+// three partial sums go to ws[b][3] in a fixed order.  Stage 2: one workgroup adds the B partials in order.  Subgradients: sign(0) = 0, and 0
+// for a column whose norm is exactly 0.
+constexpr int S2S_LOSS_THREADS = 128;
+__device__ __forceinline__ float sgnf(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
+__global__ __launch_bounds__(S2S_LOSS_THREADS) void seq2seq_loss_stage1(const float* __restrict__ out, const float* __restrict__ tgt, int T, int P,
+                                                                        float c_reg, float c_cont, float c_var, double* __restrict__ ws,
+                                                                        float* __restrict__ d_out) {
+    __shared__ double sh[S2S_LOSS_THREADS][3];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const long base = (long)b * T * P;
+    double a_sq = 0.0, a_ct = 0.0, a_nm = 0.0;
+    for (int p = tid; p < P; p += S2S_LOSS_THREADS) {
+        double n2 = 0.0;
+        float prev = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const float o = out[base + (long)t * P + p], d = o - tgt[base + (long)t * P + p];
+            a_sq += (double)d * (double)d;
+            n2 += (double)o * (double)o;
+            if (t > 0) a_ct += (double)fabsf(o - prev);
+            prev = o;
+        }
+        const double nm = sqrt(n2);
+        a_nm += nm;
+        const double inv = nm > 0.0 ? 1.0 / nm : 0.0;
+        for (int t = 0; t < T; ++t) {
+            const float o = out[base + (long)t * P + p], d = o - tgt[base + (long)t * P + p];
+            float sg = 0.f;
+            if (t > 0) sg += sgnf(o - out[base + (long)(t - 1) * P + p]);
+            if (t + 1 < T) sg -= sgnf(out[base + (long)(t + 1) * P + p] - o);
+            d_out[base + (long)t * P + p] = (float)(2.0 * (double)c_reg * (double)d + (double)c_cont * (double)sg - (double)c_var * (double)o * inv);
+        }
+    }
+    sh[tid][0] = a_sq; sh[tid][1] = a_ct; sh[tid][2] = a_nm;
+    __syncthreads();
+    if (tid < 3) {
+        double s = 0.0;
+        for (int i = 0; i < S2S_LOSS_THREADS; ++i) s += sh[i][tid];
+        ws[(long)b * 3 + tid] = s;
+    }
+}
+__global__ __launch_bounds__(64) void seq2seq_loss_stage2(const double* __restrict__ ws, int B, float c_reg, float c_cont, float c_var,
+                                                          float* __restrict__ scalars) {
+    __shared__ double sh[3];
+    const int tid = threadIdx.x;
+    if (tid < 3) {
+        double s = 0.0;
+        for (int b = 0; b < B; ++b) s += ws[(long)b * 3 + tid];
+        sh[tid] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double reg = (double)c_reg * sh[0], cont = (double)c_cont * sh[1], var = -(double)c_var * sh[2];
+        scalars[0] = (float)reg; scalars[1] = (float)cont; scalars[2] = (float)var; scalars[3] = (float)(reg + cont + var);
+    }
+}
+
+// ---- global gradient-norm clip (torch.nn.utils.clip_grad_norm_): sum g^2 of each tensor into one device double, then the scale
+// min(1, max_norm / (sqrt(total) + 1e-6)) as a device float.  Fixed summation order: block partials into ws, one workgroup adds them.
+constexpr int SUMSQ_BLOCKS = 256;
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, long n, double* __restrict__ ws) {
+    __shared__ double sh[256];
+    double a = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) { const double x = (double)g[i]; a += x * x; }
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) ws[blockIdx.x] = sh[0];
+}
+__global__ __launch_bounds__(64) void sumsq_finish_kernel(const double* __restrict__ ws, int nb, double* __restrict__ total) {
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < nb; ++i) s += ws[i];
+        total[0] += s;
+    }
+}
+__global__ __launch_bounds__(64) void clip_scale_kernel(const double* __restrict__ total, float max_norm, float* __restrict__ out) {
+    if (threadIdx.x == 0) {
+        const double nrm = sqrt(total[0]);
+        const double c = (double)max_norm / (nrm + 1e-6);
+        out[0] = c >= 1.0 ? 1.f : (float)c;          // (a NaN total gives a NaN scale, as clip_grad_norm_ does; an infinite one gives 0)
+        out[1] = (float)nrm;
+    }
+}
+__global__ __launch_bounds__(256) void scale_by_kernel(float* __restrict__ x, long n, const float* __restrict__ scale) {
+    const float s = scale[0];
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) x[i] *= s;
+}
+
 }  // namespace tg
 
 using namespace tg;
@@ -525,6 +619,40 @@ int tg_ae_loss(const float* recon, const float* target, int32_t B, int32_t T, in
     if (zero_async(out, sizeof(float), ST)) return 1;
     hipLaunchKernelGGL(ae_loss_kernel, dim3(ew_grid((long)B * T * D, 256, 4)), dim3(256), 0, ST, recon, target, B, T, D, out, d_recon);
     return check_launch("tg_ae_loss");
+}
+
+int tg_seq2seq_loss(const float* output, const float* target, int32_t B, int32_t T, int32_t P, float w_reg, float w_cont, float w_var, double* ws,
+                    float* scalars, float* d_output, void* stream) {
+    TG_REQUIRE(output && target && ws && scalars && d_output, "tg_seq2seq_loss: null pointer");
+    TG_REQUIRE(B > 0 && T > 0 && P > 0 && (int64_t)B * T * P <= 0x7fffffffLL, "tg_seq2seq_loss: bad sizes (B=%d T=%d P=%d)", B, T, P);
+    TG_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, "tg_seq2seq_loss: ws must be 8-byte aligned (double)");
+    const double numel = (double)B * T * P;
+    const float c_reg = (float)((double)w_reg / numel), c_cont = (float)((double)w_cont / numel), c_var = (float)((double)w_var / numel);
+    hipLaunchKernelGGL(seq2seq_loss_stage1, dim3(B), dim3(S2S_LOSS_THREADS), 0, ST, output, target, T, P, c_reg, c_cont, c_var, ws, d_output);
+    hipLaunchKernelGGL(seq2seq_loss_stage2, dim3(1), dim3(64), 0, ST, ws, B, c_reg, c_cont, c_var, scalars);
+    return check_launch("tg_seq2seq_loss");
+}
+
+int tg_sumsq_accumulate(const float* g, int64_t n, double* ws, double* total, void* stream) {
+    TG_REQUIRE(g && ws && total && n > 0, "tg_sumsq_accumulate: bad arguments");
+    TG_REQUIRE(((reinterpret_cast<uintptr_t>(ws) | reinterpret_cast<uintptr_t>(total)) & 7u) == 0, "tg_sumsq_accumulate: ws / total must be 8-byte aligned (double)");
+    int64_t nb = (n + 4095) / 4096;
+    if (nb > SUMSQ_BLOCKS) nb = SUMSQ_BLOCKS;
+    hipLaunchKernelGGL(sumsq_partial_kernel, dim3((int)nb), dim3(256), 0, ST, g, (long)n, ws);
+    hipLaunchKernelGGL(sumsq_finish_kernel, dim3(1), dim3(64), 0, ST, ws, (int)nb, total);
+    return check_launch("tg_sumsq_accumulate");
+}
+
+int tg_clip_scale(const double* total, float max_norm, float* out, void* stream) {
+    TG_REQUIRE(total && out && max_norm > 0.f, "tg_clip_scale: bad arguments");
+    hipLaunchKernelGGL(clip_scale_kernel, dim3(1), dim3(64), 0, ST, total, max_norm, out);
+    return check_launch("tg_clip_scale");
+}
+
+int tg_scale_by(float* x, int64_t n, const float* scale, void* stream) {
+    TG_REQUIRE(x && scale && n > 0, "tg_scale_by: bad arguments");
+    hipLaunchKernelGGL(scale_by_kernel, dim3(ew_grid(n, 256, 4)), dim3(256), 0, ST, x, (long)n, scale);
+    return check_launch("tg_scale_by");
 }
 
 }  // extern "C"

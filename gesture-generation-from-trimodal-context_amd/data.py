@@ -103,6 +103,23 @@ def default_collate_fn(data):
             default_collate(audio), default_collate(spectrogram), aux_info)
 
 
+def word_seq_collate_fn(data):
+    """The Seq2Seq baseline's collate (what lmdb_data_loader.py:22-41 returns; host Python).  `data`: a list of dataset items (word indices of
+    any length, text_padded, poses, direction vectors, audio, spectrogram, aux dict).  The list is reordered IN PLACE, longest word sequence
+    first (ties keep their order), as the reference's packing wants it.  Returns (word_seq (B, T) int64 padded with 0, words_lengths (B,) int64,
+    then the five fixed-size fields stacked over the batch, then the aux dict collated key by key)."""
+    from torch.utils.data.dataloader import default_collate
+    data.sort(key=lambda item: -len(item[0]))
+    columns = list(zip(*data))
+    words, aux = columns[0], columns[6]
+    lengths = torch.tensor([len(w) for w in words], dtype=torch.int64)
+    padded = torch.zeros(len(words), int(lengths.max()) if len(words) else 0, dtype=torch.int64)
+    for row, w in zip(padded, words):
+        row[:len(w)] = torch.as_tensor(w, dtype=torch.int64)
+    stacked = tuple(default_collate(list(col)) for col in columns[1:6])
+    return (padded, lengths) + stacked + ({k: default_collate([a[k] for a in aux]) for k in aux[0]},)
+
+
 collate_reference = default_collate_fn
 
 

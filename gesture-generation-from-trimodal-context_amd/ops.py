@@ -935,6 +935,120 @@ def gru_seq_backward(dy, save, w_hh_t, dgi, dgh, lengths=None, dh_n=None, dh0=No
          B, T, H, D, _stream())
 
 
+# ------------------------------------------------------------------------------------------------- Seq2Seq attention step (csrc/attn.hip)
+ATTN_ENVELOPE = "B >= 1, 1 <= Te <= 128, H % 4 == 0, 8 <= H <= 320"
+
+
+def attn_step_supported(B, Te, H):
+    """True when tg_attn_step_forward / tg_attn_step_backward take the shape (ATTN_ENVELOPE)."""
+    if min(int(B), int(Te), int(H)) < 1:
+        return False
+    out = C.c_int32(0)
+    call("tg_attn_step_supported", int(B), int(Te), int(H), C.cast(C.byref(out), C.c_void_p))
+    return bool(out.value)
+
+
+def _strided_rows(t, B, H, name):
+    """(row stride in floats) of a [B, H] view with unit inner stride whose rows lie inside its storage."""
+    _f32(t, name)
+    if t.dim() != 2 or tuple(t.shape) != (B, H) or (H > 1 and t.stride(1) != 1) or t.stride(0) < H:
+        raise ValueError(f"{name}: expected a [{B}, {H}] view with unit inner stride and row stride >= {H}, got {tuple(t.shape)} / {t.stride()}")
+    if (B - 1) * t.stride(0) + H > _room(t):
+        raise ValueError(f"{name}: rows exceed the storage")
+    return t.stride(0)
+
+
+def _attn_dims(q, keys, enc, v):
+    _flat(q, "q"); _flat(keys, "keys"); _flat(enc, "enc"); _flat(v, "v")
+    if keys.dim() != 3 or q.dim() != 2:
+        raise ValueError("attn_step: q [B, H], keys / enc [B, Te, H]")
+    B, Te, H = keys.shape
+    if not attn_step_supported(B, Te, H):
+        raise ValueError(f"attn_step: (B, Te, H) = {(B, Te, H)} is outside the kernel envelope {ATTN_ENVELOPE}")
+    if tuple(q.shape) != (B, H) or tuple(enc.shape) != (B, Te, H) or v.numel() != H:
+        raise ValueError(f"attn_step: shapes q {tuple(q.shape)}, keys {tuple(keys.shape)}, enc {tuple(enc.shape)}, v {tuple(v.shape)} do not agree")
+    return B, Te, H
+
+
+def attn_step_forward(q, keys, enc, v, w, ctx):
+    """One decoder step of the Bahdanau attention.  q [B, H]; keys, enc [B, Te, H]; v [H]; writes w [B, Te] (softmax over all Te positions)
+    and ctx, a [B, H] view whose rows may be strided (a column block of the concatenated pre_linear input)."""
+    B, Te, H = _attn_dims(q, keys, enc, v)
+    _flat(w, "w")
+    if tuple(w.shape) != (B, Te):
+        raise ValueError(f"attn_step_forward: w must be [{B}, {Te}]")
+    ld = _strided_rows(ctx, B, H, "ctx")
+    call("tg_attn_step_forward", _p(q), _p(keys), _p(enc), _p(v), _p(w), _p(ctx), ld, B, Te, H, _stream())
+    return w, ctx
+
+
+def attn_step_backward(dctx, q, w, keys, enc, v, dq, dkeys_acc, denc_acc, dv_rows):
+    """Backward of attn_step_forward for one step.  dctx: [B, H] view (strided rows allowed); q, w: that step's saved tensors.  Writes dq [B, H];
+    ADDS into dkeys_acc, denc_acc [B, Te, H] and dv_rows [B, H] (reduce the latter over the rows with colsum)."""
+    B, Te, H = _attn_dims(q, keys, enc, v)
+    for t_, shape, name in ((w, (B, Te), "w"), (dq, (B, H), "dq"), (dkeys_acc, (B, Te, H), "dkeys_acc"), (denc_acc, (B, Te, H), "denc_acc"),
+                            (dv_rows, (B, H), "dv_rows")):
+        _flat(t_, name)
+        if tuple(t_.shape) != shape:
+            raise ValueError(f"attn_step_backward: {name} must be {list(shape)}, got {list(t_.shape)}")
+    ld = _strided_rows(dctx, B, H, "dctx")
+    call("tg_attn_step_backward", _p(dctx), ld, _p(q), _p(w), _p(keys), _p(enc), _p(v), _p(dq), _p(dkeys_acc), _p(denc_acc), _p(dv_rows),
+         B, Te, H, _stream())
+    return dq
+
+
+# ------------------------------------------------------------------------------------------------- Seq2Seq loss and gradient clip (csrc/losses.hip)
+def seq2seq_loss(output, target, weights, scalars, d_output):
+    """custom_loss (train_seq2seq.py:6-33) and its gradient.  output, target, d_output [B, T, P]; weights = (loss_regression_weight,
+    loss_kld_weight, loss_reg_weight); scalars: >= 4 floats <- the three weighted terms and the total."""
+    _flat(output, "output"); _flat(target, "target"); _flat(d_output, "d_output"); _flat(scalars, "scalars")
+    if output.dim() != 3 or target.shape != output.shape or d_output.shape != output.shape or scalars.numel() < 4:
+        raise ValueError("seq2seq_loss: output, target, d_output [B, T, P] of one shape; scalars >= 4 floats")
+    B, T, P = output.shape
+    if len(weights) != 3:
+        raise ValueError(f"seq2seq_loss: weights must hold the three loss weights, got {len(weights)}")
+    ws = torch.empty(3 * B, device=output.device, dtype=torch.float64)
+    call("tg_seq2seq_loss", _p(output), _p(target), B, T, P, *[float(x) for x in weights], _p(ws), _p(scalars), _p(d_output), _stream())
+    return scalars
+
+
+def _f64_word(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() >= 1):
+        raise TypeError(f"{name}: expected a contiguous CUDA float64 tensor")
+    return t
+
+
+def grad_sumsq(g, total, ws=None):
+    """total[0] += sum(g ** 2) for one contiguous float32 tensor; total: device float64 (the caller zeroes it); ws: 256 float64 of scratch."""
+    _flat(g, "g"); _f64_word(total, "total")
+    if g.numel() == 0:
+        return total
+    if ws is None:
+        ws = torch.empty(256, device=g.device, dtype=torch.float64)
+    if _f64_word(ws, "ws").numel() < 256:
+        raise ValueError("grad_sumsq: ws needs 256 float64")
+    call("tg_sumsq_accumulate", _p(g), g.numel(), _p(ws), _p(total), _stream())
+    return total
+
+
+def clip_scale(total, max_norm, out):
+    """out[0] = min(1, max_norm / (sqrt(total[0]) + 1e-6)) (clip_grad_norm_'s coefficient; NaN for a NaN total, as there), out[1] = the norm; out: >= 2
+    device floats."""
+    _f64_word(total, "total"); _flat(out, "out")
+    if out.numel() < 2 or not max_norm > 0:
+        raise ValueError("clip_scale: out needs 2 floats and max_norm must be positive")
+    call("tg_clip_scale", _p(total), float(max_norm), _p(out), _stream())
+    return out
+
+
+def scale_by(x, scale):
+    """x *= scale[0], scale a device float (no host read)."""
+    _flat(x, "x"); _flat(scale, "scale")
+    if x.numel():
+        call("tg_scale_by", _p(x), x.numel(), _p(scale), _stream())
+    return x
+
+
 # ------------------------------------------------------------------------------------------------- BatchNorm
 def bn_train_stats(x2d, groups, ws, mean, rstd, running_mean, running_var, nbt, eps=1e-5, momentum=0.1, repeats=1):
     _flat(x2d, "x"); rows, Cc = x2d.shape

@@ -876,6 +876,37 @@ int tg_gru_seq_backward(const float* dy, const float* dh_n, const float* save, c
                         const void* lengths, float* dgi, float* dgh, float* dh0, float* dh_scratch, int32_t B, int32_t T, int32_t H,
                         int32_t D, void* stream);
 
+/* ---- Bahdanau attention of the Seq2Seq decoder, one decoder step per launch (csrc/attn.hip; model/seq2seq_net.py:59-89, 165-167):
+ *   e[b,t,:] = tanh(q[b] + keys[b,t,:]), s[b,t] = v . e[b,t,:], w[b,:] = softmax_t(s[b,:]) over ALL Te positions (no padding mask: the
+ *   reference has none), ctx[b,:] = sum_t w[b,t] enc[b,t,:].
+ *   q    [B][H]      h_top W_h^T of this step (W_a = [W_h | W_e]; tg_gemm_nt)
+ *   keys [B][Te][H]  enc W_e^T + b_a, once per forward (tg_gemm_nt);  enc [B][Te][H];  v [H]
+ *   w    [B][Te];    ctx [B][.] with row stride ctx_ld >= H floats (it can sit inside a concatenated input)
+ * backward: dctx (row stride dctx_ld), the step's saved q and w -> dq [B][H] (written); dkeys_acc, denc_acc [B][Te][H] and dv_rows [B][H]
+ * ACCUMULATE (one call per decoder step into the same buffers; the caller zeroes them and reduces dv_rows over the rows with tg_colsum).  e is
+ * recomputed, not taped.  One workgroup owns one batch row: no float atomics, results are bit-identical from run to run.
+ * Envelope: B >= 1, 1 <= Te <= 128, H % 4 == 0, 8 <= H <= 320; outside it the entries return non-zero, set tg_last_error ("envelope") and
+ * launch nothing; tg_attn_step_supported writes 1 / 0 for a shape of positive sizes.  keys, enc, dkeys_acc, denc_acc: 16-byte aligned. */
+int tg_attn_step_supported(int32_t B, int32_t Te, int32_t H, int32_t* supported);
+int tg_attn_step_forward(const float* q, const float* keys, const float* enc, const float* v, float* w, float* ctx, int64_t ctx_ld, int32_t B,
+                         int32_t Te, int32_t H, void* stream);
+int tg_attn_step_backward(const float* dctx, int64_t dctx_ld, const float* q, const float* w, const float* keys, const float* enc, const float* v,
+                          float* dq, float* dkeys_acc, float* denc_acc, float* dv_rows, int32_t B, int32_t Te, int32_t H, void* stream);
+
+/* ---- Seq2Seq training loss and gradient clip (csrc/losses.hip; train_eval/train_seq2seq.py:6-33, 48)
+ * tg_seq2seq_loss: custom_loss forward and d_output in one pass over output, target [B][T][P]:
+ *   w_reg mean((o - t)^2) + w_cont sum_n |o[:, n] - o[:, n-1]| / numel - w_var sum_{b,p} ||o[b, :, p]||_2 / numel   (norm over the TIME axis)
+ * fp64 sums in a fixed order; ws: 3 B doubles; scalars[0..3] = the three weighted terms and their total; subgradients: sign(0) = 0, and 0 for
+ * a column whose norm is exactly 0.
+ * tg_sumsq_accumulate: total[0] += sum g^2 (ws: 256 doubles of scratch; fixed order).  tg_clip_scale: out[0] = min(1, max_norm /
+ * (sqrt(total) + 1e-6)) (torch.nn.utils.clip_grad_norm_), out[1] = sqrt(total).  tg_scale_by: x *= scale[0] (a device scalar: no host read
+ * between the backward and the optimiser). */
+int tg_seq2seq_loss(const float* output, const float* target, int32_t B, int32_t T, int32_t P, float w_reg, float w_cont, float w_var, double* ws,
+                    float* scalars, float* d_output, void* stream);
+int tg_sumsq_accumulate(const float* g, int64_t n, double* ws, double* total, void* stream);
+int tg_clip_scale(const double* total, float max_norm, float* out, void* stream);
+int tg_scale_by(float* x, int64_t n, const float* scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
