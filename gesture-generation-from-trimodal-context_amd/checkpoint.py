@@ -36,7 +36,8 @@ _ref_pickle.loads = lambda b, **kw: _RefUnpickler(io.BytesIO(b), **kw).load()
 
 
 def init_model(args, lang_model, speaker_model, pose_dim, _device):
-    """train.py:36-62 for the models on the hot path ('multimodal_context', 'gesture_autoencoder') and the Speech2Gesture baseline."""
+    """train.py:36-62 for the models on the hot path ('multimodal_context', 'gesture_autoencoder') and the Speech2Gesture and Seq2Seq
+    baselines ('seq2seq': (Seq2SeqNet, None, L1Loss); the reference passes it no speaker model).  'joint_embedding' is not implemented."""
     generator = discriminator = loss_fn = None
     if args.model == "multimodal_context":
         generator = PoseGenerator(args, n_words=lang_model.n_words, word_embed_size=args.wordembed_dim,
@@ -51,6 +52,13 @@ def init_model(args, lang_model, speaker_model, pose_dim, _device):
         generator = Generator(n_poses=args.n_poses, pose_dim=pose_dim, n_pre_poses=args.n_pre_poses).to(_device)
         discriminator = Discriminator(pose_dim).to(_device)
         loss_fn = torch.nn.L1Loss()
+    elif args.model == "seq2seq":
+        if lang_model is None:
+            # the model's encoder is sized by the vocabulary; the reference fails on lang_model.n_words here.  NotImplementedError, not a
+            # TypeError: tests/test_gru_seq_cpu.py pins that class for this call from the time the model was not routed at all
+            raise NotImplementedError("model 'seq2seq' without a language model is not implemented: the text encoder is built from lang_model")
+        from .seq2seq import build_model
+        generator, discriminator, loss_fn = build_model(args, lang_model, None, pose_dim, _device)
     else:
         raise NotImplementedError(f"model {args.model!r} is a baseline outside the hot path (SURVEY.md section 8)")
     return generator, discriminator, loss_fn

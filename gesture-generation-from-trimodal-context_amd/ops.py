@@ -997,6 +997,84 @@ def attn_step_backward(dctx, q, w, keys, enc, v, dq, dkeys_acc, denc_acc, dv_row
     return dq
 
 
+# ------------------------------------------------------------------------------------------------- Seq2Seq eval decoder loop (csrc/seq2seq_decode.hip)
+SEQ2SEQ_DECODE_ENVELOPE = ("B >= 1, 1 <= Te <= 128, H % 4 == 0, 8 <= H <= 320, 1 <= n_layers <= 4, n_frames >= 2, 0 <= n_pre <= n_frames, "
+                           "Po == Pd or n_frames == 2, 1 <= Po <= Pd, Pd + Z + H + S8 <= 1024")
+
+
+def seq2seq_decode_supported(B, Te, H, n_layers, n_frames, n_pre, Pd, Po, Z=0, S8=0):
+    """True when tg_seq2seq_decode_eval takes the shape (SEQ2SEQ_DECODE_ENVELOPE)."""
+    dims = [int(x) for x in (B, Te, H, n_layers, n_frames, n_pre, Pd, Po, Z, S8)]
+    if min(dims[:5] + dims[6:8]) < 1 or min(dims) < 0:
+        return False
+    out = C.c_int32(0)
+    call("tg_seq2seq_decode_supported", *dims, C.cast(C.byref(out), C.c_void_p))
+    return bool(out.value)
+
+
+def seq2seq_decode_lengths(te_len, B, Te, device):
+    """Device int64 [B] of per-row encoder lengths, or None.  Validated on the host (ValueError), as gru_seq_lengths validates a list; a
+    device tensor is read back for that (synthesis builds its lengths on the host, so the usual caller passes a list)."""
+    if te_len is None:
+        return None
+    vals = [int(v) for v in (te_len.tolist() if isinstance(te_len, torch.Tensor) else te_len)]
+    if len(vals) != B:
+        raise ValueError(f"seq2seq_decode: {len(vals)} encoder lengths for a batch of {B} rows")
+    bad = [(i, v) for i, v in enumerate(vals) if not 1 <= v <= Te]
+    if bad:
+        raise ValueError(f"seq2seq_decode: encoder lengths must lie in [1, Te = {Te}]; (row, length) {bad[:4]}")
+    if isinstance(te_len, torch.Tensor) and te_len.is_cuda and te_len.dtype == torch.int64 and te_len.is_contiguous():
+        return te_len
+    return torch.tensor(vals, dtype=torch.int64).to(device)
+
+
+def seq2seq_decode_eval(enc, keys, h0, poses, n_frames, n_pre, w_attn, v, w_pre, b_pre, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, gru_params,
+                        w_out, b_out, outputs, h_n, attn_w=None, te_len=None, z=None, spk=None):
+    """The eval-mode decoder loop of Seq2SeqNet.forward in one launch (one workgroup per batch row).  enc, keys [B, Te, H]; h0 [n_layers, B, H];
+    poses [B, >= max(n_pre, 1), Pd]; gru_params: per layer (w_ih, w_hh, b_ih, b_hh); te_len: None (softmax over all Te positions) or one
+    length per row (list / tensor, validated here); z [B, Z], spk [B, S8] or None.  Writes outputs [B, n_frames, Po], h_n [n_layers, B, H]
+    and, when given, attn_w [n_frames - 1, B, Te] (zeros at positions >= te_len[b])."""
+    for t_, name in ((enc, "enc"), (keys, "keys"), (h0, "h0"), (poses, "poses"), (w_attn, "w_attn"), (v, "v"), (w_pre, "w_pre"), (b_pre, "b_pre"),
+                     (bn_gamma, "bn_gamma"), (bn_beta, "bn_beta"), (bn_mean, "bn_mean"), (bn_var, "bn_var"), (w_out, "w_out"), (b_out, "b_out"),
+                     (outputs, "outputs"), (h_n, "h_n")):
+        _flat(t_, name)
+    if enc.dim() != 3 or keys.shape != enc.shape or h0.dim() != 3 or poses.dim() != 3 or outputs.dim() != 3:
+        raise ValueError("seq2seq_decode_eval: enc / keys [B, Te, H], h0 [n_layers, B, H], poses [B, frames, Pd], outputs [B, n_frames, Po]")
+    B, Te, H = enc.shape
+    nl, Pd, Po = h0.shape[0], poses.shape[2], w_out.shape[0]
+    Z = 0 if z is None else _flat(z, "z").shape[1]
+    S8 = 0 if spk is None else _flat(spk, "spk").shape[1]
+    n_frames, n_pre = int(n_frames), int(n_pre)
+    if not seq2seq_decode_supported(B, Te, H, nl, n_frames, n_pre, Pd, Po, Z, S8):
+        raise ValueError(f"seq2seq_decode_eval: (B, Te, H, n_layers, n_frames, n_pre, Pd, Po, Z, S8) = {(B, Te, H, nl, n_frames, n_pre, Pd, Po, Z, S8)} "
+                         f"is outside the kernel envelope {SEQ2SEQ_DECODE_ENVELOPE}")
+    Lin = Pd + Z + H + S8
+    want = ((h0, (nl, B, H)), (w_attn, (H, 2 * H)), (w_pre, (H, Lin)), (w_out, (Po, H)), (outputs, (B, n_frames, Po)), (h_n, (nl, B, H)))
+    for t_, shape in want:
+        if tuple(t_.shape) != shape:
+            raise ValueError(f"seq2seq_decode_eval: expected a tensor of shape {list(shape)}, got {list(t_.shape)}")
+    for t_, n in ((v, H), (b_pre, H), (bn_gamma, H), (bn_beta, H), (bn_mean, H), (bn_var, H), (b_out, Po)):
+        if t_.numel() != n:
+            raise ValueError(f"seq2seq_decode_eval: expected a vector of {n} entries, got {list(t_.shape)}")
+    if poses.shape[0] != B or poses.shape[1] < max(n_pre, 1) or (z is not None and z.shape[0] != B) or (spk is not None and spk.shape[0] != B):
+        raise ValueError(f"seq2seq_decode_eval: poses {list(poses.shape)} / z / spk do not fit B = {B}, n_pre = {n_pre}")
+    if len(gru_params) != nl:
+        raise ValueError(f"seq2seq_decode_eval: {len(gru_params)} GRU layers of parameters for h0 of {nl} layers")
+    table = (_lib.P * (4 * nl))()
+    for l, (w_ih, w_hh, b_ih, b_hh) in enumerate(gru_params):
+        for t_, shape in ((w_ih, (3 * H, H)), (w_hh, (3 * H, H)), (b_ih, (3 * H,)), (b_hh, (3 * H,))):
+            if tuple(_flat(t_, "GRU parameter").shape) != shape:
+                raise ValueError(f"seq2seq_decode_eval: GRU parameter of layer {l}: expected {list(shape)}, got {list(t_.shape)}")
+        table[4 * l:4 * l + 4] = [w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr()]
+    if attn_w is not None and tuple(_flat(attn_w, "attn_w").shape) != (n_frames - 1, B, Te):
+        raise ValueError(f"seq2seq_decode_eval: attn_w must be {[n_frames - 1, B, Te]}")
+    ldev = seq2seq_decode_lengths(te_len, B, Te, enc.device)
+    call("tg_seq2seq_decode_eval", _p(enc), _p(keys), _p(ldev), _p(h0), _p(poses), int(poses.shape[1]), _p(z), _p(spk), _p(w_attn), _p(v),
+         _p(w_pre), _p(b_pre), _p(bn_gamma), _p(bn_beta), _p(bn_mean), _p(bn_var), float(bn_eps), table, _p(w_out), _p(b_out), _p(outputs),
+         _p(h_n), _p(attn_w), B, Te, H, nl, n_frames, n_pre, Pd, Po, Z, S8, _stream())
+    return outputs, h_n, attn_w
+
+
 # ------------------------------------------------------------------------------------------------- Seq2Seq loss and gradient clip (csrc/losses.hip)
 def seq2seq_loss(output, target, weights, scalars, d_output):
     """custom_loss (train_seq2seq.py:6-33) and its gradient.  output, target, d_output [B, T, P]; weights = (loss_regression_weight,

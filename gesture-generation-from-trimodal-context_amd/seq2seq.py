@@ -6,6 +6,10 @@ ways).  All arithmetic runs in libtrimodal_hip.so: the attention step kernels of
 kernels, the general GRU recurrence (T = 1 with h0) and the loss / clip kernels of csrc/losses.hip; torch is plumbing (parameter containers,
 copies into the concatenated inputs, the autograd bridge).  CPU tensors raise TypeError, shapes outside a kernel envelope raise ValueError:
 there is no torch fallback.  Not implemented: discrete_representation=True.
+
+In eval mode the decoder loop is row-local (BatchNorm on running statistics, no dropout) and runs as ONE launch, tg_seq2seq_decode_eval
+(csrc/seq2seq_decode.hip), which also takes a per-row encoder length: Seq2SeqNet.synthesize() gives every row of a padded batch the result of
+its own B = 1 run, as the reference synthesises.  FUSED_EVAL_DECODE = False keeps eval mode on the per-step path.
 """
 import math
 
@@ -16,6 +20,11 @@ from . import layers as L
 from . import ops
 from .ops import Win
 from .rnn import GRU, EncoderRNN, _EmbedFn
+
+
+# eval-mode decode through the one-launch kernel (csrc/seq2seq_decode.hip) where the shape is inside its envelope; False: the per-step path of
+# _DecodeFn (benchmarks and parity tests compare the two).  Train mode never takes the kernel.
+FUSED_EVAL_DECODE = True
 
 
 class Attn(nn.Module):
@@ -178,6 +187,31 @@ class _DecodeFn(torch.autograd.Function):
             tuple(G[n] if ni[6 + i] else None for i, n in enumerate(names))
 
 
+class _FusedEvalDecodeFn(torch.autograd.Function):
+    """The eval-mode loop as one launch.  Like the tape-less eval forward of _DecodeFn, it has a graph node only so that a backward through it
+    raises instead of silently giving no gradients."""
+
+    @staticmethod
+    def forward(ctx, dec, n_frames, n_pre, enc_lengths, enc, h0, poses, z, spk, *params):
+        P = dict(zip(_DEC_NAMES + tuple(dec.gru._names), params))
+        B, Te, H = enc.shape
+        wa, bn = P["attn.attn.weight"], dec.pre_linear[1]
+        keys = ops.gemm_nt(Win.plain(enc.view(B * Te, H)), wa[:, H:], P["attn.attn.bias"], L.empty(B * Te, H, like=enc)).view(B, Te, H)
+        gru = [tuple(P[f"{k}_l{l}"] for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")) for l in range(dec.n_layers)]
+        outputs, h_n = L.empty(B, n_frames, dec.output_size, like=enc), L.empty(dec.n_layers, B, H, like=enc)
+        wat = L.empty(n_frames - 1, B, Te, like=enc)
+        ops.seq2seq_decode_eval(enc, keys, h0, poses, n_frames, n_pre, wa, P["attn.v"], P["pre_linear.0.weight"], P["pre_linear.0.bias"],
+                                P["pre_linear.1.weight"], P["pre_linear.1.bias"], bn.running_mean, bn.running_var, bn.eps, gru, P["out.weight"],
+                                P["out.bias"], outputs, h_n, wat, te_len=enc_lengths, z=z, spk=spk)
+        ctx.mark_non_differentiable(h_n, wat)
+        return outputs, h_n, wat
+
+    @staticmethod
+    def backward(ctx, *_grads):
+        raise NotImplementedError("Seq2Seq decoder: the forward ran without a tape (eval mode: gradients through BatchNorm on running "
+                                  "statistics are not implemented)")
+
+
 class BahdanauAttnDecoderRNN(nn.Module):
     """seq2seq_net.py:92-187.  forward(motion_input (B, dim), last_hidden (n_layers, B, H), encoder_outputs (T, B, H), vid_indices=None) ->
     (output (B, output_size), hidden, attn_weights (B, 1, T)) runs ONE step without gradient (inference use; in train mode it advances the
@@ -208,9 +242,11 @@ class BahdanauAttnDecoderRNN(nn.Module):
         sd = dict(self.named_parameters())
         return [sd[n] for n in _DEC_NAMES] + [getattr(self.gru, n) for n in self.gru._names]
 
-    def decode(self, enc_bt, h0, poses, n_frames, n_pre, z=None, vid_indices=None):
+    def decode(self, enc_bt, h0, poses, n_frames, n_pre, z=None, vid_indices=None, enc_lengths=None):
         """The loop of Seq2SeqNet.forward: enc_bt (B, Te, H), h0 (n_layers, B, H), poses (B, >= max(n_pre, 1), pose_dim) -> (outputs (B, n_frames,
-        pose_dim), final hidden, attention weights (n_frames - 1, B, Te) without gradient)."""
+        pose_dim), final hidden, attention weights (n_frames - 1, B, Te) without gradient).  enc_lengths (eval mode only): one encoder length
+        per row; the row's softmax runs over its first enc_lengths[b] positions and the later weights are exact zeros.  None: all Te
+        positions, padded ones included, as in training."""
         B, Te, H = enc_bt.shape
         _need_attn(B, Te, H)
         spk = None
@@ -219,6 +255,14 @@ class BahdanauAttnDecoderRNN(nn.Module):
             spk = _EmbedFn.apply(self.speaker_embedding.weight, vid_indices.contiguous())
         if self.pre_linear[0].in_features != poses.shape[2] + (0 if z is None else z.shape[1]) + H + (8 if self.speaker_model else 0):
             raise ValueError("Seq2Seq decoder: pose / noise widths do not match pre_linear's input size")
+        if not self.training:
+            Z, S8 = 0 if z is None else z.shape[1], 0 if spk is None else spk.shape[1]
+            if FUSED_EVAL_DECODE and ops.seq2seq_decode_supported(B, Te, H, self.n_layers, n_frames, n_pre, poses.shape[2], self.output_size, Z, S8):
+                return _FusedEvalDecodeFn.apply(self, n_frames, n_pre, enc_lengths, enc_bt.contiguous(), h0.contiguous(), poses.contiguous(),
+                                                None if z is None else z.contiguous(), spk, *self._params())
+        if enc_lengths is not None and any(int(v) != Te for v in (enc_lengths.tolist() if isinstance(enc_lengths, torch.Tensor) else enc_lengths)):
+            raise ValueError("Seq2Seq decoder: the per-step path has no per-row encoder lengths (they need eval mode, seq2seq.FUSED_EVAL_DECODE "
+                             f"and a shape inside {ops.SEQ2SEQ_DECODE_ENVELOPE})")
         params = self._params()
         training = self.training
         S = n_frames - 1
@@ -279,6 +323,9 @@ class Seq2SeqNet(nn.Module):
         self.n_pre_poses = args.n_pre_poses
 
     def forward(self, in_text, in_lengths, poses, vid_indices, z=None):
+        return self._run(in_text, in_lengths, poses, vid_indices, z, None)
+
+    def _run(self, in_text, in_lengths, poses, vid_indices, z, enc_lengths):
         _need_cuda(poses, "Seq2SeqNet: poses")
         if not (isinstance(in_text, torch.Tensor) and in_text.is_cuda):
             raise TypeError("Seq2SeqNet: in_text must be a CUDA int64 tensor: there is no torch fallback")
@@ -287,8 +334,21 @@ class Seq2SeqNet(nn.Module):
         encoder_outputs, encoder_hidden = self.encoder(in_text.transpose(0, 1), in_lengths, None)
         decoder_hidden = encoder_hidden[:self.decoder.n_layers]
         outputs, _, _ = self.decoder.decoder.decode(encoder_outputs.transpose(0, 1), decoder_hidden, poses, self.n_frames, self.n_pre_poses, z,
-                                                 vid_indices)
+                                                 vid_indices, enc_lengths)
         return outputs
+
+    def synthesize(self, in_text, in_lengths, pre_poses):
+        """The reference's synthesis call pose_decoder(in_text, words_lengths, pre_seq_partial, None) (scripts/synthesize.py:134-136) for a
+        padded batch: in_text (B, T) int64 padded with 0, in_lengths one word count per row (any order), pre_poses (B, >= max(n_pre_poses, 1),
+        pose_dim).  Eval arithmetic whatever the module's mode (the BatchNorm buffers do not move), no gradient; every row's attention runs over its own
+        in_lengths[b] encoder positions, so row b equals the B = 1 run of that utterance."""
+        was_training = self.training
+        self.train(False)
+        try:
+            with torch.no_grad():
+                return self._run(in_text, in_lengths, pre_poses, None, None, [int(v) for v in in_lengths])
+        finally:
+            self.train(was_training)
 
 
 # ----------------------------------------------------------------------------------------------------------------------- training

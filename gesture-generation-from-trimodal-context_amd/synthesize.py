@@ -8,7 +8,14 @@ per-window forward is captured into a hipGraph (WindowDecoder).
 
 With args.model == 'speech2gesture' the same window loop feeds the Speech2Gesture generator (:42-44,52-56,65,86-93,137-138): one log-mel
 spectrogram per utterance made on the device (melspec.extract_melspectrogram), one 70-frame slice per window, pose_decoder(in_spec,
-pre_seq_partial); seed hand-over, cross-fade and fade-out as above.  The joint_embedding and seq2seq branches are not implemented.
+pre_seq_partial); seed hand-over, cross-fade and fade-out as above.
+
+With args.model == 'seq2seq' (:105-119,134-136,162-185) a window's text is the UNPADDED word list [SOS, words in the window ..., EOS]
+(seq2seq_window_text), the model sees it with the previous window's last n_pre_poses frames and nothing else (no speaker, audio or noise).
+Utterances run in lock-step as one padded batch with per-row text lengths (Seq2SeqNet.synthesize: every row attends over its own words
+only, so the batch reproduces the reference's one-by-one runs); the decoder loop of a window is one launch (csrc/seq2seq_decode.hip).  No
+graph capture: the text length changes from window to window.  After stacking, the reference's extra cubic fit around every window
+boundary (seq2seq_smooth, :162-185) runs on the host, then the fade-out.  The joint_embedding branch is not implemented.
 
 TTS / Gentle alignment / LMDB front-ends of the reference script are network services and out of scope; `words` is the
 reference's word list [[word, start_s, end_s], ...].
@@ -64,6 +71,66 @@ def window_inputs(args, lang_model, audio, words, i, audio_sr=16000):
         idx = max(0, int(np.floor((w[1] - start_time) / frame_duration)))
         ids[idx] = lang_model.get_word_index(w[0])
     return piece, ids, max(pad, 0)
+
+
+def seq2seq_window_text(lang_model, words, i, n_poses=34, n_pre_poses=4, fps=15):
+    """Word ids of window i for the Seq2Seq model (synthesize.py:105-119): [SOS, every word of the time range ..., EOS], unpadded (numpy int64;
+    a window without words gives [SOS, EOS])."""
+    unit_time, stride_time = n_poses / fps, (n_poses - n_pre_poses) / fps
+    start_time = i * stride_time
+    seq = words_in_time_range(words, start_time, start_time + unit_time)
+    return np.array([lang_model.SOS_token] + [lang_model.get_word_index(w[0]) for w in seq] + [lang_model.EOS_token], dtype=np.int64)
+
+
+def seq2seq_smooth(out_dir_vec, n_windows, n_poses=34, n_pre_poses=4):
+    """synthesize.py:162-185, in place: around the start of every window (the 2 n_pre frames of the utterance's head for window 0, the 3 n_pre
+    frames from n_pre before the boundary for the others) each dimension is replaced by its unweighted cubic least-squares fit (the
+    reference builds weights and does not pass them).  Slices past the end are clipped as numpy clips them."""
+    n_smooth = n_pre_poses
+    for i in range(n_windows):
+        start_frame = n_pre_poses + i * (n_poses - n_pre_poses) - n_smooth
+        if start_frame < 0:
+            start_frame = 0
+            end_frame = start_frame + n_smooth * 2
+        else:
+            end_frame = start_frame + n_smooth * 3
+        y = out_dir_vec[start_frame:end_frame]
+        x = np.arange(y.shape[0])
+        coeffs = np.polyfit(x, y, 3)
+        out_dir_vec[start_frame:end_frame] = np.stack([np.poly1d(coeffs[:, k])(x) for k in range(y.shape[1])], axis=1)
+    return out_dir_vec
+
+
+def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr):
+    """The seq2seq branch for several utterances in lock-step; returns the stacked windows BEFORE seq2seq_smooth, one array per utterance."""
+    dev = next(pose_decoder.parameters()).device
+    B, T, n_pre, fps = len(audios), args.n_poses, args.n_pre_poses, args.motion_resampling_framerate
+    if T != pose_decoder.n_frames or n_pre != pose_decoder.n_pre_poses:
+        raise ValueError(f"seq2seq synthesis: args (n_poses, n_pre_poses) = {(T, n_pre)} but the model decodes {(pose_decoder.n_frames, pose_decoder.n_pre_poses)}")
+    stride, D = T - n_pre, pose_decoder.decoder.output_size
+    n_win = [num_windows(len(a) / audio_sr, T, n_pre, fps) for a in audios]
+    pre = torch.zeros(B, max(n_pre, 1), D, device=dev)
+    if seed_seqs is not None and n_pre > 0:                                      # synthesize.py:46-50
+        pre[:, :n_pre].copy_(torch.as_tensor(np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]), dtype=torch.float32))
+    tail = torch.zeros(B, n_pre, D, device=dev)
+    total = torch.zeros(B, max(n_win) * stride + n_pre, D, device=dev)
+    for i in range(max(n_win)):
+        texts = [seq2seq_window_text(lang_model, words_list[b], min(i, n_win[b] - 1), T, n_pre, fps) for b in range(B)]   # finished utterances idle
+        lens = [len(t) for t in texts]
+        in_text = np.zeros((B, max(lens)), dtype=np.int64)                      # 0 = PAD
+        for b, t in enumerate(texts):
+            in_text[b, :len(t)] = t
+        out = pose_decoder.synthesize(torch.from_numpy(in_text).to(dev), lens, pre).contiguous()     # (B, T, D), synthesize.py:135-136
+        if i > 0 and n_pre > 0:
+            ops.window_blend(tail, out)                                          # :145-153
+        if n_pre > 0:
+            tail.copy_(out[:, T - n_pre:, :])
+            pre = tail.clone()                                                   # :122-126
+        for b in range(B):
+            if i < n_win[b]:                                                     # an idling utterance's frames are not written
+                total[b, i * stride:i * stride + T, :].copy_(out[b])
+    res = total.cpu().numpy()
+    return [res[b, :n_win[b] * stride + n_pre] for b in range(B)], n_win
 
 
 class WindowDecoder:
@@ -215,9 +282,13 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
     vectors, like the reference's return value without fade-out).  vids: one speaker id per utterance, or None / a falsy entry to
     draw it like the reference (synthesize.py:67-74; ignored unless args.z_type == 'speaker').  _draws (parity tests): per window,
     the (B, 16) eps / z to replay instead of the device RNG.  args.model == 'speech2gesture': lang_model, words_list, vids, graph are unused
-    (the model sees the spectrogram only; no capture), spec_pad_mode is melspec.extract_melspectrogram's pad_mode."""
+    (the model sees the spectrogram only; no capture), spec_pad_mode is melspec.extract_melspectrogram's pad_mode.  args.model == 'seq2seq':
+    the audios matter through their lengths only; the result includes the reference's cubic smoothing around every window boundary."""
     if getattr(args, "model", "multimodal_context") == "speech2gesture":
         return _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode)
+    if getattr(args, "model", "multimodal_context") == "seq2seq":             # audio matters through its length only; vids, graph unused
+        outs, n_win = _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr)
+        return [seq2seq_smooth(o, n, args.n_poses, args.n_pre_poses) for o, n in zip(outs, n_win)]
     dev = next(pose_decoder.parameters()).device
     B = len(audios)
     n_win = [num_windows(len(a) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate) for a in audios]
@@ -267,12 +338,12 @@ def fade_out_to_mean(out_dir_vec, end_padding_samples, args, audio_sr=16000):
 
 def generate_gestures(args, pose_decoder, lang_model, audio, words, audio_sr=16000, vid=None, seed_seq=None, fade_out=False,
                       _draws=None, spec_pad_mode="reflect"):
-    """Single-utterance API of the reference (synthesize.py:36-209, multimodal_context and speech2gesture models)."""
+    """Single-utterance API of the reference (synthesize.py:36-209, multimodal_context, speech2gesture and seq2seq models)."""
     out = generate_gestures_batch(args, pose_decoder, lang_model, [audio], [words], [vid], None if seed_seq is None else [seed_seq],
                                   audio_sr, graph=True, _draws=_draws, spec_pad_mode=spec_pad_mode)[0]
     if not fade_out:
         return out
-    if getattr(args, "model", "multimodal_context") == "speech2gesture":
+    if getattr(args, "model", "multimodal_context") in ("speech2gesture", "seq2seq"):
         return fade_out_to_mean(out, end_padding_samples(args, len(audio), audio_sr), args, audio_sr)
     n_win = num_windows(len(audio) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate)
     _, _, end_padding = window_inputs(args, lang_model, audio, words, n_win - 1, audio_sr)

@@ -893,6 +893,30 @@ int tg_attn_step_forward(const float* q, const float* keys, const float* enc, co
 int tg_attn_step_backward(const float* dctx, int64_t dctx_ld, const float* q, const float* w, const float* keys, const float* enc, const float* v,
                           float* dq, float* dkeys_acc, float* denc_acc, float* dv_rows, int32_t B, int32_t Te, int32_t H, void* stream);
 
+/* ---- Eval-mode decoder loop of the Seq2Seq baseline in ONE launch (csrc/seq2seq_decode.hip; model/seq2seq_net.py:241-252), one workgroup per
+ * batch row: BatchNorm on running statistics, no dropout, so no row depends on another and no workgroup waits on another.
+ *   enc, keys [B][Te][H] (keys = enc W_e^T + b_a by tg_gemm_nt, once per forward; both 16-byte aligned);  te_len: device int64 [B] or NULL --
+ *   the softmax of row b runs over its first te_len[b] positions (NULL: all Te, the padded-batch semantics of training; entries are clamped
+ *   to [1, Te], the caller validates them);  h0 [n_layers][B][H];  poses [B][pose_frames][Pd], pose_frames >= max(n_pre, 1);  z [B][Z] / spk
+ *   [B][S8] or NULL when Z / S8 = 0;  w_attn [H][2H] (W_h = its left half), v [H];  w_pre [H][Pd + Z + H + S8], b_pre [H];  bn_*: gamma, beta,
+ *   running mean and variance [H], folded once per launch;  gru_params: a table of 4 n_layers pointers, w_ih [3H][H], w_hh [3H][H], b_ih [3H],
+ *   b_hh [3H] of layer 0, then of layer 1, ...;  w_out [Po][H], b_out [Po].  Weight rows need no alignment beyond 4 bytes.
+ *   outputs [B][n_frames][Po]: frame 0 = poses[:, 0, :Po], frame t = the decoder's output, whose input pose is seed pose t - 1 while
+ *   t - 1 < max(n_pre, 1), else its own previous output;  h_n [n_layers][B][H];  attn_w [n_frames-1][B][Te] or NULL, exact zeros at positions
+ *   >= te_len[b].  fp32 FMA, libm expf / tanhf, the GRU cell of gru_step.hpp; every sum in a fixed order that does not depend on B or on the
+ *   row's place in the batch.
+ * Envelope: B >= 1, 1 <= Te <= 128, H % 4 == 0, 8 <= H <= 320, 1 <= n_layers <= 4, n_frames >= 2, 0 <= n_pre <= n_frames, Po == Pd or
+ * n_frames == 2, 1 <= Po <= Pd, Pd + Z + H + S8 <= 1024 (the row's state lives in LDS); outside it tg_seq2seq_decode_eval returns non-zero,
+ * sets tg_last_error ("envelope") and launches nothing; tg_seq2seq_decode_supported writes 1 / 0 for positive sizes. */
+int tg_seq2seq_decode_supported(int32_t B, int32_t Te, int32_t H, int32_t n_layers, int32_t n_frames, int32_t n_pre, int32_t Pd, int32_t Po,
+                                int32_t Z, int32_t S8, int32_t* supported);
+int tg_seq2seq_decode_eval(const float* enc, const float* keys, const void* te_len, const float* h0, const float* poses, int32_t pose_frames,
+                           const float* z, const float* spk, const float* w_attn, const float* v, const float* w_pre, const float* b_pre,
+                           const float* bn_gamma, const float* bn_beta, const float* bn_mean, const float* bn_var, float bn_eps,
+                           const void* const* gru_params, const float* w_out, const float* b_out, float* outputs, float* h_n, float* attn_w,
+                           int32_t B, int32_t Te, int32_t H, int32_t n_layers, int32_t n_frames, int32_t n_pre, int32_t Pd, int32_t Po, int32_t Z,
+                           int32_t S8, void* stream);
+
 /* ---- Seq2Seq training loss and gradient clip (csrc/losses.hip; train_eval/train_seq2seq.py:6-33, 48)
  * tg_seq2seq_loss: custom_loss forward and d_output in one pass over output, target [B][T][P]:
  *   w_reg mean((o - t)^2) + w_cont sum_n |o[:, n] - o[:, n-1]| / numel - w_var sum_{b,p} ||o[b, :, p]||_2 / numel   (norm over the TIME axis)
