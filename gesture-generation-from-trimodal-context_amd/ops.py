@@ -1445,6 +1445,56 @@ def embed_gather_drop(table, idx, out, p, state, site):
     return out, Drop(state, site, p, out.shape)
 
 
+# csrc/tcn_fused.hip: the text encoder's eight convs and its decoder as one clip-local launch.  TG_TCN_FUSED=0 keeps the conv-by-conv chain (A/B timing).
+TCN_FUSED = os.environ.get("TG_TCN_FUSED", "1") != "0"
+TCN_FUSED_ENVELOPE = "T = 34, C = E = 300, kernel size 2, 4 blocks, decoder width 32, fp16 x 2 weight planes, fp32-accurate math mode, 16-byte aligned operands"
+
+
+def tcn_fused_takes(x0, w_pl, ksize, n_blocks, dec_w, biases=()):
+    """True when tcn_fwd_fused runs this encoder: x0 (clips, T, E) the embedding output, w_pl the Planes of the 2 n_blocks packed conv weights
+    stacked [2 n_blocks C][ksize C], dec_w the decoder weight (TCN_FUSED_ENVELOPE)."""
+    if not (TCN_FUSED and gemm_h2() and w_pl is not None and w_pl.kind == "h2"):
+        return False
+    if not (x0.dim() == 3 and x0.is_contiguous() and x0.dtype == torch.float32 and x0.data_ptr() % 16 == 0):
+        return False
+    _, T, E = x0.shape
+    return (T == 34 and E == 300 and ksize == 2 and n_blocks == 4 and w_pl.rows == 2 * n_blocks * E and w_pl.cw == ksize * E
+            and tuple(dec_w.shape) == (32, E) and dec_w.is_contiguous() and dec_w.data_ptr() % 16 == 0
+            and all(b.is_contiguous() and b.numel() == E and b.data_ptr() % 16 == 0 for b in biases))
+
+
+def tcn_fwd_fused(x0, w_pl, biases, dec_w, dec_b, out, *, p=0.0, state=None, site=0, save_rows=None, tape=None):
+    """x0 (clips, T, C) -> `out` (clips, T, 32), a column slice of a wider row-major buffer allowed.  Dropout p at the eight sites from (state, site)
+    with index0 = j * clips * T * C (ops.Drop).  save_rows = (clip0, n): those clips of tape = (o0, o1, y), each (n_blocks, clips, T, C), are
+    written (the tensors of every block the backward reads); None / n == 0: nothing is taped.  Returns out."""
+    _flat(x0, "x0"); _f32(out, "out"); _flat(dec_w, "dec_w"); _flat(dec_b, "dec_b")
+    clips, T, Cc = x0.shape
+    nb = len(biases) // 2
+    for b in biases:
+        _flat(b, "bias")
+    if len(biases) != 2 * nb or not tcn_fused_takes(x0, w_pl, 2, nb, dec_w, biases):
+        raise ValueError(f"tcn_fwd_fused: outside the envelope ({TCN_FUSED_ENVELOPE})")
+    assert dec_b.numel() == 32 and w_pl.inv.numel() >= w_pl.rows and w_pl.t.is_contiguous()
+    assert tuple(out.shape) == (clips, T, 32) and out.stride(2) == 1 and out.stride(0) == T * out.stride(1) and out.stride(1) >= 32
+    if (clips * T - 1) * out.stride(1) + 32 > _room(out):
+        raise ValueError("tcn_fwd_fused: out exceeds its tensor")
+    r0, rn = (0, 0) if save_rows is None else (int(save_rows[0]), int(save_rows[1]))
+    assert 0 <= r0 and 0 <= rn and r0 + rn <= clips
+    if rn:
+        assert tape is not None and len(tape) == 3
+        for tt in tape:
+            _flat(tt, "tape"); assert tuple(tt.shape) == (nb, clips, T, Cc) and tt.data_ptr() % 16 == 0
+    p = float(p)
+    assert 0.0 <= p < 1.0
+    if p > 0.0:
+        _i64(state, "rng_state"); assert state.numel() >= 2
+    bp = (C.c_void_p * len(biases))(*[b.data_ptr() for b in biases])
+    tp = tape if rn else (None, None, None)
+    call("tg_tcn_fwd_fused", _p(x0), C.c_void_p(w_pl.t.data_ptr()), w_pl.plane_stride, w_pl.rows, _p(w_pl.inv), bp, _p(dec_w), _p(dec_b),
+         _p(state) if p > 0.0 else None, int(site), p, clips, T, Cc, nb, _p(tp[0]), _p(tp[1]), _p(tp[2]), r0, rn, _p(out), out.stride(1), _stream())
+    return out
+
+
 def embed_scatter_add(dout, idx, dtable):
     _flat(dout, "dout"); _i64(idx, "idx"); _flat(dtable, "dtable")
     n_rows, D = dtable.shape

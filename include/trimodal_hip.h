@@ -525,6 +525,18 @@ int tg_embed_gather(const float* table, const int64_t* idx, float* out, int32_t 
  * slope 1).  D % 4 == 0, 16-byte aligned table and out. */
 int tg_embed_gather_drop(const float* table, const int64_t* idx, float* out, int32_t n_idx, int32_t D, int32_t n_rows, float p,
                          const uint64_t* rng_state, uint32_t site, void* stream);
+/* The text encoder's TCN forward (model/tcn.py:16-46, multimodal_context_net.py:57-61) as ONE clip-local launch (csrc/tcn_fused.hip):
+ * x0 [clips][T][C] (the embedding-dropout output) -> n_blocks TemporalBlocks (two weight-normed causal convs of kernel 2, dilation 2^i, each
+ * + ReLU + dropout p, then relu(out + x)) -> Linear(C, 32) written to out + (clip * T + t) * out_ld.  Envelope: T = 34, C = 300, n_blocks = 4,
+ * fp32-accurate math mode.  w_planes / w_inv: the fp16 x 2 planes (tg_split2h_planes) of the 2 n_blocks packed conv weights stacked as
+ * [w_rows = 2 n_blocks C][2 C], planes w_plane_stride elements apart; biases: 2 n_blocks pointers to C floats.  Dropout: element
+ * j * clips * T * C + i of the draw tg_dropout_mask(.., p, rng_state, site) would write scales element i of conv j's output (not stored;
+ * rng_state may be null when p == 0).  o0 / o1 / y: [n_blocks][clips][T][C] each (conv1 output, conv2 output, block output, post-dropout);
+ * only the clips [save_row0, save_row0 + save_rows) are written (save_rows == 0: nothing, the three may be null).  16-byte aligned operands. */
+int tg_tcn_fwd_fused(const float* x0, const void* w_planes, int64_t w_plane_stride, int32_t w_rows, const float* w_inv, const float* const* biases,
+                     const float* dec_w, const float* dec_b, const uint64_t* rng_state, uint32_t site, float p, int32_t clips, int32_t T, int32_t C,
+                     int32_t n_blocks, float* o0, float* o1, float* y, int32_t save_row0, int32_t save_rows, float* out, int64_t out_ld,
+                     void* stream);
 /* dtable[idx[i]*D + :] += dout[i*D + :]  (dense embedding gradient; accumulates). */
 int tg_embed_scatter_add(const float* dout, const int64_t* idx, float* dtable, int32_t n_idx, int32_t D,
                          int32_t n_rows, void* stream);
