@@ -16,12 +16,11 @@
 // of the tile, so accumulator register i of lane l is frame 4 i + (l >> 4), channel l & 15: the 64 lanes of register i cover 64 CONSECUTIVE
 // floats of the channel-last output -- coalesced 256-byte stores / loads, and a wave ballot of register i is the gate word of those 64 elements.
 // The bias rides in the product (tap 15 of the window operand is 1, of the weight operand the bias).
-#include "common.hpp"
+#include "operand_split.hpp"
 
 namespace tg {
 
 constexpr int WV_CO = 16, WV_KW = 15;
-constexpr unsigned WV_RSRC3 = 0x00020000u;      // buffer descriptor word 3: raw buffer, 32-bit data format, bounds check on the byte offset
 constexpr int WV_XA = 256;                 // fstat layout: [X^T A | sum X] 16 x 16, then sum A [16]
 constexpr int WV_FSTAT = WV_XA + 16;
 constexpr int WV_PART = WV_FSTAT + 32;     // per-workgroup partial of the statistics pass: fstat + sum x [16] + sum x^2 [16]
@@ -237,7 +236,7 @@ __global__ __launch_bounds__(256) void wav_apply_kernel(WavGeom g, const float* 
     const float mu = mean[c], rs = rstd[c], ga = gamma[c], be = beta[c];
     const int tiles = g.B * g.TT;
     const int tstep = gridDim.x * 4;
-    __amdgpu_buffer_rsrc_t gate_rsrc = __builtin_amdgcn_make_buffer_rsrc(gate ? (void*)gate : (void*)y, 0, gate ? tiles * 32 : 0, WV_RSRC3);
+    __amdgpu_buffer_rsrc_t gate_rsrc = __builtin_amdgcn_make_buffer_rsrc(gate ? (void*)gate : (void*)y, 0, gate ? tiles * 32 : 0, RSRC3_RAW32);
     float a_cur[4], a_nxt[4];
     int tile = blockIdx.x * 4 + wave;
     auto load_tile = [&](int tl, float (&a)[4]) {
@@ -255,7 +254,7 @@ __global__ __launch_bounds__(256) void wav_apply_kernel(WavGeom g, const float* 
         // stores through buffer descriptors whose range ends with the clip (frames past T1 of the last tile) / is empty (no gate wanted):
         // the hardware drops out-of-range lanes, so no lane-predicated store makes the vector-memory count dynamic (the compiler would then
         // drain everything before the prefetched samples are used)
-        __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(y + (long)b * g.T1 * WV_CO, 0, g.T1 * WV_CO * 4, WV_RSRC3);
+        __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(y + (long)b * g.T1 * WV_CO, 0, g.T1 * WV_CO * 4, RSRC3_RAW32);
         unsigned long long mine = 0ull;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -267,8 +266,7 @@ __global__ __launch_bounds__(256) void wav_apply_kernel(WavGeom g, const float* 
             const unsigned long long word = __ballot(ok && pos);
             mine = l == i ? word : mine;
         }
-        typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-        __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{(unsigned)mine, (unsigned)(mine >> 32)}, gate_rsrc, l < 4 ? (unsigned)(l * 8) : 0x80000000u, tile * 32, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{(unsigned)mine, (unsigned)(mine >> 32)}, gate_rsrc, l < 4 ? (unsigned)(l * 8) : VOFF_OOB, tile * 32, 0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) a_cur[i] = a_nxt[i];
     }

@@ -188,32 +188,12 @@ __device__ __forceinline__ void split3_bits(float x, unsigned& hi, unsigned& mid
 // upper halves of two fp32 words -> one dword holding two bf16 (first element in the low half)
 __device__ __forceinline__ unsigned pack_hi16(unsigned first, unsigned second) { return __builtin_amdgcn_perm(second, first, 0x07060302u); }
 
-// Plane buffer of an fp32 matrix [rows][cw] (gemm_planes.hip): three bf16 planes (hi / mid / lo), each SLAB-TILED -- [cwp / 32 slabs][rows + 1]
+// Plane buffer of an fp32 matrix [rows][cw] (planes.hip): three bf16 planes (hi / mid / lo), each SLAB-TILED -- [cwp / 32 slabs][rows + 1]
 // [32 columns], cwp = cw rounded up to 32, zero past cw and in the extra row `rows` of every slab.  One 32-deep K slab of 16 consecutive
 // rows is then 1 KB of contiguous memory: a single LDS-DMA instruction fetches it as eight whole cache lines (with row-major planes the
 // same instruction touched 16 half lines 2 cwp bytes apart and cost the CU's address unit ~60 cycles: profiles/r3_g_nt_mw_probe.txt).
+// The device functions that write such buffers are in operand_split.hpp.
 __device__ __host__ __forceinline__ long plane_tiled_off(long r, int c, int rows) { return ((long)(c >> 5) * (rows + 1) + r) * 32 + (c & 31); }
-// one 8-column piece of such a buffer: columns c .. c + 7 (c % 8 == 0) of row r of the fp32 matrix (row stride ldx)
-typedef unsigned tg_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void split3_write_piece(const float* __restrict__ x, long ldx, int rows, int cw, int cwp, __bf16* __restrict__ planes,
-                                                   long plane_stride, long r, int c, bool vec) {
-    float v[8];
-    if (r < rows && vec && c + 8 <= cw) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(x + r * ldx + c), b = *reinterpret_cast<const f32x4*>(x + r * ldx + c + 4);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { v[q] = a[q]; v[4 + q] = b[q]; }
-    } else {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = (r < rows && c + q < cw) ? x[r * ldx + c + q] : 0.f;
-    }
-    unsigned h[8], m[8], l[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) split3_bits(v[q], h[q], m[q], l[q]);
-    const long o = plane_tiled_off(r, c, rows);
-    *reinterpret_cast<tg_u32x4*>(planes + o) = tg_u32x4{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]), pack_hi16(h[4], h[5]), pack_hi16(h[6], h[7])};
-    *reinterpret_cast<tg_u32x4*>(planes + plane_stride + o) = tg_u32x4{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]), pack_hi16(m[4], m[5]), pack_hi16(m[6], m[7])};
-    *reinterpret_cast<tg_u32x4*>(planes + 2 * plane_stride + o) = tg_u32x4{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]), pack_hi16(l[4], l[5]), pack_hi16(l[6], l[7])};
-}
 
 // ---- two-term fp16 split of an fp32 value ("fp16 x 2": three matrix instructions per product instead of bf16 x 3's six) -------------------
 // x * s = hi + lo + eps: hi = fp16(x * s) (round to nearest even), lo = fp16(x * s - hi) (the residual is exact in fp32), |eps| <= 2^-23 |x s|
@@ -246,96 +226,6 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) { const unsigned w = (unsigned)__shfl_xor((int)v, o, 64); v = v > w ? v : w; }
     return v;
-}
-
-// One WAVE writes row r (r <= rows; r == rows is the all-zero row) of the fp16 x 2 plane buffer of an fp32 matrix [rows][cw] (row stride ldx):
-// two fp16 planes (hi / lo of x * s_r) in the slab-tiled layout of plane_tiled_off, `plane_stride` elements apart, and inv[r] = 1 / s_r.
-__device__ __forceinline__ void h2_write_row(const float* __restrict__ x, long ldx, int rows, int cw, int cwp, _Float16* __restrict__ planes,
-                                             long plane_stride, float* __restrict__ inv, long r, int lane, bool vec) {
-    const int c8n = cwp / 8;
-    const bool live = r < rows;
-    unsigned mx = 0;
-    if (live) {
-        for (int c = lane * 4; c < cw; c += 256) {
-            if (vec && c + 4 <= cw) {
-                const f32x4 v = *reinterpret_cast<const f32x4*>(x + r * ldx + c);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) { const float f = v[q]; const unsigned b = __float_as_uint(f) & 0x7fffffffu; mx = mx > b ? mx : b; }
-            } else {
-                for (int q = 0; q < 4 && c + q < cw; ++q) { const unsigned b = __float_as_uint(x[r * ldx + c + q]) & 0x7fffffffu; mx = mx > b ? mx : b; }
-            }
-        }
-        mx = wave_max_u32(mx);
-    }
-    const int e = h2_exp_of_bits(mx);
-    const float s = h2_scale_of_exp(e);
-    if (lane == 0) inv[r] = live ? h2_inv_of_exp(e) : 0.f;
-    for (int p8 = lane; p8 < c8n; p8 += 64) {
-        const int c = p8 * 8;
-        float v[8];
-        if (live && vec && c + 8 <= cw) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(x + r * ldx + c), b = *reinterpret_cast<const f32x4*>(x + r * ldx + c + 4);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { v[q] = a[q]; v[4 + q] = b[q]; }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = (live && c + q < cw) ? x[r * ldx + c + q] : 0.f;
-        }
-        unsigned h[4], l[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) h2_split2(v[2 * q] * s, v[2 * q + 1] * s, h[q], l[q]);
-        const long o = plane_tiled_off(r, c, rows);
-        *reinterpret_cast<tg_u32x4*>(planes + o) = tg_u32x4{h[0], h[1], h[2], h[3]};
-        *reinterpret_cast<tg_u32x4*>(planes + plane_stride + o) = tg_u32x4{l[0], l[1], l[2], l[3]};
-    }
-}
-
-// fp16 x 2 planes of the K-CONCATENATED TRANSPOSE of two matrices: out row n (n < cols), column k (k < 2 rows) = w{k / rows}[k % rows][n], w0 / w1
-// [rows][cols] fp32 contiguous -- the weight operand of dx = [dgi_fwd | dgi_rev] @ [W_ih_fwd ; W_ih_rev] (one product over K = 6H) straight from
-// the two nn.GRU parameters.  One 256-thread workgroup per 8 output rows: thread (n_l = t % 8, kg = t / 8): a read instruction fetches 32-byte
-// pieces of eight source rows, and a thread walks only 2 rows / 32 columns per pass (round 6, first form: 32 rows per workgroup -- 19 workgroups
-// per matrix, 225 dependent-latency loads per thread: 100 us for three layers).  `wg` of `nwg` workgroups walk the row blocks; planes as
-// h2_write_row writes them (zero row `cols` included).
-constexpr int H2_TCAT_ROWS = 8;
-__device__ __forceinline__ void h2_planes_tcat_block(const float* __restrict__ w0, const float* __restrict__ w1, int rows, int cols, int cwp,
-                                                     _Float16* __restrict__ planes, long plane_stride, float* __restrict__ inv, int wg, int nwg,
-                                                     unsigned (&smax)[32][H2_TCAT_ROWS]) {
-    const int t = threadIdx.x, n_l = t & 7, kg = t >> 3;
-    const int K = 2 * rows;
-    for (int n0 = wg * H2_TCAT_ROWS; n0 <= cols; n0 += nwg * H2_TCAT_ROWS) {
-        const int n = n0 + n_l;
-        const bool live = n < cols;
-        unsigned mx = 0u;
-        if (live)
-            for (int k = kg; k < K; k += 32) {
-                const float v = (k < rows ? w0 : w1)[(long)(k < rows ? k : k - rows) * cols + n];
-                const unsigned b = __float_as_uint(v) & 0x7fffffffu;
-                mx = mx > b ? mx : b;
-            }
-        smax[kg][n_l] = mx;
-        __syncthreads();
-#pragma unroll
-        for (int q = 0; q < 32; ++q) { const unsigned b = smax[q][n_l]; mx = mx > b ? mx : b; }
-        __syncthreads();
-        const int e = h2_exp_of_bits(mx);
-        const float sc = h2_scale_of_exp(e);
-        if (kg == 0 && n <= cols) inv[n] = live ? h2_inv_of_exp(e) : 0.f;
-        if (n <= cols)
-            for (int p8 = kg; p8 < cwp / 8; p8 += 32) {
-                float v[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const int k = 8 * p8 + q;
-                    v[q] = (live && k < K) ? (k < rows ? w0 : w1)[(long)(k < rows ? k : k - rows) * cols + n] : 0.f;
-                }
-                unsigned h[4], l[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) h2_split2(v[2 * q] * sc, v[2 * q + 1] * sc, h[q], l[q]);
-                const long o = plane_tiled_off(n, 8 * p8, cols);
-                *reinterpret_cast<tg_u32x4*>(planes + o) = tg_u32x4{h[0], h[1], h[2], h[3]};
-                *reinterpret_cast<tg_u32x4*>(planes + plane_stride + o) = tg_u32x4{l[0], l[1], l[2], l[3]};
-            }
-    }
 }
 
 // ---- Philox4x32-10 ------------------------------------------------------------------------------------

@@ -17,13 +17,9 @@
 // v_mfma_f32_16x16x32_bf16 -- the accuracy contract of gemm_split.hip.  Math mode 1 (tg_set_math_mode) uses one round-to-nearest bf16
 // term and one MFMA instead.  Workgroup tile 64 x 64, four waves as 2 x 2, wave tile 32 x 32 (2 x 2 MFMA tiles); the next slab's global
 // loads are in flight while the current one is multiplied.
-#include "common.hpp"
+#include "operand_split.hpp"
 
 namespace tg {
-
-typedef __bf16 c2_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned c2_u32x2 __attribute__((ext_vector_type(2)));
-typedef float c2_f32x4 __attribute__((ext_vector_type(4)));
 
 struct C2Geom {
     int B, H, W, Ci, Co, kh, kw, s, pt, pl, Ho, Wo;
@@ -51,10 +47,10 @@ __device__ __forceinline__ void c2_store(const float (&v)[NV], __bf16* dst, long
     for (int s = 0; s < SPLITS; ++s) {
         const unsigned* src = s == 0 ? h : (s == 1 ? m : l);
         if constexpr (NV == 4) {
-            *reinterpret_cast<c2_u32x2*>(dst + s * plane) = c2_u32x2{pack_hi16(src[0], src[1]), pack_hi16(src[2], src[3])};
+            *reinterpret_cast<u32x2*>(dst + s * plane) = u32x2{pack_hi16(src[0], src[1]), pack_hi16(src[2], src[3])};
         } else {
-            *reinterpret_cast<tg_u32x4*>(dst + s * plane) =
-                tg_u32x4{pack_hi16(src[0], src[1]), pack_hi16(src[2], src[3]), pack_hi16(src[4], src[5]), pack_hi16(src[6], src[7])};
+            *reinterpret_cast<u32x4*>(dst + s * plane) =
+                u32x4{pack_hi16(src[0], src[1]), pack_hi16(src[2], src[3]), pack_hi16(src[4], src[5]), pack_hi16(src[6], src[7])};
         }
     }
 }
@@ -177,11 +173,11 @@ __global__ __launch_bounds__(256) void conv2d_mfma_kernel(const C2Geom g, const 
         }
     };
 
-    c2_f32x4 acc[2][2];
+    f32x4 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = c2_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int j = 0; j < 2; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     if (kbeg < kend) load(kbeg);
     for (int k0 = kbeg; k0 < kend; k0 += C2_BK) {
@@ -203,20 +199,20 @@ __global__ __launch_bounds__(256) void conv2d_mfma_kernel(const C2Geom g, const 
         }
         __syncthreads();
         if (k0 + C2_BK < kend) load(k0 + C2_BK);                   // in flight during the MFMAs below
-        c2_bf16x8 fa[NS][2], fb[NS][2];
+        bf16x8 fa[NS][2], fb[NS][2];
         const int fr = lane & 15, fk = 8 * (lane >> 4);
 #pragma unroll
         for (int s = 0; s < NS; ++s)
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                fa[s][i] = *reinterpret_cast<const c2_bf16x8*>(&lds[s][0][wm * 32 + i * 16 + fr][fk]);
-                fb[s][i] = *reinterpret_cast<const c2_bf16x8*>(&lds[s][1][wn * 32 + i * 16 + fr][fk]);
+                fa[s][i] = *reinterpret_cast<const bf16x8*>(&lds[s][0][wm * 32 + i * 16 + fr][fk]);
+                fb[s][i] = *reinterpret_cast<const bf16x8*>(&lds[s][1][wn * 32 + i * 16 + fr][fk]);
             }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
-                c2_f32x4 c = acc[i][j];
+                f32x4 c = acc[i][j];
                 if constexpr (SPLITS == 3) {                      // smallest terms first
                     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[2][i], fb[0][j], c, 0, 0, 0);
                     c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[0][i], fb[2][j], c, 0, 0, 0);

@@ -1,6 +1,6 @@
 // Element-wise, data-movement, embedding, weight-norm, RNG and optimiser kernels.  All are HBM- or latency-bound:
 // grid-stride loops, 16-byte accesses where the layout allows, no host synchronisation, graph-capture safe.
-#include "common.hpp"
+#include "operand_split.hpp"
 
 namespace tg {
 
@@ -377,7 +377,7 @@ __global__ __launch_bounds__(256) void permute3_batch_kernel(const long* __restr
         return;
     }
     if (p0 == 11) {
-        // fp16 x 2 planes of the K-concatenated transpose of two [d0 rows][d1 cols] matrices (src and the pointer in p1): common.hpp h2_planes_tcat_block
+        // fp16 x 2 planes of the K-concatenated transpose of two [d0 rows][d1 cols] matrices (src and the pointer in p1): operand_split.hpp h2_planes_tcat_block
         const int rows = d[0], cols = d[1], cwp = d[2];
         const long plane = (long)(cols + 1) * cwp;
         _Float16* const planes = reinterpret_cast<_Float16*>(out);

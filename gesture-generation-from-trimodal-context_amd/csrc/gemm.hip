@@ -15,7 +15,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.hpp"
+#include "operand_split.hpp"
 
 namespace tg {
 
@@ -56,11 +56,6 @@ __device__ __forceinline__ void load_nt_frags(const Win& A, const long (&a_off)[
         }
     }
 }
-
-template <int N, typename F, int... I>
-__device__ __forceinline__ void nt_static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void nt_static_for(F&& f) { nt_static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 
 // Workgroup = 4 waves arranged WM x WN, each wave a 32x32 output tile (2x2 MFMA tiles of 16x16).
 // KS = 4 (with WM = WN = 1, VEC): the four waves share ONE 32 x 32 tile and split its K range; the partial tiles meet in LDS and wave 0
@@ -157,9 +152,9 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const NtGroup g) {
             c += 16;
             while (c >= A.cw) { c -= A.cw; ++kk; }
         };
-        nt_static_for<R>([&](auto j) { load(j); });
+        static_for<R>([&](auto j) { load(j); });
         for (int k0 = K_beg; k0 < K; k0 += 16 * R) {
-            nt_static_for<R>([&](auto jc) {
+            static_for<R>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 {                                           // (k-steps past K multiply masked zeros: no branch, so the counts stay static)
                     const f32x4 z = {0.f, 0.f, 0.f, 0.f};

@@ -28,57 +28,14 @@
 // Weight rows past N read the plane buffer's zero row.
 // Precondition (host): the activation is addressable with 31-bit byte offsets, pieces never straddle a tap (cw % 4 == 0), ONE weight
 // matrix [N][K] with planes (no K-concatenated segments), C on the vectorisable layout.  Everything else stays on gemm_split.hip.
-#include "common.hpp"
+#include "operand_split.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace tg {
 
-constexpr unsigned MW_RSRC3 = 0x00020000u;
-constexpr unsigned MW_OOB = 0x80000000u;            // voffset of a piece that must read as zero (>= num_records: extents are < 2^31)
 typedef __attribute__((address_space(3))) void mw_lds_void;
 
-template <int NS>
-__device__ __forceinline__ void mw_split4(const f32x4 v, const float scale, u32x2 (&out)[NS]) {
-    if constexpr (NS == 2) {                         // fp16 x 2 (common.hpp): hi / lo of the scaled values
-        const float x0 = v[0] * scale, x1 = v[1] * scale, x2 = v[2] * scale, x3 = v[3] * scale;
-        unsigned h0, l0, h1, l1;
-        h2_split2(x0, x1, h0, l0);
-        h2_split2(x2, x3, h1, l1);
-        out[0] = u32x2{h0, h1};
-        out[1] = u32x2{l0, l1};
-    } else if constexpr (NS == 1) {                         // plain bf16 tier: round to nearest even
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        bf16x4 r;
-        r[0] = (__bf16)v[0]; r[1] = (__bf16)v[1]; r[2] = (__bf16)v[2]; r[3] = (__bf16)v[3];
-        out[0] = __builtin_bit_cast(u32x2, r);
-    } else {
-        static_assert(NS == 3, "1, 2 or 3 terms");
-        unsigned h[4], m[4], l[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const float xf = v[i];                   // (bit_cast on an ext-vector ELEMENT is miscompiled by hipcc 7.2: scalar copy first)
-            split3_bits(xf, h[i], m[i], l[i]);
-        }
-        out[0] = u32x2{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3])};
-        out[1] = u32x2{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3])};
-        out[2] = u32x2{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3])};
-    }
-}
-
-__device__ __forceinline__ int mw_swz(int row) { return ((row >> 3) & 1) << 4; }      // as gemm_split.hip: XOR for a bf16 column index
-
-// a buffer descriptor whose every input is PROVABLY wave-uniform to the compiler (cdna_hip_programming.md T20: otherwise each buffer
-// operation is wrapped in a readfirstlane / saveexec "waterfall" loop)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t mw_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), MW_RSRC3);
-}
 // one DMA: 64 lanes x 16 bytes from the buffer (per-lane byte offset `voff`, uniform `soff`) to 1 KB of LDS at byte offset `lds_off` of smem
 // (the address-space cast only exists in the device pass: the host pass of this template would otherwise drop the kernel's launch stub)
 __device__ __forceinline__ void mw_dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned char* smem, unsigned lds_off, unsigned voff, unsigned soff) {
@@ -150,7 +107,7 @@ __global__ __launch_bounds__(768, 3) void gemm_nt_mw_kernel(const NtGroup g) {
         // row piece.  Its cursor (tile vb_a, slab s_a) runs three slabs ahead of the slab the matrix waves multiply.
         const int mt = t - 512;
         const int sp = 4 * (mt & 7), sr0 = mt >> 3;
-        const int sp_wb = (sp ^ mw_swz(sr0)) * 2;                              // byte offset of the piece's 8-byte slot inside its 64-byte row
+        const int sp_wb = (sp ^ slab_swz(sr0)) * 2;                            // byte offset of the piece's 8-byte slot inside its 64-byte row
         int vb_a = blockIdx.x - G, s_a = 0, nslab_a = 0;
         bool live_a = true;                                    // false once the cursor has run past this workgroup's last tile
         unsigned a_boff[NPA];
@@ -215,7 +172,7 @@ __global__ __launch_bounds__(768, 3) void gemm_nt_mw_kernel(const NtGroup g) {
 #pragma unroll
                 for (int q = 0; q < NPA; ++q) ga_s[set][q] = a_s[q];
             }
-            const __amdgpu_buffer_rsrc_t a_rsrc = mw_rsrc(a_ptr, a_bytes);
+            const __amdgpu_buffer_rsrc_t a_rsrc = uniform_rsrc(a_ptr, a_bytes);
             const bool inb = kcur < K_a;
             const unsigned c4 = (unsigned)(c * 4);
 #pragma unroll
@@ -223,7 +180,7 @@ __global__ __launch_bounds__(768, 3) void gemm_nt_mw_kernel(const NtGroup g) {
                 const int sr = a_r[q] + kk * a_dil;
                 const bool ok = a_ok[q] & inb & ((unsigned)sr < (unsigned)a_rows_in);
                 if constexpr (ABL & 4) ga[set][q] = u32x4{0x3f800000u + (unsigned)lane, 0x40000000u, 0x3fc00000u + (unsigned)kcur, ok ? 0x3e800000u : 0u};
-                else ga[set][q] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, ok ? a_boff[q] + (unsigned)sr * rs4 + c4 : MW_OOB, 0, 0);
+                else ga[set][q] = __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, ok ? a_boff[q] + (unsigned)sr * rs4 + c4 : VOFF_OOB, 0, 0);
             }
             kcur += 32;
             c += 32;
@@ -241,7 +198,8 @@ __global__ __launch_bounds__(768, 3) void gemm_nt_mw_kernel(const NtGroup g) {
 #pragma unroll
             for (int q = 0; q < NPA; ++q) {
                 u32x2 o[NS];
-                mw_split4<NS>(__builtin_bit_cast(f32x4, ga[set][q]), NS == 2 ? ga_s[set][q] : 1.f, o);
+                if constexpr (NS == 2) split4(__builtin_bit_cast(f32x4, ga[set][q]), ga_s[set][q], o);
+                else split4<NS>(__builtin_bit_cast(f32x4, ga[set][q]), o);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) *reinterpret_cast<u32x2*>(lb + s * A_PLANE + (sr0 + 32 * q) * 64 + sp_wb) = o[s];
             }
@@ -267,7 +225,7 @@ __global__ __launch_bounds__(768, 3) void gemm_nt_mw_kernel(const NtGroup g) {
                 // past this workgroup's last tile: the DMAs of the remaining steps are still ISSUED (a fixed number of vector-memory
                 // operations per step on every path, see `step`), every lane past num_records: they write zeros into a ring slot nobody reads
 #pragma unroll
-                for (int u = 0; u < MAXGB; ++u) b_voff[u] = MW_OOB;
+                for (int u = 0; u < MAXGB; ++u) b_voff[u] = VOFF_OOB;
                 return;
             }
             const NtProb& pr = g.p[pi];
@@ -295,7 +253,7 @@ __global__ __launch_bounds__(768, 3) void gemm_nt_mw_kernel(const NtGroup g) {
                     const unsigned soff = (unsigned)__builtin_amdgcn_readfirstlane(s_b * (int)b_slab_b);
 #pragma unroll
                     for (int s = 0; s < NS; ++s) {
-                        const __amdgpu_buffer_rsrc_t rs = mw_rsrc(b_ptr + s * b_plane, b_bytes);
+                        const __amdgpu_buffer_rsrc_t rs = uniform_rsrc(b_ptr + s * b_plane, b_bytes);
 #pragma unroll
                         for (int u = 0; u < NG; ++u) {
                             // a group past the tile's GB (BN = 160: waves 2, 3 own two groups, not three) is still issued -- out of range, into
@@ -303,7 +261,7 @@ __global__ __launch_bounds__(768, 3) void gemm_nt_mw_kernel(const NtGroup g) {
                             const int grp = mw + 4 * u;
                             const bool own = (GB % 4 == 0) || grp < GB;
                             mw_dma16(rs, smem, own ? (unsigned)(B_BASE + slot * B_BUF + s * B_PLANE + grp * 1024) : (unsigned)DUMMY_OFF,
-                                     own ? b_voff[u] : MW_OOB, soff);
+                                     own ? b_voff[u] : VOFF_OOB, soff);
                         }
                     }
                 }
@@ -347,8 +305,8 @@ __global__ __launch_bounds__(768, 3) void gemm_nt_mw_kernel(const NtGroup g) {
         // ============================================================================================ matrix waves (0-7)
         const int wm = wave / WNW, wn = wave % WNW;
         const int r16 = lane & 15, kq = lane >> 4;
-        const int fa_off = (wm * (16 * TM) + r16) * 64 + ((8 * kq) ^ mw_swz(r16)) * 2;                 // byte offset of the lane's first A fragment
-        const int fb_off = B_BASE + (wn * (16 * TN) + r16) * 64 + ((8 * kq) ^ mw_swz(r16)) * 2;        // ... and first B fragment (slot 0)
+        const int fa_off = (wm * (16 * TM) + r16) * 64 + ((8 * kq) ^ slab_swz(r16)) * 2;                 // byte offset of the lane's first A fragment
+        const int fb_off = B_BASE + (wn * (16 * TN) + r16) * 64 + ((8 * kq) ^ slab_swz(r16)) * 2;        // ... and first B fragment (slot 0)
         f32x4 acc[TM][TN];
         auto load_fb = [&](bf16x8 (&fb)[NS], int slot_, int j) {
 #pragma unroll

@@ -17,12 +17,10 @@
 // next slab's global loads are in flight (registers) while the current slab is split, stored and multiplied.  DB = 0 keeps ONE
 // LDS buffer (two barriers per slab, <= 54 KB: two workgroups per CU, the better choice when the grid has >= 2 workgroups per
 // CU); DB = 1 double-buffers (one barrier per slab): used with the 64-row tiles of the small grids of the backward shapes.
-#include "common.hpp"
+#include "operand_split.hpp"
 #include "tr_image.hpp"
 #include <stdlib.h>
 #include <type_traits>
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 namespace tg {
 
@@ -32,30 +30,6 @@ namespace tg {
 // former 80-byte padded rows were 2-way conflicted on every fragment read (SQ_LDS_BANK_CONFLICT = 49 % of SQ_LDS_IDX_ACTIVE,
 // profiles/r2_pmc_gemm_split.txt); the 8-byte staging stores stay conflict-free (16 consecutive lanes = two whole rows).
 constexpr int SP_LD = 32;
-__device__ __forceinline__ int sp_swz(int row) { return ((row >> 3) & 1) << 4; }      // XOR for a bf16 column index
-
-template <int SPLITS>
-__device__ __forceinline__ void split4(const f32x4 v, u32x2 (&out)[SPLITS]) {
-    if constexpr (SPLITS == 1) {          // plain bf16 tier: round to nearest even (v_cvt_pk_bf16_f32)
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        bf16x4 r;
-        r[0] = (__bf16)v[0]; r[1] = (__bf16)v[1]; r[2] = (__bf16)v[2]; r[3] = (__bf16)v[3];
-        out[0] = __builtin_bit_cast(u32x2, r);
-    } else {
-        static_assert(SPLITS == 3, "1 or 3 terms");
-        unsigned t[4], u[4], s[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            // (__builtin_bit_cast(unsigned, v[i]) on an ext_vector ELEMENT is miscompiled by hipcc 7.2 -- every i reads element 0:
-            // copy the element to a scalar first)
-            const float xf = v[i];
-            split3_bits(xf, t[i], u[i], s[i]);
-        }
-        out[0] = u32x2{pack_hi16(t[0], t[1]), pack_hi16(t[2], t[3])};
-        out[1] = u32x2{pack_hi16(u[0], u[1]), pack_hi16(u[2], u[3])};
-        out[2] = u32x2{pack_hi16(s[0], s[1]), pack_hi16(s[2], s[3])};
-    }
-}
 
 // C(m, n) = act(sum_k A(m,k) * Bw[n][k] + bias[n]) (+ C).  A: fp32 row window (vectorisable layout: checked by the caller),
 // Bw: fp32 [N][ldb].  Same contract as gemm_nt_big_kernel (gemm.hip).
@@ -111,7 +85,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_nt_split_kernel(const NtGroup g
     // staging map: 8 consecutive lanes cover one 128-byte row piece of the slab (32 fp32): whole cache lines per load instruction;
     // thread t owns piece (t & 7) of rows (t >> 3) + 32 q
     const int sp = 4 * (t & 7), sr0 = t >> 3;
-    const int sp_w = sp ^ sp_swz(sr0), fcol = (8 * kq) ^ sp_swz(r16);     // swizzled store / fragment columns (row bases are multiples of 16)
+    const int sp_w = sp ^ slab_swz(sr0), fcol = (8 * kq) ^ slab_swz(r16);     // swizzled store / fragment columns (row bases are multiples of 16)
     long a_off[NPA];
     int a_r[NPA];
     bool a_ok[NPA];

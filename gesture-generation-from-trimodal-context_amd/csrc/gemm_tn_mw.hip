@@ -15,35 +15,19 @@
 // The bias gradient costs nothing: a tile whose k range has a padding column past K stages a column of ONES there, so the product's
 // column K is sum_m dY[m][n] = dbias[n] (exact: 1.0 = its own hi term).
 // Out-of-range pieces (rows past the item's range, columns past N / K, window padding) are bounds-checked buffer loads that return zero.
-#include "common.hpp"
+#include "operand_split.hpp"
 #include "tr_image.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace tg {
-
-constexpr unsigned TW_RSRC3 = 0x00020000u;
-constexpr unsigned TW_OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t tw_rsrc(const void* base, unsigned bytes) {     // provably wave-uniform descriptor (guide T20)
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)a), hi = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32));
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo), 0, __builtin_amdgcn_readfirstlane(bytes), TW_RSRC3);
-}
 
 // fp16 x 2: the piece's four COLUMNS each carry their own power-of-two scale 2^k (the reduction runs over rows, so scales are per column);
 // `kb` packs the four k as signed bytes, first column in the low byte
 __device__ __forceinline__ void tw_split4_h2(const f32x4 v, const int kb, u32x2 (&out)[2]) {
     const float x0 = __builtin_ldexpf(v[0], (kb << 24) >> 24), x1 = __builtin_ldexpf(v[1], (kb << 16) >> 24);
     const float x2 = __builtin_ldexpf(v[2], (kb << 8) >> 24), x3 = __builtin_ldexpf(v[3], kb >> 24);
-    unsigned h0, l0, h1, l1;
-    h2_split2(x0, x1, h0, l0);
-    h2_split2(x2, x3, h1, l1);
-    out[0] = u32x2{h0, h1};
-    out[1] = u32x2{l0, l1};
+    h2_split4(x0, x1, x2, x3, out);
 }
 // four column magnitudes -> their packed scale exponents k = 141 - e (in [-109, 109])
 __device__ __forceinline__ int tw_pack_k(const f32x4 cm) {
@@ -51,29 +35,6 @@ __device__ __forceinline__ int tw_pack_k(const f32x4 cm) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) { const float f = cm[q]; kb |= ((141 - h2_exp_of_bits(__float_as_uint(f))) & 0xff) << (8 * q); }
     return kb;
-}
-
-template <int NS>
-__device__ __forceinline__ void tw_split4(const f32x4 v, u32x2 (&out)[NS]) {
-    static_assert(NS != 2, "fp16 x 2 pieces go through tw_split4_h2");
-    if constexpr (NS == 1) {                         // plain bf16 tier (math mode 1): round to nearest even
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        bf16x4 r;
-        r[0] = (__bf16)v[0]; r[1] = (__bf16)v[1]; r[2] = (__bf16)v[2]; r[3] = (__bf16)v[3];
-        out[0] = __builtin_bit_cast(u32x2, r);
-        return;
-    }
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float xf = v[i];
-        split3_bits(xf, h[i], m[i], l[i]);
-    }
-    if constexpr (NS == 3) {
-        out[0] = u32x2{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3])};
-        out[1] = u32x2{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3])};
-        out[2] = u32x2{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3])};
-    }
 }
 
 // wave tile (16 TNT) x (16 TKT) of dW; matrix waves WNW (n) x WKW (k); workgroup tile BN x BK.  NS = 3: bf16 x 3 (fp32-accurate); NS = 1: plain
@@ -141,12 +102,12 @@ __global__ __launch_bounds__(768, 3) void gemm_tn_mw_kernel(const TnGroup g) {
         // Per-slab address work is kept to a few full-rate instructions per piece (round 5: the float-reciprocal row division, the row-range
         // compares and four 32-bit integer multiplies per A piece had made the fetch as expensive as the staging arithmetic -- ~680 vector
         // instructions per mover wave and slab, the movers then set the pace of the kernel):
-        //   * dY: the piece's offset is fixed per item (TW_OOB for columns past N) and the slab advances through the instruction's scalar
+        //   * dY: the piece's offset is fixed per item (VOFF_OOB for columns past N) and the slab advances through the instruction's scalar
         //     offset; rows past the item's range read ZERO because the buffer descriptor ends at the item's last row -- and with dY zero there
         //     the A rows (and the ones column of the bias trick) need no row check at all: 0 x finite = 0;
         //   * A: offset and row-in-batch advance by increments (one compare-and-select per slab for the batch wrap: windows have >= 32 rows
         //     per batch on this path), the padding check (r * step + tap displacement inside [0, rows_in)) only for windows that have padding.
-        unsigned y_off[NPY];                                   // byte offset of (row m_begin + yrow, column n0 + ycol) in dY, or TW_OOB
+        unsigned y_off[NPY];                                   // byte offset of (row m_begin + yrow, column n0 + ycol) in dY, or VOFF_OOB
         unsigned x_off[NPX];                                   // byte offset of the piece for the cursor's slab (valid columns), advanced per slab
         int x_r[NPX];                                          // its row inside the batch (before step / tap displacement)
         int x_tapd[NPX];                                       // tap row displacement
@@ -172,9 +133,9 @@ __global__ __launch_bounds__(768, 3) void gemm_tn_mw_kernel(const TnGroup g) {
             asm volatile("" : "+v"(mt_l));                       // (keeps the row / column arithmetic below inside this function)
             if (!live) {
 #pragma unroll
-                for (int i = 0; i < NPY; ++i) y_off[i] = TW_OOB;
+                for (int i = 0; i < NPY; ++i) y_off[i] = VOFF_OOB;
 #pragma unroll
-                for (int i = 0; i < NPX; ++i) x_off[i] = TW_OOB;
+                for (int i = 0; i < NPX; ++i) x_off[i] = VOFF_OOB;
                 x_one = -1;
                 y_slab_b = 0; x_inc = 0; x_wrap = 0;
                 return;
@@ -186,7 +147,7 @@ __global__ __launch_bounds__(768, 3) void gemm_tn_mw_kernel(const TnGroup g) {
 #pragma unroll
             for (int i = 0; i < NPY; ++i) {
                 const int p = mt_l + 256 * i, yrow = p / PY, ycol = 4 * (p % PY);
-                y_off[i] = n0 + ycol < pr.N ? (unsigned)(((long)(mb + yrow) * pr.ldy + n0 + ycol) * 4) : TW_OOB;
+                y_off[i] = n0 + ycol < pr.N ? (unsigned)(((long)(mb + yrow) * pr.ldy + n0 + ycol) * 4) : VOFF_OOB;
                 if constexpr (NS == 2) kexp[item_par][i][mt] = tw_pack_k(*reinterpret_cast<const f32x4*>(pr.y_cmax + (n0 + ycol < pr.N ? n0 + ycol : 0)));
             }
             const bool bias_here = pr.dbias != nullptr && k0 <= A.K && A.K < k0 + BK;       // this tile holds the padding column K
@@ -204,9 +165,9 @@ __global__ __launch_bounds__(768, 3) void gemm_tn_mw_kernel(const TnGroup g) {
                 const int b = m / A.rows_out;
                 x_r[i] = m - b * A.rows_out;
                 // (unsigned wrap-around arithmetic: a row before the tensor's start gives an offset the padding check replaces anyway.  A
-                // column past K starts at TW_OOB: the increments of an item add up to less than the tensor's 2^31 bytes, so it stays past
+                // column past K starts at VOFF_OOB: the increments of an item add up to less than the tensor's 2^31 bytes, so it stays past
                 // num_records for the item's life)
-                x_off[i] = cok ? (unsigned)b * bs4 + (unsigned)(x_r[i] * A.step + x_tapd[i]) * rs4 + (unsigned)((kc - tap * A.cw) * 4) : TW_OOB;
+                x_off[i] = cok ? (unsigned)b * bs4 + (unsigned)(x_r[i] * A.step + x_tapd[i]) * rs4 + (unsigned)((kc - tap * A.cw) * 4) : VOFF_OOB;
                 if (bias_here && ak <= A.K && A.K < ak + 4) x_one = 4 * i + (A.K - ak);
                 if constexpr (NS == 2) {
                     int kb = tw_pack_k(*reinterpret_cast<const f32x4*>(pr.a_cmax + (kc - tap * A.cw)));
@@ -246,7 +207,7 @@ __global__ __launch_bounds__(768, 3) void gemm_tn_mw_kernel(const TnGroup g) {
                 xo[i] = x_off[i];
                 if (a_pad) {                                   // (wave-uniform)
                     const int sr = __mul24(x_r[i], a_step) + x_tapd[i];
-                    xo[i] = (unsigned)sr < (unsigned)a_rows_in ? xo[i] : TW_OOB;
+                    xo[i] = (unsigned)sr < (unsigned)a_rows_in ? xo[i] : VOFF_OOB;
                 }
                 // advance to the next slab: 32 rows on, at most one batch wrap (rows_out >= 32: checked by the planner)
                 const int r2 = x_r[i] + 32;
@@ -254,7 +215,7 @@ __global__ __launch_bounds__(768, 3) void gemm_tn_mw_kernel(const TnGroup g) {
                 x_r[i] = wrap ? r2 - a_rows_out : r2;
                 x_off[i] += x_inc + (wrap ? x_wrap : 0u);
             }
-            const __amdgpu_buffer_rsrc_t yr = tw_rsrc(y_ptr, y_bytes), ar = tw_rsrc(a_ptr, a_bytes);
+            const __amdgpu_buffer_rsrc_t yr = uniform_rsrc(y_ptr, y_bytes), ar = uniform_rsrc(a_ptr, a_bytes);
 #pragma unroll
             for (int i = 0; i < NPY; ++i) {
                 if constexpr (ABL & 4) gy[set][i] = u32x4{0x3f800000u + (unsigned)lane, 0x40000000u, y_off[i] | 0x3f000000u, ysoff | 0x3e800000u};
@@ -285,7 +246,7 @@ __global__ __launch_bounds__(768, 3) void gemm_tn_mw_kernel(const TnGroup g) {
             for (int i = 0; i < NPY; ++i) {
                 u32x2 o[NS];
                 if constexpr (NS == 2) tw_split4_h2(__builtin_bit_cast(f32x4, gy[set][i]), kk[i], o);
-                else tw_split4<NS>(__builtin_bit_cast(f32x4, gy[set][i]), o);
+                else split4<NS>(__builtin_bit_cast(f32x4, gy[set][i]), o);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) *reinterpret_cast<u32x2*>(&ys[buf][s][0] + ypos[i]) = o[s];
             }
@@ -297,7 +258,7 @@ __global__ __launch_bounds__(768, 3) void gemm_tn_mw_kernel(const TnGroup g) {
                 for (int q = 0; q < 4; ++q) v[q] = e == q ? 1.0f : v[q];
                 u32x2 o[NS];
                 if constexpr (NS == 2) tw_split4_h2(v, kk[NPY + i], o);
-                else tw_split4<NS>(v, o);
+                else split4<NS>(v, o);
 #pragma unroll
                 for (int s = 0; s < NS; ++s) *reinterpret_cast<u32x2*>(&xs[buf][s][0] + xpos[i]) = o[s];
             }

@@ -1,9 +1,10 @@
 // Persistent, cluster-synchronised GRU recurrence for the generator (H <= 320), recurrent product on the bf16 matrix cores at fp32
-// accuracy.  Same cluster structure and hand-off protocol as gru_cluster.hip (the f32-MFMA version, kept as the reference and the
-// TG_GRU_X3=0 fallback): the CW = ceil(H / 32) workgroups that share a batch tile exchange h_t through write-through (sc1) stores
-// + a drained flag word per member, one polling wave, sc1 loads straight into MFMA fragments; every spin is bounded.
+// accuracy.  These are the only kernels of the cluster recurrence (gru_cluster.hip is their host side: plan, workspace layout, entry
+// points; the f32-MFMA kernels were removed in round 4).  The CW = ceil(H / 32) workgroups that share a batch tile exchange h_t
+// through write-through (sc1) stores + a drained flag word per member, one polling wave, sc1 loads straight into MFMA fragments;
+// every spin is bounded.
 //
-// What changes is the arithmetic of the dependent chain.  v_mfma_f32_16x16x4_f32 runs at 1/16 of the bf16 matrix rate, and the 120
+// Against those f32-MFMA kernels, what changed is the arithmetic of the dependent chain.  v_mfma_f32_16x16x4_f32 runs at 1/16 of the bf16 matrix rate, and the 120
 // f32 MFMAs per wave and step (3.2 us at two waves per SIMD) were half of the ~7 us step.  Here every fp32 operand is split EXACTLY
 // into three bf16 terms (common.hpp split3_bits) and the six significant partial products run on v_mfma_f32_16x16x32_bf16:
 //   * W_hh: member m's 96 rows are split ONCE, when the kernel starts, and stay in registers as bf16 A-fragments (<= 108 VGPRs);
@@ -13,21 +14,12 @@
 // batch row.  K steps of 32 coincide with the members' 32-unit slices: k-step j of the product reads exactly the block member j
 // published, [member][plane][row][32 units], 64 bytes per row and plane -- a wave's epilogue stores cover whole 128-byte lines.
 // Per wave and step: <= 108 bf16 MFMAs of 16 cycles instead of 120 f32 MFMAs of 32.
-#include "common.hpp"
+#include "operand_split.hpp"
 #include <stdlib.h>
 #include <type_traits>
 #include <utility>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace tg {
-
-template <int N, typename Fn, int... I>
-__device__ __forceinline__ void xc_static_for_impl(Fn&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename Fn>
-__device__ __forceinline__ void xc_static_for(Fn&& f) { xc_static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 
 typedef __attribute__((address_space(1))) unsigned gu32x;
 
@@ -36,7 +28,6 @@ constexpr int XC_FLAG_STRIDE = 16;    // flag words per cluster (one 64-byte lin
 constexpr unsigned XC_SPIN_LIMIT = 1u << 26;
 constexpr int XC_GEN_WORD = 15;       // generation word of a cluster's 16-word flag line (members use words 0 .. CW - 1 <= 9)
 constexpr int XC_POLL_WAVE = 7;       // of 8; epilogue threads live in waves 0 .. 3 (forward) / 0 .. 1 (backward)
-constexpr unsigned XC_RSRC3 = 0x00020000u;
 #ifndef XC_SAME_XCD_FAST
 #define XC_SAME_XCD_FAST 1            // 0: always the write-through protocol (A/B builds: make CXXFLAGS+=-DXC_SAME_XCD_FAST=0)
 #endif
@@ -45,51 +36,28 @@ __device__ __forceinline__ bf16x8 as_bf16x8(u32x4 v) { return __builtin_bit_cast
 __device__ __forceinline__ f32x4 as_f32x4(u32x4 v) { return __builtin_bit_cast(f32x4, v); }
 __device__ __forceinline__ u32x4 as_u32x4(f32x4 v) { return __builtin_bit_cast(u32x4, v); }
 
-// eight consecutive fp32 (two float4) -> three bf16x8 fragments (hi / mid / lo planes)
-__device__ __forceinline__ void xc_split8(const f32x4 a, const f32x4 b, bf16x8 (&out)[3]) {
-    unsigned h[8], m[8], l[8];
+// The kernels keep a value's planes in arrays of THREE whatever NS is: the shared split (operand_split.hpp) fills the first NS, the rest repeat
+// the last one (plain bf16: hi, hi, hi; fp16 x 2: hi, lo, lo).  `scale` is the fp16 x 2 power of two (unused otherwise).
+template <int NS>
+__device__ __forceinline__ void xc_split8(const f32x4 a, const f32x4 b, const float scale, bf16x8 (&out)[3]) {
+    bf16x8 (&first)[NS] = reinterpret_cast<bf16x8 (&)[NS]>(out);
+    if constexpr (NS == 2) split8(a, b, scale, first);
+    else split8<NS>(a, b, first);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float xa = a[i], xb = b[i];
-        split3_bits(xa, h[i], m[i], l[i]);
-        split3_bits(xb, h[4 + i], m[4 + i], l[4 + i]);
-    }
-    out[0] = as_bf16x8(u32x4{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]), pack_hi16(h[4], h[5]), pack_hi16(h[6], h[7])});
-    out[1] = as_bf16x8(u32x4{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]), pack_hi16(m[4], m[5]), pack_hi16(m[6], m[7])});
-    out[2] = as_bf16x8(u32x4{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]), pack_hi16(l[4], l[5]), pack_hi16(l[6], l[7])});
+    for (int s = NS; s < 3; ++s) out[s] = out[NS - 1];
 }
-
-// four consecutive fp32 -> three 8-byte words (4 bf16 each)
-__device__ __forceinline__ void xc_split4(const f32x4 v, u32x2 (&out)[3]) {
-    unsigned h[4], m[4], l[4];
+template <int NS>
+__device__ __forceinline__ void xc_split4(const f32x4 v, const float scale, u32x2 (&out)[3]) {
+    u32x2 (&first)[NS] = reinterpret_cast<u32x2 (&)[NS]>(out);
+    if constexpr (NS == 2) {             // scaled and split pair by pair, not through the shared split4 (all four products first): the backward
+        unsigned h0, l0, h1, l1;         // kernel's schedule follows this order, and its instruction stream is pinned
+        h2_split2(v[0] * scale, v[1] * scale, h0, l0);
+        h2_split2(v[2] * scale, v[3] * scale, h1, l1);
+        first[0] = u32x2{h0, h1};
+        first[1] = u32x2{l0, l1};
+    } else split4<NS>(v, first);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float x = v[i];
-        split3_bits(x, h[i], m[i], l[i]);
-    }
-    out[0] = u32x2{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3])};
-    out[1] = u32x2{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3])};
-    out[2] = u32x2{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3])};
-}
-
-// fp16 x 2 (common.hpp "two-term fp16 split"): eight / four consecutive fp32, already multiplied by their power-of-two scale, -> hi and lo planes
-__device__ __forceinline__ void xc_split8_h2(const f32x4 a, const f32x4 b, const float scale, bf16x8 (&out)[3]) {
-    unsigned h[4], l[4];
-    h2_split2(a[0] * scale, a[1] * scale, h[0], l[0]);
-    h2_split2(a[2] * scale, a[3] * scale, h[1], l[1]);
-    h2_split2(b[0] * scale, b[1] * scale, h[2], l[2]);
-    h2_split2(b[2] * scale, b[3] * scale, h[3], l[3]);
-    out[0] = as_bf16x8(u32x4{h[0], h[1], h[2], h[3]});
-    out[1] = as_bf16x8(u32x4{l[0], l[1], l[2], l[3]});
-    out[2] = out[1];
-}
-__device__ __forceinline__ void xc_split4_h2(const f32x4 v, const float scale, u32x2 (&out)[3]) {
-    unsigned h0, l0, h1, l1;
-    h2_split2(v[0] * scale, v[1] * scale, h0, l0);
-    h2_split2(v[2] * scale, v[3] * scale, h1, l1);
-    out[0] = u32x2{h0, h1};
-    out[1] = u32x2{l0, l1};
-    out[2] = out[1];
+    for (int s = NS; s < 3; ++s) out[s] = out[NS - 1];
 }
 
 // fp16 x 2 exchange of the backward recurrence: a block's values are scaled to |v| < 2^11 (four binades below the usual target), so every lo
@@ -112,21 +80,6 @@ __device__ __forceinline__ unsigned xc_max8(unsigned v) {
     w = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true); v = v > w ? v : w;             // quad_perm [2, 3, 0, 1]
     w = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true); v = v > w ? v : w;            // row_half_mirror
     return v;
-}
-
-// plain-bf16 tier (math mode 1): one term per operand, rounded to nearest even; plane 0 of the exchange buffer carries it
-__device__ __forceinline__ bf16x8 xc_rne8(const f32x4 a, const f32x4 b) {
-    bf16x8 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { r[i] = (__bf16)a[i]; r[4 + i] = (__bf16)b[i]; }
-    return r;
-}
-__device__ __forceinline__ u32x2 xc_rne4(const f32x4 v) {
-    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-    bf16x4 r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r[i] = (__bf16)v[i];
-    return __builtin_bit_cast(u32x2, r);
 }
 
 // wa: hi and mid planes of the weight fragment (registers); w_lo: its lo plane (read back from LDS: it feeds one MFMA in six)
@@ -279,9 +232,7 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_cluster_x3_kernel(
                 const f32x4 a = (ok && k < H) ? *reinterpret_cast<const f32x4*>(src) : z;          // H % 4 == 0
                 const f32x4 b = (ok && k + 4 < H) ? *reinterpret_cast<const f32x4*>(src + 4) : z;
                 bf16x8 pl[3];
-                if constexpr (NS == 1) { pl[0] = xc_rne8(a, b); pl[1] = pl[2] = pl[0]; }
-                else if constexpr (NS == 2) xc_split8_h2(a, b, wsc[g], pl);
-                else xc_split8(a, b, pl);
+                xc_split8<NS>(a, b, wsc[g], pl);
                 wa[g][p][0] = pl[0]; wa[g][p][1] = pl[1];
                 if constexpr (NS == 3) wlo[wave][g * SPS + p][lane] = pl[2];
             }
@@ -319,7 +270,7 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_cluster_x3_kernel(
 
     const int plane_bytes = b_pad * 64;
     const int slot_bytes = CW * 3 * plane_bytes;                       // one (slot, dir)
-    __amdgpu_buffer_rsrc_t hx_rsrc = __builtin_amdgcn_make_buffer_rsrc(hx, 0, 4 * slot_bytes, XC_RSRC3);
+    __amdgpu_buffer_rsrc_t hx_rsrc = __builtin_amdgcn_make_buffer_rsrc(hx, 0, 4 * slot_bytes, RSRC3_RAW32);
     gu32x* my_flag = (gu32x*)(flags + cl * XC_FLAG_STRIDE + m);
     gu32x* cl_flags = (gu32x*)(flags + cl * XC_FLAG_STRIDE);
     bool aborted = false;
@@ -337,18 +288,17 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_cluster_x3_kernel(
     // at the top of every step for the previous step's output stores, then for the gi loads, then for the bias loads -- three exposed
     // round trips per step.  Now gi for step s + 1 is requested right after step s has published its flag and is in flight during the
     // next hand-off; nothing but the exchange itself is waited for.  (All byte sizes < 2^31: checked by the host.)
-    constexpr unsigned OOB = 0x80000000u;
     const int epi_wave = wave < 2 * MT;                                // scalar: waves that own epilogue threads
-    __amdgpu_buffer_rsrc_t gi_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gi + dir * gi_ds), 0, B * T * 3 * H * 4, XC_RSRC3);
-    __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(Y, 0, B * T * 2 * H * 4, XC_RSRC3);
-    __amdgpu_buffer_rsrc_t yd_rsrc = __builtin_amdgcn_make_buffer_rsrc(y_drop ? y_drop : Y, 0, B * T * 2 * H * 4, XC_RSRC3);
-    __amdgpu_buffer_rsrc_t dm_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(drop_mask ? drop_mask : Y), 0, B * T * 2 * H * 4, XC_RSRC3);
-    __amdgpu_buffer_rsrc_t sv_rsrc = __builtin_amdgcn_make_buffer_rsrc(save ? save + dir * save_ds : Y, 0, save ? B * T * 4 * H * 4 : 0, XC_RSRC3);
-    const unsigned gi_v = e_ok ? (unsigned)((row * T * 3 * H + unit0) * 4) : OOB;          // + (tau * 3H + g * H) * 4 (scalar)
-    const unsigned y_v = e_ok ? (unsigned)((row * T * 2 * H + dir * H + unit0) * 4) : OOB;  // + tau * 2H * 4
+    __amdgpu_buffer_rsrc_t gi_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(gi + dir * gi_ds), 0, B * T * 3 * H * 4, RSRC3_RAW32);
+    __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(Y, 0, B * T * 2 * H * 4, RSRC3_RAW32);
+    __amdgpu_buffer_rsrc_t yd_rsrc = __builtin_amdgcn_make_buffer_rsrc(y_drop ? y_drop : Y, 0, B * T * 2 * H * 4, RSRC3_RAW32);
+    __amdgpu_buffer_rsrc_t dm_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(drop_mask ? drop_mask : Y), 0, B * T * 2 * H * 4, RSRC3_RAW32);
+    __amdgpu_buffer_rsrc_t sv_rsrc = __builtin_amdgcn_make_buffer_rsrc(save ? save + dir * save_ds : Y, 0, save ? B * T * 4 * H * 4 : 0, RSRC3_RAW32);
+    const unsigned gi_v = e_ok ? (unsigned)((row * T * 3 * H + unit0) * 4) : VOFF_OOB;          // + (tau * 3H + g * H) * 4 (scalar)
+    const unsigned y_v = e_ok ? (unsigned)((row * T * 2 * H + dir * H + unit0) * 4) : VOFF_OOB;  // + tau * 2H * 4
     // gates are saved only for the batch rows that will be differentiated (of the three stacked generator calls of a GAN iteration one is:
     // two thirds of the 125 MB per layer were written for nobody); the other lanes' stores fall outside the descriptor and are dropped
-    const unsigned sv_v = (e_ok && row >= save_row0 && row < save_row0 + save_rows) ? (unsigned)((row * T * 4 * H + unit0) * 4) : OOB;   // + (tau * 4H + j * H) * 4
+    const unsigned sv_v = (e_ok && row >= save_row0 && row < save_row0 + save_rows) ? (unsigned)((row * T * 4 * H + unit0) * 4) : VOFF_OOB;   // + (tau * 4H + j * H) * 4
     f32x4 gn[3] = {zero4, zero4, zero4}, mkn = zero4;                  // gi (and the dropout mask) of the NEXT step
     auto prefetch = [&](int st) {
         const int sl = st < T ? st : T - 1;                            // past the end: a valid address again, never used
@@ -398,8 +348,8 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_cluster_x3_kernel(
                         else fb[p % FW][i][s] = as_bf16x8(__builtin_amdgcn_raw_buffer_load_b128(hx_rsrc, r16 * 64 + kq * 16, soff, 16));   // aux 16 = sc1
                     }
             };
-            xc_static_for<FW>([&](auto pc) { if (decltype(pc)::value < s_cnt) load_kstep(pc); });
-            xc_static_for<SPS>([&](auto pc) {
+            static_for<FW>([&](auto pc) { if (decltype(pc)::value < s_cnt) load_kstep(pc); });
+            static_for<SPS>([&](auto pc) {
                 constexpr int p = decltype(pc)::value;
                 if (p < s_cnt) {
 #pragma unroll
@@ -447,9 +397,7 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_cluster_x3_kernel(
             // publish h_t as three bf16 planes: 8-byte write-through stores; the 8 threads of a row cover its 64 bytes, a wave's 8 rows
             // four whole 128-byte lines per plane
             u32x2 pl[3];
-            if constexpr (NS == 1) pl[0] = xc_rne4(h);
-            else if constexpr (NS == 2) xc_split4_h2(h, H_SCALE, pl);
-            else xc_split4(h, pl);
+            xc_split4<NS>(h, H_SCALE, pl);
             const int woff = (dir * 2 + (step & 1)) * slot_bytes + m * 3 * plane_bytes + row * 64 + ug * 8;
             if constexpr (ABL & 16) { asm volatile("" :: "v"(pl[0]), "v"(woff)); }
             else if (fast) {                                   // one XCD: the line stays in the shared L2
@@ -581,9 +529,7 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_cluster_x3_kernel(
                 const f32x4 a = (ok && ku < H) ? *reinterpret_cast<const f32x4*>(src) : z;
                 const f32x4 b = (ok && ku + 4 < H) ? *reinterpret_cast<const f32x4*>(src + 4) : z;
                 bf16x8 pl[3];
-                if constexpr (NS == 1) { pl[0] = xc_rne8(a, b); pl[1] = pl[2] = pl[0]; }
-                else if constexpr (NS == 2) xc_split8_h2(a, b, wscb[u], pl);
-                else xc_split8(a, b, pl);
+                xc_split8<NS>(a, b, wscb[u], pl);
                 wa[u][p][0] = pl[0]; wa[u][p][1] = pl[1];
                 if constexpr (NS == 3) wlo[wave][u * XC_SPB8 + p][lane] = pl[2];
             }
@@ -612,7 +558,7 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_cluster_x3_kernel(
 
     const int plane_bytes = b_pad * 64;
     const int slot_bytes = 3 * CW * 3 * plane_bytes;
-    __amdgpu_buffer_rsrc_t gx_rsrc = __builtin_amdgcn_make_buffer_rsrc(gx, 0, 4 * slot_bytes, XC_RSRC3);
+    __amdgpu_buffer_rsrc_t gx_rsrc = __builtin_amdgcn_make_buffer_rsrc(gx, 0, 4 * slot_bytes, RSRC3_RAW32);
     gu32x* my_flag = (gu32x*)(flags + cl * XC_FLAG_STRIDE + m);
     gu32x* cl_flags = (gu32x*)(flags + cl * XC_FLAG_STRIDE);
     bool aborted = false;
@@ -624,17 +570,16 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_cluster_x3_kernel(
     const unsigned gen = __builtin_amdgcn_readfirstlane(__hip_atomic_load(cl_flags + XC_GEN_WORD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 
     // per-step streams through bounds-checked buffer instructions, requested one step ahead (see the forward kernel)
-    constexpr unsigned OOB = 0x80000000u;
     const int epi_wave = wave < 2;
-    __amdgpu_buffer_rsrc_t dy_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dY), 0, B * T * 2 * H * 4, XC_RSRC3);
-    __amdgpu_buffer_rsrc_t dm_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy_mask ? dy_mask : dY), 0, B * T * 2 * H * 4, XC_RSRC3);
-    __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Y), 0, B * T * 2 * H * 4, XC_RSRC3);
-    __amdgpu_buffer_rsrc_t sv_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(save + dir * save_ds), 0, B * T * 4 * H * 4, XC_RSRC3);
-    __amdgpu_buffer_rsrc_t gi_rsrc = __builtin_amdgcn_make_buffer_rsrc(dgi + dir * dg_ds, 0, B * T * H3 * 4, XC_RSRC3);
-    __amdgpu_buffer_rsrc_t gh_rsrc = __builtin_amdgcn_make_buffer_rsrc(dgh + dir * dg_ds, 0, B * T * H3 * 4, XC_RSRC3);
-    const unsigned y_v = e_ok ? (unsigned)((row * T * 2 * H + dir * H + unit0) * 4) : OOB;  // + tau * 2H * 4
-    const unsigned sv_v = e_ok ? (unsigned)((row * T * 4 * H + unit0) * 4) : OOB;           // + (tau * 4H + j * H) * 4
-    const unsigned dg_v = e_ok ? (unsigned)((row * T * H3 + unit0) * 4) : OOB;              // + (tau * 3H + g * H) * 4
+    __amdgpu_buffer_rsrc_t dy_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dY), 0, B * T * 2 * H * 4, RSRC3_RAW32);
+    __amdgpu_buffer_rsrc_t dm_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(dy_mask ? dy_mask : dY), 0, B * T * 2 * H * 4, RSRC3_RAW32);
+    __amdgpu_buffer_rsrc_t y_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Y), 0, B * T * 2 * H * 4, RSRC3_RAW32);
+    __amdgpu_buffer_rsrc_t sv_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(save + dir * save_ds), 0, B * T * 4 * H * 4, RSRC3_RAW32);
+    __amdgpu_buffer_rsrc_t gi_rsrc = __builtin_amdgcn_make_buffer_rsrc(dgi + dir * dg_ds, 0, B * T * H3 * 4, RSRC3_RAW32);
+    __amdgpu_buffer_rsrc_t gh_rsrc = __builtin_amdgcn_make_buffer_rsrc(dgh + dir * dg_ds, 0, B * T * H3 * 4, RSRC3_RAW32);
+    const unsigned y_v = e_ok ? (unsigned)((row * T * 2 * H + dir * H + unit0) * 4) : VOFF_OOB;  // + tau * 2H * 4
+    const unsigned sv_v = e_ok ? (unsigned)((row * T * 4 * H + unit0) * 4) : VOFF_OOB;           // + (tau * 4H + j * H) * 4
+    const unsigned dg_v = e_ok ? (unsigned)((row * T * H3 + unit0) * 4) : VOFF_OOB;              // + (tau * 3H + g * H) * 4
     f32x4 dy = zero, dm = zero, r = zero, z = zero, n = zero, hn = zero, hp = zero;         // operands of the NEXT step's cell
     unsigned rmx = 0u;                                 // running maximum of this thread's dgi values over all steps (its batch row)
     unsigned cmx[4][4];                                // running column maxima of this thread's four units: gates r, z, n (dgi) and n * r (dgh's third)
@@ -654,7 +599,7 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_cluster_x3_kernel(
         z = as_f32x4(__builtin_amdgcn_raw_buffer_load_b128(sv_rsrc, sv_v, so + H * 4, 0));
         n = as_f32x4(__builtin_amdgcn_raw_buffer_load_b128(sv_rsrc, sv_v, so + 2 * H * 4, 0));
         hn = as_f32x4(__builtin_amdgcn_raw_buffer_load_b128(sv_rsrc, sv_v, so + 3 * H * 4, 0));
-        hp = as_f32x4(__builtin_amdgcn_raw_buffer_load_b128(y_rsrc, has_prev ? y_v : OOB, (has_prev ? tp : 0) * 2 * H * 4, 0));   // h_prev = 0 at the sequence end
+        hp = as_f32x4(__builtin_amdgcn_raw_buffer_load_b128(y_rsrc, has_prev ? y_v : VOFF_OOB, (has_prev ? tp : 0) * 2 * H * 4, 0));   // h_prev = 0 at the sequence end
     };
     if (epi_wave) prefetch(0);
     for (int step = 0; step < T; ++step) {
@@ -731,8 +676,7 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_cluster_x3_kernel(
             // publish this step's dgh tile: blocks (gate 0..2, member m), three bf16 planes each
             const int woff = (dir * 2 + (step & 1)) * slot_bytes + row * 64 + ug * 8;
             u32x2 pl[3][3];
-            if constexpr (NS == 1) { pl[0][0] = xc_rne4(g_r); pl[1][0] = xc_rne4(g_z); pl[2][0] = xc_rne4(g_nr); }
-            else if constexpr (NS == 2) {
+            if constexpr (NS == 2) {
                 // one power of two for the row's 96 values of this member: over this thread's twelve, then over the row's eight threads
                 unsigned mx = 0u;
 #pragma unroll
@@ -744,7 +688,7 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_cluster_x3_kernel(
                 mx = xc_max8(mx);
                 const unsigned eb = (unsigned)h2_exp_of_bits(mx) + XC_GX_EXP_SHIFT;
                 const float sc = h2_scale_of_exp((int)eb);
-                xc_split4_h2(g_r, sc, pl[0]); xc_split4_h2(g_z, sc, pl[1]); xc_split4_h2(g_nr, sc, pl[2]);
+                xc_split4<2>(g_r, sc, pl[0]); xc_split4<2>(g_z, sc, pl[1]); xc_split4<2>(g_nr, sc, pl[2]);
                 // the exponent rides in bit 14 of the lo plane's values (clear by the choice of scale): the consumer's 16-byte chunk is two threads'
                 // values = dwords c = 2 (ug & 1) + k, dword c carries bit c (low half) and bit 4 + c (high half)
                 const int c0 = 2 * (ug & 1);
@@ -753,7 +697,7 @@ __global__ __launch_bounds__(512) void gru_seq_bwd_cluster_x3_kernel(
 #pragma unroll
                 for (int g = 0; g < 3; ++g) { pl[g][1][0] |= in0; pl[g][1][1] |= in1; }
             }
-            else { xc_split4(g_r, pl[0]); xc_split4(g_z, pl[1]); xc_split4(g_nr, pl[2]); }
+            else { xc_split4<NS>(g_r, 1.f, pl[0]); xc_split4<NS>(g_z, 1.f, pl[1]); xc_split4<NS>(g_nr, 1.f, pl[2]); }
             if (fast) {
 #pragma unroll
                 for (int g = 0; g < 3; ++g)

@@ -15,66 +15,13 @@
 // y_drop = y * mask (the next layer's input) and the backward multiplies the incoming gradient by the mask while loading it --
 // the separate dropout / mask-multiply passes and their launches disappear.  The mask is drawn beforehand for all layers of a
 // pass by ONE tg_dropout_mask launch (or injected by the parity tests).
-#include "common.hpp"
+#include "operand_split.hpp"
 #include <type_traits>
 #include <utility>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 namespace tg {
 
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), unrolled
-template <int N, typename F, int... I>
-__device__ __forceinline__ void static_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void static_for(F&& f) { static_for_impl<N>(f, std::make_integer_sequence<int, N>{}); }
-
 constexpr int HS = 64;
-
-// eight consecutive fp32 -> three bf16x8 fragments (hi / mid / lo planes)
-// bf16m (wave-uniform, math mode 1 = plain bf16 operands): plane 0 holds the value rounded to nearest even and is the only plane multiplied
-__device__ __forceinline__ void split8(const f32x4 a, const f32x4 b, bf16x8 (&out)[3], int bf16m) {
-    if (bf16m) {
-        bf16x8 r;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { r[i] = (__bf16)a[i]; r[4 + i] = (__bf16)b[i]; }
-        out[0] = out[1] = out[2] = r;
-        return;
-    }
-    unsigned h[8], m[8], l[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float xa = a[i], xb = b[i];
-        split3_bits(xa, h[i], m[i], l[i]);
-        split3_bits(xb, h[4 + i], m[4 + i], l[4 + i]);
-    }
-    out[0] = __builtin_bit_cast(bf16x8, u32x4{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3]), pack_hi16(h[4], h[5]), pack_hi16(h[6], h[7])});
-    out[1] = __builtin_bit_cast(bf16x8, u32x4{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3]), pack_hi16(m[4], m[5]), pack_hi16(m[6], m[7])});
-    out[2] = __builtin_bit_cast(bf16x8, u32x4{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3]), pack_hi16(l[4], l[5]), pack_hi16(l[6], l[7])});
-}
-
-// four consecutive fp32 -> three 8-byte LDS words (4 bf16 each)
-__device__ __forceinline__ void split4_store(const f32x4 v, __bf16* p0, __bf16* p1, __bf16* p2, int bf16m) {
-    if (bf16m) {
-        typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-        bf16x4 r;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = (__bf16)v[i];
-        *reinterpret_cast<u32x2*>(p0) = __builtin_bit_cast(u32x2, r);
-        return;
-    }
-    unsigned h[4], m[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float x = v[i];
-        split3_bits(x, h[i], m[i], l[i]);
-    }
-    *reinterpret_cast<u32x2*>(p0) = u32x2{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3])};
-    *reinterpret_cast<u32x2*>(p1) = u32x2{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3])};
-    *reinterpret_cast<u32x2*>(p2) = u32x2{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3])};
-}
 
 // Make a fragment opaque to the optimiser.  Without this hipcc REMATERIALISES the pre-split weight fragments inside the step loop -- it keeps
 // only the loaded fp32 weights live and redoes the whole three-way split (and / sub / and / sub / perm per element: ~290 of the 570
@@ -147,18 +94,27 @@ constexpr int OB_LD = 6 * HS + 4;      // floats per LDS row of an output record
 constexpr int IB_LD = 4 * HS + 4;      // floats per LDS row of an operand record [gi_r | gi_z | gi_n | mask]
 constexpr int MOVER_LAG = 1;           // s_sleep argument of the movers after each barrier (64 cycles per unit)
 
-// eight consecutive fp32 -> NS bf16x8 fragments (NS == 1: rounded to nearest even; NS == 3: exact hi / mid / lo)
-// fp16 x 2: eight consecutive fp32 times their power-of-two scale -> hi / lo fp16 fragments (bit patterns in bf16x8 registers)
-__device__ __forceinline__ void split8_h2(const f32x4 a, const f32x4 b, const float scale, bf16x8 (&out)[2]) {
-    unsigned h[4], l[4];
-    h2_split2(a[0] * scale, a[1] * scale, h[0], l[0]);
-    h2_split2(a[2] * scale, a[3] * scale, h[1], l[1]);
-    h2_split2(b[0] * scale, b[1] * scale, h[2], l[2]);
-    h2_split2(b[2] * scale, b[3] * scale, h[3], l[3]);
-    out[0] = __builtin_bit_cast(bf16x8, u32x4{h[0], h[1], h[2], h[3]});
-    out[1] = __builtin_bit_cast(bf16x8, u32x4{l[0], l[1], l[2], l[3]});
+// four consecutive fp32 -> NS 8-byte LDS words.  Kept beside the kernels instead of going through operand_split.hpp's split4: each plane's word
+// is packed and STORED before the next one is packed, and the fp16 x 2 form scales and splits pair by pair -- with the shared function (all
+// words first, then the stores) the step loop's schedule changes, and this file's kernels are pinned instruction for instruction.
+template <int NS>
+__device__ __forceinline__ void split4_store(const f32x4 v, __bf16* p0, __bf16* p1, __bf16* p2) {
+    if constexpr (NS == 1) {
+        u32x2 o[1];
+        split4<1>(v, o);
+        *reinterpret_cast<u32x2*>(p0) = o[0];
+    } else {
+        unsigned h[4], m[4], l[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const float x = v[i];                    // (scalar copy: see the hipcc 7.2 note in operand_split.hpp)
+            split3_bits(x, h[i], m[i], l[i]);
+        }
+        *reinterpret_cast<u32x2*>(p0) = u32x2{pack_hi16(h[0], h[1]), pack_hi16(h[2], h[3])};
+        *reinterpret_cast<u32x2*>(p1) = u32x2{pack_hi16(m[0], m[1]), pack_hi16(m[2], m[3])};
+        *reinterpret_cast<u32x2*>(p2) = u32x2{pack_hi16(l[0], l[1]), pack_hi16(l[2], l[3])};
+    }
 }
-// ... four consecutive fp32 -> two 8-byte LDS words
 __device__ __forceinline__ void split4_store_h2(const f32x4 v, const float scale, __bf16* p0, __bf16* p1) {
     unsigned h0, l0, h1, l1;
     h2_split2(v[0] * scale, v[1] * scale, h0, l0);
@@ -166,24 +122,6 @@ __device__ __forceinline__ void split4_store_h2(const f32x4 v, const float scale
     *reinterpret_cast<u32x2*>(p0) = u32x2{h0, h1};
     *reinterpret_cast<u32x2*>(p1) = u32x2{l0, l1};
 }
-
-template <int NS>
-__device__ __forceinline__ void split8_ns(const f32x4 a, const f32x4 b, bf16x8 (&out)[NS]) {
-    static_assert(NS != 2, "fp16 x 2 operands are split with their scale: split8_h2");
-    if constexpr (NS == 1) {
-        bf16x8 r;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { r[i] = (__bf16)a[i]; r[4 + i] = (__bf16)b[i]; }
-        out[0] = r;
-    } else {
-        bf16x8 t[3];
-        split8(a, b, t, 0);
-        out[0] = t[0]; out[1] = t[1]; out[2] = t[2];
-    }
-}
-// four consecutive fp32 -> NS 8-byte LDS words
-template <int NS>
-__device__ __forceinline__ void split4_store_ns(const f32x4 v, __bf16* p0, __bf16* p1, __bf16* p2) { split4_store(v, p0, p1, p2, NS == 1 ? 1 : 0); }
 template <int NS>
 __device__ __forceinline__ f32x4 mma_ns(const bf16x8 (&wa)[NS], const bf16x8 (&fb)[NS], f32x4 acc) {
     static_assert(NS != 2, "lab projection: bf16 operands only");
@@ -303,7 +241,7 @@ __global__ __launch_bounds__(512) void gru_h64_fwd2_kernel(
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks) {
                     const float* p = whh0 + (long)((((wave - 4) * 6 + tl) * 16 + pr16) % 192) * HS + 32 * ks + 8 * pkq;
-                    split8_ns<NS>(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4), pw[tl][ks]);
+                    split8<NS>(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4), pw[tl][ks]);
 #pragma unroll
                     for (int sp = 0; sp < NS; ++sp) pin_fragment(pw[tl][ks][sp]);
                 }
@@ -315,7 +253,7 @@ __global__ __launch_bounds__(512) void gru_h64_fwd2_kernel(
                 bf16x8 fbp[2][NS];
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
-                    split8_ns<NS>(*reinterpret_cast<const f32x4*>(rec + 32 * ks), *reinterpret_cast<const f32x4*>(rec + 32 * ks + 4), fbp[ks]);
+                    split8<NS>(*reinterpret_cast<const f32x4*>(rec + 32 * ks), *reinterpret_cast<const f32x4*>(rec + 32 * ks + 4), fbp[ks]);
                 const int rowg = min((int)blockIdx.x * RW + (pr16 & (RW - 1)), B - 1);
                 float* dst = save + dir * save_ds + ((long)rowg * T + tau_o) * (4 * HS) + 4 * pkq;
 #pragma unroll
@@ -397,10 +335,10 @@ __global__ __launch_bounds__(512) void gru_h64_fwd2_kernel(
                 winv[g][q] = h2_inv_of_exp(h2_exp_of_bits(mq)) * (1.f / H_SCALE);
             }
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) split8_h2(wv[ks][0], wv[ks][1], wsc, wa[g][ks]);
+            for (int ks = 0; ks < 2; ++ks) split8(wv[ks][0], wv[ks][1], wsc, wa[g][ks]);
         } else {
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) split8_ns<NS>(wv[ks][0], wv[ks][1], wa[g][ks]);
+            for (int ks = 0; ks < 2; ++ks) split8<NS>(wv[ks][0], wv[ks][1], wa[g][ks]);
         }
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
@@ -554,7 +492,7 @@ __global__ __launch_bounds__(512) void gru_h64_fwd2_kernel(
         if constexpr (!(ABL & 16)) {
             const int cs = swz_col(rr, u0);
             if constexpr (NS == 2) split4_store_h2(h, H_SCALE, &hs[wb][0][rr][cs], &hs[wb][1][rr][cs]);
-            else split4_store_ns<NS>(h, &hs[wb][0][rr][cs], &hs[wb][1][rr][cs], &hs[wb][2][rr][cs]);
+            else split4_store<NS>(h, &hs[wb][0][rr][cs], &hs[wb][1][rr][cs], &hs[wb][2][rr][cs]);
         }
         else asm volatile("" :: "v"(h));
         TG_STAMP(step, 4);                   // h_t split and in LDS (stores complete)
@@ -684,7 +622,7 @@ __global__ __launch_bounds__(512) void gru_h64_bwd2_kernel(
 #pragma unroll
     for (int ks = 0; ks < 6; ++ks) {
         const float* p = wt + (long)(16 * wave + r16) * (3 * HS) + 32 * ks + 8 * kq;
-        split8_ns<NS>(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4), wa[ks]);
+        split8<NS>(*reinterpret_cast<const f32x4*>(p), *reinterpret_cast<const f32x4*>(p + 4), wa[ks]);
 #pragma unroll
         for (int s = 0; s < NS; ++s) pin_fragment(wa[ks][s]);
     }
@@ -798,9 +736,9 @@ __global__ __launch_bounds__(512) void gru_h64_bwd2_kernel(
         if constexpr (ABL & 16) { asm volatile("" :: "v"(g_r), "v"(g_z), "v"(g_nr)); }
         else {
             const int c0 = swz_col(rr, u0), c1 = swz_col(rr, HS + u0), c2 = swz_col(rr, 2 * HS + u0);
-            split4_store_ns<NS>(g_r, &dgs[wb][0][rr][c0], &dgs[wb][1][rr][c0], &dgs[wb][2][rr][c0]);
-            split4_store_ns<NS>(g_z, &dgs[wb][0][rr][c1], &dgs[wb][1][rr][c1], &dgs[wb][2][rr][c1]);
-            split4_store_ns<NS>(g_nr, &dgs[wb][0][rr][c2], &dgs[wb][1][rr][c2], &dgs[wb][2][rr][c2]);
+            split4_store<NS>(g_r, &dgs[wb][0][rr][c0], &dgs[wb][1][rr][c0], &dgs[wb][2][rr][c0]);
+            split4_store<NS>(g_z, &dgs[wb][0][rr][c1], &dgs[wb][1][rr][c1], &dgs[wb][2][rr][c1]);
+            split4_store<NS>(g_nr, &dgs[wb][0][rr][c2], &dgs[wb][1][rr][c2], &dgs[wb][2][rr][c2]);
         }
         TG_STAMP(step, 4);
         q_r = g_r; q_z = g_z; q_n = g_n; q_nr = g_nr;

@@ -23,7 +23,7 @@
 // leave at once): when the ids published with h_0 confirm it, stores become plain (the line stays in that XCD's L2) instead of write-through;
 // loads are sc1 (L1 bypass) either way -- the same instruction flavours as the cluster kernels' hand-off.
 // Every spin is bounded; a timeout sets the workspace's sticky word (ops.check_async_errors raises and refills the workspace).
-#include "common.hpp"
+#include "operand_split.hpp"
 
 namespace tg {
 
@@ -34,7 +34,6 @@ constexpr int VEC_KSL = 20;           // a lane's K slice at most (H <= 320 over
 constexpr int VEC_PAD = 16;           // words behind a row's H values: the members' hello words (row 0 of a direction)
 constexpr int VEC_HDR = 32;           // workspace words in front of the exchange buffers: [0, 16) timeout block, [16] launch counter
 constexpr unsigned VEC_SPIN_LIMIT = 1u << 22;
-constexpr unsigned VEC_RSRC3 = 0x00020000u;
 
 __device__ __forceinline__ unsigned vec_my_xcc() {
     unsigned v;
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_vec_kernel(
     const int buf_w = 3 * slot_w;
     const unsigned launch = __builtin_amdgcn_readfirstlane(__hip_atomic_load((vgu32*)ws + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     const int P = (int)(launch & 1u);
-    __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(ws + VEC_HDR, 0, 2 * buf_w * 4, VEC_RSRC3);
+    __amdgpu_buffer_rsrc_t x_rsrc = __builtin_amdgcn_make_buffer_rsrc(ws + VEC_HDR, 0, 2 * buf_w * 4, RSRC3_RAW32);
     const int my_w = (dir * VEC_ROWS + row) * LD + unit;   // this lane's word inside a slot (own lanes)
     const int hello_w = dir * VEC_ROWS * LD + H;           // + member
     const unsigned my_xcc = vec_my_xcc();

@@ -4,7 +4,7 @@
 // go global -> LDS by DMA in the mover-wave kernel (gemm_mw.hip), which then multiplies without any split arithmetic on that operand.
 // (Rounds 2-3 also had kernels that took BOTH operands pre-split -- level with splitting the activation while it is staged, DESIGN.md
 // section 5; removed in round 4.)
-#include "common.hpp"
+#include "operand_split.hpp"
 #include <stdlib.h>
 
 namespace tg {
@@ -22,7 +22,7 @@ __global__ __launch_bounds__(256) void split3_planes_kernel(const float* __restr
     }
 }
 
-// fp32 [rows][cw] -> fp16 x 2 planes [2][rows + 1][cwp] + inv[rows + 1] (common.hpp h2_write_row): one wave per row
+// fp32 [rows][cw] -> fp16 x 2 planes [2][rows + 1][cwp] + inv[rows + 1] (operand_split.hpp h2_write_row): one wave per row
 __global__ __launch_bounds__(256) void split2h_planes_kernel(const float* __restrict__ x, long ldx, int rows, int cw, int cwp, _Float16* __restrict__ planes,
                                                              long plane_stride, float* __restrict__ inv, int vec) {
     const int lane = threadIdx.x & 63;

@@ -22,7 +22,7 @@
 // result is bit-identical from run to run.
 //
 // LDS: 68 x 300 fp32 block input 81 600 B | 2 planes x 68 x 600 B = 81 600 B | 16 B zero | 2 x 68 row maxima 544 B = 163 760 of 163 840 B.
-#include "common.hpp"
+#include "operand_split.hpp"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -35,9 +35,6 @@ constexpr int TF_X_OFF = 0, TF_PL_OFF = TF_ROWS * TF_C * 4, TF_ZERO_OFF = TF_PL_
 constexpr int TF_LDS = TF_RMAX_OFF + 2 * TF_ROWS * 4;
 constexpr int TF_Q_TAP = TF_C / 4;                      // 8-byte pieces (4 channels) per tap
 static_assert(TF_LDS <= 163840 && TF_PL_OFF % 16 == 0 && TF_PLANE % 8 == 0 && TF_ROWB % 8 == 0, "LDS layout");
-
-typedef unsigned tf_u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned tf_u32x4 __attribute__((ext_vector_type(4)));
 
 struct TcnArgs {
     const float* x0;                 // [clips][T][C]: the embedding-dropout output
@@ -80,8 +77,8 @@ __device__ __forceinline__ void tcn_fwd_fused_body(const TcnArgs& a, unsigned ch
         h2_split2(v[0] * s, v[1] * s, h0, l0);
         h2_split2(v[2] * s, v[3] * s, h1, l1);
         unsigned char* const q = pl + row * TF_ROWB + col * 2;
-        *reinterpret_cast<tf_u32x2*>(q) = tf_u32x2{h0, h1};
-        *reinterpret_cast<tf_u32x2*>(q + TF_PLANE) = tf_u32x2{l0, l1};
+        *reinterpret_cast<u32x2*>(q) = u32x2{h0, h1};
+        *reinterpret_cast<u32x2*>(q + TF_PLANE) = u32x2{l0, l1};
     };
     auto absmax4 = [](unsigned m, const f32x4 v) __attribute__((always_inline)) {
 #pragma unroll
@@ -170,15 +167,15 @@ __device__ __forceinline__ void tcn_fwd_fused_body(const TcnArgs& a, unsigned ch
 #pragma unroll
             for (int i = 0; i < TF_MT; ++i) {
                 const int ro = TAP ? rowoff1[i] : rowoff0[i];
-                tf_u32x2 xh[2], xl[2];
+                u32x2 xh[2], xl[2];
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
                     const bool v = ok[h] && ro >= 0;
-                    xh[h] = *reinterpret_cast<const tf_u32x2*>(pl + (v ? ro + cb[h] : ZREL));
-                    xl[h] = *reinterpret_cast<const tf_u32x2*>(pl + (v ? ro + cb[h] + TF_PLANE : ZREL));
+                    xh[h] = *reinterpret_cast<const u32x2*>(pl + (v ? ro + cb[h] : ZREL));
+                    xl[h] = *reinterpret_cast<const u32x2*>(pl + (v ? ro + cb[h] + TF_PLANE : ZREL));
                 }
-                const tg_f16x8 fh = __builtin_bit_cast(tg_f16x8, tf_u32x4{xh[0][0], xh[0][1], xh[1][0], xh[1][1]});
-                const tg_f16x8 fl = __builtin_bit_cast(tg_f16x8, tf_u32x4{xl[0][0], xl[0][1], xl[1][0], xl[1][1]});
+                const tg_f16x8 fh = __builtin_bit_cast(tg_f16x8, u32x4{xh[0][0], xh[0][1], xh[1][0], xh[1][1]});
+                const tg_f16x8 fl = __builtin_bit_cast(tg_f16x8, u32x4{xl[0][0], xl[0][1], xl[1][0], xl[1][1]});
                 // lo_w hi_x + hi_w lo_x + hi_w hi_x (smallest terms first, as gemm_mw.hip)
                 // (term-major over the column tiles: the instructions that accumulate into one tile are NJ issues apart)
 #pragma unroll

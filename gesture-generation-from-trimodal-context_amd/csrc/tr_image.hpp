@@ -1,9 +1,7 @@
 // LDS image of a 32-row operand slab whose fragments are read TRANSPOSED (ds_read_b64_tr_b16): the weight-gradient kernels' operands are
 // row (m) major in memory while the MFMA wants eight consecutive m of one column per lane.  Shared by gemm_split.hip and gemm_tn_mw.hip.
 #pragma once
-#include "common.hpp"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+#include "operand_split.hpp"
 
 namespace tg {
 

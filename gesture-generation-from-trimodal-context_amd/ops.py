@@ -424,8 +424,7 @@ def deterministic():
     return bool(_lib.load().tg_get_deterministic())
 
 
-import os as _os
-TN_MW_WS = _os.environ.get("TG_TN_MW_WS", "1") != "0"              # mover-wave weight gradients combine their row splits through a workspace + fixed-order second pass (not float atomics)
+TN_MW_WS = os.environ.get("TG_TN_MW_WS", "1") != "0"              # mover-wave weight gradients combine their row splits through a workspace + fixed-order second pass (not float atomics)
 
 
 def absmax_rows_cols(x2d, *, groups=1, want_rows=False, want_cols=True, rowmax=None, colmax=None):
