@@ -176,6 +176,9 @@ SIGNATURES = {
     "tg_sumsq_accumulate": [P, I64, P, P, P],
     "tg_clip_scale": [P, F32, P, P],
     "tg_scale_by": [P, I64, P, P],
+    "tg_latent_head_supported": [I32, I32, I32, I32, I32, P],
+    "tg_latent_head_fwd": [P, I64] + [P] * 15 + [U32, P, I64] + [P] * 6 + [I32] * 5 + [F32, F32, F32, P],
+    "tg_latent_head_bwd": [P, I64, P, P, P, I64] + [P] * 23 + [I64] + [I32] * 5 + [F32, P],
 }
 
 ABI_VERSION = 11

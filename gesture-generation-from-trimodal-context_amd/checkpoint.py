@@ -37,7 +37,8 @@ _ref_pickle.loads = lambda b, **kw: _RefUnpickler(io.BytesIO(b), **kw).load()
 
 def init_model(args, lang_model, speaker_model, pose_dim, _device):
     """train.py:36-62 for the models on the hot path ('multimodal_context', 'gesture_autoencoder') and the Speech2Gesture and Seq2Seq
-    baselines ('seq2seq': (Seq2SeqNet, None, L1Loss); the reference passes it no speaker model).  'joint_embedding' is not implemented."""
+    baselines ('seq2seq': (Seq2SeqNet, None, L1Loss); the reference passes it no speaker model).  'joint_embedding' keeps raising NotImplementedError here (callers rely on it): that model is built by
+    joint_embed.build_model and loaded by joint_embed.load_checkpoint_and_model."""
     generator = discriminator = loss_fn = None
     if args.model == "multimodal_context":
         generator = PoseGenerator(args, n_words=lang_model.n_words, word_embed_size=args.wordembed_dim,

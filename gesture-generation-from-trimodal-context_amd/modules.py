@@ -238,26 +238,48 @@ class _PoseDecoderParams(nn.Module):
 
 
 class EmbeddingNet(nn.Module):
-    """FGD feature extractor / pose autoencoder: the mode='pose' variant of model/embedding_net.py:262-314."""
+    """model/embedding_net.py:262-314.  mode='pose': the FGD feature extractor / pose autoencoder (PoseEncoderConv + PoseDecoderConv) on
+    AutoencoderEngine.  mode in ('random', 'speech'): the joint-embedding baseline -- ContextEncoder, PoseEncoderConv and PoseDecoderGRU
+    (joint_embed.py); both encoders run whenever their inputs are given, the decoder takes the latent `input_mode` names ('random': Python's
+    random.random() > 0.5 picks 'speech', as the reference).  Parity tests queue one dict of injected draws per forward in `_replay_draws`
+    ('c.eps', 'c.emb_drop', 'c.tcn<i>.drop<j>', 'g.gru.drop<l>')."""
 
     def __init__(self, args, pose_dim, n_frames, n_words=None, word_embed_size=None, word_embeddings=None, mode="pose"):
         super().__init__()
-        if mode != "pose" or n_frames != 34:
-            raise NotImplementedError("HIP path implements mode='pose' with 34-frame clips (config/gesture_autoencoder.yml)")
-        self.context_encoder = None
+        if mode not in ("pose", "random", "speech") or n_frames != 34:
+            raise NotImplementedError("HIP path implements mode in ('pose', 'random', 'speech') with 34-frame clips")
         self.pose_dim = pose_dim
-        self.pose_encoder = _PoseEncoderParams(pose_dim)
-        self.decoder = _PoseDecoderParams(pose_dim)
         self.mode = mode
         self._engine = None
+        self._replay_draws = []
+        if mode != "pose":
+            from .joint_embed import ContextEncoder, PoseDecoderGRU
+            self.context_encoder = ContextEncoder(args, n_frames, n_words, word_embed_size, word_embeddings)
+            self.pose_encoder = _PoseEncoderParams(pose_dim)
+            self.decoder = PoseDecoderGRU(n_frames, pose_dim)
+            return
+        self.context_encoder = None
+        self.pose_encoder = _PoseEncoderParams(pose_dim)
+        self.decoder = _PoseDecoderParams(pose_dim)
 
     @property
     def engine(self) -> AutoencoderEngine:
+        if self.mode != "pose":
+            raise AttributeError("EmbeddingNet: only mode='pose' runs on an AutoencoderEngine")
         if self._engine is None:
             object.__setattr__(self, "_engine", AutoencoderEngine(self))
         return self._engine
 
+    def freeze_pose_nets(self):
+        for param in self.pose_encoder.parameters():
+            param.requires_grad = False
+        for param in self.decoder.parameters():
+            param.requires_grad = False
+
     def forward(self, in_text, in_audio, pre_poses, poses, input_mode=None, variational_encoding=False):
+        if self.mode != "pose":
+            from .joint_embed import embedding_forward
+            return embedding_forward(self, in_text, in_audio, pre_poses, poses, input_mode, variational_encoding)
         if variational_encoding:
             raise NotImplementedError("variational_encoding=True is not on the reference's configured path")
         eng = self.engine

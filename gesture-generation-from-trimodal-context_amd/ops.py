@@ -2256,3 +2256,93 @@ def fgd_from_stats(mu1, sigma1, mu2, sigma2, out=None):
         raise ValueError(f"fgd_from_stats: out needs {FGD_OUT_DOUBLES} doubles")
     call("tg_fgd_from_stats", _p(mu1), _p(sigma1), _p(mu2), _p(sigma2), D, _p(out), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------------- latent heads (csrc/latent_head.hip)
+LATENT_HEAD_ENVELOPE = "1 <= B <= 512 (2 <= B in train mode), 1 <= K0 <= 384, 1 <= N1 <= 256, 1 <= N2 <= 64"
+
+
+def latent_head_supported(B, K0, N1, N2, training):
+    """True when tg_latent_head_fwd / tg_latent_head_bwd take the shape (LATENT_HEAD_ENVELOPE)."""
+    if min(int(B), int(K0), int(N1), int(N2)) < 1:
+        return False
+    out = C.c_int32(0)
+    call("tg_latent_head_supported", int(B), int(K0), int(N1), int(N2), int(bool(training)), C.cast(C.byref(out), C.c_void_p))
+    return bool(out.value)
+
+
+class LatentHeadTape:
+    __slots__ = ("x", "h1", "stats", "h2", "mu", "logvar", "eps", "dims", "training", "slope")
+
+
+def _lh_dims(x, w1, w2, training):
+    _f32(x, "x"); assert x.dim() == 2 and x.stride(1) == 1, "x: a 2-D view with unit inner stride"
+    B, K0 = x.shape
+    N1, N2 = w1.shape[0], w2.shape[0]
+    assert tuple(w1.shape) == (N1, K0) and tuple(w2.shape) == (N2, N1)
+    if training and B == 1:
+        raise ValueError("latent head: BatchNorm in train mode needs more than one row (B = 1)")
+    if not latent_head_supported(B, K0, N1, N2, training):
+        raise ValueError(f"latent head: (B, K0, N1, N2) = {(B, K0, N1, N2)} is outside the kernel envelope {LATENT_HEAD_ENVELOPE}; there is no torch fallback")
+    _chk2d(x, B, K0, "x")
+    return B, K0, N1, N2
+
+
+def latent_head_fwd(x, w1, b1, gamma, beta, running_mean, running_var, nbt, w2, b2, out, *, training, slope, tail=None, eps=None, draw=None,
+                    bn_eps=1e-5, momentum=0.1):
+    """One launch: out = Linear2(act(BatchNorm(Linear1(x)))) or, with tail = (Wmu, bmu, Wlv, blv), out = z = mu + eps exp(logvar / 2) over it.
+    x: 2-D view (row stride free); out: 2-D view [B, N2] (a column block of a wider row).  eps [B, N2] is read, or -- draw = (rng_state, site) --
+    written by the launch.  Returns the tape for latent_head_bwd (with mu / logvar for the tail)."""
+    B, K0, N1, N2 = _lh_dims(x, w1, w2, training)
+    for t, n in ((w1, N1 * K0), (b1, N1), (gamma, N1), (beta, N1), (running_mean, N1), (running_var, N1), (w2, N2 * N1), (b2, N2)):
+        _flat(t, "parameter"); assert t.numel() == n
+    assert nbt is None or (nbt.dtype == torch.int64 and nbt.is_cuda)
+    _chk2d(out, B, N2, "out"); assert tuple(out.shape) == (B, N2)
+    dev = x.device
+    tp = LatentHeadTape()
+    tp.x, tp.dims, tp.training, tp.slope = x, (B, K0, N1, N2), bool(training), float(slope)
+    tp.h1, tp.stats = torch.empty(B, N1, device=dev), torch.empty(2 * N1, device=dev, dtype=torch.float64)
+    act_ws = torch.empty(B, N1, device=dev)
+    tp.h2 = tp.mu = tp.logvar = tp.eps = None
+    tw = [None] * 4
+    state, site = None, 0
+    if tail is not None:
+        tw = list(tail)
+        for t, n in zip(tw, (N2 * N2, N2, N2 * N2, N2)):
+            _flat(t, "tail parameter"); assert t.numel() == n
+        tp.h2, tp.mu, tp.logvar = (torch.empty(B, N2, device=dev) for _ in range(3))
+        if draw is not None:
+            state, site = _i64(draw[0], "rng_state"), int(draw[1])
+            tp.eps = torch.empty(B, N2, device=dev)
+        else:
+            if eps is None:
+                raise ValueError("latent head: the variational tail needs eps [B, N2] or draw = (rng_state, site)")
+            tp.eps = _flat(eps, "eps"); assert tuple(eps.shape) == (B, N2)
+    call("tg_latent_head_fwd", _p(x), x.stride(0), _p(w1), _p(b1), _p(gamma), _p(beta), _p(running_mean), _p(running_var), _p(nbt), _p(w2), _p(b2),
+         _p(tw[0]), _p(tw[1]), _p(tw[2]), _p(tw[3]), _p(tp.eps), _p(state), site, _p(out), out.stride(0), _p(tp.h1), _p(act_ws), _p(tp.stats),
+         _p(tp.h2), _p(tp.mu), _p(tp.logvar), B, K0, N1, N2, int(bool(training)), float(slope), float(bn_eps), float(momentum), _stream())
+    return tp
+
+
+def latent_head_bwd(dout, tp, w1, gamma, beta, w2, *, tail=None, dmu=None, dlv=None, dx=None):
+    """One launch: every parameter gradient of the head (written, not accumulated) -> dict; dout: 2-D view [B, N2]; dx: optional 2-D view
+    [B, K0] (row stride free) that receives the input gradient."""
+    B, K0, N1, N2 = tp.dims
+    _chk2d(dout, B, N2, "dout"); assert tuple(dout.shape) == (B, N2)
+    dev = dout.device
+    G = {"w1": torch.empty(N1, K0, device=dev), "b1": torch.empty(N1, device=dev), "gamma": torch.empty(N1, device=dev),
+         "beta": torch.empty(N1, device=dev), "w2": torch.empty(N2, N1, device=dev), "b2": torch.empty(N2, device=dev)}
+    wmu = wlv = None
+    if tail is not None:
+        wmu, wlv = tail
+        G.update(wmu=torch.empty(N2, N2, device=dev), bmu=torch.empty(N2, device=dev), wlv=torch.empty(N2, N2, device=dev), blv=torch.empty(N2, device=dev))
+        for t in (dmu, dlv):
+            assert t is None or tuple(_flat(t, "direct gradient").shape) == (B, N2)
+    if dx is not None:
+        _chk2d(dx, B, K0, "dx"); assert tuple(dx.shape) == (B, K0)
+    ws = torch.empty(2 * B * N1 + 3 * B * N2, device=dev)
+    call("tg_latent_head_bwd", _p(dout), dout.stride(0), _p(dmu), _p(dlv), _p(tp.x), tp.x.stride(0), _p(w1), _p(gamma), _p(beta), _p(w2), _p(wmu),
+         _p(wlv), _p(tp.eps), _p(tp.h1), _p(tp.stats), _p(tp.h2), _p(tp.logvar), _p(ws), _p(G["w1"]), _p(G["b1"]), _p(G["gamma"]), _p(G["beta"]),
+         _p(G["w2"]), _p(G["b2"]), _p(G.get("wmu")), _p(G.get("bmu")), _p(G.get("wlv")), _p(G.get("blv")), _p(dx), dx.stride(0) if dx is not None else 0,
+         B, K0, N1, N2, int(tp.training), float(tp.slope), _stream())
+    return G

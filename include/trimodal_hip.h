@@ -943,6 +943,30 @@ int tg_sumsq_accumulate(const float* g, int64_t n, double* ws, double* total, vo
 int tg_clip_scale(const double* total, float max_norm, float* out, void* stream);
 int tg_scale_by(float* x, int64_t n, const float* scale, void* stream);
 
+/* ---- latent-head MLPs of the joint-embedding baseline (csrc/latent_head.hip; model/embedding_net.py:138-143, 230-259)
+ * Linear(K0, N1) -> BatchNorm1d(N1) over the B rows -> act(slope: 0 ReLU, 1 identity) -> Linear(N1, N2) [-> fc_mu, fc_logvar (N2 x N2) ->
+ * z = mu + eps exp(logvar / 2) when Wmu != NULL], ONE launch of one workgroup each way, no atomics, fixed summation order.
+ * x is read with row stride ldx (the last step of a [B][T][K0] GRU output: x + (T - 1) K0, ldx = T K0); the result (z with the tail, the
+ * second linear's output without) is written with row stride ldo (a column block of a wider row).  Train mode: batch statistics in fp64, the
+ * biased variance normalises, the unbiased one feeds running_var (momentum), *nbt += 1; eval mode: the running statistics.
+ * tg_latent_head_fwd leaves for the backward: h1 [B][N1] (pre-BatchNorm), stats [2 N1] DOUBLES (mean, 1 / sqrt(var + eps): the BatchNorm backward cancels almost completely at B = 2), and with the tail h2 [B][N2],
+ * mu, logvar, eps [B][N2] (eps is READ when rng_state == NULL, otherwise WRITTEN: element i of tg_normal(eps, B N2, rng_state, site));
+ * act_ws [B][N1] is scratch.  tg_latent_head_bwd: dout with row stride ldo, optional direct gradients dmu / dlv [B][N2] (tail), ws of
+ * 2 B N1 + 3 B N2 floats; every gradient is WRITTEN (not accumulated); dx (optional) with row stride lddx.
+ * Envelope: 1 <= B <= 512 (B >= 2 in train mode), 1 <= K0 <= 384, 1 <= N1 <= 256, 1 <= N2 <= 64; outside it both return non-zero, set
+ * tg_last_error ("envelope") and launch nothing; tg_latent_head_supported writes 1 / 0. */
+int tg_latent_head_supported(int32_t B, int32_t K0, int32_t N1, int32_t N2, int32_t training, int32_t* supported);
+int tg_latent_head_fwd(const float* x, int64_t ldx, const float* W1, const float* b1, const float* gamma, const float* beta,
+                       float* running_mean, float* running_var, int64_t* nbt, const float* W2, const float* b2, const float* Wmu,
+                       const float* bmu, const float* Wlv, const float* blv, float* eps, const uint64_t* rng_state, uint32_t site,
+                       float* out, int64_t ldo, float* h1, float* act_ws, double* stats, float* h2, float* mu, float* logvar, int32_t B,
+                       int32_t K0, int32_t N1, int32_t N2, int32_t training, float slope, float bn_eps, float momentum, void* stream);
+int tg_latent_head_bwd(const float* dout, int64_t ldo, const float* dmu, const float* dlv, const float* x, int64_t ldx, const float* W1,
+                       const float* gamma, const float* beta, const float* W2, const float* Wmu, const float* Wlv, const float* eps,
+                       const float* h1, const double* stats, const float* h2, const float* logvar, float* ws, float* dW1, float* db1,
+                       float* dgamma, float* dbeta, float* dW2, float* db2, float* dWmu, float* dbmu, float* dWlv, float* dblv, float* dx,
+                       int64_t lddx, int32_t B, int32_t K0, int32_t N1, int32_t N2, int32_t training, float slope, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
