@@ -23,6 +23,8 @@
 // leave at once): when the ids published with h_0 confirm it, stores become plain (the line stays in that XCD's L2) instead of write-through;
 // loads are sc1 (L1 bypass) either way -- the same instruction flavours as the cluster kernels' hand-off.
 // Every spin is bounded; a timeout sets the workspace's sticky word (ops.check_async_errors raises and refills the workspace).
+// The direction count ND is a template parameter: ND = 2 is the generator's / PoseDecoderGRU's layer, ND = 1 (tg_gru_forward_vec1) the
+// ContextEncoder's unidirectional H = 256 GRU of the joint-embedding baseline (embedding_net.py:233) with ceil(H / 32) members.
 #include "operand_split.hpp"
 
 namespace tg {
@@ -49,14 +51,14 @@ __device__ __forceinline__ float vec_row_sum(float v) {
     return v;
 }
 
-template <int RB>
+template <int RB, int ND>
 __global__ __launch_bounds__(512) void gru_seq_fwd_vec_kernel(
     const float* __restrict__ gi, long gi_ds, const float* __restrict__ whh0, const float* __restrict__ whh1,
     const float* __restrict__ bhh0, const float* __restrict__ bhh1, float* __restrict__ Y, unsigned* ws, int B, int T, int H, int CW) {
     __shared__ __attribute__((aligned(16))) float hbuf[2][RB][16 * VEC_KSL];
     if (blockIdx.x & 7) return;
     const int id = blockIdx.x >> 3;
-    const int dir = id / CW, m = id - dir * CW;
+    const int dir = ND == 2 ? id / CW : 0, m = id - dir * CW;       // ND == 1: one direction, whh1 / bhh1 unused
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int ksl = lane & 15;
     const int unit = 32 * m + wave * 4 + (lane >> 4);
@@ -88,7 +90,7 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_vec_kernel(
     }
 
     const int LD = H + VEC_PAD;
-    const int slot_w = 2 * VEC_ROWS * LD;                  // words per slot (both directions)
+    const int slot_w = ND * VEC_ROWS * LD;                 // words per slot (all directions)
     const int buf_w = 3 * slot_w;
     const unsigned launch = __builtin_amdgcn_readfirstlane(__hip_atomic_load((vgu32*)ws + 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     const int P = (int)(launch & 1u);
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_vec_kernel(
 
     // the step's gi values of (unit, row), requested one step ahead
     const float* gi_p = gi + dir * gi_ds + (long)(r_ok ? row : 0) * T * 3 * H + (r_ok ? unit : 0);
-    float* y_p = Y + (long)(r_ok ? row : 0) * T * 2 * H + dir * H + (r_ok ? unit : 0);
+    float* y_p = Y + (long)(r_ok ? row : 0) * T * ND * H + dir * H + (r_ok ? unit : 0);
     float gx[3] = {0.f, 0.f, 0.f};
     auto prefetch = [&](int st) {
         const int tl = dir ? T - 1 - st : st;
@@ -212,7 +214,7 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_vec_kernel(
                 if (step == 0 && threadIdx.x == 0) __builtin_amdgcn_raw_buffer_store_b32(my_xcc + 1u, x_rsrc, (hello_w + m) * 4, po, 16);
             }
         }
-        if (r_ok) y_p[(long)tau * 2 * H] = h;
+        if (r_ok) y_p[(long)tau * ND * H] = h;
         if (step + 1 < T) prefetch(step + 1);
     }
     // the next launch takes the other buffer.  Member 0 of direction 0 can only be here after every member has published step T - 2, i.e. has
@@ -256,8 +258,36 @@ extern "C" int tg_gru_forward_vec(const float* gi, int64_t gi_dir_stride, const 
     const dim3 grid(8 * 2 * cw);
     hipStream_t s = (hipStream_t)stream;
     unsigned* w = (unsigned*)ws;
-    if (B == 1) hipLaunchKernelGGL(gru_seq_fwd_vec_kernel<1>, grid, dim3(512), 0, s, gi, (long)gi_dir_stride, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, y, w, B, T, H, cw);
-    else if (B == 2) hipLaunchKernelGGL(gru_seq_fwd_vec_kernel<2>, grid, dim3(512), 0, s, gi, (long)gi_dir_stride, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, y, w, B, T, H, cw);
-    else hipLaunchKernelGGL(gru_seq_fwd_vec_kernel<4>, grid, dim3(512), 0, s, gi, (long)gi_dir_stride, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, y, w, B, T, H, cw);
+    if (B == 1) hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<1, 2>), grid, dim3(512), 0, s, gi, (long)gi_dir_stride, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, y, w, B, T, H, cw);
+    else if (B == 2) hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<2, 2>), grid, dim3(512), 0, s, gi, (long)gi_dir_stride, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, y, w, B, T, H, cw);
+    else hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<4, 2>), grid, dim3(512), 0, s, gi, (long)gi_dir_stride, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, y, w, B, T, H, cw);
     return check_launch("tg_gru_forward_vec");
+}
+
+// The one-direction form (ContextEncoder's GRU, embedding_net.py:233: H = 256, unidirectional): the same kernel with ND = 1 -- ceil(H / 32)
+// members, gi [B][T][3H], y [B][T][H].  Same envelope as the two-direction form (half as many members: co-resident wherever that one is).
+// A workspace belongs to ONE direction count: a launch resets only its own directions' words of the other launch buffer, and a slot holds
+// ND * 4 rows, so a two-direction launch after a one-direction one on the same words would find stale values.  tg_gru_vec_ws_bytes(H) is
+// large enough for either.
+extern "C" int tg_gru_vec1_supported(int32_t B, int32_t H, int32_t* supported) {
+    TG_REQUIRE(supported, "tg_gru_vec1_supported: null pointer");
+    TG_REQUIRE(B > 0 && H > 0, "tg_gru_vec1_supported: sizes must be positive (B=%d H=%d)", B, H);
+    *supported = tg_gru_vec_supported(B, H) ? 1 : 0;
+    return 0;
+}
+
+extern "C" int tg_gru_forward_vec1(const float* gi, const float* w_hh, const float* b_hh, float* y, void* ws, int64_t ws_bytes, int32_t B, int32_t T,
+                                   int32_t H, void* stream) {
+    TG_REQUIRE(gi && w_hh && b_hh && y && ws, "tg_gru_forward_vec1: null pointer");
+    TG_REQUIRE(T > 0 && tg_gru_vec_supported(B, H), "tg_gru_forward_vec1: unsupported shape B=%d H=%d (envelope: 1 <= B <= 4, 64 < H <= 320, H %% 4 == 0)", B, H);
+    TG_REQUIRE(ws_bytes >= tg_gru_vec_ws_bytes(H), "tg_gru_forward_vec1: workspace too small");
+    TG_REQUIRE(aligned16(w_hh) && aligned16(ws), "tg_gru_forward_vec1: W_hh and the workspace must be 16-byte aligned");
+    const int cw = cdiv(H, 32);
+    const dim3 grid(8 * cw);
+    hipStream_t s = (hipStream_t)stream;
+    unsigned* w = (unsigned*)ws;
+    if (B == 1) hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<1, 1>), grid, dim3(512), 0, s, gi, 0L, w_hh, w_hh, b_hh, b_hh, y, w, B, T, H, cw);
+    else if (B == 2) hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<2, 1>), grid, dim3(512), 0, s, gi, 0L, w_hh, w_hh, b_hh, b_hh, y, w, B, T, H, cw);
+    else hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<4, 1>), grid, dim3(512), 0, s, gi, 0L, w_hh, w_hh, b_hh, b_hh, y, w, B, T, H, cw);
+    return check_launch("tg_gru_forward_vec1");
 }

@@ -1,5 +1,5 @@
 """Test-set evaluation of the generator: scripts/train.py:evaluate_testset (:234-329), multimodal_context, gesture_autoencoder,
-speech2gesture and seq2seq branches, with the reference's signature so that train.py:117 can call it unchanged.
+speech2gesture, seq2seq and joint_embedding branches, with the reference's signature so that train.py:117 can call it unchanged.
 
 Per batch: eval-mode forward with randomly drawn speaker ids (:255-260; None when the generator has no speaker Vocab), L1 loss
 (:282), FGD feature push (:290), joint-position MAE through convert_dir_vec_to_pose (utils/data_utils.py:77-98) over the non-seed
@@ -72,7 +72,7 @@ def evaluate_testset(test_data_loader, generator, loss_fn, embed_space_evaluator
     """train.py:234-329.  test_data_loader yields (in_text, text_lengths, in_text_padded, _, target_vec, in_audio, in_spec,
     aux_info) like the reference's DataLoader (default_collate_fn).  `loss_fn` is unused by the two models on the hot path
     (kept for the signature).  Leaves the generator in train mode, like the reference (:313)."""
-    if args.model not in ("multimodal_context", "gesture_autoencoder", "speech2gesture", "seq2seq"):
+    if args.model not in ("multimodal_context", "gesture_autoencoder", "speech2gesture", "seq2seq", "joint_embedding"):
         raise NotImplementedError(f"model {args.model!r} is a baseline outside the hot path")
     device = next(generator.parameters()).device
     generator.train(False)
@@ -101,6 +101,9 @@ def evaluate_testset(test_data_loader, generator, loss_fn, embed_space_evaluator
                 out_dir_vec = generator(in_spec.to(device), target[:, 0:args.n_pre_poses])
             elif args.model == "seq2seq":                      # :274-276: the unpadded word lists and their lengths; loss_fn is L1Loss (mean)
                 out_dir_vec = generator(in_text.to(device), text_lengths, target.contiguous(), None)
+            elif args.model == "joint_embedding":              # :269-271: eval_embed(..., mode='speech'); its loss, the mean over clips of the
+                # per-clip L1 mean, is batch_metrics' l1 (clips have equal size).  The pose encoder's eval-mode output is unused: not run
+                out_dir_vec = generator.synthesize(in_text_padded, in_audio.float(), target[:, 0:args.n_pre_poses].contiguous())
             else:
                 pre_seq = ops.make_pre_seq(target.contiguous(), torch.empty(batch_size, target.shape[1], target.shape[2] + 1, device=device),
                                            args.n_pre_poses)

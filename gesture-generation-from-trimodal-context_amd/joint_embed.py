@@ -324,6 +324,22 @@ def embedding_forward(net, in_text, in_audio, pre_poses, poses, input_mode=None,
     return context_feat, context_mu, context_logvar, poses_feat, pose_mu, pose_logvar, out_poses
 
 
+def embedding_synthesize(net, in_text, in_audio, pre_poses, inject=None):
+    """EmbeddingNet.synthesize: the 'speech' path of embedding_net.py:276-308 in eval mode, (B, n_frames, pose_dim).  The pose encoder is not
+    run (in eval mode it has no side effect and 'speech' does not read its output).  Both GRUs are switched to rnn.GRU.few_row_eval: with
+    B <= 4 each of their layers is one few-row recurrence launch (csrc/gru_vec.hip) instead of one launch per time step; larger batches
+    stay on the per-step kernels.  ContextEncoder reparameterises in eval mode too: eps from inject['c.eps'] or the counter RNG, as forward."""
+    if net.context_encoder is None:
+        raise ValueError("EmbeddingNet.synthesize: mode='pose' has no context encoder")
+    if net.training:
+        raise RuntimeError("EmbeddingNet.synthesize runs in eval mode: call .eval() / .train(False) first")
+    net.context_encoder.gru.few_row_eval = True
+    net.decoder.gru.few_row_eval = True
+    with torch.no_grad():
+        latent, _, _ = net.context_encoder(in_text, in_audio.float(), inject=inject)
+        return net.decoder(latent, pre_poses.float())
+
+
 # ----------------------------------------------------------------------------------------------------------------------- training
 class _L1SumFn(torch.autograd.Function):
     """sum over clips of mean_{t,d} |recon - target| (train_joint_embed.py:20-28; clips have equal size: B x the mean over everything)."""

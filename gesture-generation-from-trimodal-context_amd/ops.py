@@ -633,10 +633,12 @@ def _gru_vec_fill(ws):
     return ws
 
 
-def _gru_vec_ws(dev, H):
-    """One workspace per (device, H), like the cluster kernels': launches that share it must be stream-ordered (two decoders replaying on
-    different streams at the same time would need one each)."""
-    key = (dev, H)
+def _gru_vec_ws(dev, H, nd=2):
+    """One workspace per (device, H, direction count), like the cluster kernels': launches that share it must be stream-ordered (two decoders
+    replaying on different streams at the same time would need one each).  The direction count is part of the key because a launch resets
+    only its own directions' words of the other launch buffer: a one-direction launch between two two-direction launches on the same
+    words would leave the second one stale direction-1 values (csrc/gru_vec.hip)."""
+    key = (dev, H) if nd == 2 else (dev, H, nd)
     ws = _gru_vec_ws_cache.get(key)
     if ws is None:
         ws = _gru_vec_fill(torch.empty((_lib.load().tg_gru_vec_ws_bytes(H) + 3) // 4, dtype=torch.int32, device=dev))
@@ -647,6 +649,27 @@ def _gru_vec_ws(dev, H):
 def gru_vec_takes(B, H, save, drop_mask):
     """Will gru_forward run the few-row inference kernel for this call?"""
     return bool(GRU_VEC and H > 64 and save is None and drop_mask is None and _lib.load().tg_gru_vec_supported(int(B), int(H)))
+
+
+def gru_vec1_supported(B, H):
+    """True when tg_gru_forward_vec1 (one direction, csrc/gru_vec.hip) takes the shape: 1 <= B <= 4, 64 < H <= 320, H % 4 == 0."""
+    if not GRU_VEC or min(int(B), int(H)) < 1:
+        return False
+    out = C.c_int32(0)
+    call("tg_gru_vec1_supported", int(B), int(H), C.cast(C.byref(out), C.c_void_p))
+    return bool(out.value)
+
+
+def gru_forward_vec1(gi, w_hh, b_hh, y):
+    """One-direction few-row inference recurrence: gi [B, T, 3H] contiguous, w_hh [3H, H], b_hh [3H], y [B, T, H]; no h0, no lengths, no saved
+    gates.  Raises outside the envelope (gru_vec1_supported).  Its workspace is its own (_gru_vec_ws(..., nd=1))."""
+    _flat(gi, "gi"); _flat(y, "y"); _flat(w_hh, "w_hh"); _flat(b_hh, "b_hh")
+    B, T, H3 = gi.shape
+    H = H3 // 3
+    assert H3 == 3 * H and tuple(y.shape) == (B, T, H) and tuple(w_hh.shape) == (3 * H, H) and b_hh.numel() == 3 * H
+    ws = _gru_vec_ws(gi.device, H, nd=1)
+    call("tg_gru_forward_vec1", _p(gi), _p(w_hh), _p(b_hh), _p(y), C.c_void_p(ws.data_ptr()), ws.numel() * 4, B, T, H, _stream())
+    return y
 
 
 _cluster_caps = {}
@@ -732,7 +755,7 @@ def check_async_errors():
         if int(ws[0].item()) != 0:
             info = ws[:3].tolist()
             _gru_vec_fill(ws)       # exchange words of the aborted launch are out of step: back to the state of a fresh allocation
-            raise RuntimeError(f"few-row GRU kernel timed out waiting for a member's h words (device, H) = {key}: step {info[1]}, workgroup {info[2]}; "
+            raise RuntimeError(f"few-row GRU kernel timed out waiting for a member's h words (device, H[, directions if not 2]) = {key}: step {info[1]}, workgroup {info[2]}; "
                                "results are invalid")
     for key, ws in _gru_ws.items():
         if int(ws[0].item()) != 0:

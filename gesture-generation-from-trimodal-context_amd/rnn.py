@@ -57,6 +57,41 @@ class GRU(nn.Module):
             self._names.append(name)
         self._rng = None
         self._replay_draws = []
+        # opt-in: eval-mode forwards of at most four rows without a tape, lengths or hx run each layer's recurrence as ONE launch of the
+        # few-row kernel (csrc/gru_vec.hip) instead of one launch per time step.  Off by default: every existing call keeps its kernel
+        self.few_row_eval = False
+
+    def _few_row_takes(self, B, lengths, hx, save):
+        if not self.few_row_eval or self.training or save or lengths is not None or hx is not None or B > 4:
+            return False
+        H = self.hidden_size
+        return ops.gru_vec_takes(B, H, None, None) if self.bidirectional else ops.gru_vec1_supported(B, H)
+
+    def _few_row_forward(self, x):
+        """The stack for B <= 4 rows in eval mode: per layer one grouped input projection (the GEMM entry of the per-step path) and one
+        recurrence launch carrying every direction.  h_n is read from y: the last step forward, the first step reverse."""
+        D, H = (2 if self.bidirectional else 1), self.hidden_size
+        B, T, _ = x.shape
+        sfxs = ("", "_reverse")[:D]
+        h_n = L.empty(self.num_layers * D, B, H, like=x)
+        cur = x
+        for l in range(self.num_layers):
+            gi = L.empty(D, B, T, 3 * H, like=x)
+            a_win = ops.Win.plain(cur.view(B * T, cur.shape[2]))
+            ops.gemm_nt_group([dict(A=a_win, W=getattr(self, f"weight_ih_l{l}{s}"), bias=getattr(self, f"bias_ih_l{l}{s}"),
+                                    out=gi[d].view(B * T, 3 * H)) for d, s in enumerate(sfxs)])
+            y = L.empty(B, T, D * H, like=x)
+            whh = tuple(getattr(self, f"weight_hh_l{l}{s}").detach() for s in sfxs)
+            bhh = tuple(getattr(self, f"bias_hh_l{l}{s}").detach() for s in sfxs)
+            if D == 2:
+                ops.gru_forward(gi, whh, bhh, y, None)
+            else:
+                ops.gru_forward_vec1(gi[0], whh[0], bhh[0], y)
+            h_n[l * D].copy_(y[:, T - 1, :H])
+            if D == 2:
+                h_n[l * D + 1].copy_(y[:, 0, H:])
+            cur = y
+        return cur, h_n
 
     def extra_repr(self):
         return (f"{self.input_size}, {self.hidden_size}, num_layers={self.num_layers}, batch_first={self.batch_first}, dropout={self.dropout}, "
@@ -90,6 +125,9 @@ class GRU(nn.Module):
             self._rng.advance()
             rng = self._rng
         save = torch.is_grad_enabled() and (x.requires_grad or (hx is not None and hx.requires_grad) or any(p.requires_grad for p in params))
+        if self._few_row_takes(B, lengths, hx, save):
+            with torch.no_grad():
+                return self._few_row_forward(x.contiguous())
         cfg = (tuple(self._names), self.num_layers, H, D, lengths, self.dropout, training, rng, inject, save)
         return _GRUFn.apply(cfg, x.contiguous(), hx, *params)
 

@@ -1,4 +1,4 @@
-"""Long-utterance synthesis: the multimodal_context and speech2gesture branches of scripts/synthesize.py:generate_gestures (:36-209).
+"""Long-utterance synthesis: the multimodal_context, speech2gesture, seq2seq and joint_embedding branches of scripts/synthesize.py:generate_gestures (:36-209).
 
 An utterance is cut into 34-frame windows with a 30-frame stride; window i is seeded with the last 4 output frames of window
 i-1 (:122-124) and its first 4 frames are cross-faded with them (:145-153).  Here the windows stay on the GPU: the seed
@@ -15,7 +15,13 @@ With args.model == 'seq2seq' (:105-119,134-136,162-185) a window's text is the U
 Utterances run in lock-step as one padded batch with per-row text lengths (Seq2SeqNet.synthesize: every row attends over its own words
 only, so the batch reproduces the reference's one-by-one runs); the decoder loop of a window is one launch (csrc/seq2seq_decode.hip).  No
 graph capture: the text length changes from window to window.  After stacking, the reference's extra cubic fit around every window
-boundary (seq2seq_smooth, :162-185) runs on the host, then the fade-out.  The joint_embedding branch is not implemented.
+boundary (seq2seq_smooth, :162-185) runs on the host, then the fade-out.
+
+With args.model == 'joint_embedding' (:132-133) a window feeds EmbeddingNet's 'speech' path: the padded per-frame word ids and the audio slice
+of multimodal_context, and the previous window's last n_pre_poses frames (zeros or seed_seq on the first window) as pre_seq_partial; no
+speaker, no constraint bit.  EmbeddingNet.synthesize runs it without the pose encoder and, for up to four utterances in lock-step, with
+both GRUs on the few-row recurrence kernel (one launch per layer, csrc/gru_vec.hip); the context encoder draws a fresh eps per window, as the
+reference does in eval mode.  Cross-fade on the device, fade-out on the host, no extra smoothing.  No graph capture.
 
 TTS / Gentle alignment / LMDB front-ends of the reference script are network services and out of scope; `words` is the
 reference's word list [[word, start_s, end_s], ...].
@@ -131,6 +137,43 @@ def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
                 total[b, i * stride:i * stride + T, :].copy_(out[b])
     res = total.cpu().numpy()
     return [res[b, :n_win[b] * stride + n_pre] for b in range(B)], n_win
+
+
+def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list):
+    """The joint_embedding branch (synthesize.py:132-133) for several utterances in lock-step; same return value as generate_gestures_batch.
+    eps_list (parity tests): per window, the (B, 32) eps of ContextEncoder's reparameterize instead of the counter RNG."""
+    dev = next(pose_decoder.parameters()).device
+    B, T, n_pre = len(audios), args.n_poses, args.n_pre_poses
+    dec = pose_decoder.decoder
+    if T != dec.gen_length or n_pre * dec.pose_dim != dec.pre_pose_net[0].in_features:
+        raise ValueError(f"joint_embedding synthesis: args (n_poses, n_pre_poses) = {(T, n_pre)} but the model decodes {dec.gen_length} frames "
+                         f"from {dec.pre_pose_net[0].in_features // dec.pose_dim} seed poses")
+    if pose_decoder.training:
+        raise RuntimeError("joint_embedding synthesis: the model must be in eval mode (joint_embed.load_checkpoint_and_model leaves it so)")
+    stride, D = T - n_pre, dec.pose_dim
+    n_win = [num_windows(len(a) / audio_sr, T, n_pre, args.motion_resampling_framerate) for a in audios]
+    pre = torch.zeros(B, n_pre, D, device=dev)
+    if seed_seqs is not None:                                                   # synthesize.py:46-50
+        pre.copy_(torch.as_tensor(np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]), dtype=torch.float32))
+    tail = torch.zeros(B, n_pre, D, device=dev)
+    total = torch.zeros(B, max(n_win) * stride + n_pre, D, device=dev)
+    for i in range(max(n_win)):
+        a_np, t_np = [], []
+        for b in range(B):
+            a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], min(i, n_win[b] - 1), audio_sr)   # finished utterances idle
+            a_np.append(a); t_np.append(ids)
+        inject = None if eps_list is None else {"c.eps": torch.as_tensor(eps_list[i], dtype=torch.float32, device=dev)}
+        out = pose_decoder.synthesize(torch.from_numpy(np.stack(t_np)).to(dev), torch.from_numpy(np.stack(a_np)).to(dev), pre,
+                                      inject=inject).contiguous()                # (B, T, D), synthesize.py:133
+        if i > 0:
+            ops.window_blend(tail, out)                                          # :145-153
+        tail.copy_(out[:, T - n_pre:, :])
+        pre = tail.clone()                                                       # :122-126
+        for b in range(B):
+            if i < n_win[b]:                                                     # an idling utterance's frames are not written
+                total[b, i * stride:i * stride + T, :].copy_(out[b])
+    res = total.cpu().numpy()
+    return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
 
 
 class WindowDecoder:
@@ -277,18 +320,22 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
 
 
 def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, vids=None, seed_seqs=None, audio_sr=16000,
-                            graph=True, _draws=None, spec_pad_mode="reflect"):
+                            graph=True, _draws=None, spec_pad_mode="reflect", eps_list=None):
     """Lock-step synthesis of several utterances.  Returns a list of (n_i * 30 + 4, D) numpy arrays (mean-subtracted direction
     vectors, like the reference's return value without fade-out).  vids: one speaker id per utterance, or None / a falsy entry to
     draw it like the reference (synthesize.py:67-74; ignored unless args.z_type == 'speaker').  _draws (parity tests): per window,
     the (B, 16) eps / z to replay instead of the device RNG.  args.model == 'speech2gesture': lang_model, words_list, vids, graph are unused
     (the model sees the spectrogram only; no capture), spec_pad_mode is melspec.extract_melspectrogram's pad_mode.  args.model == 'seq2seq':
-    the audios matter through their lengths only; the result includes the reference's cubic smoothing around every window boundary."""
+    the audios matter through their lengths only; the result includes the reference's cubic smoothing around every window boundary.
+    args.model == 'joint_embedding': pose_decoder is an EmbeddingNet(mode='random' / 'speech') in eval mode; vids, graph unused; eps_list
+    (parity tests): per window, the (B, 32) eps of the context encoder's reparameterize instead of the counter RNG."""
     if getattr(args, "model", "multimodal_context") == "speech2gesture":
         return _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode)
     if getattr(args, "model", "multimodal_context") == "seq2seq":             # audio matters through its length only; vids, graph unused
         outs, n_win = _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr)
         return [seq2seq_smooth(o, n, args.n_poses, args.n_pre_poses) for o, n in zip(outs, n_win)]
+    if getattr(args, "model", "multimodal_context") == "joint_embedding":
+        return _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list)
     dev = next(pose_decoder.parameters()).device
     B = len(audios)
     n_win = [num_windows(len(a) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate) for a in audios]
@@ -337,10 +384,10 @@ def fade_out_to_mean(out_dir_vec, end_padding_samples, args, audio_sr=16000):
 
 
 def generate_gestures(args, pose_decoder, lang_model, audio, words, audio_sr=16000, vid=None, seed_seq=None, fade_out=False,
-                      _draws=None, spec_pad_mode="reflect"):
-    """Single-utterance API of the reference (synthesize.py:36-209, multimodal_context, speech2gesture and seq2seq models)."""
+                      _draws=None, spec_pad_mode="reflect", eps_list=None):
+    """Single-utterance API of the reference (synthesize.py:36-209; multimodal_context, speech2gesture, seq2seq and joint_embedding models)."""
     out = generate_gestures_batch(args, pose_decoder, lang_model, [audio], [words], [vid], None if seed_seq is None else [seed_seq],
-                                  audio_sr, graph=True, _draws=_draws, spec_pad_mode=spec_pad_mode)[0]
+                                  audio_sr, graph=True, _draws=_draws, spec_pad_mode=spec_pad_mode, eps_list=eps_list)[0]
     if not fade_out:
         return out
     if getattr(args, "model", "multimodal_context") in ("speech2gesture", "seq2seq"):

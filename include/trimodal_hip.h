@@ -310,6 +310,15 @@ int64_t tg_gru_vec_ws_bytes(int32_t H);
 int32_t tg_gru_vec_ws_header_bytes(void);
 int tg_gru_forward_vec(const float* gi, int64_t gi_dir_stride, const float* w_hh_fwd, const float* w_hh_rev, const float* b_hh_fwd,
                        const float* b_hh_rev, float* y, void* ws, int64_t ws_bytes, int32_t B, int32_t T, int32_t H, void* stream);
+/* The one-direction form of the same kernel (ContextEncoder's GRU of the joint-embedding baseline, embedding_net.py:233): gi [B][T][3H],
+ * w_hh [3H][H] (16-byte aligned), b_hh [3H], y [B][T][H]; no h0, no lengths.  Envelope as tg_gru_vec_supported: 1 <= B <= 4, 64 < H <= 320,
+ * H % 4 == 0, T >= 1; outside it the entry returns non-zero ("unsupported shape ... envelope" in tg_last_error) and launches nothing;
+ * tg_gru_vec1_supported writes 1 / 0 for a shape of positive sizes.  A WORKSPACE BELONGS TO ONE DIRECTION COUNT: a launch resets only the
+ * words of its own directions in the other launch buffer, so a workspace used by tg_gru_forward_vec1 must never be handed to
+ * tg_gru_forward_vec or the other way round (size and initial fill are the same: tg_gru_vec_ws_bytes(H)). */
+int tg_gru_vec1_supported(int32_t B, int32_t H, int32_t* supported);
+int tg_gru_forward_vec1(const float* gi, const float* w_hh, const float* b_hh, float* y, void* ws, int64_t ws_bytes, int32_t B, int32_t T,
+                        int32_t H, void* stream);
 
 /* Persistent cluster-synchronised variant of tg_gru_backward (B <= 192 at H = 300; no dh_scratch: the carried dh stays in
  * registers).  Same workspace / timeout-word convention as tg_gru_forward_cluster. */
