@@ -69,6 +69,8 @@ SIGNATURES = {
     "tg_gru_forward_vec": [P, I64, P, P, P, P, P, P, I64, I32, I32, I32, P],
     "tg_gru_vec1_supported": [I32, I32, P],
     "tg_gru_forward_vec1": [P, P, P, P, P, I64, I32, I32, I32, P],
+    "tg_gru_vec_const_supported": [I32, I32, I32, P],
+    "tg_gru_forward_vec_const": [P, I64, P, P, P, P, P, P, I64, I32, I32, I32, I32, P],
     "tg_gru_backward_cluster": [P, P, P, P, I64, P, P, P, P, I64, P, I64, I32, I32, I32, P],
     "tg_gru_backward_cluster_stats": [P, P, P, P, I64, P, P, P, P, I64, P, I64, I32, I32, I32, P, I64, P, P, P],
     "tg_bn_train_stats": [P, I32, I32, I32, P, P, P, P, P, P, F32, F32, I32, P],

@@ -25,6 +25,7 @@
 // Every spin is bounded; a timeout sets the workspace's sticky word (ops.check_async_errors raises and refills the workspace).
 // The direction count ND is a template parameter: ND = 2 is the generator's / PoseDecoderGRU's layer, ND = 1 (tg_gru_forward_vec1) the
 // ContextEncoder's unidirectional H = 256 GRU of the joint-embedding baseline (embedding_net.py:233) with ceil(H / 32) members.
+// A third parameter, CI, marks a layer whose input is the same at every step (tg_gru_forward_vec_const): gi is then one row per sequence.
 #include "operand_split.hpp"
 
 namespace tg {
@@ -51,7 +52,10 @@ __device__ __forceinline__ float vec_row_sum(float v) {
     return v;
 }
 
-template <int RB, int ND>
+// CI (constant input): gi is [ND][B][3H] -- ONE row per sequence and direction, the input projection of an input that is the same at every
+// time step (PoseDecoderGRU repeats one 64-float row over its 34 steps, embedding_net.py:153-157).  The three gate inputs of (unit, row) are
+// loaded once in front of the time loop and stay in the registers the time-varying form prefetches into; nothing else differs.
+template <int RB, int ND, bool CI = false>
 __global__ __launch_bounds__(512) void gru_seq_fwd_vec_kernel(
     const float* __restrict__ gi, long gi_ds, const float* __restrict__ whh0, const float* __restrict__ whh1,
     const float* __restrict__ bhh0, const float* __restrict__ bhh1, float* __restrict__ Y, unsigned* ws, int B, int T, int H, int CW) {
@@ -109,11 +113,12 @@ __global__ __launch_bounds__(512) void gru_seq_fwd_vec_kernel(
     }
 
     // the step's gi values of (unit, row), requested one step ahead
-    const float* gi_p = gi + dir * gi_ds + (long)(r_ok ? row : 0) * T * 3 * H + (r_ok ? unit : 0);
+    const float* gi_p = gi + dir * gi_ds + (long)(r_ok ? row : 0) * (CI ? 1 : T) * 3 * H + (r_ok ? unit : 0);
     float* y_p = Y + (long)(r_ok ? row : 0) * T * ND * H + dir * H + (r_ok ? unit : 0);
     float gx[3] = {0.f, 0.f, 0.f};
     auto prefetch = [&](int st) {
-        const int tl = dir ? T - 1 - st : st;
+        if (CI && st > 0) return;                          // constant input: the row read in front of the loop serves every step
+        const int tl = CI ? 0 : (dir ? T - 1 - st : st);
         if (r_ok) {
 #pragma unroll
             for (int g = 0; g < 3; ++g) gx[g] = gi_p[(long)tl * 3 * H + g * H];
@@ -290,4 +295,42 @@ extern "C" int tg_gru_forward_vec1(const float* gi, const float* w_hh, const flo
     else if (B == 2) hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<2, 1>), grid, dim3(512), 0, s, gi, 0L, w_hh, w_hh, b_hh, b_hh, y, w, B, T, H, cw);
     else hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<4, 1>), grid, dim3(512), 0, s, gi, 0L, w_hh, w_hh, b_hh, b_hh, y, w, B, T, H, cw);
     return check_launch("tg_gru_forward_vec1");
+}
+
+// The constant-input form (PoseDecoderGRU's layer 0, embedding_net.py:153-157: the same row at all 34 steps): gi [n_dir][B][3H] -- one projected
+// row per sequence and direction (gi_dir_stride floats between the directions) -- instead of [B][T][3H]; y [B][T][n_dir * H].  Same envelope,
+// grid, exchange protocol and workspace words as the time-varying form of the same direction count (the instantiations differ in the gi
+// address alone), so the two may share a workspace: tg_gru_forward_vec with n_dir = 2, tg_gru_forward_vec1 with n_dir = 1.
+extern "C" int tg_gru_vec_const_supported(int32_t B, int32_t H, int32_t n_dir, int32_t* supported) {
+    TG_REQUIRE(supported, "tg_gru_vec_const_supported: null pointer");
+    TG_REQUIRE(B > 0 && H > 0 && n_dir > 0, "tg_gru_vec_const_supported: sizes must be positive (B=%d H=%d n_dir=%d)", B, H, n_dir);
+    *supported = (n_dir <= 2 && tg_gru_vec_supported(B, H)) ? 1 : 0;
+    return 0;
+}
+
+template <int ND>
+static void vec_const_launch(const float* gi, long gi_ds, const float* w0, const float* w1, const float* b0, const float* b1, float* y, unsigned* w,
+                             int B, int T, int H, int cw, hipStream_t s) {
+    const dim3 grid(8 * ND * cw);
+    if (B == 1) hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<1, ND, true>), grid, dim3(512), 0, s, gi, gi_ds, w0, w1, b0, b1, y, w, B, T, H, cw);
+    else if (B == 2) hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<2, ND, true>), grid, dim3(512), 0, s, gi, gi_ds, w0, w1, b0, b1, y, w, B, T, H, cw);
+    else hipLaunchKernelGGL((gru_seq_fwd_vec_kernel<4, ND, true>), grid, dim3(512), 0, s, gi, gi_ds, w0, w1, b0, b1, y, w, B, T, H, cw);
+}
+
+extern "C" int tg_gru_forward_vec_const(const float* gi, int64_t gi_dir_stride, const float* w_hh_fwd, const float* w_hh_rev, const float* b_hh_fwd,
+                                        const float* b_hh_rev, float* y, void* ws, int64_t ws_bytes, int32_t B, int32_t T, int32_t H, int32_t n_dir,
+                                        void* stream) {
+    TG_REQUIRE(gi && w_hh_fwd && b_hh_fwd && y && ws, "tg_gru_forward_vec_const: null pointer");
+    TG_REQUIRE(T > 0 && n_dir >= 1 && n_dir <= 2 && tg_gru_vec_supported(B, H),
+               "tg_gru_forward_vec_const: unsupported shape B=%d H=%d n_dir=%d (envelope: 1 <= B <= 4, 64 < H <= 320, H %% 4 == 0, n_dir 1 or 2)", B, H, n_dir);
+    TG_REQUIRE(n_dir == 1 || (w_hh_rev && b_hh_rev), "tg_gru_forward_vec_const: null pointer (reverse direction)");
+    TG_REQUIRE(n_dir == 1 || gi_dir_stride >= (int64_t)B * 3 * H, "tg_gru_forward_vec_const: gi_dir_stride %lld is smaller than a direction's B * 3H floats",
+               (long long)gi_dir_stride);
+    TG_REQUIRE(ws_bytes >= tg_gru_vec_ws_bytes(H), "tg_gru_forward_vec_const: workspace too small");
+    TG_REQUIRE(aligned16(w_hh_fwd) && (n_dir == 1 || aligned16(w_hh_rev)) && aligned16(ws), "tg_gru_forward_vec_const: W_hh and the workspace must be 16-byte aligned");
+    const int cw = cdiv(H, 32);
+    hipStream_t s = (hipStream_t)stream;
+    if (n_dir == 2) vec_const_launch<2>(gi, (long)gi_dir_stride, w_hh_fwd, w_hh_rev, b_hh_fwd, b_hh_rev, y, (unsigned*)ws, B, T, H, cw, s);
+    else vec_const_launch<1>(gi, 0L, w_hh_fwd, w_hh_fwd, b_hh_fwd, b_hh_fwd, y, (unsigned*)ws, B, T, H, cw, s);
+    return check_launch("tg_gru_forward_vec_const");
 }

@@ -283,6 +283,25 @@ class PoseDecoderGRU(nn.Module):
         o = _LinearFn.apply(_LinearFn.apply(o, self.out[0].weight, self.out[0].bias), self.out[2].weight, self.out[2].bias)
         return o.view(B, self.gen_length, -1)
 
+    def forward_constant(self, latent_code, pre_poses):
+        """forward in eval mode for at most four clips WITHOUT materialising the repeated input: the GRU is told that its input is one row
+        (rnn.GRU.forward_constant: layer 0 projects (B, 64) instead of (B * gen_length, 64) and its recurrence reads one gi row per clip);
+        no tg_repeat_rows launch.  Same head, direction sum and output MLP as forward.  Raises ValueError where forward_constant does."""
+        if self.training:
+            raise ValueError("PoseDecoderGRU.forward_constant runs in eval mode only: call .eval() first")
+        _need_cuda(latent_code, "PoseDecoderGRU: latent_code"); _need_cuda(pre_poses, "PoseDecoderGRU: pre_poses")
+        B = pre_poses.shape[0]
+        pre = pre_poses.reshape(B, -1).contiguous()
+        if pre.shape[1] != self.pre_pose_net[0].in_features or tuple(latent_code.shape) != (B, 32):
+            raise ValueError(f"PoseDecoderGRU: pre_poses {tuple(pre_poses.shape)} / latent_code {tuple(latent_code.shape)} do not match the network")
+        with torch.no_grad():
+            hcfg = (self.pre_pose_net[1], False, 0.0, False, False, None, None)
+            feat = _LatentHeadFn.apply(hcfg, pre, latent_code, *_head_params(self.pre_pose_net))      # (B, 64) = [pre_pose_feat | latent]
+            output, _ = self.gru.forward_constant(feat, self.gen_length)
+            o = _SumHalvesFn.apply(output).view(B * self.gen_length, self.hidden_size)
+            o = _LinearFn.apply(_LinearFn.apply(o, self.out[0].weight, self.out[0].bias), self.out[2].weight, self.out[2].bias)
+        return o.view(B, self.gen_length, -1)
+
 
 def embedding_forward(net, in_text, in_audio, pre_poses, poses, input_mode=None, variational_encoding=False):
     """EmbeddingNet.forward of the speech / random modes (embedding_net.py:276-308)."""
@@ -324,11 +343,13 @@ def embedding_forward(net, in_text, in_audio, pre_poses, poses, input_mode=None,
     return context_feat, context_mu, context_logvar, poses_feat, pose_mu, pose_logvar, out_poses
 
 
-def embedding_synthesize(net, in_text, in_audio, pre_poses, inject=None):
+def embedding_synthesize(net, in_text, in_audio, pre_poses, inject=None, constant_input=False):
     """EmbeddingNet.synthesize: the 'speech' path of embedding_net.py:276-308 in eval mode, (B, n_frames, pose_dim).  The pose encoder is not
     run (in eval mode it has no side effect and 'speech' does not read its output).  Both GRUs are switched to rnn.GRU.few_row_eval: with
     B <= 4 each of their layers is one few-row recurrence launch (csrc/gru_vec.hip) instead of one launch per time step; larger batches
-    stay on the per-step kernels.  ContextEncoder reparameterises in eval mode too: eps from inject['c.eps'] or the counter RNG, as forward."""
+    stay on the per-step kernels.  ContextEncoder reparameterises in eval mode too: eps from inject['c.eps'] or the counter RNG, as forward.
+    constant_input=True (opt-in, at most four clips): the decoder runs PoseDecoderGRU.forward_constant -- no repeated input, layer 0 of its GRU
+    on the constant-input recurrence; the default keeps today's launches and bits."""
     if net.context_encoder is None:
         raise ValueError("EmbeddingNet.synthesize: mode='pose' has no context encoder")
     if net.training:
@@ -337,6 +358,8 @@ def embedding_synthesize(net, in_text, in_audio, pre_poses, inject=None):
     net.decoder.gru.few_row_eval = True
     with torch.no_grad():
         latent, _, _ = net.context_encoder(in_text, in_audio.float(), inject=inject)
+        if constant_input:
+            return net.decoder.forward_constant(latent, pre_poses.float())
         return net.decoder(latent, pre_poses.float())
 
 

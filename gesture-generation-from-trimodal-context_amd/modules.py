@@ -276,10 +276,11 @@ class EmbeddingNet(nn.Module):
         for param in self.decoder.parameters():
             param.requires_grad = False
 
-    def synthesize(self, in_text, in_audio, pre_poses, inject=None):
-        """Eval-mode 'speech' forward without the pose encoder -> (B, n_frames, pose_dim); see joint_embed.embedding_synthesize."""
+    def synthesize(self, in_text, in_audio, pre_poses, inject=None, constant_input=False):
+        """Eval-mode 'speech' forward without the pose encoder -> (B, n_frames, pose_dim); see joint_embed.embedding_synthesize
+        (constant_input=True: the decoder GRU is told its input is one row per clip, at most four clips)."""
         from .joint_embed import embedding_synthesize
-        return embedding_synthesize(self, in_text, in_audio, pre_poses, inject)
+        return embedding_synthesize(self, in_text, in_audio, pre_poses, inject, constant_input)
 
     def forward(self, in_text, in_audio, pre_poses, poses, input_mode=None, variational_encoding=False):
         if self.mode != "pose":

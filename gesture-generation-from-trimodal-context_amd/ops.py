@@ -672,6 +672,32 @@ def gru_forward_vec1(gi, w_hh, b_hh, y):
     return y
 
 
+def gru_vec_const_supported(B, H, n_dir):
+    """True when tg_gru_forward_vec_const takes the shape: the few-row envelope (1 <= B <= 4, 64 < H <= 320, H % 4 == 0) and 1 or 2 directions."""
+    if not GRU_VEC or min(int(B), int(H), int(n_dir)) < 1:
+        return False
+    out = C.c_int32(0)
+    call("tg_gru_vec_const_supported", int(B), int(H), int(n_dir), C.cast(C.byref(out), C.c_void_p))
+    return bool(out.value)
+
+
+def gru_forward_vec_const(gi, w_hh, b_hh, y):
+    """Few-row inference recurrence of a layer whose input is the same at every step: gi [D, B, 3H] contiguous -- ONE projected row per
+    direction and sequence -- w_hh / b_hh: D-tuples, y [B, T, D * H] (T is read from y); no h0, no lengths, no saved gates.  Bit-identical to
+    the time-varying kernels on that row repeated T times.  Raises outside the envelope (gru_vec_const_supported).  The workspace is the one
+    of the time-varying form with the same direction count (_gru_vec_ws(dev, H, nd=D)): same grid, slots, resets and launch counter."""
+    _flat(gi, "gi"); _flat(y, "y")
+    D, B, H3 = gi.shape
+    H, T = H3 // 3, y.shape[1]
+    assert H3 == 3 * H and len(w_hh) == D and len(b_hh) == D and tuple(y.shape) == (B, T, D * H)
+    for w, b in zip(w_hh, b_hh):
+        _flat(w, "w_hh"); _flat(b, "b_hh"); assert tuple(w.shape) == (3 * H, H) and b.numel() == 3 * H
+    ws = _gru_vec_ws(gi.device, H, nd=1 if D == 1 else 2)         # (D > 2: the entry refuses it)
+    call("tg_gru_forward_vec_const", _p(gi), B * H3, _p(w_hh[0]), _p(w_hh[-1]), _p(b_hh[0]), _p(b_hh[-1]), _p(y), C.c_void_p(ws.data_ptr()), ws.numel() * 4,
+         B, T, H, D, _stream())
+    return y
+
+
 _cluster_caps = {}
 
 

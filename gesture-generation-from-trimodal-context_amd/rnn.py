@@ -67,15 +67,17 @@ class GRU(nn.Module):
         H = self.hidden_size
         return ops.gru_vec_takes(B, H, None, None) if self.bidirectional else ops.gru_vec1_supported(B, H)
 
-    def _few_row_forward(self, x):
+    def _few_row_forward(self, x, first_layer=0, h_n=None):
         """The stack for B <= 4 rows in eval mode: per layer one grouped input projection (the GEMM entry of the per-step path) and one
-        recurrence launch carrying every direction.  h_n is read from y: the last step forward, the first step reverse."""
+        recurrence launch carrying every direction.  h_n is read from y: the last step forward, the first step reverse.
+        forward_constant enters at first_layer = 1 with layer 0's output as x and layer 0's rows of h_n filled in."""
         D, H = (2 if self.bidirectional else 1), self.hidden_size
         B, T, _ = x.shape
         sfxs = ("", "_reverse")[:D]
-        h_n = L.empty(self.num_layers * D, B, H, like=x)
+        if h_n is None:
+            h_n = L.empty(self.num_layers * D, B, H, like=x)
         cur = x
-        for l in range(self.num_layers):
+        for l in range(first_layer, self.num_layers):
             gi = L.empty(D, B, T, 3 * H, like=x)
             a_win = ops.Win.plain(cur.view(B * T, cur.shape[2]))
             ops.gemm_nt_group([dict(A=a_win, W=getattr(self, f"weight_ih_l{l}{s}"), bias=getattr(self, f"bias_ih_l{l}{s}"),
@@ -92,6 +94,43 @@ class GRU(nn.Module):
                 h_n[l * D + 1].copy_(y[:, 0, H:])
             cur = y
         return cur, h_n
+
+    def forward_constant(self, x_row, T, hx=None):
+        """The stack on an input that is the SAME row at every one of T steps: x_row (B, input_size) -> (y (B, T, D*H), h_n), batch-first
+        whatever `batch_first` says.  Layer 0 projects the row ONCE per direction ((B, in) x (in, 3H), the GEMM entry of the other paths)
+        and runs one constant-input few-row recurrence launch (ops.gru_forward_vec_const); layers 1 and above are the few_row_eval path.
+        Eval mode, no hx, B <= 4 inside the few-row envelope -- anything else raises ValueError: the input is never repeated silently."""
+        D, H = (2 if self.bidirectional else 1), self.hidden_size
+        if self.training:
+            raise ValueError("GRU.forward_constant runs in eval mode only (no dropout, no tape): call .eval() first")
+        if hx is not None:
+            raise ValueError("GRU.forward_constant takes no initial state")
+        if not isinstance(x_row, torch.Tensor) or x_row.dim() != 2 or x_row.shape[1] != self.input_size:
+            raise ValueError(f"GRU.forward_constant: x_row must be (B, {self.input_size}), got {tuple(getattr(x_row, 'shape', ()))}")
+        B, T = x_row.shape[0], int(T)
+        if not 1 <= B <= 4 or T < 1:
+            raise ValueError(f"GRU.forward_constant: 1 <= B <= 4 rows and T >= 1 steps, got B = {B}, T = {T}")
+        if not (x_row.is_cuda and x_row.dtype == torch.float32):
+            raise TypeError(f"GRU.forward_constant: expected a CUDA float32 input, got {x_row.dtype} on {x_row.device}")
+        if not ops.gru_vec_const_supported(B, H, D):
+            raise ValueError(f"GRU.forward_constant: (B, H, D) = {(B, H, D)} is outside the few-row kernel envelope (1 <= B <= 4, 64 < H <= 320, "
+                             "H % 4 == 0); there is no torch fallback")
+        sfxs = ("", "_reverse")[:D]
+        with torch.no_grad():
+            x_row = x_row.contiguous()
+            gi = L.empty(D, B, 3 * H, like=x_row)
+            ops.gemm_nt_group([dict(A=ops.Win.plain(x_row), W=getattr(self, f"weight_ih_l0{s}"), bias=getattr(self, f"bias_ih_l0{s}"), out=gi[d])
+                               for d, s in enumerate(sfxs)])
+            y = L.empty(B, T, D * H, like=x_row)
+            ops.gru_forward_vec_const(gi, tuple(getattr(self, f"weight_hh_l0{s}").detach() for s in sfxs),
+                                      tuple(getattr(self, f"bias_hh_l0{s}").detach() for s in sfxs), y)
+            h_n = L.empty(self.num_layers * D, B, H, like=x_row)
+            h_n[0].copy_(y[:, T - 1, :H])
+            if D == 2:
+                h_n[1].copy_(y[:, 0, H:])
+            if self.num_layers == 1:
+                return y, h_n
+            return self._few_row_forward(y, 1, h_n)
 
     def extra_repr(self):
         return (f"{self.input_size}, {self.hidden_size}, num_layers={self.num_layers}, batch_first={self.batch_first}, dropout={self.dropout}, "

@@ -21,7 +21,9 @@ With args.model == 'joint_embedding' (:132-133) a window feeds EmbeddingNet's 's
 of multimodal_context, and the previous window's last n_pre_poses frames (zeros or seed_seq on the first window) as pre_seq_partial; no
 speaker, no constraint bit.  EmbeddingNet.synthesize runs it without the pose encoder and, for up to four utterances in lock-step, with
 both GRUs on the few-row recurrence kernel (one launch per layer, csrc/gru_vec.hip); the context encoder draws a fresh eps per window, as the
-reference does in eval mode.  Cross-fade on the device, fade-out on the host, no extra smoothing.  No graph capture.
+reference does in eval mode.  Cross-fade on the device, fade-out on the host, no extra smoothing.  No graph capture -- unless the
+caller keeps a JointEmbedWindowDecoder (static buffers, the decoder GRU told that its input is constant over time, the non-first window
+captured into a hipGraph once and replayed) and hands it in as window_decoder; window_decoder=True builds one per call, without the graph.
 
 TTS / Gentle alignment / LMDB front-ends of the reference script are network services and out of scope; `words` is the
 reference's word list [[word, start_s, end_s], ...].
@@ -248,6 +250,117 @@ class WindowDecoder:
         return self.out
 
 
+class JointEmbedWindowDecoder:
+    """WindowDecoder's counterpart for the joint-embedding baseline (args.model == 'joint_embedding', at most four utterances in lock-step):
+    one window = ContextEncoder -> PoseDecoderGRU.forward_constant -> cross-fade -> tail copy -> `pre` hand-over, on static buffers, on the
+    current stream, as one linear chain (nothing forks), so that the non-first window can be captured into a hipGraph once and replayed.
+    eps of the context encoder's reparameterize: the encoder's counter RNG, advanced on the device once per window (captured with the
+    window), or -- replay_draws (parity tests) -- the static (B, 32) buffer self.draw, filled by the caller before each window.
+    Host-side validation raises ValueError before anything touches the GPU."""
+
+    def __init__(self, args, net, batch, device, graph=True, replay_draws=False, audio_sr=16000):
+        if getattr(args, "model", "multimodal_context") != "joint_embedding":
+            raise ValueError(f"JointEmbedWindowDecoder: args.model is {getattr(args, 'model', 'multimodal_context')!r}, not 'joint_embedding'")
+        dec = getattr(net, "decoder", None)
+        if getattr(net, "context_encoder", None) is None or not hasattr(dec, "forward_constant"):
+            raise ValueError("JointEmbedWindowDecoder: the model must be an EmbeddingNet of mode 'random' or 'speech'")
+        if net.training:
+            raise ValueError("JointEmbedWindowDecoder: the model must be in eval mode (joint_embed.load_checkpoint_and_model leaves it so)")
+        T, n_pre = args.n_poses, args.n_pre_poses
+        if T != dec.gen_length or n_pre * dec.pose_dim != dec.pre_pose_net[0].in_features:
+            raise ValueError(f"JointEmbedWindowDecoder: args (n_poses, n_pre_poses) = {(T, n_pre)} but the model decodes {dec.gen_length} frames "
+                             f"from {dec.pre_pose_net[0].in_features // dec.pose_dim} seed poses")
+        if not 1 <= batch <= 4:
+            raise ValueError(f"JointEmbedWindowDecoder: 1 to 4 utterances in lock-step (the few-row recurrence kernel's rows), got {batch}")
+        self.args, self.net, self.B, self.dev = args, net, batch, device
+        self.T, self.n_pre, self.D = T, n_pre, dec.pose_dim
+        self.audio_len = int(T / args.motion_resampling_framerate * audio_sr)
+        self.draw = torch.zeros(batch, 32, device=device) if replay_draws else None
+        self.text = torch.zeros(batch, T, dtype=torch.int64, device=device)
+        self.audio = torch.zeros(batch, self.audio_len, device=device)
+        self.pre = torch.zeros(batch, n_pre, self.D, device=device)
+        self.tail = torch.zeros(batch, n_pre, self.D, device=device)
+        self.out = torch.zeros(batch, T, self.D, device=device)
+        self.use_graph, self.graph = graph, None
+        # as WindowDecoder: weight-only operands are formed by the first window and kept -- a decoder must not outlive a change of the parameters
+        self.frozen = L.FrozenWeights()
+
+    def seed(self, seed_seq=None):
+        """`pre` of the first window: zeros, or the seed poses (B, >= n_pre, D) (synthesize.py:46-50)."""
+        self.pre.zero_()
+        if seed_seq is not None:
+            self.pre.copy_(torch.as_tensor(seed_seq, dtype=torch.float32, device=self.dev)[..., :self.n_pre, :])
+
+    def _forward(self, first):
+        net = self.net
+        net.context_encoder.gru.few_row_eval = True              # one launch per layer (EmbeddingNet.synthesize sets it the same way)
+        inject = None if self.draw is None else {"c.eps": self.draw}       # None: the encoder advances its counter RNG on the device
+        latent, _, _ = net.context_encoder(self.text, self.audio, inject=inject)
+        res = net.decoder.forward_constant(latent, self.pre)
+        ops.copy2d(res.view(self.B * self.T, self.D), self.out.view(self.B * self.T, self.D))
+        if not first:                                            # cross-fade with the previous window's last frames (:145-153)
+            ops.window_blend(self.tail, self.out)
+        self.tail.copy_(self.out[:, self.T - self.n_pre:, :])    # strided device copy: kept for the next cross-fade ...
+        self.pre.copy_(self.tail)                                # ... and seeds the next window (:122-126)
+
+    def window(self, in_text, in_audio, first, draw=None):
+        """One window for the whole batch.  Inputs may be CPU or GPU tensors; returns the (B, T, D) output buffer (device, overwritten by the
+        next call)."""
+        self.text.copy_(in_text, non_blocking=True)
+        self.audio.copy_(in_audio, non_blocking=True)
+        if draw is not None:
+            self.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
+        with torch.no_grad(), self.frozen:
+            if not self.use_graph or first:
+                self._forward(first)
+            else:
+                if self.graph is None:
+                    torch.cuda.synchronize()
+                    self.graph = torch.cuda.CUDAGraph()
+                    keep = [t.clone() for t in (self.pre, self.tail, self.out)]
+                    pg_alive = torch.distributed.is_available() and torch.distributed.is_initialized()     # RCCL helper threads: see train_gan.GraphedGanStep
+                    with torch.cuda.graph(self.graph, capture_error_mode="thread_local" if pg_alive else "global"):
+                        self._forward(False)
+                    for t, k in zip((self.pre, self.tail, self.out), keep):       # capture does not execute: restore state
+                        t.copy_(k)
+                self.graph.replay()
+        return self.out
+
+
+def _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, window_decoder):
+    """_joint_embed_gestures_batch on a JointEmbedWindowDecoder: same windows, same lock-step rule, same return value.  window_decoder=True
+    builds a decoder for this call WITHOUT graph capture (a capture per call costs more than four windows save: DESIGN.md section 22); a
+    JointEmbedWindowDecoder instance is used as it is -- kept across calls, its graph is captured once."""
+    B, T, n_pre = len(audios), args.n_poses, args.n_pre_poses
+    if B > 4:
+        raise ValueError(f"window_decoder runs at most 4 utterances in lock-step, got {B}")
+    if isinstance(window_decoder, JointEmbedWindowDecoder):
+        dec = window_decoder
+        if dec.net is not pose_decoder or dec.B != B or (dec.T, dec.n_pre) != (T, n_pre) or (eps_list is not None) != (dec.draw is not None):
+            raise ValueError(f"window_decoder: the decoder was built for another model, {dec.B} utterance(s), (n_poses, n_pre_poses) = "
+                             f"{(dec.T, dec.n_pre)} or replay_draws = {dec.draw is not None}; this call has {B} utterance(s), {(T, n_pre)} and "
+                             f"eps_list {'given' if eps_list is not None else 'absent'}")
+    else:
+        dec = JointEmbedWindowDecoder(args, pose_decoder, B, next(pose_decoder.parameters()).device, graph=False, replay_draws=eps_list is not None,
+                                      audio_sr=audio_sr)
+    dec.seed(None if seed_seqs is None else np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]))
+    stride = T - n_pre
+    n_win = [num_windows(len(a) / audio_sr, T, n_pre, args.motion_resampling_framerate) for a in audios]
+    total = torch.zeros(B, max(n_win) * stride + n_pre, dec.D, device=dec.dev)
+    for i in range(max(n_win)):
+        a_np, t_np = [], []
+        for b in range(B):
+            a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], min(i, n_win[b] - 1), audio_sr)   # finished utterances idle
+            a_np.append(a); t_np.append(ids)
+        out = dec.window(torch.from_numpy(np.stack(t_np)), torch.from_numpy(np.stack(a_np)), first=(i == 0),
+                         draw=None if eps_list is None else eps_list[i])
+        for b in range(B):
+            if i < n_win[b]:                                                     # an idling utterance's frames are not written
+                total[b, i * stride:i * stride + T, :].copy_(out[b])
+    res = total.cpu().numpy()
+    return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
+
+
 def spec_slice_length(n_poses=34, fps=15, sr=16000):
     """synthesize.py:65: spectrogram frames fed per window, int(round(unit_time * sr / 512)): 71 for 34 poses at 15 fps -- one more than
     speech2gesture.spectrogram_length's 70 the generator was trained on; its 2-D convolutions reduce both widths to the same 7 columns."""
@@ -320,7 +433,7 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
 
 
 def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, vids=None, seed_seqs=None, audio_sr=16000,
-                            graph=True, _draws=None, spec_pad_mode="reflect", eps_list=None):
+                            graph=True, _draws=None, spec_pad_mode="reflect", eps_list=None, window_decoder=False):
     """Lock-step synthesis of several utterances.  Returns a list of (n_i * 30 + 4, D) numpy arrays (mean-subtracted direction
     vectors, like the reference's return value without fade-out).  vids: one speaker id per utterance, or None / a falsy entry to
     draw it like the reference (synthesize.py:67-74; ignored unless args.z_type == 'speaker').  _draws (parity tests): per window,
@@ -328,13 +441,22 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
     (the model sees the spectrogram only; no capture), spec_pad_mode is melspec.extract_melspectrogram's pad_mode.  args.model == 'seq2seq':
     the audios matter through their lengths only; the result includes the reference's cubic smoothing around every window boundary.
     args.model == 'joint_embedding': pose_decoder is an EmbeddingNet(mode='random' / 'speech') in eval mode; vids, graph unused; eps_list
-    (parity tests): per window, the (B, 32) eps of the context encoder's reparameterize instead of the counter RNG."""
+    (parity tests): per window, the (B, 32) eps of the context encoder's reparameterize instead of the counter RNG.  window_decoder
+    (joint_embedding only, at most 4 utterances; ValueError otherwise; off by default): True -- the windows run on a JointEmbedWindowDecoder
+    built for this call (static buffers, the decoder GRU on the constant-input recurrence, no graph capture) instead of fresh tensors per
+    window; a JointEmbedWindowDecoder instance -- that decoder, kept by the caller across calls, replaying the window graph it captured once
+    (built for the same model, utterance count and, with eps_list, replay_draws=True)."""
+    if window_decoder and getattr(args, "model", "multimodal_context") != "joint_embedding":
+        raise ValueError(f"window_decoder=True is the joint_embedding model's window decoder; args.model is {getattr(args, 'model', 'multimodal_context')!r} "
+                         "(the multimodal_context model always runs on its WindowDecoder)")
     if getattr(args, "model", "multimodal_context") == "speech2gesture":
         return _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode)
     if getattr(args, "model", "multimodal_context") == "seq2seq":             # audio matters through its length only; vids, graph unused
         outs, n_win = _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr)
         return [seq2seq_smooth(o, n, args.n_poses, args.n_pre_poses) for o, n in zip(outs, n_win)]
     if getattr(args, "model", "multimodal_context") == "joint_embedding":
+        if window_decoder:
+            return _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, window_decoder)
         return _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list)
     dev = next(pose_decoder.parameters()).device
     B = len(audios)
@@ -384,10 +506,12 @@ def fade_out_to_mean(out_dir_vec, end_padding_samples, args, audio_sr=16000):
 
 
 def generate_gestures(args, pose_decoder, lang_model, audio, words, audio_sr=16000, vid=None, seed_seq=None, fade_out=False,
-                      _draws=None, spec_pad_mode="reflect", eps_list=None):
-    """Single-utterance API of the reference (synthesize.py:36-209; multimodal_context, speech2gesture, seq2seq and joint_embedding models)."""
+                      _draws=None, spec_pad_mode="reflect", eps_list=None, window_decoder=False):
+    """Single-utterance API of the reference (synthesize.py:36-209; multimodal_context, speech2gesture, seq2seq and joint_embedding models).
+    window_decoder: see generate_gestures_batch."""
     out = generate_gestures_batch(args, pose_decoder, lang_model, [audio], [words], [vid], None if seed_seq is None else [seed_seq],
-                                  audio_sr, graph=True, _draws=_draws, spec_pad_mode=spec_pad_mode, eps_list=eps_list)[0]
+                                  audio_sr, graph=True, _draws=_draws, spec_pad_mode=spec_pad_mode, eps_list=eps_list,
+                                  window_decoder=window_decoder)[0]
     if not fade_out:
         return out
     if getattr(args, "model", "multimodal_context") in ("speech2gesture", "seq2seq"):

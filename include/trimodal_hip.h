@@ -319,6 +319,18 @@ int tg_gru_forward_vec(const float* gi, int64_t gi_dir_stride, const float* w_hh
 int tg_gru_vec1_supported(int32_t B, int32_t H, int32_t* supported);
 int tg_gru_forward_vec1(const float* gi, const float* w_hh, const float* b_hh, float* y, void* ws, int64_t ws_bytes, int32_t B, int32_t T,
                         int32_t H, void* stream);
+/* The constant-input form of the same kernel, for a layer whose input is the same row at every time step (PoseDecoderGRU's layer 0,
+ * embedding_net.py:153-157): gi [n_dir][B][3H] is ONE projected row per sequence and direction (gi_dir_stride floats between the directions,
+ * at least B * 3H; ignored with n_dir = 1) and is used at all T steps; y [B][T][n_dir * H]; w_hh_rev / b_hh_rev are ignored with n_dir = 1.
+ * Same arithmetic as the time-varying entries on that row repeated T times: y is bit-identical.  Envelope: that of tg_gru_vec_supported and
+ * n_dir in {1, 2}, T >= 1; outside it the entry returns non-zero ("unsupported shape ... envelope" in tg_last_error) and launches nothing;
+ * tg_gru_vec_const_supported writes 1 / 0 for positive sizes.  WORKSPACE: the rule of one direction count per workspace holds, and the
+ * constant-input form MAY SHARE a workspace with the time-varying form of the same direction count (tg_gru_forward_vec for n_dir = 2,
+ * tg_gru_forward_vec1 for n_dir = 1): grid, slot layout, resets and the launch counter are the same code, only the gi address differs. */
+int tg_gru_vec_const_supported(int32_t B, int32_t H, int32_t n_dir, int32_t* supported);
+int tg_gru_forward_vec_const(const float* gi, int64_t gi_dir_stride, const float* w_hh_fwd, const float* w_hh_rev, const float* b_hh_fwd,
+                             const float* b_hh_rev, float* y, void* ws, int64_t ws_bytes, int32_t B, int32_t T, int32_t H, int32_t n_dir,
+                             void* stream);
 
 /* Persistent cluster-synchronised variant of tg_gru_backward (B <= 192 at H = 300; no dh_scratch: the carried dh stays in
  * registers).  Same workspace / timeout-word convention as tg_gru_forward_cluster. */
