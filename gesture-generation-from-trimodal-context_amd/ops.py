@@ -1842,6 +1842,70 @@ def window_blend(prev_tail, nxt):
     call("tg_window_blend", _p(prev_tail), _p(nxt), B, nxt.shape[1], D, n, _stream()); return nxt
 
 
+# ------------------------------------------------------------------------------------------------- long-utterance synthesis (csrc/utterance.hip)
+def _dev_int(t, dtype, numel, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and t.numel() >= numel):
+        raise TypeError(f"{name}: expected a contiguous CUDA {dtype} tensor of at least {numel} elements")
+    return t
+
+
+def window_stage(plan, win_idx, text_out=None, audio_out=None):
+    """Window inputs of B utterances from their device-resident plan (synthesize.UtteranceBatch builds and validates it: every slice lies
+    inside its utterance): audio_out (B, L) fp32 = the audio slice, then zeros; text_out (B, W) int64 = the first W ids of the window's text
+    row.  win_idx (B,) int32 on the device: each row's window."""
+    B, G = plan["B"], plan["G"]
+    _dev_int(win_idx, torch.int32, B, "win_idx"); _dev_int(plan["win_off"], torch.int32, B + 1, "win_off")
+    _dev_int(plan["win"], torch.int64, 4 * G, "plan_win")
+    L = W = 0
+    if audio_out is not None:
+        _flat(audio_out, "audio_out"); _f32(plan["audio"], "audio"); _dev_int(plan["audio_off"], torch.int64, B + 1, "audio_off")
+        assert audio_out.dim() == 2 and audio_out.shape[0] == B and plan["audio"].numel() >= plan["audio_total"]
+        L = audio_out.shape[1]
+    if text_out is not None:
+        _i64(text_out, "text_out")
+        assert text_out.dim() == 2 and text_out.shape[0] == B and 0 < text_out.shape[1] <= plan["text_stride"]
+        _dev_int(plan["text"], torch.int64, G * plan["text_stride"], "plan_text")
+        W = text_out.shape[1]
+    call("tg_window_stage", _p(plan["audio"] if audio_out is not None else None), _p(plan["audio_off"] if audio_out is not None else None),
+         _p(plan["win_off"]), _p(win_idx), _p(plan["win"]), _p(plan["text"] if text_out is not None else None), plan["text_stride"], B, L, W,
+         _p(audio_out), _p(text_out), _stream())
+
+
+def spec_stage(plan, win_idx, spec, spec_off, n_mels, out):
+    """out (B, n_mels, width) = every row's spectrogram columns [spec_start, spec_start + width) of its window, zeros past the last column.
+    spec: the utterances' (n_mels, frames) spectrograms (fp16 or fp32) packed in one buffer, spec_off (B + 1,) int64 their offsets in elements."""
+    B, G = plan["B"], plan["G"]
+    _dev_int(win_idx, torch.int32, B, "win_idx"); _dev_int(plan["win_off"], torch.int32, B + 1, "win_off")
+    _dev_int(plan["win"], torch.int64, 4 * G, "plan_win"); _dev_int(spec_off, torch.int64, B + 1, "spec_off")
+    if not (spec.is_cuda and out.is_cuda and spec.dtype == out.dtype and spec.dtype in (torch.float16, torch.float32) and spec.is_contiguous() and out.is_contiguous()):
+        raise TypeError("spec_stage: spec and out must be contiguous CUDA tensors of one dtype, fp16 or fp32")
+    assert out.dim() == 3 and out.shape[0] == B and out.shape[1] == n_mels and spec.numel() >= plan["spec_total"]
+    call("tg_spec_stage", _p(spec), _p(spec_off), _p(plan["win_off"]), _p(win_idx), _p(plan["win"]), B, n_mels, out.shape[2], spec.element_size(),
+         _p(out), _stream())
+
+
+def utterance_finish(total, n_win, max_win, n_poses, n_pre, *, smooth=False, proj=None, fade_start=None, mean=None, joints=None):
+    """In place on total (B, F, D): seq2seq's cubic smoothing (smooth), the fade-out (fade_start (B,) int32, < 0: row left alone) and joint
+    positions (joints (B, Fj, 10, 3) fp64 with mean (27,) fp64).  proj: the fp64 projection tables of synthesize.projection_tables(n_pre).
+    Shapes outside the kernel's envelope are refused by the library (RuntimeError naming the envelope), nothing is launched."""
+    _flat(total, "total")
+    assert total.dim() == 3
+    B, F, D = total.shape
+    _dev_int(n_win, torch.int32, B, "n_win")
+    if proj is not None:
+        assert proj.is_cuda and proj.dtype == torch.float64 and proj.is_contiguous() and proj.numel() >= 13 * n_pre * n_pre
+    if fade_start is not None:
+        _dev_int(fade_start, torch.int32, B, "fade_start")
+    Fj = 0
+    if joints is not None:
+        assert joints.is_cuda and joints.dtype == torch.float64 and joints.is_contiguous() and joints.dim() == 4
+        assert joints.shape[0] == B and tuple(joints.shape[2:]) == (10, 3) and joints.shape[1] <= F
+        assert mean is not None and mean.is_cuda and mean.dtype == torch.float64 and mean.is_contiguous() and mean.numel() == 27
+        Fj = joints.shape[1]
+    call("tg_utterance_finish", _p(total), F, B, D, _p(n_win), int(max_win), int(n_poses), int(n_pre), int(bool(smooth)), _p(proj), _p(fade_start),
+         _p(mean), _p(joints), Fj, _stream())
+
+
 def pose_metrics(out, target, mean_dir_vec, n_pre, sums):
     _same(out, target); _flat(mean_dir_vec, "mean"); B, T, D = out.shape
     assert D == 27 and mean_dir_vec.numel() == 27 and sums.dtype == torch.float64 and sums.numel() >= 3 and sums.is_cuda

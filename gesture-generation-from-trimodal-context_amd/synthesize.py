@@ -25,6 +25,12 @@ reference does in eval mode.  Cross-fade on the device, fade-out on the host, no
 caller keeps a JointEmbedWindowDecoder (static buffers, the decoder GRU told that its input is constant over time, the non-first window
 captured into a hipGraph once and replayed) and hands it in as window_decoder; window_decoder=True builds one per call, without the graph.
 
+on_device=True (every model; opt-in) takes the host out of the window loop: utterance_plan computes every window of an utterance once, as
+integers, with the very expressions of window_inputs / seq2seq_window_text; UtteranceBatch uploads the packed audio and plans once; per window
+one launch (csrc/utterance.hip) cuts all rows' inputs on the device, into the window decoders' static buffers where there are any; seq2seq's
+smoothing, the fade-out and -- on request -- the joint positions are one more call on the stacked result (UtteranceBatch.finish), which
+return_device=True hands back without a read-back.  The scheduler is unchanged: lock-step, finished utterances idle.
+
 TTS / Gentle alignment / LMDB front-ends of the reference script are network services and out of scope; `words` is the
 reference's word list [[word, start_s, end_s], ...].
 """
@@ -58,26 +64,34 @@ def num_windows(clip_length, n_poses=34, n_pre_poses=4, fps=15):
     return math.ceil((clip_length - unit) / stride) + 1
 
 
-def window_inputs(args, lang_model, audio, words, i, audio_sr=16000):
-    """Audio slice (zero padded) and per-frame word ids of window i (synthesize.py:82-119).  Returns (audio (L,), ids (n_poses,),
-    end_padding_samples)."""
+def _window_geometry(args, lang_model, audio_len, words, i, audio_sr=16000):
+    """The integers of window i (synthesize.py:82-119): (audio_start, valid samples, zero samples appended, per-frame word ids).  The one place
+    where the reference's Python doubles decide them: window_inputs and utterance_plan both take them from here."""
     n_frames = args.n_poses
     unit_time = n_frames / args.motion_resampling_framerate
     stride_time = (n_frames - args.n_pre_poses) / args.motion_resampling_framerate
-    clip_length = len(audio) / audio_sr
+    clip_length = audio_len / audio_sr
     audio_sample_length = int(unit_time * audio_sr)
     start_time = i * stride_time
     end_time = start_time + unit_time
-    a0 = math.floor(start_time / clip_length * len(audio))
-    piece = np.asarray(audio[a0:a0 + audio_sample_length], dtype=np.float32)
-    pad = audio_sample_length - len(piece)
-    if pad > 0:
-        piece = np.pad(piece, (0, pad), "constant")
+    a0 = math.floor(start_time / clip_length * audio_len)
+    n_valid = len(range(audio_len)[a0:a0 + audio_sample_length])        # what the slice audio[a0:a0 + audio_sample_length] holds
+    pad = audio_sample_length - n_valid
     ids = np.zeros(n_frames, dtype=np.int64)                      # 0 = PAD
     frame_duration = (end_time - start_time) / n_frames
-    for w in words_in_time_range(words, start_time, end_time):
+    for w in words_in_time_range(words, start_time, end_time) if words else ():
         idx = max(0, int(np.floor((w[1] - start_time) / frame_duration)))
         ids[idx] = lang_model.get_word_index(w[0])
+    return a0, n_valid, pad, ids
+
+
+def window_inputs(args, lang_model, audio, words, i, audio_sr=16000):
+    """Audio slice (zero padded) and per-frame word ids of window i (synthesize.py:82-119).  Returns (audio (L,), ids (n_poses,),
+    end_padding_samples)."""
+    a0, n_valid, pad, ids = _window_geometry(args, lang_model, len(audio), words, i, audio_sr)
+    piece = np.asarray(audio[a0:a0 + n_valid + max(pad, 0)], dtype=np.float32)
+    if pad > 0:
+        piece = np.pad(piece, (0, pad), "constant")
     return piece, ids, max(pad, 0)
 
 
@@ -91,8 +105,8 @@ def seq2seq_window_text(lang_model, words, i, n_poses=34, n_pre_poses=4, fps=15)
 
 
 def seq2seq_smooth(out_dir_vec, n_windows, n_poses=34, n_pre_poses=4):
-    """synthesize.py:162-185, in place: around the start of every window (the 2 n_pre frames of the utterance's head for window 0, the 3 n_pre
-    frames from n_pre before the boundary for the others) each dimension is replaced by its unweighted cubic least-squares fit (the
+    """synthesize.py:162-185, in place: around the start of every window (the 3 n_pre frames from n_pre before the boundary; with n_smooth == n_pre
+    window 0's start_frame is 0, not negative, so its segment is as long as the others') each dimension is replaced by its unweighted cubic least-squares fit (the
     reference builds weights and does not pass them).  Slices past the end are clipped as numpy clips them."""
     n_smooth = n_pre_poses
     for i in range(n_windows):
@@ -109,8 +123,10 @@ def seq2seq_smooth(out_dir_vec, n_windows, n_poses=34, n_pre_poses=4):
     return out_dir_vec
 
 
-def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr):
-    """The seq2seq branch for several utterances in lock-step; returns the stacked windows BEFORE seq2seq_smooth, one array per utterance."""
+def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, device_opts=None):
+    """The seq2seq branch for several utterances in lock-step; returns the stacked windows BEFORE seq2seq_smooth, one array per utterance.
+    device_opts (fade_out, joints, return_device): the on_device path -- texts staged from the UtteranceBatch's plan, smoothing and fade-out in
+    its finish; returns generate_gestures_batch's value."""
     dev = next(pose_decoder.parameters()).device
     B, T, n_pre, fps = len(audios), args.n_poses, args.n_pre_poses, args.motion_resampling_framerate
     if T != pose_decoder.n_frames or n_pre != pose_decoder.n_pre_poses:
@@ -121,14 +137,21 @@ def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
     if seed_seqs is not None and n_pre > 0:                                      # synthesize.py:46-50
         pre[:, :n_pre].copy_(torch.as_tensor(np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]), dtype=torch.float32))
     tail = torch.zeros(B, n_pre, D, device=dev)
-    total = torch.zeros(B, max(n_win) * stride + n_pre, D, device=dev)
+    ub = None if device_opts is None else UtteranceBatch(args, lang_model, audios, words_list, dev, audio_sr)
+    total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), D, device=dev)
     for i in range(max(n_win)):
-        texts = [seq2seq_window_text(lang_model, words_list[b], min(i, n_win[b] - 1), T, n_pre, fps) for b in range(B)]   # finished utterances idle
-        lens = [len(t) for t in texts]
-        in_text = np.zeros((B, max(lens)), dtype=np.int64)                      # 0 = PAD
-        for b, t in enumerate(texts):
-            in_text[b, :len(t)] = t
-        out = pose_decoder.synthesize(torch.from_numpy(in_text).to(dev), lens, pre).contiguous()     # (B, T, D), synthesize.py:135-136
+        if ub is not None:
+            lens = ub.seq_lens(i)
+            text_dev = ub.text_buffer(max(lens))
+            ub.stage(i, text_out=text_dev)
+        else:
+            texts = [seq2seq_window_text(lang_model, words_list[b], min(i, n_win[b] - 1), T, n_pre, fps) for b in range(B)]   # finished utterances idle
+            lens = [len(t) for t in texts]
+            in_text = np.zeros((B, max(lens)), dtype=np.int64)                      # 0 = PAD
+            for b, t in enumerate(texts):
+                in_text[b, :len(t)] = t
+            text_dev = torch.from_numpy(in_text).to(dev)
+        out = pose_decoder.synthesize(text_dev, lens, pre).contiguous()     # (B, T, D), synthesize.py:135-136
         if i > 0 and n_pre > 0:
             ops.window_blend(tail, out)                                          # :145-153
         if n_pre > 0:
@@ -137,11 +160,13 @@ def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
         for b in range(B):
             if i < n_win[b]:                                                     # an idling utterance's frames are not written
                 total[b, i * stride:i * stride + T, :].copy_(out[b])
+    if ub is not None:
+        return _device_result(ub, total, *device_opts)
     res = total.cpu().numpy()
     return [res[b, :n_win[b] * stride + n_pre] for b in range(B)], n_win
 
 
-def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list):
+def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, device_opts=None):
     """The joint_embedding branch (synthesize.py:132-133) for several utterances in lock-step; same return value as generate_gestures_batch.
     eps_list (parity tests): per window, the (B, 32) eps of ContextEncoder's reparameterize instead of the counter RNG."""
     dev = next(pose_decoder.parameters()).device
@@ -158,15 +183,21 @@ def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_li
     if seed_seqs is not None:                                                   # synthesize.py:46-50
         pre.copy_(torch.as_tensor(np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]), dtype=torch.float32))
     tail = torch.zeros(B, n_pre, D, device=dev)
-    total = torch.zeros(B, max(n_win) * stride + n_pre, D, device=dev)
+    ub = None if device_opts is None else UtteranceBatch(args, lang_model, audios, words_list, dev, audio_sr)
+    total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), D, device=dev)
+    if ub is not None:                                                          # device_opts: the on_device path (see _seq2seq_gestures_batch)
+        text_dev, audio_dev = torch.zeros(B, T, dtype=torch.int64, device=dev), torch.zeros(B, ub.L, device=dev)
     for i in range(max(n_win)):
-        a_np, t_np = [], []
-        for b in range(B):
-            a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], min(i, n_win[b] - 1), audio_sr)   # finished utterances idle
-            a_np.append(a); t_np.append(ids)
+        if ub is not None:
+            ub.stage(i, text_dev, audio_dev)
+        else:
+            a_np, t_np = [], []
+            for b in range(B):
+                a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], min(i, n_win[b] - 1), audio_sr)   # finished utterances idle
+                a_np.append(a); t_np.append(ids)
+            text_dev, audio_dev = torch.from_numpy(np.stack(t_np)).to(dev), torch.from_numpy(np.stack(a_np)).to(dev)
         inject = None if eps_list is None else {"c.eps": torch.as_tensor(eps_list[i], dtype=torch.float32, device=dev)}
-        out = pose_decoder.synthesize(torch.from_numpy(np.stack(t_np)).to(dev), torch.from_numpy(np.stack(a_np)).to(dev), pre,
-                                      inject=inject).contiguous()                # (B, T, D), synthesize.py:133
+        out = pose_decoder.synthesize(text_dev, audio_dev, pre, inject=inject).contiguous()                # (B, T, D), synthesize.py:133
         if i > 0:
             ops.window_blend(tail, out)                                          # :145-153
         tail.copy_(out[:, T - n_pre:, :])
@@ -174,6 +205,8 @@ def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_li
         for b in range(B):
             if i < n_win[b]:                                                     # an idling utterance's frames are not written
                 total[b, i * stride:i * stride + T, :].copy_(out[b])
+    if ub is not None:
+        return _device_result(ub, total, *device_opts)
     res = total.cpu().numpy()
     return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
 
@@ -225,10 +258,12 @@ class WindowDecoder:
         ops.make_pre_seq(self.seedwin, self.pre_seq, self.n_pre)          # frames < n_pre + constraint bit, zeros elsewhere
 
     def window(self, in_text, in_audio, vid, first, draw=None):
-        """One window for the whole batch.  Inputs may be CPU or GPU tensors; returns the (B, T, D) output buffer (device,
-        overwritten by the next call)."""
-        self.text.copy_(in_text, non_blocking=True)
-        self.audio.copy_(in_audio, non_blocking=True)
+        """One window for the whole batch.  Inputs may be CPU or GPU tensors, or None: self.text / self.audio were filled in place
+        (UtteranceBatch.stage); returns the (B, T, D) output buffer (device, overwritten by the next call)."""
+        if in_text is not None:
+            self.text.copy_(in_text, non_blocking=True)
+        if in_audio is not None:
+            self.audio.copy_(in_audio, non_blocking=True)
         if vid is not None:
             self.vid.copy_(vid, non_blocking=True)
         if draw is not None:
@@ -304,10 +339,12 @@ class JointEmbedWindowDecoder:
         self.pre.copy_(self.tail)                                # ... and seeds the next window (:122-126)
 
     def window(self, in_text, in_audio, first, draw=None):
-        """One window for the whole batch.  Inputs may be CPU or GPU tensors; returns the (B, T, D) output buffer (device, overwritten by the
-        next call)."""
-        self.text.copy_(in_text, non_blocking=True)
-        self.audio.copy_(in_audio, non_blocking=True)
+        """One window for the whole batch.  Inputs may be CPU or GPU tensors, or None: self.text / self.audio were filled in place
+        (UtteranceBatch.stage); returns the (B, T, D) output buffer (device, overwritten by the next call)."""
+        if in_text is not None:
+            self.text.copy_(in_text, non_blocking=True)
+        if in_audio is not None:
+            self.audio.copy_(in_audio, non_blocking=True)
         if draw is not None:
             self.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
         with torch.no_grad(), self.frozen:
@@ -327,7 +364,8 @@ class JointEmbedWindowDecoder:
         return self.out
 
 
-def _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, window_decoder):
+def _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, window_decoder,
+                                       device_opts=None):
     """_joint_embed_gestures_batch on a JointEmbedWindowDecoder: same windows, same lock-step rule, same return value.  window_decoder=True
     builds a decoder for this call WITHOUT graph capture (a capture per call costs more than four windows save: DESIGN.md section 22); a
     JointEmbedWindowDecoder instance is used as it is -- kept across calls, its graph is captured once."""
@@ -346,17 +384,24 @@ def _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, w
     dec.seed(None if seed_seqs is None else np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]))
     stride = T - n_pre
     n_win = [num_windows(len(a) / audio_sr, T, n_pre, args.motion_resampling_framerate) for a in audios]
-    total = torch.zeros(B, max(n_win) * stride + n_pre, dec.D, device=dec.dev)
+    ub = None if device_opts is None else UtteranceBatch(args, lang_model, audios, words_list, dec.dev, audio_sr)
+    total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), dec.D, device=dec.dev)
     for i in range(max(n_win)):
-        a_np, t_np = [], []
-        for b in range(B):
-            a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], min(i, n_win[b] - 1), audio_sr)   # finished utterances idle
-            a_np.append(a); t_np.append(ids)
-        out = dec.window(torch.from_numpy(np.stack(t_np)), torch.from_numpy(np.stack(a_np)), first=(i == 0),
-                         draw=None if eps_list is None else eps_list[i])
+        if ub is not None:                                                       # the on_device path: straight into the decoder's static buffers
+            ub.stage(i, dec.text, dec.audio)
+            t_in = a_in = None
+        else:
+            a_np, t_np = [], []
+            for b in range(B):
+                a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], min(i, n_win[b] - 1), audio_sr)   # finished utterances idle
+                a_np.append(a); t_np.append(ids)
+            t_in, a_in = torch.from_numpy(np.stack(t_np)), torch.from_numpy(np.stack(a_np))
+        out = dec.window(t_in, a_in, first=(i == 0), draw=None if eps_list is None else eps_list[i])
         for b in range(B):
             if i < n_win[b]:                                                     # an idling utterance's frames are not written
                 total[b, i * stride:i * stride + T, :].copy_(out[b])
+    if ub is not None:
+        return _device_result(ub, total, *device_opts)
     res = total.cpu().numpy()
     return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
 
@@ -384,7 +429,178 @@ def end_padding_samples(args, n_samples, audio_sr=16000):
     return max(0, int(args.n_poses / args.motion_resampling_framerate * audio_sr) - (n_samples - a0))
 
 
-def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode):
+def utterance_plan(args, lang_model, audio_len, words, audio_sr=16000, model=None):
+    """Every window of one utterance as integers, computed once on the host by the expressions of window_inputs, seq2seq_window_text, num_windows
+    and spec_window_start themselves (_window_geometry; no floating-point step is restated).  Returns a dict: n_win; audio_start, n_valid
+    (n_win,) int64 -- window i is audio[audio_start[i]:][:n_valid[i]] followed by zeros; end_padding (the zeros appended to the last window);
+    ids (n_win, n_poses) int64 per-frame word ids (zeros for speech2gesture); model 'seq2seq': seq -- the list of [SOS, ..., EOS] arrays --
+    and seq_len (n_win,); model 'speech2gesture': spec_start (n_win,) int64.  model defaults to args.model."""
+    model = model or getattr(args, "model", "multimodal_context")
+    T, n_pre, fps = args.n_poses, args.n_pre_poses, args.motion_resampling_framerate
+    n_win = num_windows(audio_len / audio_sr, T, n_pre, fps)
+    text = model != "speech2gesture"
+    geo = [_window_geometry(args, lang_model, audio_len, words if text else None, i, audio_sr) for i in range(n_win)]
+    plan = dict(n_win=n_win, audio_len=int(audio_len), audio_start=np.array([g[0] for g in geo], dtype=np.int64),
+                n_valid=np.array([g[1] for g in geo], dtype=np.int64), end_padding=max(geo[-1][2], 0), ids=np.stack([g[3] for g in geo]))
+    if model == "seq2seq":
+        plan["seq"] = [seq2seq_window_text(lang_model, words, i, T, n_pre, fps) for i in range(n_win)]
+        plan["seq_len"] = np.array([len(t) for t in plan["seq"]], dtype=np.int64)
+    if model == "speech2gesture":
+        plan["spec_start"] = np.array([spec_window_start(i, audio_len / audio_sr, melspec.N_MELS, T, n_pre, fps) for i in range(n_win)], dtype=np.int64)
+    return plan
+
+
+def _projection(n, deg, w=None):
+    """(n, n) fp64 matrix P with P @ y = the degree-`deg` least-squares fit of y on the abscissae 0 .. n-1, evaluated there; weights w as
+    np.polyfit applies them (to the residuals).  From an orthonormal basis Q of the weighted polynomial columns: P = W^-1 Q Q^T W.  With
+    n <= deg + 1 the fit interpolates and P is the identity, as np.polyfit's minimum-norm solution gives."""
+    w = np.ones(n) if w is None else np.asarray(w, dtype=np.float64)
+    x = np.arange(n, dtype=np.float64) / max(n - 1, 1)                  # the fitted VALUES do not depend on the abscissae's scale
+    q, _ = np.linalg.qr(w[:, None] * np.vander(x, min(deg + 1, n)))
+    return (q @ q.T) * (w[None, :] / w[:, None])
+
+
+def projection_tables(n_pre):
+    """The two fits of the utterance's finish as projections (fp64): 'smooth' (3 n_pre points, cubic: seq2seq_smooth, whose segment of window 0
+    starts at frame 0 and is as long as the others') and 'fade' (2 n_pre points, quadratic, weight 5 on both ends: fade_out_to_mean)."""
+    w = np.ones(2 * n_pre); w[0] = 5; w[-1] = 5
+    return dict(smooth=_projection(3 * n_pre, 3), fade=_projection(2 * n_pre, 2, w))
+
+
+def _fade_start_frame(n_frames, end_padding_samples, args, audio_sr=16000):
+    """synthesize.py:190: the frame where the real audio ended."""
+    return n_frames - int(end_padding_samples / audio_sr * args.motion_resampling_framerate)
+
+
+class UtteranceBatch:
+    """The device-resident side of a lock-step synthesis call: the utterances' audio packed in one buffer and their window plans
+    (utterance_plan) packed in integer tables, built and uploaded ONCE.  stage(i, ...) then writes window i's inputs of every utterance into
+    caller-given device buffers in one launch (ops.window_stage; a finished utterance repeats its last window), finish(total, ...) runs
+    seq2seq's smoothing, the fade-out and the joint integration on the stacked windows (ops.utterance_finish).  Every slice is checked against
+    its utterance here, on the host, before anything is uploaded."""
+
+    def __init__(self, args, lang_model, audios, words_list, device, audio_sr=16000):
+        self.args, self.dev, self.audio_sr = args, device, audio_sr
+        self.model = getattr(args, "model", "multimodal_context")
+        self.T, self.n_pre = args.n_poses, args.n_pre_poses
+        self.stride = self.T - self.n_pre
+        self.L = int(self.T / args.motion_resampling_framerate * audio_sr)
+        B = self.B = len(audios)
+        words_list = [None] * B if words_list is None else words_list
+        self.plans = [utterance_plan(args, lang_model, len(a), w, audio_sr, self.model) for a, w in zip(audios, words_list)]
+        self.n_win = [p["n_win"] for p in self.plans]
+        self.max_win = max(self.n_win)
+        self.lengths = [n * self.stride + self.n_pre for n in self.n_win]              # frames of every utterance's result
+        win_off = np.concatenate([[0], np.cumsum(self.n_win)]).astype(np.int32)
+        G = int(win_off[-1])
+        for p in self.plans:
+            if (p["audio_start"] < 0).any() or (p["n_valid"] < 0).any() or (p["audio_start"] + p["n_valid"] > p["audio_len"]).any() or (p["n_valid"] > self.L).any():
+                raise ValueError("UtteranceBatch: a window's audio slice leaves its utterance")
+        win = np.zeros((G, 4), dtype=np.int64)
+        win[:, 0] = np.concatenate([p["audio_start"] for p in self.plans])
+        win[:, 1] = np.concatenate([p["n_valid"] for p in self.plans])
+        if self.model == "speech2gesture":
+            win[:, 2] = np.concatenate([p["spec_start"] for p in self.plans])
+        if self.model == "seq2seq":
+            seqs = [t for p in self.plans for t in p["seq"]]
+            win[:, 3] = [len(t) for t in seqs]
+            text = np.zeros((G, max(len(t) for t in seqs)), dtype=np.int64)             # 0 = PAD
+            for g, t in enumerate(seqs):
+                text[g, :len(t)] = t
+        else:
+            text = np.concatenate([p["ids"] for p in self.plans])
+            win[:, 3] = self.T
+        self.plan = dict(B=B, G=G, text_stride=text.shape[1], win_off=torch.from_numpy(win_off).to(device), win=torch.from_numpy(win).to(device),
+                         text=torch.from_numpy(np.ascontiguousarray(text)).to(device), audio=None, audio_off=None, audio_total=0)
+        if self.model in ("multimodal_context", "joint_embedding"):                    # the other two models never see the samples
+            off = np.concatenate([[0], np.cumsum([len(a) for a in audios])]).astype(np.int64)
+            packed = np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1) for a in audios])
+            self.plan.update(audio=torch.from_numpy(packed).to(device), audio_off=torch.from_numpy(off).to(device), audio_total=int(off[-1]))
+        # row b's window in lock-step step i: min(i, n_win[b] - 1), for every step, uploaded once
+        idx = np.minimum(np.arange(self.max_win)[:, None], np.array(self.n_win)[None, :] - 1).astype(np.int32)
+        self.win_idx = torch.from_numpy(np.ascontiguousarray(idx)).to(device)
+        self.n_win_dev = torch.tensor(self.n_win, dtype=torch.int32, device=device)
+        self._text_buf = self._tables = None
+        self.spec = self.spec_off = self.spec_frames = self.joints = None
+
+    def seq_lens(self, i):
+        """seq2seq: the text lengths of lock-step step i, one per utterance (host integers from the plan)."""
+        return [int(p["seq_len"][min(i, p["n_win"] - 1)]) for p in self.plans]
+
+    def text_buffer(self, width):
+        """A contiguous (B, width) int64 view of one static buffer (seq2seq: the batch's text width changes from window to window)."""
+        if self._text_buf is None:
+            self._text_buf = torch.zeros(self.B * self.plan["text_stride"], dtype=torch.int64, device=self.dev)
+        return self._text_buf[:self.B * width].view(self.B, width)
+
+    def stage(self, i, text_out=None, audio_out=None):
+        """Window i of every utterance: text_out (B, n_poses) -- seq2seq: (B, max(seq_lens(i))) -- int64 and / or audio_out (B, L) fp32,
+        device buffers written in place by one launch."""
+        if not 0 <= i < self.max_win:
+            raise IndexError(f"UtteranceBatch.stage: window {i} of {self.max_win}")
+        if audio_out is not None and self.plan["audio"] is None:
+            raise ValueError(f"UtteranceBatch.stage: the {self.model} model takes no audio samples")
+        if audio_out is not None and tuple(audio_out.shape) != (self.B, self.L):
+            raise ValueError(f"UtteranceBatch.stage: audio_out is {tuple(audio_out.shape)}, a window is {(self.B, self.L)}")
+        ops.window_stage(self.plan, self.win_idx[i], text_out, audio_out)
+
+    def set_spectrograms(self, specs):
+        """speech2gesture: the utterances' (n_mels, frames) device spectrograms, packed once."""
+        self.spec_frames = [int(s.shape[1]) for s in specs]
+        self.spec = torch.cat([s.reshape(-1) for s in specs]).contiguous()
+        off = np.concatenate([[0], np.cumsum([s.shape[0] * s.shape[1] for s in specs])]).astype(np.int64)
+        self.spec_off = torch.from_numpy(off).to(self.dev)
+        self.plan["spec_total"] = int(off[-1])
+
+    def spec_widths(self, i, width):
+        """speech2gesture: spectrogram frames each utterance's slice of step i really has (a slice at the spectrogram's end is short)."""
+        return [min(width, f - int(p["spec_start"][min(i, p["n_win"] - 1)])) for p, f in zip(self.plans, self.spec_frames)]
+
+    def stage_spec(self, i, out):
+        ops.spec_stage(self.plan, self.win_idx[i], self.spec, self.spec_off, melspec.N_MELS, out)
+
+    def frames(self, fade_out=False):
+        """Frames total must hold per row for finish(fade_out=...)."""
+        return self.max_win * self.stride + self.n_pre + (2 * self.n_pre if fade_out else 0)
+
+    def finish(self, total, fade_out=False, joints=False, smooth=None):
+        """In place on total (B, >= frames(fade_out), D), device: seq2seq's smoothing (smooth; default: the model is seq2seq), the fade-out of
+        every row, joint positions.  Returns (rows, joint_rows): row b is the view total[b, :its length] (with fade_out the reference's
+        max(length, end_frame)), joint_rows the matching fp64 (frames, 10, 3) views or None.  Nothing is read back."""
+        smooth = self.model == "seq2seq" if smooth is None else smooth
+        n, lengths, fade_start, tab, mean, jt = self.n_pre, list(self.lengths), None, None, None, None
+        if total.dim() != 3 or total.shape[0] != self.B or total.shape[1] < self.frames(fade_out):
+            raise ValueError(f"UtteranceBatch.finish: total is {tuple(total.shape)}, needs ({self.B}, >= {self.frames(fade_out)}, D)")
+        if fade_out:
+            starts = [_fade_start_frame(l, p["end_padding"], self.args, self.audio_sr) for l, p in zip(lengths, self.plans)]
+            lengths = [max(l, s + 2 * n) for l, s in zip(lengths, starts)]
+            fade_start = torch.tensor(starts, dtype=torch.int32, device=self.dev)
+        if (smooth or fade_out) and 1 <= n <= 8:                   # (outside: the library refuses the call and names its envelope)
+            if self._tables is None:
+                t = projection_tables(n)
+                self._tables = torch.from_numpy(np.concatenate([t["smooth"].ravel(), t["fade"].ravel()])).to(self.dev)
+            tab = self._tables
+        if joints:
+            mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
+            jt = self.joints = torch.zeros(self.B, total.shape[1], 10, 3, dtype=torch.float64, device=self.dev)
+        if smooth or fade_out or joints:
+            ops.utterance_finish(total, self.n_win_dev, self.max_win, self.T, n, smooth=smooth, proj=tab, fade_start=fade_start, mean=mean, joints=jt)
+        return [total[b, :l] for b, l in enumerate(lengths)], None if jt is None else [jt[b, :l] for b, l in enumerate(lengths)]
+
+
+def _device_result(ub, total, fade_out, joints, return_device):
+    """finish + the return value of an on_device synthesis call: device row views, or one read-back of the whole buffer."""
+    rows, jrows = ub.finish(total, fade_out=fade_out, joints=joints)
+    if not return_device:
+        res = total.cpu().numpy()
+        rows = [res[b, :len(r)] for b, r in enumerate(rows)]
+        if joints:
+            jres = ub.joints.cpu().numpy()
+            jrows = [jres[b, :len(r)] for b, r in enumerate(rows)]
+    return (rows, jrows) if joints else rows
+
+
+def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode, device_opts=None):
     """The speech2gesture branch for several utterances in lock-step; same return value as generate_gestures_batch."""
     if audio_sr != melspec.SR:
         raise ValueError(f"speech2gesture synthesis: audio_sr = {audio_sr}; the spectrogram is defined for {melspec.SR} Hz audio")
@@ -407,14 +623,24 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
     if seed_seqs is not None:                                                   # synthesize.py:46-50
         pre.copy_(torch.as_tensor(np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]), dtype=torch.float32))
     tail = torch.zeros(B, n_pre, D, device=dev)
-    total = torch.zeros(B, max(n_win) * stride + n_pre, D, device=dev)
+    ub = None
+    if device_opts is not None:                                                 # the on_device path: slices cut by ops.spec_stage from the packed spectrograms
+        ub = UtteranceBatch(args, None, audios, None, dev, audio_sr)
+        ub.set_spectrograms(specs)
+        spec_dev = torch.zeros(B, melspec.N_MELS, width, device=dev, dtype=specs[0].dtype)
+    total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), D, device=dev)
     was_training = pose_decoder.training
     pose_decoder.eval()
     try:
         with torch.no_grad():
             for i in range(max(n_win)):
-                a0 = [st[min(i, len(st) - 1)] for st in starts]                 # finished utterances idle on their last window
-                pieces = [specs[b][:, a0[b]:a0[b] + width] for b in range(B)]   # :90-92 (a slice at the spectrogram's end is one frame short)
+                if ub is not None:
+                    ub.stage_spec(i, spec_dev)
+                    widths = ub.spec_widths(i, width)
+                    pieces = [spec_dev[b, :, :widths[b]] for b in range(B)]
+                else:
+                    a0 = [st[min(i, len(st) - 1)] for st in starts]                 # finished utterances idle on their last window
+                    pieces = [specs[b][:, a0[b]:a0[b] + width] for b in range(B)]   # :90-92 (a slice at the spectrogram's end is one frame short)
                 out = torch.empty(B, T, D, device=dev)
                 for w in sorted({p.shape[1] for p in pieces}):
                     idx = [b for b in range(B) if pieces[b].shape[1] == w]
@@ -428,12 +654,15 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
                         total[b, i * stride:i * stride + T, :].copy_(out[b])
     finally:
         pose_decoder.train(was_training)
+    if ub is not None:
+        return _device_result(ub, total, *device_opts)
     res = total.cpu().numpy()
     return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
 
 
 def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, vids=None, seed_seqs=None, audio_sr=16000,
-                            graph=True, _draws=None, spec_pad_mode="reflect", eps_list=None, window_decoder=False):
+                            graph=True, _draws=None, spec_pad_mode="reflect", eps_list=None, window_decoder=False, on_device=False,
+                            return_device=False, joints=False, fade_out=False):
     """Lock-step synthesis of several utterances.  Returns a list of (n_i * 30 + 4, D) numpy arrays (mean-subtracted direction
     vectors, like the reference's return value without fade-out).  vids: one speaker id per utterance, or None / a falsy entry to
     draw it like the reference (synthesize.py:67-74; ignored unless args.z_type == 'speaker').  _draws (parity tests): per window,
@@ -445,19 +674,37 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
     (joint_embedding only, at most 4 utterances; ValueError otherwise; off by default): True -- the windows run on a JointEmbedWindowDecoder
     built for this call (static buffers, the decoder GRU on the constant-input recurrence, no graph capture) instead of fresh tensors per
     window; a JointEmbedWindowDecoder instance -- that decoder, kept by the caller across calls, replaying the window graph it captured once
-    (built for the same model, utterance count and, with eps_list, replay_draws=True)."""
+    (built for the same model, utterance count and, with eps_list, replay_draws=True).
+    on_device (every model; off by default): the utterances' audio and window plans are uploaded once (UtteranceBatch), every window's inputs
+    are cut on the device (no numpy and no host-to-device copy of text or audio in the loop; the window decoders' static buffers are written
+    in place), seq2seq's smoothing and the fade-out run in ops.utterance_finish.  Window inputs are bit-equal to the default path's, so the
+    forward's results are; the fitted frames agree with the numpy fits to one fp32 rounding.  With it: return_device=True returns device
+    tensors (row views of one buffer; nothing is read back) and joints=True returns (rows, joint_rows), joint_rows[b] the fp64
+    (frames, 10, 3) joint positions of rows[b] + args.mean_dir_vec.  fade_out: every utterance faded out to the mean pose
+    (fade_out_to_mean), on either path."""
+    model = getattr(args, "model", "multimodal_context")
+    if (return_device or joints) and not on_device:
+        raise ValueError("return_device and joints belong to the on_device path: pass on_device=True")
+    dopts = (bool(fade_out), bool(joints), bool(return_device)) if on_device else None
+    if not on_device and fade_out:                                               # the host path: numpy fits, utterance by utterance
+        outs = generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, vids, seed_seqs, audio_sr, graph, _draws, spec_pad_mode,
+                                       eps_list, window_decoder)
+        return [fade_out_to_mean(o, end_padding_samples(args, len(a), audio_sr), args, audio_sr) for o, a in zip(outs, audios)]
     if window_decoder and getattr(args, "model", "multimodal_context") != "joint_embedding":
         raise ValueError(f"window_decoder=True is the joint_embedding model's window decoder; args.model is {getattr(args, 'model', 'multimodal_context')!r} "
                          "(the multimodal_context model always runs on its WindowDecoder)")
     if getattr(args, "model", "multimodal_context") == "speech2gesture":
-        return _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode)
+        return _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode, dopts)
     if getattr(args, "model", "multimodal_context") == "seq2seq":             # audio matters through its length only; vids, graph unused
+        if on_device:
+            return _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, dopts)
         outs, n_win = _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr)
         return [seq2seq_smooth(o, n, args.n_poses, args.n_pre_poses) for o, n in zip(outs, n_win)]
     if getattr(args, "model", "multimodal_context") == "joint_embedding":
         if window_decoder:
-            return _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, window_decoder)
-        return _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list)
+            return _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, window_decoder,
+                                                      dopts)
+        return _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, dopts)
     dev = next(pose_decoder.parameters()).device
     B = len(audios)
     n_win = [num_windows(len(a) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate) for a in audios]
@@ -471,18 +718,25 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
                 vids[b] = random.randrange(pose_decoder.z_obj.n_words)
         vid = torch.as_tensor(vids, dtype=torch.int64)
     stride = args.n_poses - args.n_pre_poses
-    total = torch.zeros(B, max(n_win) * stride + args.n_pre_poses, dec.D, device=dev)
+    ub = UtteranceBatch(args, lang_model, audios, words_list, dev, audio_sr) if on_device else None
+    total = torch.zeros(B, max(n_win) * stride + args.n_pre_poses if ub is None else ub.frames(fade_out), dec.D, device=dev)
     for i in range(max(n_win)):
-        a_np, t_np = [], []
-        for b in range(B):
-            j = min(i, n_win[b] - 1)                               # finished utterances idle on their last window
-            a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], j, audio_sr)
-            a_np.append(a); t_np.append(ids)
-        out = dec.window(torch.from_numpy(np.stack(t_np)), torch.from_numpy(np.stack(a_np)), vid, first=(i == 0),
-                         draw=None if _draws is None else _draws[i])
+        if ub is not None:                                         # straight into the decoder's static buffers; the speaker ids go up once
+            ub.stage(i, dec.text, dec.audio)
+            out = dec.window(None, None, vid if i == 0 else None, first=(i == 0), draw=None if _draws is None else _draws[i])
+        else:
+            a_np, t_np = [], []
+            for b in range(B):
+                j = min(i, n_win[b] - 1)                               # finished utterances idle on their last window
+                a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], j, audio_sr)
+                a_np.append(a); t_np.append(ids)
+            out = dec.window(torch.from_numpy(np.stack(t_np)), torch.from_numpy(np.stack(a_np)), vid, first=(i == 0),
+                             draw=None if _draws is None else _draws[i])
         # out_list[-1][:-n_pre] + blended window == write the whole window at frame i*stride (its first n_pre frames overwrite
         # the previous window's last n_pre frames with the cross-faded values)
         total[:, i * stride:i * stride + args.n_poses, :].copy_(out)
+    if ub is not None:
+        return _device_result(ub, total, *dopts)
     res = total.cpu().numpy()
     return [res[b, :n_win[b] * stride + args.n_pre_poses] for b in range(B)]
 
@@ -506,9 +760,15 @@ def fade_out_to_mean(out_dir_vec, end_padding_samples, args, audio_sr=16000):
 
 
 def generate_gestures(args, pose_decoder, lang_model, audio, words, audio_sr=16000, vid=None, seed_seq=None, fade_out=False,
-                      _draws=None, spec_pad_mode="reflect", eps_list=None, window_decoder=False):
+                      _draws=None, spec_pad_mode="reflect", eps_list=None, window_decoder=False, on_device=False, return_device=False, joints=False):
     """Single-utterance API of the reference (synthesize.py:36-209; multimodal_context, speech2gesture, seq2seq and joint_embedding models).
-    window_decoder: see generate_gestures_batch."""
+    window_decoder, on_device, return_device, joints: see generate_gestures_batch (with on_device the fade-out runs on the device too;
+    joints=True returns (out, joint positions))."""
+    if on_device or return_device or joints:
+        res = generate_gestures_batch(args, pose_decoder, lang_model, [audio], [words], [vid], None if seed_seq is None else [seed_seq], audio_sr,
+                                      graph=True, _draws=_draws, spec_pad_mode=spec_pad_mode, eps_list=eps_list, window_decoder=window_decoder,
+                                      on_device=on_device, return_device=return_device, joints=joints, fade_out=fade_out)
+        return (res[0][0], res[1][0]) if joints else res[0]
     out = generate_gestures_batch(args, pose_decoder, lang_model, [audio], [words], [vid], None if seed_seq is None else [seed_seq],
                                   audio_sr, graph=True, _draws=_draws, spec_pad_mode=spec_pad_mode, eps_list=eps_list,
                                   window_decoder=window_decoder)[0]

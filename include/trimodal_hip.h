@@ -670,6 +670,33 @@ int tg_sigmoid_bwd(const float* dy, const float* y, float* dx, int64_t n, void* 
  * next[b][j][:] = prev_tail[b][j][:] * (n-j)/(n+1) + next[b][j][:] * (j+1)/(n+1), j < n.  next: [B][T][D], prev_tail: [B][n][D]. */
 int tg_window_blend(const float* prev_tail, float* next, int32_t B, int32_t T, int32_t D, int32_t n, void* stream);
 
+/* Long-utterance synthesis on the device (csrc/utterance.hip; synthesize.py:82-119,162-207).  The window plan of utterance b occupies rows
+ * [win_off[b], win_off[b+1]) of plan_win [G][4] = (audio_start, n_valid, spec_start, text length) and plan_text [G][text_stride]; it holds
+ * integers only, computed once per utterance by the host.  win_idx [B] (device memory) is each row's window, clamped to the utterance's own
+ * windows.  tg_window_stage writes out_audio [B][L] = audio[audio_off[b] + audio_start ...][0:n_valid] followed by zeros (null: no audio) and
+ * out_text [B][text_w] = the first text_w entries of the window's plan_text row (null: no text); 16-byte copies where both sides are
+ * aligned.  Bit-exact against the host path. */
+int tg_window_stage(const float* audio, const int64_t* audio_off, const int32_t* win_off, const int32_t* win_idx, const int64_t* plan_win,
+                    const int64_t* plan_text, int32_t text_stride, int32_t B, int32_t L, int32_t text_w, float* out_audio, int64_t* out_text,
+                    void* stream);
+/* The speech2gesture sibling: out [B][n_mels][width] = columns [spec_start, spec_start + width) of utterance b's spectrogram
+ * [n_mels][(spec_off[b+1] - spec_off[b]) / n_mels] (offsets in elements), zeros past its last column.  Elements of elem_bytes = 2 (fp16) or 4
+ * (fp32) bytes, copied as they are. */
+int tg_spec_stage(const void* spec, const int64_t* spec_off, const int32_t* win_off, const int32_t* win_idx, const int64_t* plan_win, int32_t B,
+                  int32_t n_mels, int32_t width, int32_t elem_bytes, void* out, void* stream);
+/* In place on the stacked windows total [B][F][D] (row b holds n_win[b] * (n_poses - n_pre) + n_pre frames; n_win [B] int32 on the device,
+ * all <= max_win), in this order, each part optional:
+ *   smooth != 0        seq2seq's cubic least-squares fit around every window start (frames [i stride, i stride + 3 n_pre), i < n_win[b]);
+ *   fade_start != null  per row with fade_start[b] >= 0: frames from fade_start[b] + n_pre on are zeroed (to F), frames [fade_start[b],
+ *                      fade_start[b] + 2 n_pre) are replaced by the weighted quadratic fit; frames past the row's length count as zeros
+ *                      (F >= max_win * stride + 3 n_pre);
+ *   joints != null     joints [B][joints_frames][10][3] fp64 = bone integration of total + mean (fp64 [27]; D == 27).
+ * proj (fp64): the (3 n_pre)^2 cubic projection, then the (2 n_pre)^2 weighted quadratic one, row-major; products are
+ * accumulated in fp64 and rounded once.  Envelope: 1 <= n_pre <= 8, D <= 64, n_poses - n_pre >= 3 n_pre; refused otherwise. */
+int tg_utterance_finish(float* total, int64_t F, int32_t B, int32_t D, const int32_t* n_win, int32_t max_win, int32_t n_poses, int32_t n_pre,
+                        int32_t smooth, const double* proj, const int32_t* fade_start, const double* mean, double* joints, int64_t joints_frames,
+                        void* stream);
+
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over
  * T-2 frames, sums[2] = sum |out - target|.  (joint_mae = sums[0]/(B*(T-n_pre)*30), accel = sums[1]/(B*(T-2)*30), l1 = sums[2]/(B*T*27).) */
