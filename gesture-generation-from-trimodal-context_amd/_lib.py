@@ -186,6 +186,9 @@ SIGNATURES = {
     "tg_latent_head_supported": [I32, I32, I32, I32, I32, P],
     "tg_latent_head_fwd": [P, I64] + [P] * 15 + [U32, P, I64] + [P] * 6 + [I32] * 5 + [F32, F32, F32, P],
     "tg_latent_head_bwd": [P, I64, P, P, P, I64] + [P] * 23 + [I64] + [I32] * 5 + [F32, P],
+    "tg_vae_latent_fwd": [P] * 7 + [U32] + [P] * 4 + [I32, P],
+    "tg_vae_latent_bwd": [P] * 9 + [F32] + [P] * 6 + [I32, P],
+    "tg_vae_kld": [P, P, I32, I32, F32, P, P, P, P],
 }
 
 ABI_VERSION = 11

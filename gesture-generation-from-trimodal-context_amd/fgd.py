@@ -226,7 +226,9 @@ def _ae_plan(net, target):
     buffers = dict(net.named_buffers())
     if p is None or p.cache_key != ops.AeStep.key(slab, buffers, B):
         assert not torch.cuda.is_current_stream_capturing(), "run one eager step before capturing (the plan allocates its workspace)"
-        slab.zero_grad()                 # fc_logvar gets no gradient (:58): its slots stay zero, every other one is written by each step
+        # fc_logvar gets no gradient (:58): its slots stay zero, every other one is written by each step.  A VAE step (_vae_step) does write
+        # them; the AE step that follows it zeroes them again (_ae_after_vae), so "zero while AE steps run" keeps holding
+        slab.zero_grad()
         p = E._ae_plan = ops.AeStep(slab, buffers, B)
     return p
 
@@ -236,12 +238,86 @@ def _adam_args(opt):
     return s.m, s.v, opt.lr, opt.betas[0], opt.betas[1], opt.eps
 
 
-def train_iter(args, epoch, target_data, net, optim):
-    """scripts/train_feature_extractor.py:54-97 with variational_encoding=False; `optim` is a FusedAdam over `net`."""
+def vae_kld_weight(epoch):
+    """train_feature_extractor.py:81-84: 0 before epoch 10, then (epoch - 10) * 0.05, capped at 1."""
+    return 0.0 if epoch < 10 else min(1.0, (epoch - 10) * 0.05)
+
+
+VAE_RECON_WEIGHT = 100.0          # train_feature_extractor.py:85
+
+
+def _logvar_slots(slab):
+    """The gradient-slab range of pose_encoder.fc_logvar.{weight, bias} (adjacent in module order)."""
+    iw, ib = slab.names.index("pose_encoder.fc_logvar.weight"), slab.names.index("pose_encoder.fc_logvar.bias")
+    assert ib == iw + 1
+    return slab.offsets[iw], slab.offsets[ib] + slab.params[ib].numel()
+
+
+def _vae_step(E, optim, target, epoch, inject=None):
+    """One VAE step on the layer engine (train_feature_extractor.py:54-97 with variational_encoding=True):
+    loss = 100 recon + KLD_weight KLD.  -> (res, packed): packed holds (fp32 recon loss, fp64 KLD), see joint_embed.unpack_scalars.
+    The fused 18-launch plan (csrc/ae_step.hip) stays AE-only."""
+    slab = E.slab.ensure()
+    slab.zero_grad()
+    packed = torch.empty(2, device=target.device, dtype=torch.float64)
+    res = E.forward(target, training=True, save=True, variational=True, inject=inject, kld_out=packed[1:2])
+    d_recon = torch.empty_like(target)
+    ops.ae_loss(res["recon"], target, packed[0:1].view(torch.float32)[0:1], d_recon)
+    w = getattr(E, "_recon_weight", None)
+    if w is None or w.device != target.device:
+        w = E._recon_weight = torch.full((1,), VAE_RECON_WEIGHT, device=target.device)
+    ops.scale_by(d_recon, w)                                                  # d(100 recon)
+    E.backward(res["tape"], d_recon, kld_weight=vae_kld_weight(epoch))
+    optim.step()
+    # fc_logvar now HAS a gradient in the slab and Adam moments.  The AE steps assume neither: the fused plan never reads or writes
+    # fc_logvar's slots (its Adam skips them like a parameter whose .grad is None) but reports them as "zero since the plan was made", and
+    # the layer-engine AE step runs Adam over the whole slab.  The flag makes the next AE step restore both (see _ae_after_vae).
+    E._logvar_trained = E._logvar_grad_dirty = True
+    return res, packed
+
+
+def _ae_after_vae(E, fused):
+    """Keeps _ae_plan's "fc_logvar's gradient slots stay zero" true when AE and VAE steps alternate on one net: the first AE step after a
+    VAE step zeroes those slots again (one launch; later AE steps none), so an AE step never reports the VAE step's fc_logvar gradient.
+    -> True when the layer-engine AE step must step Adam around fc_logvar (its moments are non-zero after a VAE step and Adam with a zero
+    gradient would still move it; the reference's Adam skips a parameter whose .grad is None)."""
+    if not getattr(E, "_logvar_trained", False):
+        return False
+    if getattr(E, "_logvar_grad_dirty", True):
+        slab = E.slab.ensure()
+        lo, hi = _logvar_slots(slab)
+        ops.zero_(slab.grad[lo:hi])
+        E._logvar_grad_dirty = False
+    return not fused
+
+
+def _adam_around_logvar(optim):
+    """FusedAdam.step without fc_logvar's range (two launches)."""
+    s = optim.slab
+    lo, hi = _logvar_slots(s)
+    ops.counter_inc(s.step)
+    for a, b in ((0, lo), (hi, s.n_train)):
+        if b > a:
+            ops.adam_step(s.flat[a:b], s.grad[a:b], s.m[a:b], s.v[a:b], optim.lr, optim.betas[0], optim.betas[1], optim.eps, s.step)
+
+
+def train_iter(args, epoch, target_data, net, optim, *, variational_encoding=False):
+    """scripts/train_feature_extractor.py:54-97; `optim` is a FusedAdam over `net`.  variational_encoding (keyword only; the reference's
+    literal): False -> {'loss': recon}; True -> loss = 100 recon + KLD_weight KLD, {'loss': 100 recon, 'KLD': KLD_weight KLD} with
+    KLD_weight = vae_kld_weight(epoch); eps is drawn on the device (or taken from {'p.eps': eps} queued in net._replay_draws)."""
     E = net.engine
     target = target_data.float().contiguous()
+    if variational_encoding:
+        from .joint_embed import unpack_scalars
+        from .modules import _need_cuda_variational
+        _need_cuda_variational(target, "train_iter: target_data")
+        inject = net._replay_draws.pop(0) if net._replay_draws else None
+        _, packed = _vae_step(E, optim, target, epoch, inject)
+        recon, kld = unpack_scalars(packed)
+        return {"loss": VAE_RECON_WEIGHT * recon, "KLD": vae_kld_weight(epoch) * kld}
     loss = torch.empty(1, device=target.device)
     plan = _ae_plan(net, target)
+    around = _ae_after_vae(E, plan is not None)
     if plan is not None:                 # 18 launches, the optimiser step inside the last one (csrc/ae_step.hip)
         plan.run(target, loss, adam=_adam_args(optim))
         return {"loss": float(loss)}
@@ -250,7 +326,7 @@ def train_iter(args, epoch, target_data, net, optim):
     d_recon = torch.empty_like(target)
     ops.ae_loss(res["recon"], target, loss, d_recon)
     E.backward(res["tape"], d_recon)
-    optim.step()
+    _adam_around_logvar(optim) if around else optim.step()
     return {"loss": float(loss)}
 
 
@@ -311,15 +387,20 @@ def train_autoencoder(args, train_set, val_set, save_dir=None, log=print, genera
 
 
 class AutoencoderTrainer:
-    """train_feature_extractor.py:train_iter with variational_encoding=False: reconstruction L1 + L1 of frame differences,
-    summed over the batch; Adam(lr 5e-4, betas (0.5, 0.999)).
+    """train_feature_extractor.py:train_iter: reconstruction L1 + L1 of frame differences, summed over the batch; Adam(lr 5e-4, betas
+    (0.5, 0.999)).  variational_encoding=False (the reference's literal):
     fused (default: where supported): the whole step, optimiser included, as the 18 launches of csrc/ae_step.hip instead of the ~105 launches of
-    the layer-by-layer engine (kept for other shapes and as the test reference)."""
+    the layer-by-layer engine (kept for other shapes and as the test reference).
+    variational_encoding=True: loss = 100 recon + vae_kld_weight(epoch) KLD on the layer engine (the fused plan stays AE-only; fused=True
+    raises); train_iter returns the recon loss, `last['packed']` holds (recon, KLD) on the device (joint_embed.unpack_scalars)."""
 
-    def __init__(self, net, lr=5e-4, fused=None):
+    def __init__(self, net, lr=5e-4, fused=None, variational_encoding=False):
         self.net, self.E = net, net.engine
         self.opt = FusedAdam(self.E, lr=lr, betas=(0.5, 0.999))
         self.fused = fused
+        self.variational_encoding = bool(variational_encoding)
+        if self.variational_encoding and fused:
+            raise ValueError("AutoencoderTrainer: the fused step is AE-only; variational_encoding=True runs on the layer engine")
         self._plan = None
         self.last = {}
 
@@ -330,10 +411,17 @@ class AutoencoderTrainer:
         self._plan = plan
         return plan
 
-    def train_iter(self, target, keep_outputs=False):
+    def train_iter(self, target, keep_outputs=False, epoch=0, inject=None):
         E = self.E
         target = target.float().contiguous()
+        if self.variational_encoding:
+            res, packed = _vae_step(E, self.opt, target, epoch, inject)
+            self.last = {"packed": packed}
+            if keep_outputs:
+                self.last.update(recon=res["recon"], feat=res["feat"])
+            return packed[0:1].view(torch.float32)[0:1]
         plan = self._fused_plan(target)
+        around = _ae_after_vae(E, plan is not None)
         loss = torch.empty(1, device=target.device)
         if plan is not None:
             recon = torch.empty_like(target) if keep_outputs else None
@@ -347,7 +435,7 @@ class AutoencoderTrainer:
         d_recon = torch.empty_like(target)
         ops.ae_loss(res["recon"], target, loss, d_recon)
         E.backward(res["tape"], d_recon)
-        self.opt.step()
+        _adam_around_logvar(self.opt) if around else self.opt.step()
         if keep_outputs:
             self.last = {"recon": res["recon"], "feat": res["feat"]}
         return loss

@@ -8,7 +8,8 @@ arithmetic runs in libtrimodal_hip.so; torch is plumbing (parameter containers, 
   * both GRUs: rnn.GRU (csrc/gru_seq.hip admits H = 256 x 1 direction and H = 300 x 2 directions);
   * the latent heads (ContextEncoder.out + fc_mu / fc_logvar + reparameterize, PoseDecoderGRU.pre_pose_net): tg_latent_head_fwd / _bwd, one
     launch each way (csrc/latent_head.hip);
-  * the pose encoder: engine.AutoencoderEngine.encode / encode_backward.
+  * the pose encoder: engine.AutoencoderEngine.encode / encode_backward; with variational_encoding=True its fc_mu / fc_logvar /
+    reparameterisation tail is tg_vae_latent_fwd / _bwd and the KL term of the training step tg_vae_kld (csrc/vae_latent.hip).
 CPU tensors raise TypeError, shapes outside a kernel envelope raise ValueError: there is no torch fallback.  init_model /
 checkpoint.load_checkpoint_and_model keep refusing args.model == 'joint_embedding'; this module's build_model / load_checkpoint_and_model
 are the entry points.
@@ -82,31 +83,41 @@ class _ContextFrontFn(torch.autograd.Function):
 
 
 class _PoseEncoderFn(torch.autograd.Function):
-    """PoseEncoderConv (embedding_net.py:42-82) through AutoencoderEngine.encode: poses (B, 34, D) -> (mu, logvar)."""
+    """PoseEncoderConv (embedding_net.py:42-82) through AutoencoderEngine.encode: poses (B, 34, D) -> (z, mu, logvar).  variational False:
+    z IS mu (one tensor, returned twice); True: z = mu + eps exp(logvar / 2) from ops.vae_latent_fwd, eps injected or drawn by the launch."""
 
     @staticmethod
     def forward(ctx, cfg, poses, *params):
-        names, buffers, training, save = cfg
+        names, buffers, training, save, variational, eps, draw = cfg
         P = {"pose_encoder." + n: p for n, p in zip(names, params)}
         st = _AutoencoderStages()
         st._views = (P, None, {"pose_encoder." + k: v for k, v in buffers.items()})
         tape = {} if save else None
-        mu, logvar = st.encode(poses, training=training, tape=tape)
-        ctx.saved = (st, names, P, tape)
+        ctx.saved = (st, names, P, tape, variational)
         ctx.set_materialize_grads(False)
-        return mu, logvar
+        if variational:
+            return st.encode(poses, training=training, tape=tape, variational=True, eps=eps, draw=draw)
+        mu, logvar = st.encode(poses, training=training, tape=tape)
+        return mu.view_as(mu), mu, logvar
 
     @staticmethod
-    def backward(ctx, dmu, dlv):
-        st, names, P, tape = ctx.saved
+    def backward(ctx, dz, dmu, dlv):
+        st, names, P, tape, variational = ctx.saved
         if tape is None:
             raise NotImplementedError("pose encoder: the forward ran without a tape")
-        if dlv is not None:
-            raise NotImplementedError("pose encoder: a gradient through logvar (variational_encoding) is not implemented")
+        if dlv is not None and not variational:
+            raise ValueError("pose encoder: a gradient through logvar needs variational_encoding=True (fc_logvar feeds nothing otherwise)")
         G = {n: ops.zeros_like(p) for n, p in P.items()}
         st._views = (P, G, st._views[2])
-        if dmu is not None:
-            st.encode_backward(tape, dmu.contiguous())
+        cont = lambda t: None if t is None else t.contiguous()
+        if variational:
+            if dz is not None or dmu is not None or dlv is not None:
+                st.encode_backward(tape, cont(dz), dlv=cont(dlv), dmu_direct=cont(dmu))
+        elif dz is not None or dmu is not None:
+            d = cont(dz if dz is not None else dmu)
+            if dz is not None and dmu is not None:
+                d = ops.axpy(cont(dmu), d.clone(), 1.0, True)
+            st.encode_backward(tape, d)
         return (None, None) + tuple(G["pose_encoder." + n] if ctx.needs_input_grad[2 + i] else None for i, n in enumerate(names))
 
 
@@ -305,8 +316,9 @@ class PoseDecoderGRU(nn.Module):
 
 def embedding_forward(net, in_text, in_audio, pre_poses, poses, input_mode=None, variational_encoding=False):
     """EmbeddingNet.forward of the speech / random modes (embedding_net.py:276-308)."""
-    if variational_encoding:
-        raise NotImplementedError("variational_encoding=True is not on the reference's configured path")
+    if variational_encoding and poses is not None:
+        from .modules import _need_cuda_variational
+        _need_cuda_variational(poses, "EmbeddingNet: poses")
     if input_mode is None:
         assert net.mode is not None
         input_mode = net.mode
@@ -327,8 +339,22 @@ def embedding_forward(net, in_text, in_audio, pre_poses, poses, input_mode=None,
         names = [n for n, _ in enc.named_parameters()]
         params = [p for _, p in enc.named_parameters()]
         save = torch.is_grad_enabled() and any(p.requires_grad for p in params)
-        pose_mu, pose_logvar = _PoseEncoderFn.apply((names, dict(enc.named_buffers()), net.training, save), poses.contiguous(), *params)
-        poses_feat = pose_mu                                                     # variational_encoding=False: z = mu
+        eps = draw = None
+        if variational_encoding:
+            # the flag reaches the pose encoder only (the context encoder reparameterises regardless), in train and in eval mode alike
+            # (embedding_net.py:77-80); eps: injected under 'p.eps' or drawn by the launch from the net's RNG at the site of that name
+            eps = None if inject is None else inject.get("p.eps")
+            if eps is None:
+                rng = getattr(net, "_pose_rng", None)
+                if rng is None or rng.state.device != poses.device:
+                    rng = DeviceRNG(getattr(net, "seed", 0), poses.device)
+                    object.__setattr__(net, "_pose_rng", rng)
+                rng.advance()
+                draw = (rng.state, rng.site("p.eps"))
+            else:
+                eps = eps.contiguous()
+        cfg = (names, dict(enc.named_buffers()), net.training, save, bool(variational_encoding), eps, draw)
+        poses_feat, pose_mu, pose_logvar = _PoseEncoderFn.apply(cfg, poses.contiguous(), *params)     # variational_encoding=False: z = mu
     if input_mode == "random":
         input_mode = "speech" if random.random() > 0.5 else "pose"               # the host RNG, exactly as the reference draws it
     if input_mode == "speech":
@@ -368,8 +394,10 @@ class _L1SumFn(torch.autograd.Function):
     """sum over clips of mean_{t,d} |recon - target| (train_joint_embed.py:20-28; clips have equal size: B x the mean over everything)."""
 
     @staticmethod
-    def forward(ctx, recon, target, bscale):
-        loss = ops.l1_mean(recon, target, L.empty(1, like=recon))
+    def forward(ctx, recon, target, bscale, out=None):
+        # out: an optional one-element LIST holding the float [1] tensor to write the loss into (a slot of a packed result buffer; a
+        # list, because autograd forbids an input tensor that comes back as an output)
+        loss = ops.l1_mean(recon, target, L.empty(1, like=recon) if out is None else out[0])
         ops.scale_by(loss, bscale)
         ctx.saved = (recon, target, bscale)
         return loss
@@ -379,7 +407,7 @@ class _L1SumFn(torch.autograd.Function):
         recon, target, bscale = ctx.saved
         d = ops.s2g_l1_grad(recon, target, torch.empty_like(recon))
         ops.scale_by(d, bscale)
-        return ops.scale_by(d, g.contiguous()), None, None
+        return ops.scale_by(d, g.contiguous()), None, None, None
 
 
 class JointEmbedTrainer:
@@ -393,22 +421,42 @@ class JointEmbedTrainer:
         self.m, self.v = [torch.zeros_like(p) for p in self.params], [torch.zeros_like(p) for p in self.params]
         self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32)
         self.lr, self.betas, self.eps = lr, tuple(betas), eps
-        self._bscale = {}
+        self._bscale = {}                    # device constants by (value, device, dtype)
 
     def set_hparams(self, lr, betas, eps):
         self.lr, self.betas, self.eps = lr, tuple(betas), eps
 
-    def step(self, args, epoch, in_text, in_audio, target_data, mode=None):
+    def _const(self, value, dev, dtype=torch.float32):
+        key = (float(value), dev, dtype)
+        if key not in self._bscale:
+            self._bscale[key] = torch.full((1,), float(value), device=dev, dtype=dtype)
+        return self._bscale[key]
+
+    def step(self, args, epoch, in_text, in_audio, target_data, mode=None, variational_encoding=False):
+        """-> the recon loss as a device float [1]; with variational_encoding (loss, KLD) as ONE packed device buffer of two 8-byte slots
+        (slot 0: the fp32 loss in its first four bytes, slot 1: the fp64 KLD) -- read with unpack_scalars, one copy to the host."""
         target = target_data.float().contiguous()
-        B = target.shape[0]
-        if B not in self._bscale:
-            self._bscale[B] = torch.full((1,), float(B), device=target.device)
+        B, dev = target.shape[0], target.device
         for p in self.params:
             p.grad = None
         pre_seq = target[:, 0:args.n_pre_poses]
-        recon = self.net(in_text, in_audio, pre_seq, target, mode, variational_encoding=False)[6]
-        loss = _L1SumFn.apply(recon.contiguous(), target, self._bscale[B])
-        loss.backward()
+        out = self.net(in_text, in_audio, pre_seq, target, mode, variational_encoding=variational_encoding)
+        if not variational_encoding:
+            loss = _L1SumFn.apply(out[6].contiguous(), target, self._const(B, dev))
+            loss.backward()
+            packed = loss.detach()
+        else:
+            packed = torch.empty(2, device=dev, dtype=torch.float64)
+            loss = _L1SumFn.apply(out[6].contiguous(), target, self._const(B, dev), [packed[0:1].view(torch.float32)[0:1]])
+            # train_joint_embed.py:30-40: the context latent's KL term when the NET's mode is 'speech', the pose latent's otherwise
+            mu, logvar = (out[1], out[2]) if self.net.mode == "speech" else (out[4], out[5])
+            if mu is None:
+                raise ValueError(f"train_iter_embed: the KL term of a net with mode {self.net.mode!r} needs that encoder's inputs")
+            kld = _KldFn.apply(mu, logvar, [packed[1:2]])
+            # loss = loss_regression_weight * recon + KLD_weight * KLD: the two weights enter as the seeds of one backward pass
+            torch.autograd.backward([loss, kld], [self._const(args.loss_regression_weight, dev),
+                                                  self._const(embed_kld_weight(epoch, args.loss_kld_weight), dev, torch.float64)])
+            packed = packed.detach()
         ops.counter_inc(self.step_dev)
         for p, m, v in zip(self.params, self.m, self.v):
             if p.grad is None:
@@ -416,13 +464,44 @@ class JointEmbedTrainer:
             if not p.grad.is_contiguous():
                 p.grad = p.grad.contiguous()
             ops.adam_step(p.data, p.grad, m, v, self.lr, self.betas[0], self.betas[1], self.eps, self.step_dev)
-        return loss.detach()
+        return packed
 
 
-def train_iter_embed(args, epoch, in_text, in_audio, target_data, net, optim, mode=None):
-    """The reference's signature and return dict (train_joint_embed.py:5-51; variational_encoding is False on both of its branches, so there
-    is no KLD term).  The device Adam moments live in a JointEmbedTrainer kept on `optim`; lr, betas and eps are read from
-    optim.param_groups on every call.  One host read: the returned float.
+def embed_kld_weight(epoch, loss_kld_weight):
+    """train_joint_embed.py:37-40: 0 before epoch 10, then (epoch - 10) * loss_kld_weight, capped at 1."""
+    return 0.0 if epoch < 10 else min(1.0, (epoch - 10) * loss_kld_weight)
+
+
+def unpack_scalars(packed):
+    """The (fp32 loss, fp64 KLD) pair of a packed two-slot device buffer: one copy to the host."""
+    host = packed.cpu()
+    return float(host[0:1].view(torch.float32)[0]), float(host[1])
+
+
+class _KldFn(torch.autograd.Function):
+    """KLD = -0.5 sum(1 + logvar - mu^2 - exp(logvar)) of a latent (fp64 device scalar, written into out[0]: a one-element list, as
+    _L1SumFn's), value and gradient from ONE launch (ops.vae_kld); the backward scales the stored gradient by the incoming one (a device
+    scalar: no host read)."""
+
+    @staticmethod
+    def forward(ctx, mu, logvar, out):
+        kld, dmu, dlv = ops.vae_kld(mu.contiguous(), logvar.contiguous(), weight=1.0, kld=out[0])
+        ctx.saved = (dmu, dlv)
+        return kld
+
+    @staticmethod
+    def backward(ctx, g):
+        dmu, dlv = ctx.saved
+        g = g.float().contiguous().view(1)
+        return ops.scale_by(dmu, g), ops.scale_by(dlv, g), None
+
+
+def train_iter_embed(args, epoch, in_text, in_audio, target_data, net, optim, mode=None, *, variational_encoding=False):
+    """The reference's signature and return dict (train_joint_embed.py:5-51).  variational_encoding is False on both of the reference's
+    branches, so by default there is no KLD term; True (keyword only) is the reference with that literal flipped:
+    loss = args.loss_regression_weight * recon + KLD_weight * KLD, KLD_weight = embed_kld_weight(epoch, args.loss_kld_weight), and the dict
+    is {'loss': recon, 'KLD': KLD}, both unweighted as there.  The device Adam moments live in a JointEmbedTrainer kept on `optim`; lr,
+    betas and eps are read from optim.param_groups on every call.  One host read: the returned float (the packed pair with the KL term).
     As in train_iter_seq2seq, `optim` is a torch.optim.Adam whose hyper-parameters are used and whose own step() and state are NOT: every
     parameter of `net` that received a gradient is stepped (as Adam over net.parameters() does, which skips parameters without one).
     Anything else -- another optimiser class, several parameter groups, weight_decay, amsgrad -- raises."""
@@ -435,7 +514,10 @@ def train_iter_embed(args, epoch, in_text, in_audio, target_data, net, optim, mo
         optim._joint_embed_trainer = tr
     g = optim.param_groups[0]
     tr.set_hparams(g["lr"], g["betas"], g["eps"])
-    return {"loss": tr.step(args, epoch, in_text, in_audio, target_data, mode).item()}
+    if not variational_encoding:
+        return {"loss": tr.step(args, epoch, in_text, in_audio, target_data, mode).item()}
+    loss, kld = unpack_scalars(tr.step(args, epoch, in_text, in_audio, target_data, mode, variational_encoding=True))
+    return {"loss": loss, "KLD": kld}
 
 
 # -------------------------------------------------------------------------------------------------------------------- checkpoints

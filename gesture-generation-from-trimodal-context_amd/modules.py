@@ -69,6 +69,17 @@ class _TextEncoderParams(nn.Module):
         self.decoder.weight.data.normal_(0, 0.01)
 
 
+class CpuVariationalError(TypeError, NotImplementedError):
+    """variational_encoding=True on CPU tensors: a wrong tensor type (TypeError, as every CPU tensor on this path) for which nothing is
+    implemented (NotImplementedError: there is no torch fallback)."""
+
+
+def _need_cuda_variational(t, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise CpuVariationalError(f"{name} must be a CUDA tensor for variational_encoding=True, got {getattr(t, 'device', None)}: the "
+                                  "reparameterised latent runs in csrc/vae_latent.hip only, there is no torch fallback")
+
+
 class _Bridge(torch.autograd.Function):
     """Connects an engine's hand-written backward to torch.autograd so `loss.backward()` works on these modules.
     Parameter gradients are accumulated into param.grad (views of the gradient slab) as a side effect; only
@@ -286,17 +297,30 @@ class EmbeddingNet(nn.Module):
         if self.mode != "pose":
             from .joint_embed import embedding_forward
             return embedding_forward(self, in_text, in_audio, pre_poses, poses, input_mode, variational_encoding)
-        if variational_encoding:
-            raise NotImplementedError("variational_encoding=True is not on the reference's configured path")
         eng = self.engine
         need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        inject = None
+        if variational_encoding:
+            # (embedding_net.py:77-80: the reference reparameterises in train AND eval mode; eps from the engine's RNG at site 'p.eps',
+            # or {'p.eps': eps} queued in _replay_draws)
+            _need_cuda_variational(poses, "EmbeddingNet: poses")
+            inject = self._replay_draws.pop(0) if self._replay_draws else None
 
         def runner():
-            res = eng.forward(poses.float(), training=self.training, save=need_grad)
+            res = eng.forward(poses.float(), training=self.training, save=need_grad, variational=variational_encoding, inject=inject)
 
             def back(d_feat, d_mu, d_lv, d_recon):
-                assert d_feat is None and d_mu is None and d_lv is None, "only the reconstruction carries gradient"
-                eng.backward(res["tape"], d_recon)
+                if not variational_encoding:
+                    assert d_feat is None and d_mu is None and d_lv is None, "only the reconstruction carries gradient"
+                    eng.backward(res["tape"], d_recon)
+                    return ()
+                tp = res["tape"]
+                dz = None if d_feat is None else d_feat.contiguous()
+                direct = dict(dmu_direct=None if d_mu is None else d_mu.contiguous(), dlv=None if d_lv is None else d_lv.contiguous())
+                if d_recon is None:
+                    eng.encode_backward(tp, dz, **direct)
+                else:
+                    eng.backward(tp, d_recon, dz=dz, **direct)
                 return ()
             return (res["feat"], res["mu"], res["logvar"], res["recon"]), back
 

@@ -2459,3 +2459,85 @@ def latent_head_bwd(dout, tp, w1, gamma, beta, w2, *, tail=None, dmu=None, dlv=N
          _p(G["w2"]), _p(G["b2"]), _p(G.get("wmu")), _p(G.get("bmu")), _p(G.get("wlv")), _p(G.get("blv")), _p(dx), dx.stride(0) if dx is not None else 0,
          B, K0, N1, N2, int(tp.training), float(tp.slope), _stream())
     return G
+
+
+# ------------------------------------------------------------------------------------------------- variational tail (csrc/vae_latent.hip)
+VAE_LATENT_ENVELOPE = "1 <= B <= 1024 rows of 32 columns"
+VAE_LATENT_MAX_B = 1024
+
+
+class VaeLatentTape:
+    __slots__ = ("f3", "mu", "logvar", "z", "eps", "kld", "B")
+
+
+def _vl_rows(t, B, name):
+    _flat(t, name)
+    if tuple(t.shape) != (B, 32):
+        raise ValueError(f"{name}: expected {(B, 32)}, got {tuple(t.shape)}")
+    return t
+
+
+def vae_latent_fwd(f3, wmu, bmu, wlv, blv, *, eps=None, draw=None, kld=None):
+    """One launch: mu = fc_mu(f3), logvar = fc_logvar(f3), z = mu + eps exp(logvar / 2) and the fp64 scalar
+    kld = -0.5 sum(1 + logvar - mu^2 - exp(logvar)) over the batch.  f3: [B, 32]; eps [B, 32] is read, or -- draw = (rng_state, site) --
+    written by the launch (element i of ops.normal).  kld: optional float64 [1] tensor to write into.  Returns the tape for vae_latent_bwd."""
+    _f32(f3, "f3")
+    if f3.dim() != 2 or f3.shape[1] != 32:
+        raise ValueError(f"vae latent: f3 [B, 32] expected, got {tuple(f3.shape)}")
+    B = f3.shape[0]
+    if not 1 <= B <= VAE_LATENT_MAX_B:
+        raise ValueError(f"vae latent: B = {B} is outside the kernel envelope {VAE_LATENT_ENVELOPE}; there is no torch fallback")
+    _vl_rows(f3, B, "f3"); assert f3.data_ptr() % 16 == 0
+    for t, n in ((wmu, 1024), (bmu, 32), (wlv, 1024), (blv, 32)):
+        _flat(t, "parameter"); assert t.numel() == n
+    dev = f3.device
+    tp = VaeLatentTape()
+    tp.f3, tp.B = f3, B
+    tp.mu, tp.logvar, tp.z = (torch.empty(B, 32, device=dev) for _ in range(3))
+    tp.kld = torch.empty(1, device=dev, dtype=torch.float64) if kld is None else kld
+    assert tp.kld.is_cuda and tp.kld.dtype == torch.float64 and tp.kld.numel() == 1
+    state, site = None, 0
+    if draw is not None:
+        state, site = _i64(draw[0], "rng_state"), int(draw[1])
+        tp.eps = torch.empty(B, 32, device=dev)
+    else:
+        if eps is None:
+            raise ValueError("vae latent: needs eps [B, 32] or draw = (rng_state, site)")
+        tp.eps = _vl_rows(eps, B, "eps")
+    call("tg_vae_latent_fwd", _p(f3), _p(wmu), _p(bmu), _p(wlv), _p(blv), _p(tp.eps), _p(state), site, _p(tp.mu), _p(tp.logvar), _p(tp.z),
+         _p(tp.kld), B, _stream())
+    return tp
+
+
+def vae_latent_bwd(dz, tp, wmu, wlv, *, kld_weight=0.0, dmu=None, dlv=None, grads=None):
+    """One launch: dmu_total = dz + kld_weight mu + dmu, dlv_total = dz eps 0.5 exp(logvar / 2) + kld_weight 0.5 (exp(logvar) - 1) + dlv, then
+    dWmu, dbmu, dWlv, dblv and df3 (written, not accumulated).  dz None: the KL term (and the direct gradients) only.  grads: optional
+    (dWmu, dbmu, dWlv, dblv) tensors to write into.  Returns ({'wmu', 'bmu', 'wlv', 'blv'}, df3)."""
+    B = tp.B
+    for t, n in ((dz, "dz"), (dmu, "dmu"), (dlv, "dlv")):
+        if t is not None:
+            _vl_rows(t, B, n)
+    _flat(wmu, "wmu"); _flat(wlv, "wlv"); assert wmu.numel() == wlv.numel() == 1024
+    dev = tp.f3.device
+    if grads is None:
+        grads = (torch.empty(32, 32, device=dev), torch.empty(32, device=dev), torch.empty(32, 32, device=dev), torch.empty(32, device=dev))
+    for t, n in zip(grads, (1024, 32, 1024, 32)):
+        _flat(t, "gradient"); assert t.numel() == n
+    df3 = torch.empty(B, 32, device=dev)
+    ws = torch.empty(2 * B * 32, device=dev)
+    call("tg_vae_latent_bwd", _p(dz), _p(dmu), _p(dlv), _p(tp.mu), _p(tp.logvar), _p(tp.eps), _p(tp.f3), _p(wmu), _p(wlv), float(kld_weight),
+         _p(ws), _p(grads[0]), _p(grads[1]), _p(grads[2]), _p(grads[3]), _p(df3), B, _stream())
+    return dict(zip(("wmu", "bmu", "wlv", "blv"), grads)), df3
+
+
+def vae_kld(mu, logvar, *, weight=1.0, kld=None, want_grads=True):
+    """One launch: the fp64 scalar kld = -0.5 sum(1 + logvar - mu^2 - exp(logvar)) of a latent [B, N] and (want_grads) the gradient of
+    weight * kld: (kld, dmu, dlv)."""
+    _flat(mu, "mu"); _flat(logvar, "logvar")
+    if mu.dim() != 2 or mu.shape != logvar.shape or not 1 <= mu.numel() <= 65536:
+        raise ValueError(f"vae_kld: two [B, N] tensors with B N <= 65536 expected, got {tuple(mu.shape)} and {tuple(logvar.shape)}")
+    kld = torch.empty(1, device=mu.device, dtype=torch.float64) if kld is None else kld
+    assert kld.is_cuda and kld.dtype == torch.float64 and kld.numel() == 1
+    dmu, dlv = (torch.empty_like(mu), torch.empty_like(mu)) if want_grads else (None, None)
+    call("tg_vae_kld", _p(mu), _p(logvar), mu.shape[0], mu.shape[1], float(weight), _p(kld), _p(dmu), _p(dlv), _stream())
+    return kld, dmu, dlv

@@ -1015,6 +1015,27 @@ int tg_latent_head_bwd(const float* dout, int64_t ldo, const float* dmu, const f
                        float* dgamma, float* dbeta, float* dW2, float* db2, float* dWmu, float* dbmu, float* dWlv, float* dblv, float* dx,
                        int64_t lddx, int32_t B, int32_t K0, int32_t N1, int32_t N2, int32_t training, float slope, void* stream);
 
+/* ---- variational tail of the pose encoder (csrc/vae_latent.hip; model/embedding_net.py:67-82 with variational_encoding=True, the KL term
+ * of train_feature_extractor.py:74-79 and train_eval/train_joint_embed.py:30-36).  ONE launch of one workgroup each, no atomics, every sum
+ * one fp64 chain in a fixed order (two runs are bit identical).
+ * tg_vae_latent_fwd: f3 [B][32] (pose_encoder.out_net.6's output), Wmu / Wlv [32][32], bmu / blv [32] -> mu, logvar, z = mu + eps
+ * exp(logvar / 2) [B][32] and *kld = -0.5 sum(1 + logvar - mu^2 - exp(logvar)) over the batch, in fp64 from the fp32 mu / logvar written.
+ * eps [B][32] is READ when rng_state == NULL, otherwise WRITTEN: element i of tg_normal(eps, 32 B, rng_state, site).  Row b of the results
+ * depends on row b of the inputs only; its bits do not change with B.
+ * tg_vae_latent_bwd: dmu_total = dz + w mu + dmu, dlv_total = dz eps 0.5 exp(logvar / 2) + w 0.5 (exp(logvar) - 1) + dlv (w: the weight of the
+ * KL term, may be 0; dz NULL: no gradient through z; dmu / dlv: optional direct gradients of mu / logvar) -> dWmu, dbmu, dWlv, dblv and
+ * df3 = dmu_total Wmu + dlv_total Wlv, all WRITTEN (not accumulated).  ws: 64 B floats.  f3, ws 16-byte aligned.
+ * tg_vae_kld: the KL term of any latent mu, logvar [B][N] (the context encoder's): *kld as above and, when dmu / dlv != NULL, its gradient
+ * dmu = w mu, dlv = w 0.5 (exp(logvar) - 1).
+ * Envelope: 1 <= B <= 1024 (tg_vae_kld: B N <= 65536); outside it the entries return non-zero, set tg_last_error ("envelope") and launch
+ * nothing. */
+int tg_vae_latent_fwd(const float* f3, const float* Wmu, const float* bmu, const float* Wlv, const float* blv, float* eps,
+                      const uint64_t* rng_state, uint32_t site, float* mu, float* logvar, float* z, double* kld, int32_t B, void* stream);
+int tg_vae_latent_bwd(const float* dz, const float* dmu, const float* dlv, const float* mu, const float* logvar, const float* eps,
+                      const float* f3, const float* Wmu, const float* Wlv, float w, float* ws, float* dWmu, float* dbmu, float* dWlv,
+                      float* dblv, float* df3, int32_t B, void* stream);
+int tg_vae_kld(const float* mu, const float* logvar, int32_t B, int32_t N, float w, double* kld, float* dmu, float* dlv, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
