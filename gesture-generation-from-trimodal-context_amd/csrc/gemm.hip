@@ -906,6 +906,10 @@ static void tn_plan(int M, int tiles, bool two_pass, int* splits_out, int* rows_
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
     if (splits > 65535) splits = 65535;
+    // Atomic combine of 129 .. 192 rows (the B = 4 steps of the small nets: 136 .. 152 rows): two 96-row pieces, not three 64-row ones.  Two
+    // atomic adders onto a zeroed gradient commute (0 + a + b == 0 + b + a); the third made the sum depend on the order of arrival, and the
+    // decoder's conv weight gradients of two identical autoencoder steps differed in the last bit.  The two-pass combine has a fixed order.
+    if (!two_pass && splits == 3 && M <= 192) splits = 2;
     int rows = cdiv(M, splits);
     rows = ((rows + 31) / 32) * 32;
     *rows_out = rows;

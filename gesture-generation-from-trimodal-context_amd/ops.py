@@ -1906,6 +1906,59 @@ def utterance_finish(total, n_win, max_win, n_poses, n_pre, *, smooth=False, pro
          _p(mean), _p(joints), Fj, _stream())
 
 
+# ------------------------------------------------------------------------------------------------- streaming synthesis (csrc/stream.hip)
+def stream_state(B, R, S, A, W, T, device):
+    """The device-resident state of a stream of B rows: the sample ring (B, R) fp32 and the word ring (B, W, 3) int32, zeroed, their int64
+    counters `written` and `n_words` (B,) and the int32 window counter `win` (1,).  S, A: stride and window in samples, T: frames of a window."""
+    return dict(B=int(B), R=int(R), S=int(S), A=int(A), W=int(W), T=int(T), ring=torch.zeros(B, R, device=device),
+                words=torch.zeros(B, W, 3, dtype=torch.int32, device=device), written=torch.zeros(B, dtype=torch.int64, device=device),
+                n_words=torch.zeros(B, dtype=torch.int64, device=device), win=torch.zeros(1, dtype=torch.int32, device=device))
+
+
+def _stream_check(st):
+    B, R, W = st["B"], st["R"], st["W"]
+    _flat(st["ring"], "ring"); _dev_int(st["words"], torch.int32, B * W * 3, "word ring")
+    _dev_int(st["written"], torch.int64, B, "written"); _dev_int(st["n_words"], torch.int64, B, "n_words"); _dev_int(st["win"], torch.int32, 1, "win")
+    assert st["ring"].numel() >= B * R, "the ring is smaller than (B, R)"
+
+
+def stream_push(st, chunk, recs=None, m_max=0, words_live=0):
+    """Appends chunk (B, n) fp32 (device; unit inner stride) to the ring of the stream state st and advances `written`.  recs (B, >= 1 + 3 m_max)
+    int32 on the device: per row a count and that many (window, frame, word id) triples, appended to the word ring.  words_live: ring slots from
+    the oldest record a window still needs to the newest (the host's count).  A call outside the envelope (1 <= B <= 4, n >= 1, R >= A + n,
+    words_live + m_max <= W) is refused by the library (RuntimeError naming the envelope); nothing is launched."""
+    _stream_check(st)
+    _f32(chunk, "chunk")
+    if chunk.dim() != 2 or chunk.shape[0] != st["B"] or (chunk.shape[1] > 1 and chunk.stride(1) != 1):
+        raise ValueError(f"chunk: expected ({st['B']}, n) with unit inner stride, got {tuple(chunk.shape)} strides {chunk.stride()}")
+    n, cs = chunk.shape[1], chunk.stride(0) if chunk.shape[0] > 1 else max(chunk.shape[1], 1)
+    if n > 0 and (cs < n or (st["B"] - 1) * cs + n > _room(chunk)):
+        raise ValueError("chunk: rows overlap or exceed the tensor")
+    rs = 0
+    if m_max > 0:
+        if not (isinstance(recs, torch.Tensor) and recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 2 and recs.is_contiguous() and recs.shape[0] == st["B"]):
+            raise TypeError(f"recs: expected a contiguous CUDA int32 tensor ({st['B']}, >= 1 + 3 m_max)")
+        rs = recs.shape[1]
+    call("tg_stream_push", _p(chunk), cs, n, _p(recs if m_max > 0 else None), rs, int(m_max), int(words_live), _p(st["ring"]), _p(st["written"]),
+         _p(st["words"]), _p(st["n_words"]), st["B"], st["R"], st["A"], st["W"], _stream())
+
+
+def stream_stage(st, text_out=None, audio_out=None):
+    """The inputs of the window whose index is st['win'][0]: audio_out (B, A) fp32 = the window's samples from the ring, zeros where none have been
+    pushed yet; text_out (B, T) int64 = per frame the id of the last pushed record of that window, else 0.  Device buffers written in place."""
+    _stream_check(st)
+    if audio_out is not None:
+        _flat(audio_out, "audio_out")
+        if tuple(audio_out.shape) != (st["B"], st["A"]):
+            raise ValueError(f"audio_out is {tuple(audio_out.shape)}, a window is {(st['B'], st['A'])}")
+    if text_out is not None:
+        _i64(text_out, "text_out")
+        if tuple(text_out.shape) != (st["B"], st["T"]) or not text_out.is_contiguous():
+            raise ValueError(f"text_out is {tuple(text_out.shape)}, a window's text is {(st['B'], st['T'])}, contiguous")
+    call("tg_stream_stage", _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(st["win"]), st["B"], st["R"], st["S"], st["A"],
+         st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
+
+
 def pose_metrics(out, target, mean_dir_vec, n_pre, sums):
     _same(out, target); _flat(mean_dir_vec, "mean"); B, T, D = out.shape
     assert D == 27 and mean_dir_vec.numel() == 27 and sums.dtype == torch.float64 and sums.numel() >= 3 and sums.is_cuda

@@ -31,6 +31,11 @@ one launch (csrc/utterance.hip) cuts all rows' inputs on the device, into the wi
 smoothing, the fade-out and -- on request -- the joint positions are one more call on the stacked result (UtteranceBatch.finish), which
 return_device=True hands back without a read-back.  The scheduler is unchanged: lock-step, finished utterances idle.
 
+GestureStream (multimodal_context and joint_embedding) is the streaming form of the same loop: audio and words arrive in pieces (push), a window
+runs as soon as its samples are there -- cut from a device-resident ring by csrc/stream.hip into the window decoders' static buffers -- and the
+frames that became final come back at once; close() runs the padded last window, the fade-out and the joints.  Window i starts at sample i * S
+by definition (stream_matches_offline tells where that is also the reference's start).
+
 TTS / Gentle alignment / LMDB front-ends of the reference script are network services and out of scope; `words` is the
 reference's word list [[word, start_s, end_s], ...].
 """
@@ -779,3 +784,277 @@ def generate_gestures(args, pose_decoder, lang_model, audio, words, audio_sr=160
     n_win = num_windows(len(audio) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate)
     _, _, end_padding = window_inputs(args, lang_model, audio, words, n_win - 1, audio_sr)
     return fade_out_to_mean(out, end_padding, args, audio_sr)
+
+
+# ------------------------------------------------------------------------------------------------------------------ streaming synthesis
+def stream_geometry(args, audio_sr=16000):
+    """(S, A): stride and window of the stream in samples.  A is the window decoders' int(n_poses / fps * audio_sr); S = (n_poses - n_pre_poses) /
+    fps * audio_sr must be an integer (exact rational arithmetic) -- a stream addresses window i at sample i * S -- else ValueError."""
+    from fractions import Fraction
+    fps = Fraction(args.motion_resampling_framerate)
+    s = Fraction(args.n_poses - args.n_pre_poses) * audio_sr / fps
+    if s.denominator != 1 or s < 1:
+        raise ValueError(f"GestureStream: the window stride (n_poses - n_pre_poses) / fps * audio_sr = {float(s)} samples is not a positive integer")
+    return int(s), int(args.n_poses / args.motion_resampling_framerate * audio_sr)
+
+
+def stream_matches_offline(args, n_samples, audio_sr=16000):
+    """Whether an utterance of n_samples has, in utterance_plan, exactly the audio starts i * S the stream uses.  (The reference's
+    floor(start_time / clip_length * len(audio)) in doubles lands one sample lower for some lengths: DESIGN.md section 25.)"""
+    S, _ = stream_geometry(args, audio_sr)
+    starts = utterance_plan(args, None, int(n_samples), None, audio_sr, "speech2gesture")["audio_start"]       # (that model's plan needs no words)
+    return all(int(a) == i * S for i, a in enumerate(starts))
+
+
+def complete_windows(pushed, S, A):
+    """Windows whose samples [w S, w S + A) have all been pushed: w is complete when pushed >= w S + A (integers)."""
+    return 0 if pushed < A else (pushed - A) // S + 1
+
+
+def word_records(args, lang_model, words):
+    """The integer records (window, frame, word id) of a word list, in word order: one record per window a word falls in (overlapping windows
+    share words), by the expressions of words_in_time_range and _window_geometry: the word is in window i if w[1] < end_time and w[2] >
+    start_time, on frame max(0, int(floor((w[1] - start_time) / frame_duration))).  Replayed in order (a later record overwrites an earlier one on
+    its frame) they give window_inputs' ids, for words sorted by start time (what words_in_time_range's early exit assumes)."""
+    n_frames = args.n_poses
+    unit_time = n_frames / args.motion_resampling_framerate
+    stride_time = (n_frames - args.n_pre_poses) / args.motion_resampling_framerate
+    out = []
+    for w in words or ():
+        i = max(0, int((w[1] - unit_time) // stride_time) - 1)
+        while i * stride_time < w[2]:
+            start_time = i * stride_time
+            end_time = start_time + unit_time
+            if w[1] < end_time and w[2] > start_time:
+                frame_duration = (end_time - start_time) / n_frames
+                out.append((i, max(0, int(np.floor((w[1] - start_time) / frame_duration))), int(lang_model.get_word_index(w[0]))))
+            i += 1
+    return out
+
+
+class GestureStream:
+    """Gestures window by window while the audio is still arriving (args.model 'multimodal_context' on a WindowDecoder, 'joint_embedding' on a
+    JointEmbedWindowDecoder; 1 to 4 rows that share a clock).  push(chunk, words) appends samples and words to device-resident rings
+    (csrc/stream.hip), runs every window that has become complete -- window w is complete when w * S + A samples have been pushed -- and returns
+    the frames that became final: a window not yet known to be the last one finalises its first n_poses - n_pre_poses frames, its last
+    n_pre_poses are replaced by the next window's cross-fade.  close() runs the remaining, zero-padded windows of the reference's window count and
+    returns the rest.  Everything push() and close() returned, concatenated, is what generate_gestures_batch(on_device=True) gives for the
+    finished utterance with the same draws -- bit for bit where stream_matches_offline(args, n) holds:
+
+    the stream DEFINES window i's first sample as the integer i * S (S = stride in samples, 32 000 for the shipped configs).  The reference computes
+    floor(i * stride_time / clip_length * len(audio)) in doubles, which for some lengths lands one sample lower; a stream cannot know the
+    final length while it runs, and does not imitate that.
+
+    Words: (word, start, end) with absolute times in seconds, per row, in order of start time, each given once.  A word is applied to every
+    window it falls in that has NOT yet run when it is pushed; a word pushed after one of its windows ran is not applied to that window (no
+    emitted frame ever changes) and is counted in stream.late_words.  A word is in time for all its windows if it is pushed no later than the
+    chunk that holds the sample BEFORE its start.  (The chunk that holds the start itself is early enough except in one case: window w runs
+    when w * S + A samples are there, A = int(unit * sr), while its end time is the up to one sample later w * stride + unit; a word that starts
+    in that last fraction of a sample belongs to window w for the reference, but its chunk begins after w ran.)
+
+    seq2seq and speech2gesture are refused: seq2seq's smoothing rewrites frames of a window after the next window has run, and the log-mel
+    spectrogram is padded over the whole utterance.  max_chunk: the largest push, in samples; the ring holds A + max_chunk samples per row.
+    _draws / eps_list (parity tests): per window the (B, 16) / (B, 32) draws to replay; window_decoder: a kept decoder of the model's kind
+    (its window graph is captured once and replayed by every stream that uses it; the constructor re-seeds it and the stream writes its
+    static buffers, so a kept decoder serves ONE stream at a time -- start the next stream on it after the previous one was closed).
+    push() never reads from the device.  A refused push (ValueError) leaves the stream as it was; a close that raised can be called again."""
+
+    def __init__(self, args, pose_decoder, lang_model, batch=1, vids=None, seed_seqs=None, audio_sr=16000, max_chunk=16000, _draws=None, eps_list=None,
+                 window_decoder=None, graph=True, word_ring=256, ring=None):
+        model = getattr(args, "model", "multimodal_context")
+        if model == "seq2seq":
+            raise ValueError("GestureStream: the seq2seq model cannot stream: its smoothing rewrites frames of a window after the next window has run")
+        if model == "speech2gesture":
+            raise ValueError("GestureStream: the speech2gesture model cannot stream: its log-mel spectrogram is padded over the whole utterance")
+        if model not in ("multimodal_context", "joint_embedding"):
+            raise ValueError(f"GestureStream: unknown model {model!r}")
+        if not 1 <= batch <= 4:
+            raise ValueError(f"GestureStream: 1 to 4 rows, got {batch}")
+        if max_chunk < 1:
+            raise ValueError(f"GestureStream: max_chunk = {max_chunk}")
+        self.args, self.model, self.lang, self.B, self.audio_sr, self.max_chunk = args, model, lang_model, batch, audio_sr, int(max_chunk)
+        self.T, self.n_pre = args.n_poses, args.n_pre_poses
+        self.stride = self.T - self.n_pre
+        self.S, self.A = stream_geometry(args, audio_sr)
+        dev = self.dev = next(pose_decoder.parameters()).device
+        draws = _draws if model == "multimodal_context" else eps_list
+        if window_decoder is not None:
+            kind = WindowDecoder if model == "multimodal_context" else JointEmbedWindowDecoder
+            d = window_decoder
+            if not isinstance(d, kind) or (d.gen if kind is WindowDecoder else d.net) is not pose_decoder or d.B != batch or (d.T, d.n_pre) != (self.T, self.n_pre) \
+                    or (draws is not None) != (d.draw is not None):
+                raise ValueError(f"GestureStream: window_decoder must be a {kind.__name__} built for this model, {batch} row(s), (n_poses, n_pre_poses) = "
+                                 f"{(self.T, self.n_pre)} and replay_draws = {draws is not None}")
+            self.dec = d
+        elif model == "multimodal_context":
+            self.dec = WindowDecoder(args, pose_decoder, batch, dev, graph=graph, replay_draws=draws is not None)
+        else:
+            self.dec = JointEmbedWindowDecoder(args, pose_decoder, batch, dev, graph=graph, replay_draws=draws is not None, audio_sr=audio_sr)
+        if self.dec.audio_len != self.A:
+            raise ValueError(f"GestureStream: the window decoder takes {self.dec.audio_len} samples, the stream's window is {self.A} (audio_sr = {audio_sr})")
+        self.D, self.draws = self.dec.D, draws
+        self.dec.seed(None if seed_seqs is None else np.stack([np.asarray(s)[:self.n_pre] for s in seed_seqs]))
+        self.vid = None
+        if model == "multimodal_context" and args.z_type == "speaker":                  # synthesize.py:67-74
+            vids = [None] * batch if vids is None else list(vids)
+            self.vid = torch.as_tensor([v if v else random.randrange(pose_decoder.z_obj.n_words) for v in vids], dtype=torch.int64)
+        R = self.A + self.max_chunk if ring is None else int(ring)
+        if R < self.A + self.max_chunk:
+            raise ValueError(f"GestureStream: a ring of {R} samples; window + max_chunk = {self.A + self.max_chunk} are needed")
+        self.state = ops.stream_state(batch, R, self.S, self.A, word_ring, self.T, dev)
+        self.chunk_buf = torch.zeros(batch, self.max_chunk, device=dev)
+        self.pushed = self.next_window = self.late_words = 0
+        self.closed = False
+        self._live = [[] for _ in range(batch)]          # per row: (index of the record in the row's sequence, window) of records a window may still need
+        self._n_rec = [0] * batch
+        self._ones = torch.ones(batch, dtype=torch.int32, device=dev)
+        self._mean, self._closing_window = None, False
+
+    # -------------------------------------------------------------------------------------------------------------- host bookkeeping (integers)
+    def _records(self, words):
+        """words (one list per row) -> (recs tensor or None, m_max, words_live): the records of windows that have not run yet."""
+        if words is None:
+            return None, 0, 0
+        if len(words) != self.B:
+            raise ValueError(f"GestureStream.push: words for {len(words)} row(s), the stream has {self.B}")
+        rows, late = [], 0
+        for b, wl in enumerate(words):
+            keep = []
+            for w in wl or ():
+                rec = word_records(self.args, self.lang, [w])
+                late += any(r[0] < self.next_window for r in rec)
+                keep += [r for r in rec if r[0] >= self.next_window]
+            rows.append(keep)
+        m_max = max(len(r) for r in rows)
+        if m_max == 0:
+            self.late_words += late
+            return None, 0, 0
+        live = max(n - l[0][0] if l else 0 for n, l in zip(self._n_rec, self._live))
+        if live + m_max > self.state["W"]:
+            raise ValueError(f"GestureStream.push: {m_max} word record(s) on top of {live} a window still needs exceed the word ring's capacity "
+                             f"{self.state['W']} (word_ring=...)")
+        self.late_words += late                                      # (state changes only once the push can no longer be refused here)
+        table = np.zeros((self.B, 1 + 3 * m_max), dtype=np.int32)
+        for b, r in enumerate(rows):
+            table[b, 0] = len(r)
+            table[b, 1:1 + 3 * len(r)] = np.asarray(r, dtype=np.int32).reshape(-1)
+            self._live[b] += [(self._n_rec[b] + k, rec[0]) for k, rec in enumerate(r)]
+            self._n_rec[b] += len(r)
+        return torch.from_numpy(table).to(self.dev, non_blocking=True), m_max, live
+
+    def _run(self, k):
+        """The next k windows, stacked as the offline loop stacks them: (B, k * stride + n_pre, D)."""
+        B, T, D, st = self.B, self.T, self.D, self.stride
+        F = k * st + self.n_pre
+        buf = torch.empty(B, F, D, device=self.dev)                 # (the windows tile it)
+        for j in range(k):
+            i = self.next_window
+            ops.stream_stage(self.state, self.dec.text, self.dec.audio)               # straight into the decoder's static buffers
+            draw = None if self.draws is None else self.draws[i]
+            if self.model == "multimodal_context":
+                out = self.dec.window(None, None, self.vid if i == 0 else None, first=(i == 0), draw=draw)
+            else:
+                out = self.dec.window(None, None, first=(i == 0), draw=draw)
+            ops.copy2d(out.view(B, T * D), buf.view(B, F * D)[:, j * st * D:(j * st + T) * D])
+            ops.counter_inc(self.state["win"])
+            self.next_window += 1
+        self._live = [[r for r in l if r[1] >= self.next_window] for l in self._live]
+        return buf
+
+    def _joints(self, buf, k, frames):
+        """fp64 joint positions (B, frames, 10, 3) of the first `frames` frames of a stacked buffer of k windows."""
+        if self._mean is None:
+            self._mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
+        jt = torch.zeros(self.B, frames, 10, 3, dtype=torch.float64, device=self.dev)
+        ops.utterance_finish(buf, self._ones, k, self.T, self.n_pre, mean=self._mean, joints=jt)
+        return jt
+
+    @staticmethod
+    def _result(frames, jt, numpy):
+        if numpy:
+            frames, jt = frames.cpu().numpy(), None if jt is None else jt.cpu().numpy()
+        return frames if jt is None else (frames, jt)
+
+    # -------------------------------------------------------------------------------------------------------------- the interface
+    def push(self, chunk, words=None, numpy=False, joints=False):
+        """chunk: (B, n) -- or (n,) for one row -- float32, torch (host or device) or numpy, 1 <= n <= max_chunk, the same n for every row.
+        words: per row a list of (word, start, end), absolute seconds (one row: the list itself is accepted).  Returns the (B, frames, D) device
+        view of the frames that became final in this call (frames = 0 if no window completed); numpy=True reads them back; joints=True returns
+        (frames, fp64 joint positions (B, frames, 10, 3)).  A word whose window has already run is not applied to that window and counted in
+        late_words.  ValueError: closed stream, chunk over max_chunk, dtype other than float32, wrong row count."""
+        if self.closed:
+            raise ValueError("GestureStream.push: the stream is closed")
+        if isinstance(chunk, np.ndarray):
+            if chunk.dtype != np.float32:
+                raise ValueError(f"GestureStream.push: the chunk must be float32, got {chunk.dtype}")
+            chunk = torch.from_numpy(np.ascontiguousarray(chunk))
+        if not isinstance(chunk, torch.Tensor) or chunk.dtype != torch.float32:
+            raise ValueError(f"GestureStream.push: the chunk must be float32, got {getattr(chunk, 'dtype', type(chunk).__name__)}")
+        if chunk.dim() == 1 and self.B == 1:
+            chunk = chunk[None]
+        if chunk.dim() != 2 or chunk.shape[0] != self.B or chunk.shape[1] < 1:
+            raise ValueError(f"GestureStream.push: the chunk is {tuple(chunk.shape)}, expected ({self.B}, n >= 1)")
+        n = chunk.shape[1]
+        if n > self.max_chunk:
+            raise ValueError(f"GestureStream.push: a chunk of {n} samples, max_chunk is {self.max_chunk}")
+        if words is not None and self.B == 1 and (len(words) == 0 or (len(words[0]) > 0 and isinstance(words[0][0], str))):
+            words = [words]                                          # one row: its word list as it is
+        recs, m_max, live = self._records(words)
+        if not (chunk.is_cuda and chunk.stride(1) == 1 and (self.B == 1 or chunk.stride(0) >= n)):
+            dst = self.chunk_buf[:, :n]
+            dst.copy_(chunk, non_blocking=True)                      # pinned host memory: asynchronous
+            chunk = dst
+        ops.stream_push(self.state, chunk, recs, m_max, live)
+        self.pushed += n
+        k = complete_windows(self.pushed, self.S, self.A) - self.next_window
+        if k <= 0:
+            empty = self.chunk_buf.new_zeros(self.B, 0, self.D)
+            return self._result(empty, empty.new_zeros(self.B, 0, 10, 3, dtype=torch.float64) if joints else None, numpy)
+        buf = self._run(k)
+        return self._result(buf[:, :k * self.stride], self._joints(buf, k, k * self.stride) if joints else None, numpy)
+
+    def close(self, fade_out=False, joints=False, numpy=False):
+        """Ends the stream: runs the windows the reference's window count (num_windows of the final length) still asks for, zero-padded, and returns
+        the remaining frames, the last window's final n_pre_poses among them; fade_out: faded out to the mean pose on the device as
+        generate_gestures_batch(on_device=True, fade_out=True) does (the result may grow, as there); joints=True: (frames, joint positions)."""
+        if self.closed:
+            raise ValueError("GestureStream.close: the stream is closed")
+        if self.pushed == 0:
+            raise ValueError("GestureStream.close: nothing was pushed")
+        B, T, D, st, n = self.B, self.T, self.D, self.stride, self.n_pre
+        n_win = num_windows(self.pushed / self.audio_sr, T, n, self.args.motion_resampling_framerate)
+        k = n_win - self.next_window
+        if k not in (0, 1):                                         # windows run as soon as they are complete: at most the padded last one is left
+            raise RuntimeError(f"GestureStream.close: {self.next_window} windows ran, the reference counts {n_win} for {self.pushed} samples")
+        # the last window goes through the finish on a one-window buffer of its own; dec.out holds it, whether it runs here or ran in a push
+        # (then it was complete, and its first `stride` frames are out already)
+        if k:
+            self._run(1)
+            self._closing_window = True                             # (a close that raises after this point and is called again must not skip its frames)
+        skip = 0 if self._closing_window else st
+        fin = torch.zeros(B, T + 2 * n, D, device=self.dev)
+        ops.copy2d(self.dec.out.view(B, T * D), fin.view(B, (T + 2 * n) * D)[:, :T * D])
+        length, fade_start, tab = T, None, None
+        if fade_out:
+            # the padding is at most a window, so int(pad / sr * fps) <= n_poses and start_frame >= n_win * stride + n_pre - n_poses = (n_win - 1) * stride:
+            # the fade-out starts inside the last window.  That window has been emitted only if it was complete, and then pad = 0 and the fade
+            # starts at the utterance's end: no emitted frame changes
+            start = _fade_start_frame(n_win * st + n, end_padding_samples(self.args, self.pushed, self.audio_sr), self.args, self.audio_sr)
+            rel = start - (n_win - 1) * st
+            assert 0 <= rel <= T and (k > 0 or rel == T)
+            length = max(T, rel + 2 * n)
+            fade_start = torch.tensor([rel] * B, dtype=torch.int32, device=self.dev)
+            if 1 <= n <= 8:                                         # (outside: the library refuses the call and names its envelope)
+                t = projection_tables(n)
+                tab = torch.from_numpy(np.concatenate([t["smooth"].ravel(), t["fade"].ravel()])).to(self.dev)
+        jt = None
+        if joints:
+            if self._mean is None:
+                self._mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
+            jt = torch.zeros(B, T + 2 * n, 10, 3, dtype=torch.float64, device=self.dev)
+        if fade_out or joints:
+            ops.utterance_finish(fin, self._ones, 1, T, n, proj=tab, fade_start=fade_start, mean=self._mean if joints else None, joints=jt)
+        frames, jrows = fin[:, skip:length], None if jt is None else jt[:, skip:length]
+        res = self._result(frames, jrows, numpy)
+        self.closed = True                                          # only now: a close that raised can be called again
+        return res

@@ -697,6 +697,23 @@ int tg_utterance_finish(float* total, int64_t F, int32_t B, int32_t D, const int
                         int32_t smooth, const double* proj, const int32_t* fade_start, const double* mean, double* joints, int64_t joints_frames,
                         void* stream);
 
+/* Streaming synthesis (csrc/stream.hip; synthesize.GestureStream): audio and words arrive in pieces.  A stream of B rows keeps, all in device
+ * memory, ring [B][R] fp32 with written [B] int64 (samples pushed so far) and word_ring [B][W][3] int32 with n_words [B] int64 (records pushed
+ * so far).  A record is (absolute window index, frame in the window, word id): integers the host computed, one per window a word falls in.
+ * tg_stream_push appends chunk [B][n] (device memory, rows chunk_stride floats apart) at written[b] mod R -- the chunk may straddle the wrap
+ * point -- and, with m_max > 0, row b's records recs[b][1 .. 1 + 3 recs[b][0]) (recs [B][rec_stride] int32, device; recs[b][0] <= m_max) at
+ * n_words[b] mod W; it advances both counters.  words_live: the host's count of ring slots from the oldest record a window still needs to
+ * the newest.  Envelope, checked before anything is launched: 1 <= B <= 4, n >= 1, A + n <= R <= 2^30 (A: samples of a window, so that a
+ * window that was incomplete before the push is still whole after it), 1 <= W <= 1024, words_live + m_max <= W, rec_stride >= 1 + 3 m_max. */
+int tg_stream_push(const float* chunk, int64_t chunk_stride, int32_t n, const int32_t* recs, int32_t rec_stride, int32_t m_max, int32_t words_live,
+                   float* ring, int64_t* written, int32_t* word_ring, int64_t* n_words, int32_t B, int32_t R, int32_t A, int32_t W, void* stream);
+/* The inputs of window w = win[0] (int32, device memory; S: stride in samples): out_audio [B][A] = ring[b][(w S + k) mod R] for
+ * k < min(A, written[b] - w S), zeros behind (null: no audio); out_text [B][T] int64 = per frame the id of the LAST pushed record of window w
+ * on that frame, else 0 (null: no text).  Copies: bit-exact.  Envelope: 1 <= B <= 4, S >= 1, 1 <= A <= 2^25, A + 1 <= R <= 2^30,
+ * 1 <= W <= 1024, 1 <= T <= 1024. */
+int tg_stream_stage(const float* ring, const int64_t* written, const int32_t* word_ring, const int64_t* n_words, const int32_t* win, int32_t B,
+                    int32_t R, int32_t S, int32_t A, int32_t W, int32_t T, float* out_audio, int64_t* out_text, void* stream);
+
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over
  * T-2 frames, sums[2] = sum |out - target|.  (joint_mae = sums[0]/(B*(T-n_pre)*30), accel = sums[1]/(B*(T-2)*30), l1 = sums[2]/(B*T*27).) */
