@@ -1959,6 +1959,71 @@ def stream_stage(st, text_out=None, audio_out=None):
          st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
 
 
+# ------------------------------------------------------------------------------------------------- stream pool (csrc/stream_pool.hip)
+def pool_push(st, chunk, n, recs=None, m_max=0, words_live=0):
+    """stream_push with one chunk length per row: n (B host integers >= 0); row b appends chunk[b, :n[b]] (chunk (B, >= max n) fp32, device, unit
+    inner stride) and its records; a row with n[b] == 0 and no records keeps every bit.  words_live + m_max: the slot count of the fullest word
+    ring after the push.  Outside the envelope (1 <= B <= 4, a row with samples or records, R >= A + max n) the library refuses (RuntimeError
+    naming the envelope); nothing is launched."""
+    _stream_check(st)
+    _f32(chunk, "chunk")
+    n = [int(v) for v in n]
+    B, n_max = st["B"], max(n, default=0)
+    if len(n) != B:
+        raise ValueError(f"n: {len(n)} chunk lengths for {B} rows")
+    if chunk.dim() != 2 or chunk.shape[0] != B or chunk.shape[1] < n_max or (chunk.shape[1] > 1 and chunk.stride(1) != 1):
+        raise ValueError(f"chunk: expected ({B}, >= {n_max}) with unit inner stride, got {tuple(chunk.shape)} strides {chunk.stride()}")
+    cs = chunk.stride(0) if B > 1 else max(chunk.shape[1], 1)
+    if n_max > 0 and (cs < n_max or (B - 1) * cs + n_max > _room(chunk)):
+        raise ValueError("chunk: rows overlap or exceed the tensor")
+    rs = 0
+    if m_max > 0:
+        if not (isinstance(recs, torch.Tensor) and recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 2 and recs.is_contiguous() and recs.shape[0] == B):
+            raise TypeError(f"recs: expected a contiguous CUDA int32 tensor ({B}, >= 1 + 3 m_max)")
+        rs = recs.shape[1]
+    call("tg_pool_push", _p(chunk), cs, *(n + [0] * 4)[:4], _p(recs if m_max > 0 else None), rs, int(m_max), int(words_live), _p(st["ring"]),
+         _p(st["written"]), _p(st["words"]), _p(st["n_words"]), B, st["R"], st["A"], st["W"], _stream())      # (B > 4: refused by the library)
+
+
+def pool_stage(st, win, active, text_out=None, audio_out=None):
+    """stream_stage per row: row b with active[b] != 0 gets the inputs of its own window win[b] (win, active: (B,) int32 on the device); the rows of
+    audio_out / text_out that belong to the other rows are left as they are."""
+    _stream_check(st)
+    _dev_int(win, torch.int32, st["B"], "win"); _dev_int(active, torch.int32, st["B"], "active")
+    if audio_out is not None:
+        _flat(audio_out, "audio_out")
+        if tuple(audio_out.shape) != (st["B"], st["A"]):
+            raise ValueError(f"audio_out is {tuple(audio_out.shape)}, a window is {(st['B'], st['A'])}")
+    if text_out is not None:
+        _i64(text_out, "text_out")
+        if tuple(text_out.shape) != (st["B"], st["T"]) or not text_out.is_contiguous():
+            raise ValueError(f"text_out is {tuple(text_out.shape)}, a window's text is {(st['B'], st['T'])}, contiguous")
+    call("tg_pool_stage", _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(win), _p(active), st["B"], st["R"], st["S"], st["A"],
+         st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
+
+
+def pool_handover(res, out, tail, seed, win, active):
+    """The tail of a window for the rows with active[b] != 0, one launch: out = res (B, T, D), cross-faded with tail (B, n_pre, D) where win[b] > 0
+    (window_blend's arithmetic), tail = out's last n_pre frames, seed = the next window's seed -- (B, T, D + 1): make_pre_seq's layout, (B, n_pre,
+    D): the frames themselves -- and win[b] += 1.  Nothing of an inactive row is written."""
+    for t, name in ((res, "res"), (out, "out"), (tail, "tail"), (seed, "seed")):
+        _flat(t, name)
+        if t.dim() != 3:
+            raise ValueError(f"{name}: expected three dimensions, got {tuple(t.shape)}")
+    B, T, D = out.shape
+    n_pre = tail.shape[1]
+    if tuple(res.shape) != (B, T, D) or tail.shape[0] != B or tail.shape[2] != D:
+        raise ValueError(f"res {tuple(res.shape)} / tail {tuple(tail.shape)} do not belong to out {tuple(out.shape)}")
+    if tuple(seed.shape) == (B, T, D + 1):
+        layout = 0
+    elif tuple(seed.shape) == (B, n_pre, D):
+        layout = 1
+    else:
+        raise ValueError(f"seed is {tuple(seed.shape)}: expected {(B, T, D + 1)} (pre_seq) or {(B, n_pre, D)} (pre)")
+    _dev_int(win, torch.int32, B, "win"); _dev_int(active, torch.int32, B, "active")
+    call("tg_pool_handover", _p(res), _p(out), _p(tail), _p(seed), layout, _p(win), _p(active), B, T, D, n_pre, _stream())
+
+
 def pose_metrics(out, target, mean_dir_vec, n_pre, sums):
     _same(out, target); _flat(mean_dir_vec, "mean"); B, T, D = out.shape
     assert D == 27 and mean_dir_vec.numel() == 27 and sums.dtype == torch.float64 and sums.numel() >= 3 and sums.is_cuda

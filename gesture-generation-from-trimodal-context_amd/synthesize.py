@@ -36,6 +36,10 @@ runs as soon as its samples are there -- cut from a device-resident ring by csrc
 frames that became final come back at once; close() runs the padded last window, the fade-out and the joints.  Window i starts at sample i * S
 by definition (stream_matches_offline tells where that is also the reference's start).
 
+StreamPool is GestureStream for independent sessions: the 1 to 4 rows of ONE window decoder are slots, each with its own clock (per-row window
+counters on the device), opened, pushed to (ragged chunks) and closed on their own; the windows that have become complete run together, and
+the hand-over kernel (csrc/stream_pool.hip) leaves the rows that did not run untouched.  One graph serves first and later windows.
+
 TTS / Gentle alignment / LMDB front-ends of the reference script are network services and out of scope; `words` is the
 reference's word list [[word, start_s, end_s], ...].
 """
@@ -216,6 +220,47 @@ def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_li
     return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
 
 
+def _pool_buffers(dec):
+    if dec.win is None:
+        dec.win = torch.zeros(dec.B, dtype=torch.int32, device=dec.dev)
+        dec.active = torch.zeros(dec.B, dtype=torch.int32, device=dec.dev)
+    return dec.active, dec.win
+
+
+def _window_pooled(dec, state, active, win, draw):
+    """window_pooled of both window decoders; state: the tensors a capture must leave as they were (besides dec.win)."""
+    a_buf, w_buf = _pool_buffers(dec)
+    if active is not None:
+        a_buf.copy_(torch.as_tensor(active, dtype=torch.int32), non_blocking=True)
+    if win is not None:
+        w_buf.copy_(torch.as_tensor(win, dtype=torch.int32), non_blocking=True)
+    if draw is not None:
+        dec.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
+    with torch.no_grad(), dec.frozen:
+        if not dec.use_graph:
+            dec._forward_pooled()
+        else:
+            if dec.graph_pooled is None:
+                # There is no eager first window here, so the one eager pass a capture needs in front of it (the weight-only operands of
+                # layers.FrozenWeights and the kernels' workspaces are made on first use and must stay OUT of the graph) runs with no row
+                # active: the hand-over then writes nothing
+                mask = a_buf.clone()
+                a_buf.zero_()
+                dec._forward_pooled()
+                a_buf.copy_(mask)
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                keep = [t.clone() for t in state + (w_buf,)]
+                pg_alive = torch.distributed.is_available() and torch.distributed.is_initialized()     # RCCL helper threads: see train_gan.GraphedGanStep
+                with torch.cuda.graph(graph, capture_error_mode="thread_local" if pg_alive else "global"):
+                    dec._forward_pooled()
+                for t, k in zip(state + (w_buf,), keep):                   # capture does not execute: restore state
+                    t.copy_(k)
+                dec.graph_pooled = graph
+            dec.graph_pooled.replay()
+    return dec.out
+
+
 class WindowDecoder:
     """Batched window forward with device-side seed hand-over and cross-fade; optional hipGraph capture."""
 
@@ -238,7 +283,29 @@ class WindowDecoder:
         # the generator's weights stand still for the lifetime of a decoder (one synthesis call): weight-only operands are formed by the first
         # window and kept (layers.FrozenWeights) -- a decoder must not outlive a change of the parameters
         self.frozen = L.FrozenWeights()
+        self.win = self.active = self.graph_pooled = None              # window_pooled's state: made on its first use
         pose_decoder.train(False)
+
+    def _forward_pooled(self):
+        eng = self.gen.engine
+        eng.rng.advance()
+        inject = None if self.draw is None else {"g.eps": self.draw, "g.z": self.draw}
+        vid = self.vid if eng.z_mode == "speaker" else None
+        res = eng.forward(self.pre_seq, self.text, self.audio, vid, training=False, inject=inject)
+        ops.pool_handover(res["out"].view(self.B, self.T, self.D), self.out, self.tail, self.pre_seq, self.win, self.active)
+
+    def window_pooled(self, active=None, win=None, draw=None):
+        """One window for the rows of a stream pool (StreamPool): the forward runs on all B rows, then ops.pool_handover gives every row with
+        active[b] != 0 its output, cross-fade (where the row's window counter win[b] > 0), tail, next seed and win[b] + 1; the other rows'
+        out / tail / pre_seq / win keep every bit.  active, win: B integers copied into the static int32 buffers self.active / self.win
+        (pool_buffers), or None: the buffers as they are -- win counts on the device, so a pool passes it only to reset rows.  A row's first
+        window is like any other: from the first call on the window is ONE captured graph, self.graph_pooled (window() and its graph are
+        not touched).  The inputs are self.text / self.audio / self.vid, written in place."""
+        return _window_pooled(self, (self.pre_seq, self.tail, self.out), active, win, draw)
+
+    def pool_buffers(self):
+        """(active, win): the static (B,) int32 device buffers window_pooled reads -- the mask of the rows to run and every row's window index."""
+        return _pool_buffers(self)
 
     def seed(self, seed_seq=None):
         """pre_seq of the first window: optional seed poses with the constraint bit (synthesize.py:46-50)."""
@@ -324,6 +391,24 @@ class JointEmbedWindowDecoder:
         self.use_graph, self.graph = graph, None
         # as WindowDecoder: weight-only operands are formed by the first window and kept -- a decoder must not outlive a change of the parameters
         self.frozen = L.FrozenWeights()
+        self.win = self.active = self.graph_pooled = None              # window_pooled's state: made on its first use
+
+    def _forward_pooled(self):
+        net = self.net
+        net.context_encoder.gru.few_row_eval = True
+        inject = None if self.draw is None else {"c.eps": self.draw}
+        latent, _, _ = net.context_encoder(self.text, self.audio, inject=inject)
+        res = net.decoder.forward_constant(latent, self.pre)
+        ops.pool_handover(res, self.out, self.tail, self.pre, self.win, self.active)
+
+    def window_pooled(self, active=None, win=None, draw=None):
+        """WindowDecoder.window_pooled for this decoder: the forward on all B rows, then ops.pool_handover (seed layout `pre`) for the rows with
+        active[b] != 0; one captured graph, self.graph_pooled, from the first call on.  The inputs are self.text / self.audio, in place."""
+        return _window_pooled(self, (self.pre, self.tail, self.out), active, win, draw)
+
+    def pool_buffers(self):
+        """(active, win): the static (B,) int32 device buffers window_pooled reads."""
+        return _pool_buffers(self)
 
     def seed(self, seed_seq=None):
         """`pre` of the first window: zeros, or the seed poses (B, >= n_pre, D) (synthesize.py:46-50)."""
@@ -1057,4 +1142,260 @@ class GestureStream:
         frames, jrows = fin[:, skip:length], None if jt is None else jt[:, skip:length]
         res = self._result(frames, jrows, numpy)
         self.closed = True                                          # only now: a close that raised can be called again
+        return res
+
+
+# ------------------------------------------------------------------------------------------------------------------ stream pool
+def pool_rounds(pushed, next_window, S, A):
+    """The window schedule of a pool after a push, integers only: row b has k_b = complete_windows(pushed[b], S, A) - next_window[b] newly
+    complete windows (none if that is negative); they run in max k_b rounds, and round j runs the rows with k_b > j -- every row's windows in
+    its own order, as early as possible.  Returns the rounds' active masks (lists of 0 / 1, one entry per row); no round is empty."""
+    k = [max(0, complete_windows(int(p), S, A) - int(w)) for p, w in zip(pushed, next_window)]
+    return [[int(kb > j) for kb in k] for j in range(max(k, default=0))]
+
+
+class StreamPool:
+    """GestureStream for independent sessions: `slots` (1 to 4) rows on ONE window decoder, each row a session with a clock of its own.
+    open() takes a free row and returns its index, push({slot: chunk or (chunk, words)}) appends ragged chunks to any of the open rows and
+    returns, per pushed slot, the frames that became final, close(slot) ends one session and frees its row; sessions join and leave while the
+    others run.  The windows that a push completes run in rounds (pool_rounds): one decoder forward over all rows per round, of which the
+    hand-over kernel (ops.pool_handover) keeps the active rows' results -- the other rows' output, tail, seed and window counter keep every
+    bit.  The window counters live on the device, one per row, so a row's first window is the same launch sequence as any other and ONE
+    graph (the decoder's graph_pooled) serves every window of the pool.
+
+    Everything push() and close() returned for a session in slot b, concatenated, is row b of generate_gestures_batch(on_device=True) on a
+    batch of `slots` utterances with the session's utterance in row b and the same draws (joint_embedding: window_decoder=True), whatever the
+    other rows hold, for lengths where stream_matches_offline holds (see GestureStream for both conditions and for the words' timing rule;
+    late_words is counted per slot here).  The forward always runs `slots` rows: a pool of 4 with one open session pays the four-row window.
+
+    max_chunk: the largest chunk of one row in one push; ring: samples per row (default and minimum A + max_chunk); word_ring: records per row.
+    _replay_draws (parity tests): every open() then brings the session's per-window draws ((16,) multimodal_context, (32,) joint_embedding).
+    window_decoder: a kept decoder of the model's kind built for `slots` rows; its graph_pooled is captured once and replayed by every pool
+    that uses it, one pool at a time.  push() never reads from the device.  A refused call (ValueError) leaves the pool as it was."""
+
+    def __init__(self, args, pose_decoder, lang_model, slots=4, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, ring=None,
+                 window_decoder=None, _replay_draws=False):
+        model = getattr(args, "model", "multimodal_context")
+        if model == "seq2seq":
+            raise ValueError("StreamPool: the seq2seq model cannot stream: its smoothing rewrites frames of a window after the next window has run")
+        if model == "speech2gesture":
+            raise ValueError("StreamPool: the speech2gesture model cannot stream: its log-mel spectrogram is padded over the whole utterance")
+        if model not in ("multimodal_context", "joint_embedding"):
+            raise ValueError(f"StreamPool: unknown model {model!r}")
+        if not 1 <= slots <= 4:
+            raise ValueError(f"StreamPool: 1 to 4 slots, got {slots}")
+        if max_chunk < 1:
+            raise ValueError(f"StreamPool: max_chunk = {max_chunk}")
+        self.args, self.model, self.lang, self.B, self.audio_sr, self.max_chunk = args, model, lang_model, int(slots), audio_sr, int(max_chunk)
+        self.T, self.n_pre = args.n_poses, args.n_pre_poses
+        self.stride = self.T - self.n_pre
+        self.S, self.A = stream_geometry(args, audio_sr)
+        R = self.A + self.max_chunk if ring is None else int(ring)
+        if R < self.A + self.max_chunk:
+            raise ValueError(f"StreamPool: a ring of {R} samples; window + max_chunk = {self.A + self.max_chunk} are needed")
+        B = self.B
+        self.open_slots = [False] * B
+        self.pushed, self.next_window, self.late_words = [0] * B, [0] * B, [0] * B
+        self._live, self._n_rec, self._draws, self._closing_window = [[] for _ in range(B)], [0] * B, [None] * B, [False] * B
+        self.replay = bool(_replay_draws)
+        dev = self.dev = next(pose_decoder.parameters()).device
+        if window_decoder is not None:
+            kind = WindowDecoder if model == "multimodal_context" else JointEmbedWindowDecoder
+            d = window_decoder
+            if not isinstance(d, kind) or (d.gen if kind is WindowDecoder else d.net) is not pose_decoder or d.B != B or (d.T, d.n_pre) != (self.T, self.n_pre) \
+                    or self.replay != (d.draw is not None):
+                raise ValueError(f"StreamPool: window_decoder must be a {kind.__name__} built for this model, {B} row(s), (n_poses, n_pre_poses) = "
+                                 f"{(self.T, self.n_pre)} and replay_draws = {self.replay}")
+            self.dec = d
+        elif model == "multimodal_context":
+            self.dec = WindowDecoder(args, pose_decoder, B, dev, graph=graph, replay_draws=self.replay)
+        else:
+            self.dec = JointEmbedWindowDecoder(args, pose_decoder, B, dev, graph=graph, replay_draws=self.replay, audio_sr=audio_sr)
+        if self.dec.audio_len != self.A:
+            raise ValueError(f"StreamPool: the window decoder takes {self.dec.audio_len} samples, the pool's window is {self.A} (audio_sr = {audio_sr})")
+        self.D = self.dec.D
+        self.speakers = model == "multimodal_context" and args.z_type == "speaker"
+        self.state = ops.stream_state(B, R, self.S, self.A, word_ring, self.T, dev)      # (its one-entry `win` is not used: the rows' counters are dec.win)
+        self.active, self.win = self.dec.pool_buffers()
+        self.active.zero_(); self.win.zero_()
+        self.chunk_buf = torch.zeros(B, self.max_chunk, device=dev)
+        self._draw_host = None if self.dec.draw is None else torch.zeros(tuple(self.dec.draw.shape))
+        self._ones = torch.ones(B, dtype=torch.int32, device=dev)
+        self._mean = None
+
+    # -------------------------------------------------------------------------------------------------------------- sessions
+    def _slot(self, slot, what):
+        if not (isinstance(slot, (int, np.integer)) and 0 <= slot < self.B and self.open_slots[slot]):
+            raise ValueError(f"StreamPool.{what}: slot {slot!r} is not open")
+        return slot
+
+    def open(self, vid=None, seed_seq=None, _draws=None):
+        """Starts a session on the lowest free row and returns its index; ValueError if every row is taken.  vid: the speaker id (drawn like the
+        reference's if falsy; multimodal_context with z_type 'speaker' only); seed_seq: (>= n_pre, D) seed poses.  Resets the row's counters,
+        tail and seed on the device; no other row is touched."""
+        free = [b for b in range(self.B) if not self.open_slots[b]]
+        if not free:
+            raise ValueError(f"StreamPool.open: all {self.B} slot(s) are taken")
+        if self.replay and _draws is None:
+            raise ValueError("StreamPool.open: a pool with _replay_draws needs the session's _draws")
+        b, dec, n = free[0], self.dec, self.n_pre
+        seed = None if seed_seq is None else torch.as_tensor(np.asarray(seed_seq)[:n], dtype=torch.float32).to(self.dev)
+        if seed is not None and tuple(seed.shape) != (n, self.D):
+            raise ValueError(f"StreamPool.open: seed_seq gives {tuple(seed.shape)} seed poses, expected {(n, self.D)}")
+        for t in (self.state["written"], self.state["n_words"], self.win, dec.tail):
+            t[b:b + 1].zero_()
+        if self.model == "multimodal_context":
+            dec.pre_seq[b:b + 1].zero_()
+            if seed is not None:
+                dec.pre_seq[b, :n, :-1] = seed
+                dec.pre_seq[b, :n, -1] = 1
+            if self.speakers:                                                   # synthesize.py:67-74
+                dec.vid[b:b + 1].copy_(torch.tensor([vid if vid else random.randrange(dec.gen.z_obj.n_words)], dtype=torch.int64))
+        else:
+            dec.pre[b:b + 1].zero_()
+            if seed is not None:
+                dec.pre[b].copy_(seed)
+        self.pushed[b] = self.next_window[b] = self.late_words[b] = self._n_rec[b] = 0
+        self._live[b], self._draws[b], self._closing_window[b] = [], _draws, False
+        self.open_slots[b] = True
+        return b
+
+    # -------------------------------------------------------------------------------------------------------------- host bookkeeping (integers)
+    def _records(self, words):
+        """{slot: word list} -> (per-row records of windows that have not run yet, per-row late counts), GestureStream._records per row: each row
+        against its own next_window.  ValueError if a row's word ring would overflow; nothing is changed here."""
+        rows, late = [[] for _ in range(self.B)], [0] * self.B
+        for b, wl in words.items():
+            for w in wl or ():
+                rec = word_records(self.args, self.lang, [w])
+                late[b] += any(r[0] < self.next_window[b] for r in rec)
+                rows[b] += [r for r in rec if r[0] >= self.next_window[b]]
+        for b, r in enumerate(rows):
+            live = self._n_rec[b] - self._live[b][0][0] if self._live[b] else 0
+            if r and live + len(r) > self.state["W"]:
+                raise ValueError(f"StreamPool.push: slot {b}: {len(r)} word record(s) on top of {live} a window still needs exceed the word ring's "
+                                 f"capacity {self.state['W']} (word_ring=...)")
+        return rows, late
+
+    def _round(self, mask):
+        """One window for the rows of `mask`: the mask (and the rows' draws) go up by a small copy, then stage -> window_pooled."""
+        if self._draw_host is not None:
+            for b, a in enumerate(mask):
+                if a:
+                    self._draw_host[b] = torch.as_tensor(self._draws[b][self.next_window[b]], dtype=torch.float32).reshape(-1)
+        self.active.copy_(torch.tensor(mask, dtype=torch.int32), non_blocking=True)
+        ops.pool_stage(self.state, self.win, self.active, self.dec.text, self.dec.audio)     # straight into the decoder's static buffers
+        out = self.dec.window_pooled(draw=None if self._draw_host is None else self._draw_host.clone())
+        for b, a in enumerate(mask):
+            if a:
+                self.next_window[b] += 1
+                self._live[b] = [r for r in self._live[b] if r[1] >= self.next_window[b]]
+        return out
+
+    def _mean_dev(self):
+        if self._mean is None:
+            self._mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
+        return self._mean
+
+    # -------------------------------------------------------------------------------------------------------------- the interface
+    def push(self, chunks, numpy=False, joints=False):
+        """chunks: {slot: chunk} or {slot: (chunk, words)} for any non-empty subset of the open slots; chunk: 1-D float32 (numpy or a host
+        tensor), 1 <= len <= max_chunk, the lengths need not agree; words: a list of (word, start, end), absolute seconds of that session.
+        One upload, one ops.pool_push, then the rounds of pool_rounds.  Returns {slot: frames} for the pushed slots: the (k * stride, D) device
+        view of the frames that became final (k windows of that slot completed; k = 0: an empty result); numpy=True reads them back;
+        joints=True gives (frames, fp64 joint positions (k * stride, 10, 3))."""
+        B, st, T, D = self.B, self.stride, self.T, self.D
+        if not isinstance(chunks, dict) or not chunks:
+            raise ValueError("StreamPool.push: expected a non-empty {slot: chunk} dict")
+        rows, words = {}, {}
+        for slot, c in chunks.items():
+            b = self._slot(slot, "push")
+            c, w = c if isinstance(c, tuple) else (c, None)
+            if isinstance(c, torch.Tensor):
+                if c.is_cuda:
+                    raise ValueError("StreamPool.push: chunks are host arrays (one upload per push)")
+                c = c.numpy()
+            if not isinstance(c, np.ndarray) or c.dtype != np.float32:
+                raise ValueError(f"StreamPool.push: the chunk must be float32, got {getattr(c, 'dtype', type(c).__name__)}")
+            if c.ndim != 1 or not 1 <= c.shape[0] <= self.max_chunk:
+                raise ValueError(f"StreamPool.push: slot {b}: a chunk of shape {c.shape}; expected 1-D with 1 <= len <= max_chunk = {self.max_chunk}")
+            rows[b], words[b] = c, w
+        recs, late = self._records(words)                                   # (may refuse; nothing has changed yet)
+        n = [len(rows[b]) if b in rows else 0 for b in range(B)]
+        host = np.zeros((B, max(n)), np.float32)
+        for b, c in rows.items():
+            host[b, :n[b]] = c
+        dst = self.chunk_buf[:, :max(n)]
+        dst.copy_(torch.from_numpy(host), non_blocking=True)
+        m = [len(r) for r in recs]
+        m_max, table, fullest = max(m), None, 0
+        if m_max:
+            tab = np.zeros((B, 1 + 3 * m_max), dtype=np.int32)
+            for b, r in enumerate(recs):
+                if r:
+                    tab[b, 0] = len(r)
+                    tab[b, 1:1 + 3 * len(r)] = np.asarray(r, dtype=np.int32).reshape(-1)
+                    fullest = max(fullest, (self._n_rec[b] - self._live[b][0][0] if self._live[b] else 0) + len(r))
+            table = torch.from_numpy(tab).to(self.dev, non_blocking=True)
+        ops.pool_push(self.state, dst, n, table, m_max, max(0, fullest - m_max))
+        for b in range(B):
+            self.pushed[b] += n[b]
+            self.late_words[b] += late[b]
+            self._live[b] += [(self._n_rec[b] + k, rec[0]) for k, rec in enumerate(recs[b])]
+            self._n_rec[b] += len(recs[b])
+        masks = pool_rounds(self.pushed, self.next_window, self.S, self.A)
+        k = [sum(mk[b] for mk in masks) for b in range(B)]
+        buf = jt = None
+        if masks:
+            F = len(masks) * st + self.n_pre
+            buf = torch.empty(B, F, D, device=self.dev)                     # (every round writes every row's window: the rounds tile it)
+            for j, mask in enumerate(masks):
+                out = self._round(mask)
+                ops.copy2d(out.view(B, T * D), buf.view(B, F * D)[:, j * st * D:(j * st + T) * D])
+            if joints:
+                jt = torch.zeros(B, len(masks) * st, 10, 3, dtype=torch.float64, device=self.dev)
+                ops.utterance_finish(buf, self._ones, len(masks), T, self.n_pre, mean=self._mean_dev(), joints=jt)
+        res = {}
+        for b in rows:
+            frames = buf[b, :k[b] * st] if k[b] else self.chunk_buf.new_zeros(0, D)
+            jrows = None if not joints else (jt[b, :k[b] * st] if k[b] else torch.zeros(0, 10, 3, dtype=torch.float64, device=self.dev))
+            res[b] = GestureStream._result(frames, jrows, numpy)
+        return res
+
+    def close(self, slot, fade_out=False, joints=False, numpy=False):
+        """Ends the session of `slot` as GestureStream.close ends a stream, for that row alone: the at most one remaining zero-padded window
+        runs as a round with only this row active, the finish (fade_out, joints) runs on a one-row copy of the row's last window, and the row
+        is free again.  Returns the session's remaining frames (frames, D), or (frames, joint positions)."""
+        b = self._slot(slot, "close")
+        if self.pushed[b] == 0:
+            raise ValueError(f"StreamPool.close: nothing was pushed to slot {b}")
+        T, D, st, n = self.T, self.D, self.stride, self.n_pre
+        n_win = num_windows(self.pushed[b] / self.audio_sr, T, n, self.args.motion_resampling_framerate)
+        k = n_win - self.next_window[b]
+        if k not in (0, 1):                                         # windows run as soon as they are complete: at most the padded last one is left
+            raise RuntimeError(f"StreamPool.close: slot {b}: {self.next_window[b]} windows ran, the reference counts {n_win} for {self.pushed[b]} samples")
+        if k:
+            self._round([int(r == b) for r in range(self.B)])
+            self._closing_window[b] = True                          # (a close that raises after this point and is called again must not skip its frames)
+        skip = 0 if self._closing_window[b] else st
+        fin = torch.zeros(1, T + 2 * n, D, device=self.dev)
+        ops.copy2d(self.dec.out[b:b + 1].view(1, T * D), fin.view(1, (T + 2 * n) * D)[:, :T * D])
+        length, fade_start, tab = T, None, None
+        if fade_out:                                                # (GestureStream.close: the fade-out starts inside the last window)
+            start = _fade_start_frame(n_win * st + n, end_padding_samples(self.args, self.pushed[b], self.audio_sr), self.args, self.audio_sr)
+            rel = start - (n_win - 1) * st
+            assert 0 <= rel <= T and (k > 0 or self._closing_window[b] or rel == T)
+            length = max(T, rel + 2 * n)
+            fade_start = torch.tensor([rel], dtype=torch.int32, device=self.dev)
+            if 1 <= n <= 8:                                         # (outside: the library refuses the call and names its envelope)
+                t = projection_tables(n)
+                tab = torch.from_numpy(np.concatenate([t["smooth"].ravel(), t["fade"].ravel()])).to(self.dev)
+        jt = None
+        if joints:
+            jt = torch.zeros(1, T + 2 * n, 10, 3, dtype=torch.float64, device=self.dev)
+        if fade_out or joints:
+            ops.utterance_finish(fin, self._ones[:1], 1, T, n, proj=tab, fade_start=fade_start, mean=self._mean_dev() if joints else None, joints=jt)
+        res = GestureStream._result(fin[0, skip:length], None if jt is None else jt[0, skip:length], numpy)
+        self.open_slots[b] = False                                  # only now: a close that raised can be called again
+        self.pushed[b] = self.next_window[b] = 0                    # (a free row has no windows to run)
         return res

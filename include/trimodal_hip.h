@@ -714,6 +714,29 @@ int tg_stream_push(const float* chunk, int64_t chunk_stride, int32_t n, const in
 int tg_stream_stage(const float* ring, const int64_t* written, const int32_t* word_ring, const int64_t* n_words, const int32_t* win, int32_t B,
                     int32_t R, int32_t S, int32_t A, int32_t W, int32_t T, float* out_audio, int64_t* out_text, void* stream);
 
+/* Stream pool (csrc/stream_pool.hip; synthesize.StreamPool): the B <= 4 rows of a stream state are independent sessions.  Each row has its own
+ * window counter, win [B] int32, and a launch touches only the rows it is told to: a row that is skipped keeps every bit of its rings, its
+ * counters and its output rows.  One workgroup (or grid column) per row, no atomics, nothing waits on another workgroup.
+ * tg_pool_push is tg_stream_push with one chunk length per row, n0 .. n3 by value (n[b] >= 0, 0 for b >= B): row b appends chunk[b][0 .. n[b])
+ * and its records; a row with n[b] == 0 and recs[b][0] == 0 is skipped.  words_live + m_max is the slot count of the fullest word ring after
+ * the push, counted from the oldest record a window of that row still needs.  Envelope: 1 <= B <= 4, some n[b] >= 1 or m_max >= 1,
+ * A + max n <= R <= 2^30, A < R, 1 <= W <= 1024, words_live + m_max <= W, chunk_stride >= max n, rec_stride >= 1 + 3 m_max. */
+int tg_pool_push(const float* chunk, int64_t chunk_stride, int32_t n0, int32_t n1, int32_t n2, int32_t n3, const int32_t* recs, int32_t rec_stride,
+                 int32_t m_max, int32_t words_live, float* ring, int64_t* written, int32_t* word_ring, int64_t* n_words, int32_t B, int32_t R,
+                 int32_t A, int32_t W, void* stream);
+/* tg_stream_stage per row: row b with active[b] != 0 (int32 [B], device memory) gets the inputs of ITS window win[b]; the out_audio /
+ * out_text rows of the other rows are not written.  Envelope: tg_stream_stage's. */
+int tg_pool_stage(const float* ring, const int64_t* written, const int32_t* word_ring, const int64_t* n_words, const int32_t* win,
+                  const int32_t* active, int32_t B, int32_t R, int32_t S, int32_t A, int32_t W, int32_t T, float* out_audio, int64_t* out_text,
+                  void* stream);
+/* The tail of a window as one launch, for every row with active[b] != 0: out[b] = res[b] ([B][T][D], contiguous); if win[b] > 0 its first n_pre
+ * frames are cross-faded with tail[b] ([B][n_pre][D]) exactly as tg_window_blend does; tail[b] = out[b][T - n_pre ..]; the next window's seed --
+ * seed_layout 0: pre_seq [B][T][D + 1] as tg_make_pre_seq writes it (the n_pre frames and the constraint bit, zeros elsewhere), seed_layout 1:
+ * pre [B][n_pre][D] --; then win[b] += 1.  Inactive rows: nothing is written.  Envelope: 1 <= B <= 4, 1 <= n_pre <= 8, 1 <= D <= 64,
+ * n_pre < T <= 1024. */
+int tg_pool_handover(const float* res, float* out, float* tail, float* seed, int32_t seed_layout, int32_t* win, const int32_t* active, int32_t B,
+                     int32_t T, int32_t D, int32_t n_pre, void* stream);
+
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over
  * T-2 frames, sums[2] = sum |out - target|.  (joint_mae = sums[0]/(B*(T-n_pre)*30), accel = sums[1]/(B*(T-2)*30), l1 = sums[2]/(B*T*27).) */
