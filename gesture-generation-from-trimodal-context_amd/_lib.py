@@ -143,6 +143,7 @@ SIGNATURES = {
     "tg_utterance_finish": [P, I64, I32, I32, P, I32, I32, I32, I32, P, P, P, P, I64, P],
     "tg_stream_push": [P, I64, I32, P, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, P],
     "tg_stream_stage": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, P, P, P],
+    "tg_stream_stage_text": [P, P, P, I32, I32, I32, I64, I64, P, P, P],
     "tg_pool_push": [P, I64, I32, I32, I32, I32, P, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, P],
     "tg_pool_stage": [P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, P, P, P],
     "tg_pool_handover": [P, P, P, P, I32, P, P, I32, I32, I32, I32, P],
@@ -184,6 +185,8 @@ SIGNATURES = {
     "tg_attn_step_backward": [P, I64] + [P] * 9 + [I32, I32, I32, P],
     "tg_seq2seq_decode_supported": [I32] * 10 + [P],
     "tg_seq2seq_decode_eval": [P, P, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, F32, C.POINTER(P), P, P, P, P, P] + [I32] * 10 + [P],
+    "tg_seq2seq_encode_supported": [I32, I32, I32, I32, P],
+    "tg_seq2seq_encode_eval": [P] * 10 + [I32, I32, I32, I32, P],
     "tg_seq2seq_loss": [P, P, I32, I32, I32, F32, F32, F32, P, P, P, P],
     "tg_sumsq_accumulate": [P, I64, P, P, P],
     "tg_clip_scale": [P, F32, P, P],

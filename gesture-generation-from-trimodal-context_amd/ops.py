@@ -1060,11 +1060,17 @@ def seq2seq_decode_supported(B, Te, H, n_layers, n_frames, n_pre, Pd, Po, Z=0, S
     return bool(out.value)
 
 
-def seq2seq_decode_lengths(te_len, B, Te, device):
+def seq2seq_decode_lengths(te_len, B, Te, device, device_as_is=False):
     """Device int64 [B] of per-row encoder lengths, or None.  Validated on the host (ValueError), as gru_seq_lengths validates a list; a
-    device tensor is read back for that (synthesis builds its lengths on the host, so the usual caller passes a list)."""
+    device tensor is read back for that (synthesis builds its lengths on the host, so the usual caller passes a list) -- unless
+    device_as_is: a contiguous device int64 tensor of B entries is then handed on unread (a window captured into a graph: its producer,
+    tg_stream_stage_text, writes entries in [2, Te], and the kernel clamps to [1, Te])."""
     if te_len is None:
         return None
+    if device_as_is:
+        if not (isinstance(te_len, torch.Tensor) and te_len.is_cuda and te_len.dtype == torch.int64 and te_len.is_contiguous() and te_len.numel() == B):
+            raise ValueError(f"seq2seq_decode: device_as_is takes a contiguous device int64 tensor of {B} entries")
+        return te_len
     vals = [int(v) for v in (te_len.tolist() if isinstance(te_len, torch.Tensor) else te_len)]
     if len(vals) != B:
         raise ValueError(f"seq2seq_decode: {len(vals)} encoder lengths for a batch of {B} rows")
@@ -1077,10 +1083,10 @@ def seq2seq_decode_lengths(te_len, B, Te, device):
 
 
 def seq2seq_decode_eval(enc, keys, h0, poses, n_frames, n_pre, w_attn, v, w_pre, b_pre, bn_gamma, bn_beta, bn_mean, bn_var, bn_eps, gru_params,
-                        w_out, b_out, outputs, h_n, attn_w=None, te_len=None, z=None, spk=None):
+                        w_out, b_out, outputs, h_n, attn_w=None, te_len=None, z=None, spk=None, te_len_as_is=False):
     """The eval-mode decoder loop of Seq2SeqNet.forward in one launch (one workgroup per batch row).  enc, keys [B, Te, H]; h0 [n_layers, B, H];
     poses [B, >= max(n_pre, 1), Pd]; gru_params: per layer (w_ih, w_hh, b_ih, b_hh); te_len: None (softmax over all Te positions) or one
-    length per row (list / tensor, validated here); z [B, Z], spk [B, S8] or None.  Writes outputs [B, n_frames, Po], h_n [n_layers, B, H]
+    length per row (list / tensor, validated here; te_len_as_is: a device int64 tensor handed on unread); z [B, Z], spk [B, S8] or None.  Writes outputs [B, n_frames, Po], h_n [n_layers, B, H]
     and, when given, attn_w [n_frames - 1, B, Te] (zeros at positions >= te_len[b])."""
     for t_, name in ((enc, "enc"), (keys, "keys"), (h0, "h0"), (poses, "poses"), (w_attn, "w_attn"), (v, "v"), (w_pre, "w_pre"), (b_pre, "b_pre"),
                      (bn_gamma, "bn_gamma"), (bn_beta, "bn_beta"), (bn_mean, "bn_mean"), (bn_var, "bn_var"), (w_out, "w_out"), (b_out, "b_out"),
@@ -1116,11 +1122,51 @@ def seq2seq_decode_eval(enc, keys, h0, poses, n_frames, n_pre, w_attn, v, w_pre,
         table[4 * l:4 * l + 4] = [w_ih.data_ptr(), w_hh.data_ptr(), b_ih.data_ptr(), b_hh.data_ptr()]
     if attn_w is not None and tuple(_flat(attn_w, "attn_w").shape) != (n_frames - 1, B, Te):
         raise ValueError(f"seq2seq_decode_eval: attn_w must be {[n_frames - 1, B, Te]}")
-    ldev = seq2seq_decode_lengths(te_len, B, Te, enc.device)
+    ldev = seq2seq_decode_lengths(te_len, B, Te, enc.device, te_len_as_is)
     call("tg_seq2seq_decode_eval", _p(enc), _p(keys), _p(ldev), _p(h0), _p(poses), int(poses.shape[1]), _p(z), _p(spk), _p(w_attn), _p(v),
          _p(w_pre), _p(b_pre), _p(bn_gamma), _p(bn_beta), _p(bn_mean), _p(bn_var), float(bn_eps), table, _p(w_out), _p(b_out), _p(outputs),
          _p(h_n), _p(attn_w), B, Te, H, nl, n_frames, n_pre, Pd, Po, Z, S8, _stream())
     return outputs, h_n, attn_w
+
+
+# ------------------------------------------------------------------------------------------------- Seq2Seq eval encoder recurrence (csrc/seq2seq_encode.hip)
+SEQ2SEQ_ENCODE_ENVELOPE = "D in {1, 2}, B >= 1, 1 <= T <= 128, H % 4 == 0, 8 <= H <= 320"
+
+
+def seq2seq_encode_supported(B, T, H, D):
+    """True when tg_seq2seq_encode_eval takes the shape (SEQ2SEQ_ENCODE_ENVELOPE)."""
+    if min(int(B), int(T), int(H), int(D)) < 1:
+        return False
+    out = C.c_int32(0)
+    call("tg_seq2seq_encode_supported", int(B), int(T), int(H), int(D), C.cast(C.byref(out), C.c_void_p))
+    return bool(out.value)
+
+
+def seq2seq_encode_eval(gi, w_hh, b_hh, y, h_n, lengths=None, h0=None, flag=None):
+    """gru_seq_forward without a tape as ONE launch, one workgroup per (row, direction).  gi [D, B, T, 3H]; w_hh / b_hh: one tensor per
+    direction; y [B, T, D*H] (every element is written: exact zeros at t >= length); h_n [D, B, H]; lengths: a list / CPU tensor (validated
+    here) or a device int64 tensor, used as it is (the kernel skips a row whose entry is outside [1, T] and sets the flag word); h0
+    [D, B, H] or None.  Returns the flag word (ops.gru_seq_check), None for host lengths."""
+    _flat(gi, "gi")
+    if gi.dim() != 4 or gi.shape[3] % 3:
+        raise ValueError(f"seq2seq_encode_eval: gi must be [D, B, T, 3H], got {list(gi.shape)}")
+    D, B, T, H3 = gi.shape
+    H = H3 // 3
+    if not seq2seq_encode_supported(B, T, H, D):
+        raise ValueError(f"seq2seq_encode_eval: (B, T, H, D) = {(B, T, H, D)} is outside the kernel envelope {SEQ2SEQ_ENCODE_ENVELOPE}")
+    if len(w_hh) != D or len(b_hh) != D:
+        raise ValueError(f"seq2seq_encode_eval: {len(w_hh)} / {len(b_hh)} recurrent weights / biases for {D} direction(s)")
+    for w, b in zip(w_hh, b_hh):
+        if tuple(_flat(w, "w_hh").shape) != (3 * H, H) or _flat(b, "b_hh").numel() != 3 * H:
+            raise ValueError(f"seq2seq_encode_eval: w_hh must be {[3 * H, H]} and b_hh {[3 * H]}, got {list(w.shape)} / {list(b.shape)}")
+    if tuple(_flat(y, "y").shape) != (B, T, D * H) or tuple(_flat(h_n, "h_n").shape) != (D, B, H):
+        raise ValueError(f"seq2seq_encode_eval: y must be {[B, T, D * H]} and h_n {[D, B, H]}, got {list(y.shape)} / {list(h_n.shape)}")
+    if h0 is not None and tuple(_flat(h0, "h0").shape) != (D, B, H):
+        raise ValueError(f"seq2seq_encode_eval: h0 must be {[D, B, H]}, got {list(h0.shape)}")
+    ldev, flag = gru_seq_lengths(lengths, B, T, gi.device, flag)
+    call("tg_seq2seq_encode_eval", _p(gi), _p(w_hh[0]), _p(w_hh[-1]), _p(b_hh[0]), _p(b_hh[-1]), _p(h0), _p(ldev), _p(y), _p(h_n), _p(flag),
+         B, T, H, D, _stream())
+    return flag
 
 
 # ------------------------------------------------------------------------------------------------- Seq2Seq loss and gradient clip (csrc/losses.hip)
@@ -1957,6 +2003,19 @@ def stream_stage(st, text_out=None, audio_out=None):
             raise ValueError(f"text_out is {tuple(text_out.shape)}, a window's text is {(st['B'], st['T'])}, contiguous")
     call("tg_stream_stage", _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(st["win"]), st["B"], st["R"], st["S"], st["A"],
          st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
+
+
+def stream_stage_text(st, sos, eos, text_out, len_out):
+    """The Seq2Seq model's text of the window whose index is st['win'][0] (csrc/stream_seq.hip): text_out (B, Te) int64 = [sos, the ids of every
+    record of that window in push order, eos, 0 ...], len_out (B,) int64 = count + 2.  Device buffers written in place; the host refuses
+    a window with more than Te - 2 records before it is pushed (the kernel clamps)."""
+    _stream_check(st)
+    _i64(text_out, "text_out")
+    if text_out.dim() != 2 or text_out.shape[0] != st["B"] or not text_out.is_contiguous():
+        raise ValueError(f"text_out is {tuple(text_out.shape)}, expected ({st['B']}, Te), contiguous")
+    _dev_int(len_out, torch.int64, st["B"], "len_out")
+    call("tg_stream_stage_text", _p(st["words"]), _p(st["n_words"]), _p(st["win"]), st["B"], st["W"], int(text_out.shape[1]), int(sos), int(eos),
+         _p(text_out), _p(len_out), _stream())
 
 
 # ------------------------------------------------------------------------------------------------- stream pool (csrc/stream_pool.hip)

@@ -60,6 +60,37 @@ class GRU(nn.Module):
         # opt-in: eval-mode forwards of at most four rows without a tape, lengths or hx run each layer's recurrence as ONE launch of the
         # few-row kernel (csrc/gru_vec.hip) instead of one launch per time step.  Off by default: every existing call keeps its kernel
         self.few_row_eval = False
+        # opt-in: eval-mode forwards without a tape run each layer's recurrence as ONE launch of the row-local kernel (csrc/seq2seq_encode.hip:
+        # a workgroup per (row, direction), per-row lengths and hx included) where the shape is inside its envelope.  Off by default
+        self.row_local_eval = False
+
+    def _row_local_takes(self, B, T, save):
+        return self.row_local_eval and not self.training and not save and \
+            ops.seq2seq_encode_supported(B, T, self.hidden_size, 2 if self.bidirectional else 1)
+
+    def _row_local_forward(self, x, lengths, hx):
+        """The stack in eval mode without a tape: per layer one grouped input projection (the GEMM entry of the per-step path) and one launch
+        of the row-local recurrence.  lengths: None, a list / CPU tensor (validated and uploaded once) or a device int64 tensor, used as it
+        is -- nothing is read back; the flag word the kernel sets for an entry outside [1, T] is kept in self._row_local_flag
+        (ops.gru_seq_check)."""
+        D, H = (2 if self.bidirectional else 1), self.hidden_size
+        B, T, _ = x.shape
+        sfxs = ("", "_reverse")[:D]
+        ldev, flag = ops.gru_seq_lengths(lengths, B, T, x.device)
+        self._row_local_flag = flag
+        h_n = L.empty(self.num_layers * D, B, H, like=x)
+        cur = x
+        for l in range(self.num_layers):
+            gi = L.empty(D, B, T, 3 * H, like=x)
+            a_win = ops.Win.plain(cur.view(B * T, cur.shape[2]))
+            ops.gemm_nt_group([dict(A=a_win, W=getattr(self, f"weight_ih_l{l}{s}"), bias=getattr(self, f"bias_ih_l{l}{s}"),
+                                    out=gi[d].view(B * T, 3 * H)) for d, s in enumerate(sfxs)])
+            y = L.empty(B, T, D * H, like=x)
+            ops.seq2seq_encode_eval(gi, tuple(getattr(self, f"weight_hh_l{l}{s}").detach() for s in sfxs),
+                                    tuple(getattr(self, f"bias_hh_l{l}{s}").detach() for s in sfxs), y, h_n[l * D:(l + 1) * D], lengths=ldev,
+                                    h0=None if hx is None else hx[l * D:(l + 1) * D], flag=flag)
+            cur = y
+        return cur, h_n
 
     def _few_row_takes(self, B, lengths, hx, save):
         if not self.few_row_eval or self.training or save or lengths is not None or hx is not None or B > 4:
@@ -167,6 +198,9 @@ class GRU(nn.Module):
         if self._few_row_takes(B, lengths, hx, save):
             with torch.no_grad():
                 return self._few_row_forward(x.contiguous())
+        if self._row_local_takes(B, T, save):
+            with torch.no_grad():
+                return self._row_local_forward(x.contiguous(), lengths, hx)
         cfg = (tuple(self._names), self.num_layers, H, D, lengths, self.dropout, training, rng, inject, save)
         return _GRUFn.apply(cfg, x.contiguous(), hx, *params)
 
@@ -227,11 +261,26 @@ class EncoderRNN(nn.Module):
         self.gru = GRU(embed_size, hidden_size, n_layers, dropout=dropout, bidirectional=True)
         self.do_flatten_parameters = False
 
+    @property
+    def row_local_eval(self):
+        """Opt-in (False by default: every call keeps its kernel): eval-mode forwards without a tape run each GRU layer as one GEMM entry plus
+        ONE launch of the row-local recurrence (csrc/seq2seq_encode.hip) instead of one launch per time step, where the shape is inside
+        ops.SEQ2SEQ_ENCODE_ENVELOPE.  With it, input_lengths may be a device int64 tensor: it is used as it is, nothing is read back, and
+        the outputs keep all T steps of input_seqs (exact zeros behind every row's length)."""
+        return self.gru.row_local_eval
+
+    @row_local_eval.setter
+    def row_local_eval(self, on):
+        self.gru.row_local_eval = bool(on)
+
     def forward(self, input_seqs, input_lengths, hidden=None):
         if not (input_seqs.is_cuda and input_seqs.dtype == torch.int64 and input_seqs.dim() == 2):
             raise TypeError("EncoderRNN: input_seqs must be a CUDA int64 tensor of shape (T, B)")
-        lens = [int(v) for v in (input_lengths.tolist() if isinstance(input_lengths, torch.Tensor) else input_lengths)]
-        T = max(lens) if lens else 0
+        if self.row_local_eval and not self.training and isinstance(input_lengths, torch.Tensor) and input_lengths.is_cuda:
+            lens, T = input_lengths, input_seqs.shape[0]                  # no host read: the kernel checks the entries (gru._row_local_flag)
+        else:
+            lens = [int(v) for v in (input_lengths.tolist() if isinstance(input_lengths, torch.Tensor) else input_lengths)]
+            T = max(lens) if lens else 0
         if not 1 <= T <= input_seqs.shape[0]:
             raise ValueError(f"EncoderRNN: lengths up to {T} for {input_seqs.shape[0]} steps")
         idx = input_seqs[:T].t().contiguous()                            # (B, T): the kernels are batch-first

@@ -281,6 +281,29 @@ class BahdanauAttnDecoderRNN(nn.Module):
         cfg = (self, n_frames, n_pre, training, rng, injects, save)
         return _DecodeFn.apply(cfg, enc_bt.contiguous(), h0.contiguous(), poses.contiguous(), z, spk, *params)
 
+    def decode_eval_static(self, enc_bt, h0, poses, n_frames, n_pre, te_len, outputs):
+        """The eval-mode loop of decode() for a window on static buffers (synthesize.Seq2SeqWindowDecoder): te_len is a device int64 (B,)
+        tensor handed to the kernel unread, outputs (B, n_frames, output_size) is written in place; no speaker, no noise, no attention
+        weights.  The arithmetic is _FusedEvalDecodeFn's: the keys by the same GEMM entry, then tg_seq2seq_decode_eval.  Returns h_n."""
+        B, Te, H = enc_bt.shape
+        if self.training or self.speaker_model:
+            raise ValueError("Seq2Seq decoder: decode_eval_static runs in eval mode, without a speaker model")
+        if not ops.seq2seq_decode_supported(B, Te, H, self.n_layers, n_frames, n_pre, poses.shape[2], self.output_size, 0, 0):
+            raise ValueError(f"Seq2Seq decoder: (B, Te, H, n_layers, n_frames, n_pre, Pd, Po) = "
+                             f"{(B, Te, H, self.n_layers, n_frames, n_pre, poses.shape[2], self.output_size)} is outside the kernel envelope "
+                             f"{ops.SEQ2SEQ_DECODE_ENVELOPE}")
+        if self.pre_linear[0].in_features != poses.shape[2] + H:
+            raise ValueError("Seq2Seq decoder: pose width does not match pre_linear's input size")
+        P = dict(zip(_DEC_NAMES + tuple(self.gru._names), (p.detach() for p in self._params())))
+        wa, bn = P["attn.attn.weight"], self.pre_linear[1]
+        keys = ops.gemm_nt(Win.plain(enc_bt.view(B * Te, H)), wa[:, H:], P["attn.attn.bias"], L.empty(B * Te, H, like=enc_bt)).view(B, Te, H)
+        gru = [tuple(P[f"{k}_l{l}"] for k in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")) for l in range(self.n_layers)]
+        h_n = L.empty(self.n_layers, B, H, like=enc_bt)
+        ops.seq2seq_decode_eval(enc_bt, keys, h0, poses, n_frames, n_pre, wa, P["attn.v"], P["pre_linear.0.weight"], P["pre_linear.0.bias"],
+                                P["pre_linear.1.weight"], P["pre_linear.1.bias"], bn.running_mean, bn.running_var, bn.eps, gru, P["out.weight"],
+                                P["out.bias"], outputs, h_n, None, te_len=te_len, te_len_as_is=True)
+        return h_n
+
     def forward(self, motion_input, last_hidden, encoder_outputs, vid_indices=None):
         _need_cuda(motion_input, "BahdanauAttnDecoderRNN: motion_input")
         with torch.no_grad():

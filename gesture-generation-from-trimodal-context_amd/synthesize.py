@@ -36,6 +36,10 @@ runs as soon as its samples are there -- cut from a device-resident ring by csrc
 frames that became final come back at once; close() runs the padded last window, the fade-out and the joints.  Window i starts at sample i * S
 by definition (stream_matches_offline tells where that is also the reference's start).
 
+Seq2SeqGestureStream is GestureStream for the seq2seq model, on a Seq2SeqWindowDecoder: a window's unpadded word list and its length are compacted
+out of the word ring on the device (csrc/stream_seq.hip) into static buffers, the length stays on the device as the encoder's and the decoder's
+per-row length, so the window is one fixed chain -- captured once -- and each push smooths the windows it ran (their segments are final by then).
+
 StreamPool is GestureStream for independent sessions: the 1 to 4 rows of ONE window decoder are slots, each with its own clock (per-row window
 counters on the device), opened, pushed to (ragged chunks) and closed on their own; the windows that have become complete run together, and
 the hand-over kernel (csrc/stream_pool.hip) leaves the rows that did not run untouched.  One graph serves first and later windows.
@@ -437,6 +441,101 @@ class JointEmbedWindowDecoder:
             self.audio.copy_(in_audio, non_blocking=True)
         if draw is not None:
             self.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
+        with torch.no_grad(), self.frozen:
+            if not self.use_graph or first:
+                self._forward(first)
+            else:
+                if self.graph is None:
+                    torch.cuda.synchronize()
+                    self.graph = torch.cuda.CUDAGraph()
+                    keep = [t.clone() for t in (self.pre, self.tail, self.out)]
+                    pg_alive = torch.distributed.is_available() and torch.distributed.is_initialized()     # RCCL helper threads: see train_gan.GraphedGanStep
+                    with torch.cuda.graph(self.graph, capture_error_mode="thread_local" if pg_alive else "global"):
+                        self._forward(False)
+                    for t, k in zip((self.pre, self.tail, self.out), keep):       # capture does not execute: restore state
+                        t.copy_(k)
+                self.graph.replay()
+        return self.out
+
+
+class Seq2SeqWindowDecoder:
+    """The window decoders' counterpart for the Seq2Seq baseline (args.model == 'seq2seq', at most four utterances in lock-step): one window =
+    embedding -> per encoder layer one GEMM entry + the recurrence -> direction sum, h0 = encoder_hidden[:n_layers] -> keys GEMM -> the
+    one-launch decoder loop (csrc/seq2seq_decode.hip) -> cross-fade -> tail copy -> `pre` hand-over, on static buffers, on the current
+    stream, as one linear chain (nothing forks), so that the non-first window is captured into a hipGraph once and replayed (graph=True).
+
+    The text is static too: self.text (B, Te) int64 with Te = max_words + 2 holds [SOS, words ..., EOS, 0 ...] and self.len (B,) int64 -- on
+    the device -- the lists' lengths; self.len is both the encoder's per-row lengths and the decoder's te_len, so the chain is the same
+    launches whatever the windows' word counts are (ops.stream_stage_text writes both buffers in place).  A row's result does not depend
+    on Te: it is what Seq2SeqNet.synthesize gives for the unpadded list, bit for bit, with the same row_local_eval setting on the encoder.
+
+    row_local_encoder: the encoder's recurrence as ONE launch per layer (csrc/seq2seq_encode.hip) instead of one launch per time step and
+    layer -- Te of them, all but a row's length idle.  Default True: the measured choice at one row.
+    Host-side validation raises ValueError before anything touches the GPU."""
+
+    def __init__(self, args, net, batch, device, graph=True, max_words=32, row_local_encoder=True, audio_sr=16000):
+        if getattr(args, "model", "multimodal_context") != "seq2seq":
+            raise ValueError(f"Seq2SeqWindowDecoder: args.model is {getattr(args, 'model', 'multimodal_context')!r}, not 'seq2seq'")
+        gen = getattr(net, "decoder", None)
+        if getattr(net, "encoder", None) is None or not hasattr(getattr(gen, "decoder", None), "decode_eval_static"):
+            raise ValueError("Seq2SeqWindowDecoder: the model must be a seq2seq.Seq2SeqNet")
+        if net.training:
+            raise ValueError("Seq2SeqWindowDecoder: the model must be in eval mode (call .eval() first)")
+        if gen.decoder.speaker_model:
+            raise ValueError("Seq2SeqWindowDecoder: synthesis runs without a speaker model (scripts/synthesize.py:134-136 passes none)")
+        T, n_pre = args.n_poses, args.n_pre_poses
+        if (T, n_pre) != (net.n_frames, net.n_pre_poses):
+            raise ValueError(f"Seq2SeqWindowDecoder: args (n_poses, n_pre_poses) = {(T, n_pre)} but the model decodes {(net.n_frames, net.n_pre_poses)}")
+        if not 1 <= n_pre < T:
+            raise ValueError(f"Seq2SeqWindowDecoder: 1 <= n_pre_poses < n_poses, got {(n_pre, T)}")
+        if not 1 <= batch <= 4:
+            raise ValueError(f"Seq2SeqWindowDecoder: 1 to 4 utterances in lock-step (the rows of a stream), got {batch}")
+        if not 0 <= max_words <= 126:
+            raise ValueError(f"Seq2SeqWindowDecoder: 0 <= max_words <= 126 (the kernels take lists of at most 128 entries), got {max_words}")
+        self.args, self.net, self.B, self.dev = args, net, batch, device
+        self.T, self.n_pre, self.D = T, n_pre, gen.output_size
+        self.max_words, self.Te, self.row_local = int(max_words), int(max_words) + 2, bool(row_local_encoder)
+        self.audio_len = int(T / args.motion_resampling_framerate * audio_sr)      # (the stream's window; the model never sees the samples)
+        self.draw = None                                                           # (no random draw in this model)
+        self.text = torch.zeros(batch, self.Te, dtype=torch.int64, device=device)
+        self.len = torch.full((batch,), 2, dtype=torch.int64, device=device)
+        self.pre = torch.zeros(batch, n_pre, self.D, device=device)
+        self.tail = torch.zeros(batch, n_pre, self.D, device=device)
+        self.out = torch.zeros(batch, T, self.D, device=device)
+        self.use_graph, self.graph = graph, None
+        # as WindowDecoder: weight-only operands are formed by the first window and kept -- a decoder must not outlive a change of the parameters
+        self.frozen = L.FrozenWeights()
+
+    def seed(self, seed_seq=None):
+        """`pre` of the first window: zeros, or the seed poses (B, >= n_pre, D) (synthesize.py:46-50)."""
+        self.pre.zero_()
+        if seed_seq is not None:
+            self.pre.copy_(torch.as_tensor(seed_seq, dtype=torch.float32, device=self.dev)[..., :self.n_pre, :])
+
+    def _forward(self, first):
+        from .rnn import _EmbedFn, _SumHalvesFn
+        enc, dec = self.net.encoder, self.net.decoder.decoder
+        was = enc.gru.row_local_eval
+        enc.gru.row_local_eval = self.row_local
+        try:
+            embedded = _EmbedFn.apply(enc.embedding.weight.detach(), self.text)          # EncoderRNN.forward's chain at T = Te, lengths unread
+            y, hidden = enc.gru.run_batch_first(embedded, self.len, None)
+        finally:
+            enc.gru.row_local_eval = was
+        enc_bt = _SumHalvesFn.apply(y)                                               # (B, Te, H): exact zeros behind every row's length
+        dec.decode_eval_static(enc_bt, hidden[:dec.n_layers], self.pre, self.T, self.n_pre, self.len, self.out)
+        if not first:                                            # cross-fade with the previous window's last frames (:145-153)
+            ops.window_blend(self.tail, self.out)
+        self.tail.copy_(self.out[:, self.T - self.n_pre:, :])    # strided device copy: kept for the next cross-fade ...
+        self.pre.copy_(self.tail)                                # ... and seeds the next window (:122-126)
+
+    def window(self, in_text=None, in_len=None, first=False):
+        """One window for the whole batch.  in_text (B, Te) / in_len (B,) int64, CPU or GPU tensors, or None: self.text / self.len were
+        filled in place (ops.stream_stage_text); returns the (B, T, D) output buffer (device, overwritten by the next call)."""
+        if in_text is not None:
+            self.text.copy_(in_text, non_blocking=True)
+        if in_len is not None:
+            self.len.copy_(in_len, non_blocking=True)
         with torch.no_grad(), self.frozen:
             if not self.use_graph or first:
                 self._forward(first)
@@ -937,8 +1036,12 @@ class GestureStream:
     when w * S + A samples are there, A = int(unit * sr), while its end time is the up to one sample later w * stride + unit; a word that starts
     in that last fraction of a sample belongs to window w for the reference, but its chunk begins after w ran.)
 
-    seq2seq and speech2gesture are refused: seq2seq's smoothing rewrites frames of a window after the next window has run, and the log-mel
-    spectrogram is padded over the whole utterance.  max_chunk: the largest push, in samples; the ring holds A + max_chunk samples per row.
+    seq2seq and speech2gesture are refused here.  seq2seq streams on a class of its own, Seq2SeqGestureStream: scripts/synthesize.py applies that
+    model's smoothing after all windows are stacked, so in ITS order frames of a window are rewritten after the next window has run -- but window
+    i's segment [i stride, i stride + 3 n_pre) lies inside the window's own first `stride` frames (3 n_pre <= stride), its values before the fit
+    are final once window i has run (the cross-fade needs window i - 1's raw tail and window i's raw head), the next window's seed and
+    cross-fade take raw decoder output, and the segments are disjoint: smoothing a window when it runs gives the same bits.  speech2gesture
+    cannot stream: power_to_db(ref=np.max) takes the maximum over the whole utterance's spectrogram, so no prefix of it is final.  max_chunk: the largest push, in samples; the ring holds A + max_chunk samples per row.
     _draws / eps_list (parity tests): per window the (B, 16) / (B, 32) draws to replay; window_decoder: a kept decoder of the model's kind
     (its window graph is captured once and replayed by every stream that uses it; the constructor re-seeds it and the stream writes its
     static buffers, so a kept decoder serves ONE stream at a time -- start the next stream on it after the previous one was closed).
@@ -948,7 +1051,8 @@ class GestureStream:
                  window_decoder=None, graph=True, word_ring=256, ring=None):
         model = getattr(args, "model", "multimodal_context")
         if model == "seq2seq":
-            raise ValueError("GestureStream: the seq2seq model cannot stream: its smoothing rewrites frames of a window after the next window has run")
+            raise ValueError("GestureStream: the seq2seq model cannot stream: its smoothing rewrites frames of a window after the next window has run"
+                             " -- in the offline order only: synthesize.Seq2SeqGestureStream smooths every window as it runs")
         if model == "speech2gesture":
             raise ValueError("GestureStream: the speech2gesture model cannot stream: its log-mel spectrogram is padded over the whole utterance")
         if model not in ("multimodal_context", "joint_embedding"):
@@ -1141,6 +1245,157 @@ class GestureStream:
             ops.utterance_finish(fin, self._ones, 1, T, n, proj=tab, fade_start=fade_start, mean=self._mean if joints else None, joints=jt)
         frames, jrows = fin[:, skip:length], None if jt is None else jt[:, skip:length]
         res = self._result(frames, jrows, numpy)
+        self.closed = True                                          # only now: a close that raised can be called again
+        return res
+
+
+class Seq2SeqGestureStream(GestureStream):
+    """GestureStream for the Seq2Seq baseline (args.model == 'seq2seq') on a Seq2SeqWindowDecoder: the same interface (push, close, 1 to 4 rows
+    on one clock, late_words, window_decoder= reuse, no device read in push) and the same host bookkeeping.  The audio chunks drive the clock
+    exactly as there -- window w is complete at w * S + A samples; the model ignores the samples, the ring is kept so that the stream state and
+    tg_stream_push are reused unchanged.  Window w: ops.stream_stage_text writes its word list [SOS, every word of the window in push order,
+    EOS] and the list's length straight into the decoder's static buffers, the decoder runs, and after the k windows of a push the smoothing of
+    ops.utterance_finish runs with n_win = k on the push's stacked buffer, whose first k * stride frames are returned: window i's smoothing
+    segment [i stride, i stride + 3 n_pre) lies in the window's own first `stride` frames and depends on nothing a later window computes
+    (GestureStream's docstring has the argument), so there is no extra lag.  close() runs the padded last window if it has not run and applies
+    smoothing, then fade-out, on the one-window buffer in the offline finish's order; a last window a push already emitted leaves only its
+    final n_pre frames (plus the fade-out's growth), which smoothing does not touch.
+
+    Everything push() and close() returned, concatenated, equals generate_gestures_batch(args, ..., on_device=True, fade_out=...) for the
+    finished utterance bit for bit wherever stream_matches_offline(args, n) holds, with the encoder's row_local_eval set to the decoder's
+    row_local_encoder.  Words follow GestureStream's timing rule.  max_words: the most words one window of one row may hold (the text
+    buffer has max_words + 2 entries); a push that would give a window more is refused and leaves the stream as it was.
+    Refused at construction: 3 n_pre > stride, n_pre outside 1 .. 8, batch outside 1 .. 4, another model, a window_decoder built for something else."""
+
+    def __init__(self, args, pose_decoder, lang_model, batch=1, seed_seqs=None, audio_sr=16000, max_chunk=16000, window_decoder=None, graph=True,
+                 word_ring=256, ring=None, max_words=32, row_local_encoder=True):
+        model = getattr(args, "model", "multimodal_context")
+        if model != "seq2seq":
+            raise ValueError(f"Seq2SeqGestureStream: args.model is {model!r}, not 'seq2seq' (GestureStream streams multimodal_context and joint_embedding)")
+        self.T, self.n_pre = args.n_poses, args.n_pre_poses
+        self.stride = self.T - self.n_pre
+        if not 1 <= self.n_pre <= 8:
+            raise ValueError(f"Seq2SeqGestureStream: 1 <= n_pre_poses <= 8 (the smoothing kernel's tables), got {self.n_pre}")
+        if 3 * self.n_pre > self.stride:
+            raise ValueError(f"Seq2SeqGestureStream: a window's smoothing segment of 3 n_pre = {3 * self.n_pre} frames must lie inside its first "
+                             f"n_poses - n_pre_poses = {self.stride} frames, else it would rewrite frames the next window has handed out")
+        if not 1 <= batch <= 4:
+            raise ValueError(f"Seq2SeqGestureStream: 1 to 4 rows, got {batch}")
+        if max_chunk < 1:
+            raise ValueError(f"Seq2SeqGestureStream: max_chunk = {max_chunk}")
+        self.args, self.model, self.lang, self.B, self.audio_sr, self.max_chunk = args, model, lang_model, batch, audio_sr, int(max_chunk)
+        self.S, self.A = stream_geometry(args, audio_sr)
+        dev = self.dev = next(pose_decoder.parameters()).device
+        if window_decoder is not None:
+            d = window_decoder
+            if not isinstance(d, Seq2SeqWindowDecoder) or d.net is not pose_decoder or d.B != batch or (d.T, d.n_pre) != (self.T, self.n_pre) \
+                    or d.max_words != max_words or d.row_local != bool(row_local_encoder):
+                raise ValueError(f"Seq2SeqGestureStream: window_decoder must be a Seq2SeqWindowDecoder built for this model, {batch} row(s), (n_poses, "
+                                 f"n_pre_poses) = {(self.T, self.n_pre)}, max_words = {max_words} and row_local_encoder = {bool(row_local_encoder)}")
+            self.dec = d
+        else:
+            self.dec = Seq2SeqWindowDecoder(args, pose_decoder, batch, dev, graph=graph, max_words=max_words, row_local_encoder=row_local_encoder,
+                                            audio_sr=audio_sr)
+        if self.dec.audio_len != self.A:
+            raise ValueError(f"Seq2SeqGestureStream: the window decoder counts {self.dec.audio_len} samples, the stream's window is {self.A} (audio_sr = {audio_sr})")
+        self.D, self.draws, self.vid, self.max_words = self.dec.D, None, None, self.dec.max_words
+        self.dec.seed(None if seed_seqs is None else np.stack([np.asarray(s)[:self.n_pre] for s in seed_seqs]))
+        R = self.A + self.max_chunk if ring is None else int(ring)
+        if R < self.A + self.max_chunk:
+            raise ValueError(f"Seq2SeqGestureStream: a ring of {R} samples; window + max_chunk = {self.A + self.max_chunk} are needed")
+        self.state = ops.stream_state(batch, R, self.S, self.A, word_ring, self.T, dev)
+        self.chunk_buf = torch.zeros(batch, self.max_chunk, device=dev)
+        self.pushed = self.next_window = self.late_words = 0
+        self.closed = False
+        self._live = [[] for _ in range(batch)]
+        self._n_rec = [0] * batch
+        self._win_words = [{} for _ in range(batch)]     # per row: window -> words pushed for it so far (windows that have not run)
+        self._ones = torch.ones(batch, dtype=torch.int32, device=dev)
+        self._k_dev = {1: self._ones}                    # (B,) int32 window counts of a push's buffer, by k
+        t = projection_tables(self.n_pre)
+        self._tables = torch.from_numpy(np.concatenate([t["smooth"].ravel(), t["fade"].ravel()])).to(dev)
+        self._sos, self._eos = int(lang_model.SOS_token), int(lang_model.EOS_token)
+        self._mean, self._closing_window = None, False
+
+    # -------------------------------------------------------------------------------------------------------------- host bookkeeping (integers)
+    def _records(self, words):
+        """GestureStream._records behind one more refusal: no window of a row may hold more than max_words words."""
+        add = None
+        if words is not None and len(words) == self.B:
+            add = []
+            for b, wl in enumerate(words):
+                cnt = {}
+                for w in wl or ():
+                    for r in word_records(self.args, self.lang, [w]):
+                        if r[0] >= self.next_window:
+                            cnt[r[0]] = cnt.get(r[0], 0) + 1
+                for win, c in cnt.items():
+                    if self._win_words[b].get(win, 0) + c > self.max_words:
+                        raise ValueError(f"Seq2SeqGestureStream.push: row {b}: window {win} would hold {self._win_words[b].get(win, 0) + c} words, "
+                                         f"max_words is {self.max_words}")
+                add.append(cnt)
+        res = super()._records(words)                                # (may refuse too; nothing has changed yet)
+        for b, cnt in enumerate(add or ()):
+            for win, c in cnt.items():
+                self._win_words[b][win] = self._win_words[b].get(win, 0) + c
+        return res
+
+    def _run(self, k, smooth=True):
+        """The next k windows, stacked as the offline loop stacks them, (B, k * stride + n_pre, D), and -- smooth -- smoothed as its finish
+        smooths them: the k segments lie inside the buffer and are final."""
+        B, T, D, st = self.B, self.T, self.D, self.stride
+        F = k * st + self.n_pre
+        buf = torch.empty(B, F, D, device=self.dev)                 # (the windows tile it)
+        for j in range(k):
+            i = self.next_window
+            ops.stream_stage_text(self.state, self._sos, self._eos, self.dec.text, self.dec.len)     # straight into the decoder's static buffers
+            out = self.dec.window(first=(i == 0))
+            ops.copy2d(out.view(B, T * D), buf.view(B, F * D)[:, j * st * D:(j * st + T) * D])
+            ops.counter_inc(self.state["win"])
+            self.next_window += 1
+        self._live = [[r for r in l if r[1] >= self.next_window] for l in self._live]
+        self._win_words = [{w: c for w, c in d.items() if w >= self.next_window} for d in self._win_words]
+        if smooth:
+            if k not in self._k_dev:
+                self._k_dev[k] = torch.full((B,), k, dtype=torch.int32, device=self.dev)
+            ops.utterance_finish(buf, self._k_dev[k], k, T, self.n_pre, smooth=True, proj=self._tables)
+        return buf
+
+    # -------------------------------------------------------------------------------------------------------------- the interface
+    def close(self, fade_out=False, joints=False, numpy=False):
+        """GestureStream.close for this model: the padded last window if it has not run, then smoothing and fade-out in the offline finish's
+        order on the one-window buffer (a last window that a push emitted was smoothed there: its remaining n_pre frames are not in a segment)."""
+        if self.closed:
+            raise ValueError("Seq2SeqGestureStream.close: the stream is closed")
+        if self.pushed == 0:
+            raise ValueError("Seq2SeqGestureStream.close: nothing was pushed")
+        B, T, D, st, n = self.B, self.T, self.D, self.stride, self.n_pre
+        n_win = num_windows(self.pushed / self.audio_sr, T, n, self.args.motion_resampling_framerate)
+        k = n_win - self.next_window
+        if k not in (0, 1):                                         # windows run as soon as they are complete: at most the padded last one is left
+            raise RuntimeError(f"Seq2SeqGestureStream.close: {self.next_window} windows ran, the reference counts {n_win} for {self.pushed} samples")
+        if k:
+            self._run(1, smooth=False)                              # (dec.out keeps the raw window: a close that raises and is repeated smooths a fresh copy)
+            self._closing_window = True
+        skip = 0 if self._closing_window else st
+        fin = torch.zeros(B, T + 2 * n, D, device=self.dev)
+        ops.copy2d(self.dec.out.view(B, T * D), fin.view(B, (T + 2 * n) * D)[:, :T * D])
+        length, fade_start = T, None
+        if fade_out:                                                # (GestureStream.close: the fade-out starts inside the last window)
+            start = _fade_start_frame(n_win * st + n, end_padding_samples(self.args, self.pushed, self.audio_sr), self.args, self.audio_sr)
+            rel = start - (n_win - 1) * st
+            assert 0 <= rel <= T and (self._closing_window or rel == T)
+            length = max(T, rel + 2 * n)
+            fade_start = torch.tensor([rel] * B, dtype=torch.int32, device=self.dev)
+        jt = None
+        if joints:
+            if self._mean is None:
+                self._mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
+            jt = torch.zeros(B, T + 2 * n, 10, 3, dtype=torch.float64, device=self.dev)
+        if self._closing_window or fade_out or joints:
+            ops.utterance_finish(fin, self._ones, 1, T, n, smooth=self._closing_window, proj=self._tables, fade_start=fade_start,
+                                 mean=self._mean if joints else None, joints=jt)
+        res = self._result(fin[:, skip:length], None if jt is None else jt[:, skip:length], numpy)
         self.closed = True                                          # only now: a close that raised can be called again
         return res
 

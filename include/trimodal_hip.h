@@ -713,6 +713,13 @@ int tg_stream_push(const float* chunk, int64_t chunk_stride, int32_t n, const in
  * 1 <= W <= 1024, 1 <= T <= 1024. */
 int tg_stream_stage(const float* ring, const int64_t* written, const int32_t* word_ring, const int64_t* n_words, const int32_t* win, int32_t B,
                     int32_t R, int32_t S, int32_t A, int32_t W, int32_t T, float* out_audio, int64_t* out_text, void* stream);
+/* The Seq2Seq model's text of window w = win[0] (csrc/stream_seq.hip; synthesize.Seq2SeqGestureStream) from the same word ring:
+ * out_text [B][Te] int64 = [sos, the ids of EVERY record of window w in push order, eos, 0 ...], out_len [B] int64 = count + 2.  One workgroup
+ * per row, an order-preserving compaction without atomics; ids are copied bit for bit.  A row with more than Te - 2 records of the window is
+ * the host's to refuse before the push; the kernel clamps the count so that no index leaves the row.  Envelope: 1 <= B <= 4,
+ * 1 <= W <= 1024, 2 <= Te <= 128. */
+int tg_stream_stage_text(const int32_t* word_ring, const int64_t* n_words, const int32_t* win, int32_t B, int32_t W, int32_t Te, int64_t sos,
+                         int64_t eos, int64_t* out_text, int64_t* out_len, void* stream);
 
 /* Stream pool (csrc/stream_pool.hip; synthesize.StreamPool): the B <= 4 rows of a stream state are independent sessions.  Each row has its own
  * window counter, win [B] int32, and a launch touches only the rows it is told to: a row that is skipped keeps every bit of its rings, its
@@ -1016,6 +1023,21 @@ int tg_seq2seq_decode_eval(const float* enc, const float* keys, const void* te_l
                            const void* const* gru_params, const float* w_out, const float* b_out, float* outputs, float* h_n, float* attn_w,
                            int32_t B, int32_t Te, int32_t H, int32_t n_layers, int32_t n_frames, int32_t n_pre, int32_t Pd, int32_t Po, int32_t Z,
                            int32_t S8, void* stream);
+
+/* ---- Eval-mode recurrence of one GRU layer with per-row lengths in ONE launch (csrc/seq2seq_encode.hip; the Seq2Seq text encoder,
+ * model/seq2seq_net.py:14-56): the contract of tg_gru_seq_forward without a tape, one workgroup per (batch row, direction), the state in LDS,
+ * W_hh read from L2 every step; no workgroup waits on another.
+ *   gi [D][B][T][3H];  w_hh_* [3H][H] (16-byte aligned), b_hh_* [3H] per direction (the reverse pair is ignored at D = 1);  h0 [D][B][H] or
+ *   NULL (zeros);  lengths: device int64 [B] or NULL (every row T);  y [B][T][D H], exact zeros at t >= lengths[b], written by the kernel;
+ *   h_n [D][B][H], bit for bit y[b][len - 1][:H] and y[b][0][H:];  the reverse direction starts at len - 1.  A lengths entry outside [1, T]
+ *   skips the row (y = 0, h_n = h0) and sets *flag (int32, device memory, or NULL); nothing outside the row is touched.  fp32 FMA, the cell
+ *   of gru_step.hpp; every sum in an order fixed by H alone: a row's result does not depend on B, on its place in the batch or on T.
+ * Envelope: D in {1, 2}, B >= 1, 1 <= T <= 128, H % 4 == 0, 8 <= H <= 320; outside it tg_seq2seq_encode_eval returns non-zero, sets
+ * tg_last_error ("envelope") and launches nothing; tg_seq2seq_encode_supported writes 1 / 0 for positive sizes. */
+int tg_seq2seq_encode_supported(int32_t B, int32_t T, int32_t H, int32_t D, int32_t* supported);
+int tg_seq2seq_encode_eval(const float* gi, const float* w_hh_fwd, const float* w_hh_rev, const float* b_hh_fwd, const float* b_hh_rev,
+                           const float* h0, const void* lengths, float* y, float* h_n, int32_t* flag, int32_t B, int32_t T, int32_t H, int32_t D,
+                           void* stream);
 
 /* ---- Seq2Seq training loss and gradient clip (csrc/losses.hip; train_eval/train_seq2seq.py:6-33, 48)
  * tg_seq2seq_loss: custom_loss forward and d_output in one pass over output, target [B][T][P]:
