@@ -729,13 +729,55 @@ static int nt_layout(NtGroup& g, int bm, int bn) {
     return wg;
 }
 
+// The instantiation of gemm_nt_kernel a group of family 1 / 2 runs on -- the ONE place that decides (nt_launch switches on it,
+// tg_gemm_nt_variant reports it): <vec, wm, wn, ring, ks>, workgroup tile (32 wm) x (32 wn).  Family 0 has no variant (wm == 0).
+struct NtVariant { int family, vec, wm, wn, ring, ks; };
+
+// workgroups nt_layout would lay the group out over (every problem padded to a multiple of 8), without touching the group
+static int nt_count_wgs(const NtGroup& g, int bm, int bn) {
+    int wg = 0;
+    for (int i = 0; i < g.n; ++i) wg += (cdiv(g.p[i].M, bm) * cdiv(g.p[i].N, bn) + 7) / 8 * 8;
+    return wg;
+}
+
+static NtVariant nt_pick_variant(const NtGroup& g) {
+    const int fam = nt_family(g.p[0]);
+    if (fam == 0) return {0, 1, 0, 0, 0, 0};
+    bool vec = true;
+    int Kx = 0, Mmax = 0;
+    for (int i = 0; i < g.n; ++i) {
+        vec = vec && nt_vec(g.p[i]);
+        Kx = Kx > g.p[i].A.K ? Kx : g.p[i].A.K;
+        Mmax = Mmax > g.p[i].M ? Mmax : g.p[i].M;
+    }
+    const int wgs = fam == 1 ? nt_count_wgs(g, 128, 32) : nt_count_wgs(g, 64, 64);
+    const bool deep = wgs < 1024 && Kx >= 256;        // operand ring of 4 k-steps: small grid, long reduction (see the kernel)
+    // few rows, long reduction: one 32 x 32 tile per workgroup, its four waves split K (see the kernel)
+    if (fam == 1 && vec && wgs < 256 && Kx >= 256) return {1, 1, 1, 1, 2, 4};
+    // a handful of 64 x 64 tiles with a long reduction and at most 576 rows (a synthesis window of up to 16 utterances: [34 x 300 x 600]
+    // text-encoder convs are five workgroups walking 150 dependent k-steps each, 25 us): 32 x 32 tiles whose four waves split K --
+    // four times the workgroups, an eighth of the chain: ~11 us (round 6: one utterance 883 -> 723 us per window, profiles/r6_z_decode_b1.txt)
+    // Ring of ten k-steps when a wave's K range fits it (K <= 640): every operand of the wave is requested before its first MFMA, one
+    // memory latency per launch instead of five (the ring of two held 32 of a wave's 150 k: 11.4 -> see profiles/r6_bg_decode_ring.txt)
+    if (fam == 2 && vec && wgs <= 64 && Kx >= 256 && Mmax <= 576) return {2, 1, 1, 1, Kx <= 640 ? 10 : 2, 4};
+    const int wm = fam == 1 ? 4 : 2, wn = fam == 1 ? 1 : 2;
+    if (vec && deep) return {fam, 1, wm, wn, 4, 1};
+    return {fam, vec ? 1 : 0, wm, wn, 1, 1};
+}
+
+// the group's family (problem 0's), or -1 when its problems disagree
+static int nt_group_family(const NtGroup& g) {
+    const int fam = nt_family(g.p[0]);
+    for (int i = 0; i < g.n; ++i)
+        if (nt_family(g.p[i]) != fam) return -1;
+    return fam;
+}
+
 static int nt_launch(NtGroup& g, hipStream_t s) {
     const int fam = nt_family(g.p[0]);
-    bool vec = true;
     for (int i = 0; i < g.n; ++i) {
         TG_REQUIRE(nt_family(g.p[i]) == fam, "tg_gemm_nt_group: problem %d does not fit the kernel family of problem 0 (M=%d N=%d K=%d)", i,
                    g.p[i].M, g.p[i].N, g.p[i].A.K);
-        vec = vec && nt_vec(g.p[i]);
         TG_REQUIRE(fam == 0 || g.p[i].b_seg_k == g.p[i].A.K, "tg_gemm_nt: K-concatenated weights need the big-product path (problem %d)", i);
     }
     if (fam == 0 && use_split_path()) return tg_gemm_nt_split_launch(g, s);
@@ -756,39 +798,23 @@ static int nt_launch(NtGroup& g, hipStream_t s) {
         else TG_NT_BIG(2, 1);
 #undef TG_NT_BIG
     } else {
-        int Kx = 0;
-        for (int i = 0; i < g.n; ++i) Kx = Kx > g.p[i].A.K ? Kx : g.p[i].A.K;
-        const int wgs = fam == 1 ? nt_layout(g, 128, 32) : nt_layout(g, 64, 64);
-        const dim3 grid(wgs);
-        const bool deep = wgs < 1024 && Kx >= 256;        // operand ring of 4 k-steps: small grid, long reduction (see the kernel)
-        if (fam == 1 && vec && wgs < 256 && Kx >= 256) {
-            // few rows, long reduction: one 32 x 32 tile per workgroup, its four waves split K (see the kernel)
-            const dim3 grid4(nt_layout(g, 32, 32));
-            hipLaunchKernelGGL((gemm_nt_kernel<true, 1, 1, 2, 4>), grid4, dim3(256), 0, s, g);
-            return check_launch("tg_gemm_nt");
+        const NtVariant v = nt_pick_variant(g);
+        const dim3 grid(nt_layout(g, 32 * v.wm, 32 * v.wn));
+#define TG_NT_SMALL(VEC_, WM_, WN_, RING_, KS_)                                            \
+        if ((v.vec != 0) == (VEC_) && v.wm == (WM_) && v.wn == (WN_) && v.ring == (RING_) && v.ks == (KS_)) { \
+            hipLaunchKernelGGL((gemm_nt_kernel<VEC_, WM_, WN_, RING_, KS_>), grid, dim3(256), 0, s, g); \
+            return check_launch("tg_gemm_nt");                                             \
         }
-        int Mmax = 0;
-        for (int i = 0; i < g.n; ++i) Mmax = Mmax > g.p[i].M ? Mmax : g.p[i].M;
-        if (fam == 2 && vec && wgs <= 64 && Kx >= 256 && Mmax <= 576) {
-            // a handful of 64 x 64 tiles with a long reduction and at most 576 rows (a synthesis window of up to 16 utterances: [34 x 300 x 600]
-            // text-encoder convs are five workgroups walking 150 dependent k-steps each, 25 us): 32 x 32 tiles whose four waves split K --
-            // four times the workgroups, an eighth of the chain: ~11 us (round 6: one utterance 883 -> 723 us per window, profiles/r6_z_decode_b1.txt)
-            // Ring of ten k-steps when a wave's K range fits it (K <= 640): every operand of the wave is requested before its first MFMA, one
-            // memory latency per launch instead of five (the ring of two held 32 of a wave's 150 k: 11.4 -> see profiles/r6_bg_decode_ring.txt)
-            const dim3 grid4(nt_layout(g, 32, 32));
-            if (Kx <= 640) hipLaunchKernelGGL((gemm_nt_kernel<true, 1, 1, 10, 4>), grid4, dim3(256), 0, s, g);
-            else hipLaunchKernelGGL((gemm_nt_kernel<true, 1, 1, 2, 4>), grid4, dim3(256), 0, s, g);
-            return check_launch("tg_gemm_nt");
-        }
-        if (fam == 1) {
-            if (vec && deep) hipLaunchKernelGGL((gemm_nt_kernel<true, 4, 1, 4>), grid, dim3(256), 0, s, g);
-            else if (vec)    hipLaunchKernelGGL((gemm_nt_kernel<true, 4, 1, 1>), grid, dim3(256), 0, s, g);
-            else             hipLaunchKernelGGL((gemm_nt_kernel<false, 4, 1, 1>), grid, dim3(256), 0, s, g);
-        } else {
-            if (vec && deep) hipLaunchKernelGGL((gemm_nt_kernel<true, 2, 2, 4>), grid, dim3(256), 0, s, g);
-            else if (vec)    hipLaunchKernelGGL((gemm_nt_kernel<true, 2, 2, 1>), grid, dim3(256), 0, s, g);
-            else             hipLaunchKernelGGL((gemm_nt_kernel<false, 2, 2, 1>), grid, dim3(256), 0, s, g);
-        }
+        TG_NT_SMALL(true, 1, 1, 2, 4)
+        TG_NT_SMALL(true, 1, 1, 10, 4)
+        TG_NT_SMALL(true, 4, 1, 4, 1)
+        TG_NT_SMALL(true, 4, 1, 1, 1)
+        TG_NT_SMALL(false, 4, 1, 1, 1)
+        TG_NT_SMALL(true, 2, 2, 4, 1)
+        TG_NT_SMALL(true, 2, 2, 1, 1)
+        TG_NT_SMALL(false, 2, 2, 1, 1)
+#undef TG_NT_SMALL
+        TG_REQUIRE(false, "tg_gemm_nt: no kernel for variant <%d, %d, %d, %d, %d>", v.vec, v.wm, v.wn, v.ring, v.ks);
     }
     return check_launch("tg_gemm_nt");
 }
@@ -869,6 +895,22 @@ extern "C" int32_t tg_gemm_nt_kernel_plan(const tg_gemm_nt_problem* problems, in
     return 2;
 }
 
+extern "C" int32_t tg_gemm_nt_variant(const tg_gemm_nt_problem* problems, int32_t n, int32_t out[6]) {
+    if (!problems || n < 1 || n > TG_MAX_GROUP) return -1;
+    NtGroup g;
+    g.n = n;
+    for (int i = 0; i < n; ++i)
+        if (nt_fill(g.p[i], problems[i], i)) return -1;
+    for (int i = n; i < TG_MAX_GROUP; ++i) g.p[i] = g.p[0];
+    const int fam = nt_group_family(g);
+    if (fam <= 0) return fam;
+    for (int i = 0; i < n; ++i)       // what nt_launch refuses for the f32-MFMA kernels
+        if (g.p[i].b_seg_k != g.p[i].A.K || g.p[i].c_rmax || g.p[i].c2_rmax || nt_has_ext(g.p[i])) return -1;
+    const NtVariant v = nt_pick_variant(g);
+    if (out) { out[0] = v.family; out[1] = v.vec; out[2] = v.wm; out[3] = v.wn; out[4] = v.ring; out[5] = v.ks; }
+    return fam;
+}
+
 extern "C" int tg_gemm_nt_group(const tg_gemm_nt_problem* problems, int32_t n, void* stream) {
     TG_REQUIRE(problems && n >= 1 && n <= TG_MAX_GROUP, "tg_gemm_nt_group: 1..%d problems", TG_MAX_GROUP);
     NtGroup g;
@@ -916,9 +958,12 @@ static void tn_plan(int M, int tiles, bool two_pass, int* splits_out, int* rows_
     *splits_out = cdiv(M, rows);
 }
 
+// the combine of a problem's row splits: 0 = float atomics in the product kernel (no workspace), 16 / 256 = tn_reduce_kernel_t<SUB>
+static int tn_reduce_kind(bool two_pass, int splits) { return !two_pass ? 0 : splits >= 512 ? 256 : 16; }
+
 static void launch_tn_reduce(const float* partial, int splits, int N, int K, int cw, int out_kw, float* dW, long ldw, hipStream_t s) {
     const long total = (long)N * K;
-    if (splits >= 512) {
+    if (tn_reduce_kind(true, splits) == 256) {
         const long blocks = total > 4096 ? 4096 : total;
         hipLaunchKernelGGL(tn_reduce_kernel_t<256>, dim3((int)blocks), dim3(256), 0, s, partial, splits, N, K, cw, out_kw, dW, ldw);
     } else {
@@ -972,9 +1017,11 @@ static int tn_fill(TnProb& p, const tg_gemm_tn_problem& q, int idx, int group_ti
     return 0;
 }
 
-// plan_only != nullptr: decide the kernel (0 f32-MFMA, 1 bf16 x 3 staged slabs, 2 bf16 x 3 mover waves) and return without launching
+// plan_only != nullptr: decide the kernel (0 f32-MFMA, 1 bf16 x 3 staged slabs, 2 bf16 x 3 mover waves) and return without launching;
+// split_plan (with plan_only, plans 0 and 1): also report every problem's row splits, rows per split and combine (tn_reduce_kind)
+struct TnSplitPlanOut { int32_t *splits, *rows_per_split, *reduce_kind; };
 extern "C" int tg_get_tn_workgroup_cap(void);
-static int tn_group_impl(const tg_gemm_tn_problem* problems, int32_t n, void* stream, int32_t* plan_only) {
+static int tn_group_impl(const tg_gemm_tn_problem* problems, int32_t n, void* stream, int32_t* plan_only, const TnSplitPlanOut* split_plan = nullptr) {
     TG_REQUIRE(problems && n >= 1 && n <= TG_MAX_GROUP, "tg_gemm_tn_group: 1..%d problems", TG_MAX_GROUP);
     TnGroup g;
     g.n = n;
@@ -1039,7 +1086,15 @@ static int tn_group_impl(const tg_gemm_tn_problem* problems, int32_t n, void* st
             return all_ws ? tg_gemm_tn_mw_reduce_launch(g2, mw_splits, s) : 0;
         }
     }
-    if (plan_only) { *plan_only = x3 ? 1 : 0; return 0; }
+    if (plan_only) {
+        *plan_only = x3 ? 1 : 0;
+        for (int i = 0; split_plan && i < n; ++i) {
+            if (split_plan->splits) split_plan->splits[i] = splits[i];
+            if (split_plan->rows_per_split) split_plan->rows_per_split[i] = g.p[i].rows_per_split;
+            if (split_plan->reduce_kind) split_plan->reduce_kind[i] = tn_reduce_kind(g.p[i].partial != nullptr, splits[i]);
+        }
+        return 0;
+    }
     // tg_set_tn_workgroup_cap promises a launch that occupies at most that many CUs (it runs beside a cluster-synchronised recurrence whose
     // workgroups must all stay resident): only the persistent mover-wave kernel keeps that promise -- the kernels below flood the chip with short
     // workgroups.  A capped group they would take is refused; the caller probes the plan with the problems it will launch (ops.tn_kernel_plan).
@@ -1066,6 +1121,15 @@ extern "C" int32_t tg_gemm_tn_kernel_plan(const tg_gemm_tn_problem* problems, in
     for (int i = 0; i < n; ++i)
         if (!problems[i].dY || !problems[i].dW || !problems[i].A.ptr) return -1;
     return tn_group_impl(problems, n, nullptr, &plan) == 0 ? plan : -1;
+}
+
+extern "C" int32_t tg_gemm_tn_split_plan(const tg_gemm_tn_problem* problems, int32_t n, int32_t* splits, int32_t* rows_per_split, int32_t* reduce_kind) {
+    int32_t plan = -1;
+    if (!problems || n < 1 || n > TG_MAX_GROUP) return -1;
+    for (int i = 0; i < n; ++i)
+        if (!problems[i].dY || !problems[i].dW || !problems[i].A.ptr) return -1;
+    const TnSplitPlanOut out = {splits, rows_per_split, reduce_kind};
+    return tn_group_impl(problems, n, nullptr, &plan, &out) == 0 ? plan : -1;
 }
 
 extern "C" int tg_gemm_tn(const float* dY, int64_t ldy, const tg_window* A, float* dW, int64_t ldw, int32_t M, int32_t N,

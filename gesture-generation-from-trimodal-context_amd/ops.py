@@ -217,6 +217,18 @@ def nt_kernel_plan(problems):
     return plan, tm.value, tn.value
 
 
+def nt_variant(problems):
+    """(family, vec, wm, wn, ring, ks): the instantiation of the no-LDS f32-MFMA kernel (csrc/gemm.hip) a family-1 / family-2 group given as
+    gemm_nt_group's list of dicts runs on -- the launcher's own choice, not a restatement; (0,) for a big-product group (family 0)."""
+    qs = [_nt_problem(**p) for p in problems]
+    arr = (_lib.NtProblem * len(qs))(*qs)
+    out = (C.c_int32 * 6)()
+    fam = int(_lib.load().tg_gemm_nt_variant(arr, len(qs), out))
+    if fam < 0:
+        raise ValueError("nt_variant: invalid group (bad problem, mixed kernel families, or operands the f32-MFMA kernels refuse)")
+    return tuple(out) if fam > 0 else (0,)
+
+
 def gemm_nt(A: Win, W, bias, out, **kw):
     """out(m, :) = act(A(m, :) @ W^T + bias) [+ out].  W: [N, K] (row stride may exceed K).
     out: 2-D view [M, N] (unit inner stride) unless explicit C addressing is given."""
@@ -446,7 +458,14 @@ def _tn_problem(dY, A: Win, dW, *, out_kw=0, dbias=None, keep=None, force_ws=Fal
     _f32(dY, "dY"); _f32(dW, "dW")
     assert dY.dim() == 2 and dY.stride(1) == 1 and dY.shape[0] == A.M, (dY.shape, A.M)
     M, N = dY.shape
-    assert dW.is_contiguous() and dW.numel() == N * A.K and dW.shape[0] == N, (dW.shape, N, A.K)
+    ldw = A.K
+    if dW.dim() == 2 and not dW.is_contiguous():           # N rows of K floats inside a wider buffer (row stride ldw > K)
+        assert tuple(dW.shape) == (N, A.K) and dW.stride(1) == 1 and dW.stride(0) > A.K, (dW.shape, dW.stride(), N, A.K)
+        ldw = dW.stride(0)
+        if (N - 1) * ldw + A.K - 1 >= _room(dW):
+            raise ValueError("gemm_tn: dW exceeds its tensor")
+    else:
+        assert dW.is_contiguous() and dW.numel() == N * A.K and dW.shape[0] == N, (dW.shape, N, A.K)
     if dbias is not None:
         _flat(dbias, "dbias"); assert dbias.numel() == N
     if (M - 1) * dY.stride(0) + N - 1 >= _room(dY):
@@ -462,7 +481,7 @@ def _tn_problem(dY, A: Win, dW, *, out_kw=0, dbias=None, keep=None, force_ws=Fal
         if keep is not None:
             keep.append(ws)
     q = _lib.TnProblem()
-    q.dY, q.ldy, q.A, q.dW, q.ldw = dY.data_ptr(), dY.stride(0), A.s, dW.data_ptr(), A.K
+    q.dY, q.ldy, q.A, q.dW, q.ldw = dY.data_ptr(), dY.stride(0), A.s, dW.data_ptr(), ldw
     q.M, q.N, q.out_kw = M, N, int(out_kw)
     q.dbias = dbias.data_ptr() if dbias is not None else None
     q.ws, q.ws_floats = (ws.data_ptr() if ws is not None else None), nws
@@ -593,6 +612,20 @@ def tn_kernel_plan(problems, as_launched=False):
         arr = (_lib.TnProblem * len(problems))(*[_tn_problem(keep=keep, force_ws=True, **p)[0] for p in problems])
         plan = int(_lib.load().tg_gemm_tn_kernel_plan(arr, len(problems)))
     return plan
+
+
+def tn_split_plan(problems):
+    """[(splits, rows_per_split, reduce_kind)] per problem of a group given as gemm_tn_group's list of dicts, as the launcher plans it:
+    reduce_kind 0 = float atomics, 16 / 256 = the fixed-order fp64 combine (threads per output entry).  For the kernels of tn_kernel_plan 0
+    and 1; a group the mover-wave kernel takes (plan 2) has no such plan and raises."""
+    keep = []
+    n = len(problems)
+    arr = (_lib.TnProblem * n)(*[_tn_problem(keep=keep, **p)[0] for p in problems])
+    splits, rows, kind = (C.c_int32 * n)(), (C.c_int32 * n)(), (C.c_int32 * n)()
+    plan = int(_lib.load().tg_gemm_tn_split_plan(arr, n, splits, rows, kind))
+    if plan not in (0, 1):
+        raise ValueError(f"tn_split_plan: plan {plan} (invalid group, or the mover-wave kernel's)")
+    return [(splits[i], rows[i], kind[i]) for i in range(n)]
 
 
 def colsum(X, out, *, accumulate=True):

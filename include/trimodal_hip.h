@@ -169,6 +169,12 @@ int32_t tg_gemm_nt_ext_supported(const tg_gemm_nt_problem* problem);
  * Replaces nothing in the reference (torch picks its own GEMM there, multimodal_context_net.py:98-99, model/tcn.py:19-46): test
  * and profiling aid, so that a parity test can assert WHICH kernel it covered. */
 int32_t tg_gemm_nt_kernel_plan(const tg_gemm_nt_problem* problems, int32_t n, int32_t* tile_m, int32_t* tile_n);
+/* Which instantiation of the no-LDS f32-MFMA kernel (gemm.hip, families 1 and 2) a group would run on, without launching -- the choice
+ * tg_gemm_nt_group itself makes from the group's workgroup count, largest K and largest M.  Returns the family (0, 1, 2) or -1 (invalid,
+ * mixed families, or operands these kernels refuse); for families 1 and 2 fills out = {family, vec (16-byte loads), wm, wn (waves per
+ * workgroup: tile 32 wm x 32 wn), ring (k-steps of operands in flight), ks (waves splitting K: 1 or 4)}; family 0 fills nothing.
+ * Test aid like tg_gemm_nt_kernel_plan: a parity test asserts which kernel it covered. */
+int32_t tg_gemm_nt_variant(const tg_gemm_nt_problem* problems, int32_t n, int32_t out[6]);
 /* Process-wide switch of the mover-wave kernel: 1 on, 0 off (every big product on gemm_split.hip), -1 back to the environment default
  * (TG_NT_MW, on).  For same-process A/B timing (tools/nt_mw_probe.py) and tests; results are equal within the fp32 tolerance either way. */
 int tg_set_nt_mover_waves(int32_t on);
@@ -235,6 +241,10 @@ int tg_gemm_tn_group(const tg_gemm_tn_problem* problems, int32_t n, void* stream
 /* which kernel the group would run on, without launching: 0 = f32-MFMA tiles, 1 = bf16 x 3 staged slabs (gemm_split.hip), 2 = bf16 x 3 mover
  * waves (gemm_tn_mw.hip: persistent 768-thread workgroups, 192 x 160 tiles); -1 invalid.  Test / profiling aid like tg_gemm_nt_kernel_plan. */
 int32_t tg_gemm_tn_kernel_plan(const tg_gemm_tn_problem* problems, int32_t n);
+/* tg_gemm_tn_kernel_plan's answer, and for plans 0 and 1 every problem's row-split plan as launched (n entries each, any may be NULL):
+ * splits, rows_per_split (a multiple of 32; the last split may be shorter) and reduce_kind -- 0: float atomics (ws == NULL), 16 / 256: the
+ * fixed-order fp64 combine with that many threads per output entry (256 from 512 splits on).  Plan 2 fills nothing.  Test aid. */
+int32_t tg_gemm_tn_split_plan(const tg_gemm_tn_problem* problems, int32_t n, int32_t* splits, int32_t* rows_per_split, int32_t* reduce_kind);
 int tg_gemm_tn(const float* dY, int64_t ldy, const tg_window* A, float* dW, int64_t ldw, int32_t M, int32_t N,
                int32_t out_kw, float* dbias, float* ws, int64_t ws_floats, void* stream);
 
