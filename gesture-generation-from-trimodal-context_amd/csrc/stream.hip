@@ -3,21 +3,13 @@
 //                    the chunk's word records -- int32 triples (absolute window, frame in window, word id) -- to the per-row word ring [B][W][3]
 //                    at n_words[b] mod W, then advances both counters.  One workgroup per row: it reads its row's counters, passes a barrier,
 //                    copies, and its first thread writes the counters back, so nothing waits on another workgroup and nothing needs an atomic.
-//   tg_stream_stage  cuts the inputs of window w = win[0] (device memory): audio_out[b][k] = ring[b][(w S + k) mod R] for k < min(A, written[b] - w S),
-//                    zeros behind (the closing windows of a stream); text_out[b][f] = the id of the LAST pushed record with window w and frame f,
-//                    else 0 (the reference's loop overwrites in word order, synthesize.py:112-116: the records are scanned oldest to newest by
-//                    the one thread that owns the frame).
-// Every counter lives in device memory: the launches are the same for every push and every window.  As in utterance.hip the device sees integers
-// only -- the frame and the windows of a word are decided once by the host's Python doubles -- and samples move as bits: plain loads and stores.
-#include "common.hpp"
+//   tg_stream_stage  cuts the inputs of window w = win[0] (device memory): the audio from the ring, zeros behind what was pushed, and per frame
+//                    the id of the LAST pushed record of that window and frame (synthesize.py:112-116).
+// Every counter lives in device memory: the launches are the same for every push and every window.  The row bodies are stream_rows.hpp's
+// (stream_pool.hip runs the same ones on rows with clocks of their own): here every row has the chunk length n and the window win[0].
+#include "stream_rows.hpp"
 
 namespace tg {
-
-constexpr int ST_MAX_ROWS = 4;          // rows of a stream (the few-row decoders' lock-step limit)
-constexpr int ST_MAX_WORDS = 1024;      // largest word ring per row: 12 KB of LDS in the stage kernel
-constexpr int ST_MAX_FRAMES = 1024;     // frames of a window: one thread each
-constexpr int ST_MAX_RING = 1 << 30;    // samples of a row's ring: positions and their sums stay inside an int
-constexpr int ST_MAX_WINDOW = 1 << 25;  // samples of a window: the stage kernel's grid
 
 __global__ __launch_bounds__(1024) void stream_push_kernel(const float* __restrict__ chunk, long chunk_stride, int n, const int32_t* __restrict__ recs,
                                                            int rec_stride, int m_max, float* __restrict__ ring, int64_t* __restrict__ written,
@@ -26,86 +18,14 @@ __global__ __launch_bounds__(1024) void stream_push_kernel(const float* __restri
     const long wr = written[b], cnt = n_words[b];
     int m = recs ? recs[(long)b * rec_stride] : 0;
     m = m < 0 ? 0 : (m > m_max ? m_max : m);
-    __syncthreads();                                                  // every thread has the counters before thread 0 moves them
-    const int p0 = (int)(wr % R);
-    float* __restrict__ row = ring + (long)b * R;
-    const float* __restrict__ src = chunk + (long)b * chunk_stride;
-    for (int k = threadIdx.x; k < n; k += 1024) {
-        int p = p0 + k;                                               // n < R: one subtraction wraps
-        if (p >= R) p -= R;
-        row[p] = src[k];
-    }
-    const int s0 = (int)(cnt % W);
-    for (int t = threadIdx.x; t < 3 * m; t += 1024) {
-        int slot = s0 + t / 3;                                        // m <= W
-        if (slot >= W) slot -= W;
-        word_ring[((long)b * W + slot) * 3 + t % 3] = recs[(long)b * rec_stride + 1 + t];
-    }
-    if (threadIdx.x == 0) {
-        written[b] = wr + n;
-        n_words[b] = cnt + m;
-    }
+    ring_push_row(b, n, m, wr, cnt, chunk, chunk_stride, recs, rec_stride, ring, written, word_ring, n_words, R, W);
 }
 
 __global__ __launch_bounds__(256) void stream_stage_kernel(const float* __restrict__ ring, const int64_t* __restrict__ written,
                                                            const int32_t* __restrict__ word_ring, const int64_t* __restrict__ n_words,
                                                            const int32_t* __restrict__ win, int R, int S, int A, int W, int T,
                                                            float* __restrict__ out_audio, int64_t* __restrict__ out_text) {
-    __shared__ int32_t rec[ST_MAX_WORDS * 3];
-    const int b = blockIdx.x;
-    const int w = win[0];
-    if (out_text && blockIdx.y == 0) {
-        const long cnt = n_words[b];
-        const long lo = cnt > W ? cnt - W : 0;                        // the ring holds the last W records, slot = index mod W
-        const int live = (int)(cnt - lo);
-        for (int t = threadIdx.x; t < 3 * W; t += 256) rec[t] = word_ring[(long)b * W * 3 + t];
-        __syncthreads();
-        const int s0 = (int)(lo % W);
-        for (int f = threadIdx.x; f < T; f += 256) {
-            int32_t id = 0;
-            int slot = s0;
-            for (int j = 0; j < live; ++j) {                          // oldest to newest: the last match stays
-                if (rec[3 * slot] == w && rec[3 * slot + 1] == f) id = rec[3 * slot + 2];
-                if (++slot == W) slot = 0;
-            }
-            out_text[(long)b * T + f] = id;
-        }
-    }
-    if (!out_audio) return;
-    const long base = (long)w * S, wr = written[b];
-    // samples [base + lost, base + nv) of the stream are in the ring; lost > 0 only if the host ran the window too late (older samples were
-    // overwritten): those read as zeros, like everything from nv on
-    long nv = wr - base, lost = wr - R - base;
-    nv = (nv < 0 || w < 0) ? 0 : (nv > A ? A : nv);                   // (a negative window index stages silence)
-    lost = lost < 0 ? 0 : (lost > A ? A : lost);
-    const int p0 = (int)(base % R);
-    const float* __restrict__ src = ring + (long)b * R;
-    float* __restrict__ dst = out_audio + (long)b * A;
-    auto at = [&](int k) -> float {                                   // A < R: one subtraction wraps
-        if (k < lost || k >= nv) return 0.f;
-        int p = p0 + k;
-        if (p >= R) p -= R;
-        return src[p];
-    };
-    // head: the elements before dst's first 16-byte boundary; body: 16-byte stores, 16-byte loads where the four samples are valid, do not
-    // straddle the wrap point and src is aligned with dst; tail: what is left of the row
-    const int head = min((int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2), A);
-    if (blockIdx.y == 0 && (int)threadIdx.x < head) dst[threadIdx.x] = at(threadIdx.x);
-    const int i = head + 4 * (int)(blockIdx.y * 256 + threadIdx.x);
-    if (i + 3 < A) {
-        f32x4 v;
-        int p = p0 + i;
-        if (p >= R) p -= R;
-        if (i >= lost && i + 3 < nv && p + 3 < R && (reinterpret_cast<uintptr_t>(src + p) & 15u) == 0) {
-            v = *reinterpret_cast<const f32x4*>(src + p);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = at(i + q);
-        }
-        *reinterpret_cast<f32x4*>(dst + i) = v;
-    } else {
-        for (int q = i; q < A; ++q) dst[q] = at(q);
-    }
+    ring_stage_row(blockIdx.x, win[0], ring, written, word_ring, n_words, R, S, A, W, T, out_audio, out_text);
 }
 
 }  // namespace tg

@@ -8,22 +8,18 @@
 //                     (tg_window_blend's expression, operand for operand), tail = the last n_pre frames, the next window's seed
 //                     (tg_make_pre_seq's layout [T][D + 1], or the plain [n_pre][D]), and -- behind a barrier -- win[b] += 1.
 // One workgroup (push, handover) or one grid column (stage) per row; nothing waits on another workgroup, nothing needs an atomic, and the
-// results do not depend on the order in which the workgroups run.  The row bodies of push and stage restate stream.hip's kernels line for
-// line (that file stays as it is: its kernels serve every stream that shares a clock); the bounds below are its bounds.
-#include "common.hpp"
+// results do not depend on the order in which the workgroups run.  The row bodies of push and stage are stream_rows.hpp's, shared with
+// stream.hip (whose kernels serve every stream that shares a clock), and so are the bounds: here a row brings its own chunk length and
+// window index, and a row that is idle leaves before the body.
+#include "stream_rows.hpp"
 
 namespace tg {
 
-constexpr int PL_MAX_ROWS = 4;          // = ST_MAX_ROWS of stream.hip, and so on
-constexpr int PL_MAX_WORDS = 1024;
-constexpr int PL_MAX_FRAMES = 1024;
-constexpr int PL_MAX_RING = 1 << 30;
-constexpr int PL_MAX_WINDOW = 1 << 25;
 constexpr int PL_MAX_PRE = 8;           // tg_utterance_finish's n_pre and D
 constexpr int PL_MAX_DIM = 64;
 
 struct PoolLens {
-    int n[PL_MAX_ROWS];
+    int n[ST_MAX_ROWS];
 };
 
 __global__ __launch_bounds__(1024) void pool_push_kernel(const float* __restrict__ chunk, long chunk_stride, PoolLens lens,
@@ -34,85 +30,18 @@ __global__ __launch_bounds__(1024) void pool_push_kernel(const float* __restrict
     const int n = b == 0 ? lens.n[0] : (b == 1 ? lens.n[1] : (b == 2 ? lens.n[2] : lens.n[3]));
     int m = recs ? recs[(long)b * rec_stride] : 0;
     m = m < 0 ? 0 : (m > m_max ? m_max : m);
-    if (n == 0 && m == 0) return;                                     // (the whole workgroup: the row keeps its counters and its rings)
+    if (n == 0 && m == 0) return;                                     // (the whole workgroup, before any barrier: the row keeps its counters and rings)
     const long wr = written[b], cnt = n_words[b];
-    __syncthreads();                                                  // every thread has the counters before thread 0 moves them
-    const int p0 = (int)(wr % R);
-    float* __restrict__ row = ring + (long)b * R;
-    const float* __restrict__ src = chunk + (long)b * chunk_stride;
-    for (int k = threadIdx.x; k < n; k += 1024) {
-        int p = p0 + k;                                               // n < R: one subtraction wraps
-        if (p >= R) p -= R;
-        row[p] = src[k];
-    }
-    const int s0 = (int)(cnt % W);
-    for (int t = threadIdx.x; t < 3 * m; t += 1024) {
-        int slot = s0 + t / 3;                                        // m <= W
-        if (slot >= W) slot -= W;
-        word_ring[((long)b * W + slot) * 3 + t % 3] = recs[(long)b * rec_stride + 1 + t];
-    }
-    if (threadIdx.x == 0) {
-        written[b] = wr + n;
-        n_words[b] = cnt + m;
-    }
+    ring_push_row(b, n, m, wr, cnt, chunk, chunk_stride, recs, rec_stride, ring, written, word_ring, n_words, R, W);
 }
 
 __global__ __launch_bounds__(256) void pool_stage_kernel(const float* __restrict__ ring, const int64_t* __restrict__ written,
                                                          const int32_t* __restrict__ word_ring, const int64_t* __restrict__ n_words,
                                                          const int32_t* __restrict__ win, const int32_t* __restrict__ active, int R, int S, int A,
                                                          int W, int T, float* __restrict__ out_audio, int64_t* __restrict__ out_text) {
-    __shared__ int32_t rec[PL_MAX_WORDS * 3];
     const int b = blockIdx.x;
-    if (active[b] == 0) return;                                       // (the whole workgroup)
-    const int w = win[b];
-    if (out_text && blockIdx.y == 0) {
-        const long cnt = n_words[b];
-        const long lo = cnt > W ? cnt - W : 0;                        // the ring holds the last W records, slot = index mod W
-        const int live = (int)(cnt - lo);
-        for (int t = threadIdx.x; t < 3 * W; t += 256) rec[t] = word_ring[(long)b * W * 3 + t];
-        __syncthreads();
-        const int s0 = (int)(lo % W);
-        for (int f = threadIdx.x; f < T; f += 256) {
-            int32_t id = 0;
-            int slot = s0;
-            for (int j = 0; j < live; ++j) {                          // oldest to newest: the last match stays
-                if (rec[3 * slot] == w && rec[3 * slot + 1] == f) id = rec[3 * slot + 2];
-                if (++slot == W) slot = 0;
-            }
-            out_text[(long)b * T + f] = id;
-        }
-    }
-    if (!out_audio) return;
-    const long base = (long)w * S, wr = written[b];
-    long nv = wr - base, lost = wr - R - base;                        // as stream_stage_kernel: [base + lost, base + nv) is in the ring
-    nv = (nv < 0 || w < 0) ? 0 : (nv > A ? A : nv);
-    lost = lost < 0 ? 0 : (lost > A ? A : lost);
-    const int p0 = (int)(base % R);
-    const float* __restrict__ src = ring + (long)b * R;
-    float* __restrict__ dst = out_audio + (long)b * A;
-    auto at = [&](int k) -> float {                                   // A < R: one subtraction wraps
-        if (k < lost || k >= nv) return 0.f;
-        int p = p0 + k;
-        if (p >= R) p -= R;
-        return src[p];
-    };
-    const int head = min((int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2), A);
-    if (blockIdx.y == 0 && (int)threadIdx.x < head) dst[threadIdx.x] = at(threadIdx.x);
-    const int i = head + 4 * (int)(blockIdx.y * 256 + threadIdx.x);
-    if (i + 3 < A) {
-        f32x4 v;
-        int p = p0 + i;
-        if (p >= R) p -= R;
-        if (i >= lost && i + 3 < nv && p + 3 < R && (reinterpret_cast<uintptr_t>(src + p) & 15u) == 0) {
-            v = *reinterpret_cast<const f32x4*>(src + p);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = at(i + q);
-        }
-        *reinterpret_cast<f32x4*>(dst + i) = v;
-    } else {
-        for (int q = i; q < A; ++q) dst[q] = at(q);
-    }
+    if (active[b] == 0) return;                                       // (the whole workgroup, before any barrier)
+    ring_stage_row(b, win[b], ring, written, word_ring, n_words, R, S, A, W, T, out_audio, out_text);
 }
 
 // seed_bit != 0: seed is pre_seq [B][T][D + 1]; else pre [B][n][D].  out and tail are read and written here: no __restrict__ on them.
@@ -158,16 +87,16 @@ extern "C" int tg_pool_push(const float* chunk, int64_t chunk_stride, int32_t n0
                             int64_t* n_words, int32_t B, int32_t R, int32_t A, int32_t W, void* stream) {
     PoolLens lens = {{n0, n1, n2, n3}};
     int64_t n_max = 0;
-    bool rows_ok = B >= 1 && B <= PL_MAX_ROWS;
-    for (int b = 0; b < PL_MAX_ROWS; ++b) {
+    bool rows_ok = B >= 1 && B <= ST_MAX_ROWS;
+    for (int b = 0; b < ST_MAX_ROWS; ++b) {
         rows_ok = rows_ok && lens.n[b] >= 0 && (b < B || lens.n[b] == 0);
         n_max = lens.n[b] > n_max ? lens.n[b] : n_max;
     }
-    TG_REQUIRE(rows_ok && (n_max >= 1 || m_max >= 1) && A >= 1 && W >= 1 && W <= PL_MAX_WORDS && (int64_t)R >= (int64_t)A + n_max && R > A &&
-                   R <= PL_MAX_RING && chunk_stride >= n_max,
+    TG_REQUIRE(rows_ok && (n_max >= 1 || m_max >= 1) && A >= 1 && W >= 1 && W <= ST_MAX_WORDS && (int64_t)R >= (int64_t)A + n_max && R > A &&
+                   R <= ST_MAX_RING && chunk_stride >= n_max,
                "tg_pool_push: outside the envelope 1 <= B <= %d, n[b] >= 0 (0 for b >= B), a row with samples or records, A + max n <= R <= 2^30, "
                "A < R, 1 <= W <= %d, chunk_stride >= max n (B=%d n=%d,%d,%d,%d m_max=%d R=%d A=%d W=%d chunk_stride=%lld)",
-               PL_MAX_ROWS, PL_MAX_WORDS, B, n0, n1, n2, n3, m_max, R, A, W, (long long)chunk_stride);
+               ST_MAX_ROWS, ST_MAX_WORDS, B, n0, n1, n2, n3, m_max, R, A, W, (long long)chunk_stride);
     TG_REQUIRE(m_max >= 0 && words_live >= 0 && (int64_t)words_live + m_max <= W && (m_max == 0 || (recs && rec_stride >= 1 + 3 * (int64_t)m_max)),
                "tg_pool_push: outside the envelope words_live + m_max <= W -- the word ring would overwrite records a window still needs -- and "
                "rec_stride >= 1 + 3 m_max (words_live=%d m_max=%d W=%d rec_stride=%d)", words_live, m_max, W, rec_stride);
@@ -183,11 +112,11 @@ extern "C" int tg_pool_stage(const float* ring, const int64_t* written, const in
     TG_REQUIRE(win && active && (out_audio || out_text), "tg_pool_stage: null pointer");
     TG_REQUIRE(!out_audio || (ring && written), "tg_pool_stage: audio output without the ring or its counter");
     TG_REQUIRE(!out_text || (word_ring && n_words), "tg_pool_stage: text output without the word ring or its counter");
-    TG_REQUIRE(B >= 1 && B <= PL_MAX_ROWS && S >= 1 && A >= 1 && A <= PL_MAX_WINDOW && R > A && R <= PL_MAX_RING && W >= 1 && W <= PL_MAX_WORDS &&
-                   T >= 1 && T <= PL_MAX_FRAMES,
+    TG_REQUIRE(B >= 1 && B <= ST_MAX_ROWS && S >= 1 && A >= 1 && A <= ST_MAX_WINDOW && R > A && R <= ST_MAX_RING && W >= 1 && W <= ST_MAX_WORDS &&
+                   T >= 1 && T <= ST_MAX_FRAMES,
                "tg_pool_stage: outside the envelope 1 <= B <= %d, S >= 1, 1 <= A <= 2^25, A + 1 <= R <= 2^30, 1 <= W <= %d, 1 <= T <= %d (B=%d R=%d S=%d "
                "A=%d W=%d T=%d)",
-               PL_MAX_ROWS, PL_MAX_WORDS, PL_MAX_FRAMES, B, R, S, A, W, T);
+               ST_MAX_ROWS, ST_MAX_WORDS, ST_MAX_FRAMES, B, R, S, A, W, T);
     hipLaunchKernelGGL(pool_stage_kernel, dim3(B, out_audio ? cdiv(A, 1024) + 1 : 1), dim3(256), 0, (hipStream_t)stream, ring, written, word_ring,
                        n_words, win, active, R, S, A, W, T, out_audio, out_text);
     return check_launch("tg_pool_stage");
@@ -195,11 +124,11 @@ extern "C" int tg_pool_stage(const float* ring, const int64_t* written, const in
 
 extern "C" int tg_pool_handover(const float* res, float* out, float* tail, float* seed, int32_t seed_layout, int32_t* win, const int32_t* active,
                                 int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream) {
-    TG_REQUIRE(B >= 1 && B <= PL_MAX_ROWS && n_pre >= 1 && n_pre <= PL_MAX_PRE && D >= 1 && D <= PL_MAX_DIM && T <= PL_MAX_FRAMES && n_pre < T &&
+    TG_REQUIRE(B >= 1 && B <= ST_MAX_ROWS && n_pre >= 1 && n_pre <= PL_MAX_PRE && D >= 1 && D <= PL_MAX_DIM && T <= ST_MAX_FRAMES && n_pre < T &&
                    (seed_layout == 0 || seed_layout == 1),
                "tg_pool_handover: outside the envelope 1 <= B <= %d, 1 <= n_pre <= %d, 1 <= D <= %d, n_pre < T <= %d, seed_layout 0 (pre_seq "
                "[T][D + 1]) or 1 (pre [n_pre][D]) (B=%d n_pre=%d D=%d T=%d seed_layout=%d)",
-               PL_MAX_ROWS, PL_MAX_PRE, PL_MAX_DIM, PL_MAX_FRAMES, B, n_pre, D, T, seed_layout);
+               ST_MAX_ROWS, PL_MAX_PRE, PL_MAX_DIM, ST_MAX_FRAMES, B, n_pre, D, T, seed_layout);
     TG_REQUIRE(res && out && tail && seed && win && active, "tg_pool_handover: null pointer");
     hipLaunchKernelGGL(pool_handover_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, res, out, tail, seed, seed_layout == 0 ? 1 : 0, win, active, T,
                        D, n_pre);

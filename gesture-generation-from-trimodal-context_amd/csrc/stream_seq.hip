@@ -8,14 +8,12 @@
 // workgroup gives every kept record its place -- an order-preserving compaction without atomics; ids move as bits.  A row with more than
 // Te - 2 records for the window is the host's to refuse before the push (it computes the records); the kernel clamps the count so that no
 // index can leave the row.
-#include "common.hpp"
+#include "stream_rows.hpp"
 
 namespace tg {
 
-constexpr int SQ_MAX_ROWS = 4;          // rows of a stream (stream.hip: ST_MAX_ROWS)
-constexpr int SQ_MAX_WORDS = 1024;      // largest word ring per row (stream.hip: ST_MAX_WORDS): four records per thread
 constexpr int SQ_MAX_TE = 128;          // longest list (the encoder's and the decoder's envelope)
-constexpr int SQ_THREADS = 256;
+constexpr int SQ_THREADS = ST_MAX_WORDS / 4;   // four records of the word ring per thread
 
 __global__ __launch_bounds__(SQ_THREADS) void stream_stage_text_kernel(const int32_t* __restrict__ word_ring, const int64_t* __restrict__ n_words,
                                                                        const int32_t* __restrict__ win, int W, int Te, long long sos, long long eos,
@@ -77,8 +75,8 @@ using namespace tg;
 extern "C" int tg_stream_stage_text(const int32_t* word_ring, const int64_t* n_words, const int32_t* win, int32_t B, int32_t W, int32_t Te,
                                     int64_t sos, int64_t eos, int64_t* out_text, int64_t* out_len, void* stream) {
     TG_REQUIRE(word_ring && n_words && win && out_text && out_len, "tg_stream_stage_text: null pointer");
-    TG_REQUIRE(B >= 1 && B <= SQ_MAX_ROWS && W >= 1 && W <= SQ_MAX_WORDS && Te >= 2 && Te <= SQ_MAX_TE,
-               "tg_stream_stage_text: outside the envelope 1 <= B <= %d, 1 <= W <= %d, 2 <= Te <= %d (B=%d W=%d Te=%d)", SQ_MAX_ROWS, SQ_MAX_WORDS,
+    TG_REQUIRE(B >= 1 && B <= ST_MAX_ROWS && W >= 1 && W <= ST_MAX_WORDS && Te >= 2 && Te <= SQ_MAX_TE,
+               "tg_stream_stage_text: outside the envelope 1 <= B <= %d, 1 <= W <= %d, 2 <= Te <= %d (B=%d W=%d Te=%d)", ST_MAX_ROWS, ST_MAX_WORDS,
                SQ_MAX_TE, B, W, Te);
     hipLaunchKernelGGL(stream_stage_text_kernel, dim3(B), dim3(SQ_THREADS), 0, (hipStream_t)stream, word_ring, n_words, win, W, Te, (long long)sos,
                        (long long)eos, (long long*)out_text, (long long*)out_len);

@@ -44,6 +44,10 @@ StreamPool is GestureStream for independent sessions: the 1 to 4 rows of ONE win
 counters on the device), opened, pushed to (ragged chunks) and closed on their own; the windows that have become complete run together, and
 the hand-over kernel (csrc/stream_pool.hip) leaves the rows that did not run untouched.  One graph serves first and later windows.
 
+Structure: the three window decoders are subclasses of _WindowDecoderBase (buffers, the eager / capture-once / replay skeleton, the pooled
+window, check_kept; _capture is the one place a graph is captured); the streams and the pool are subclasses of _StreamCore (constructor checks,
+a row's word records, the closing window); the five offline loops stay separate and share _seed_rows, _host_window_batch and _rows_result.
+
 TTS / Gentle alignment / LMDB front-ends of the reference script are network services and out of scope; `words` is the
 reference's word list [[word, start_s, end_s], ...].
 """
@@ -136,6 +140,24 @@ def seq2seq_smooth(out_dir_vec, n_windows, n_poses=34, n_pre_poses=4):
     return out_dir_vec
 
 
+def _seed_rows(seed_seqs, n_pre):
+    """The utterances' seed poses as one (B, n_pre, D) array (synthesize.py:46-50), or None."""
+    return None if seed_seqs is None else np.stack([np.asarray(s)[:n_pre] for s in seed_seqs])
+
+
+def _host_window_batch(args, lang_model, audios, words_list, n_win, i, audio_sr):
+    """(text (B, n_poses) int64, audio (B, L) fp32), CPU tensors: window_inputs of lock-step step i, row by row; a finished utterance idles on
+    its last window."""
+    rows = [window_inputs(args, lang_model, audios[b], words_list[b], min(i, n_win[b] - 1), audio_sr) for b in range(len(audios))]
+    return torch.from_numpy(np.stack([r[1] for r in rows])), torch.from_numpy(np.stack([r[0] for r in rows]))
+
+
+def _rows_result(total, n_win, stride, n_pre):
+    """The host path's return value: one read-back of the stacked windows, row b cut to its n_win[b] windows."""
+    res = total.cpu().numpy()
+    return [res[b, :n * stride + n_pre] for b, n in enumerate(n_win)]
+
+
 def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, device_opts=None):
     """The seq2seq branch for several utterances in lock-step; returns the stacked windows BEFORE seq2seq_smooth, one array per utterance.
     device_opts (fade_out, joints, return_device): the on_device path -- texts staged from the UtteranceBatch's plan, smoothing and fade-out in
@@ -148,7 +170,7 @@ def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
     n_win = [num_windows(len(a) / audio_sr, T, n_pre, fps) for a in audios]
     pre = torch.zeros(B, max(n_pre, 1), D, device=dev)
     if seed_seqs is not None and n_pre > 0:                                      # synthesize.py:46-50
-        pre[:, :n_pre].copy_(torch.as_tensor(np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]), dtype=torch.float32))
+        pre[:, :n_pre].copy_(torch.as_tensor(_seed_rows(seed_seqs, n_pre), dtype=torch.float32))
     tail = torch.zeros(B, n_pre, D, device=dev)
     ub = None if device_opts is None else UtteranceBatch(args, lang_model, audios, words_list, dev, audio_sr)
     total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), D, device=dev)
@@ -175,8 +197,7 @@ def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
                 total[b, i * stride:i * stride + T, :].copy_(out[b])
     if ub is not None:
         return _device_result(ub, total, *device_opts)
-    res = total.cpu().numpy()
-    return [res[b, :n_win[b] * stride + n_pre] for b in range(B)], n_win
+    return _rows_result(total, n_win, stride, n_pre), n_win
 
 
 def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, device_opts=None):
@@ -194,7 +215,7 @@ def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_li
     n_win = [num_windows(len(a) / audio_sr, T, n_pre, args.motion_resampling_framerate) for a in audios]
     pre = torch.zeros(B, n_pre, D, device=dev)
     if seed_seqs is not None:                                                   # synthesize.py:46-50
-        pre.copy_(torch.as_tensor(np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]), dtype=torch.float32))
+        pre.copy_(torch.as_tensor(_seed_rows(seed_seqs, n_pre), dtype=torch.float32))
     tail = torch.zeros(B, n_pre, D, device=dev)
     ub = None if device_opts is None else UtteranceBatch(args, lang_model, audios, words_list, dev, audio_sr)
     total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), D, device=dev)
@@ -204,11 +225,7 @@ def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_li
         if ub is not None:
             ub.stage(i, text_dev, audio_dev)
         else:
-            a_np, t_np = [], []
-            for b in range(B):
-                a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], min(i, n_win[b] - 1), audio_sr)   # finished utterances idle
-                a_np.append(a); t_np.append(ids)
-            text_dev, audio_dev = torch.from_numpy(np.stack(t_np)).to(dev), torch.from_numpy(np.stack(a_np)).to(dev)
+            text_dev, audio_dev = (t.to(dev) for t in _host_window_batch(args, lang_model, audios, words_list, n_win, i, audio_sr))
         inject = None if eps_list is None else {"c.eps": torch.as_tensor(eps_list[i], dtype=torch.float32, device=dev)}
         out = pose_decoder.synthesize(text_dev, audio_dev, pre, inject=inject).contiguous()                # (B, T, D), synthesize.py:133
         if i > 0:
@@ -220,96 +237,137 @@ def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_li
                 total[b, i * stride:i * stride + T, :].copy_(out[b])
     if ub is not None:
         return _device_result(ub, total, *device_opts)
-    res = total.cpu().numpy()
-    return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
+    return _rows_result(total, n_win, stride, n_pre)
 
 
-def _pool_buffers(dec):
-    if dec.win is None:
-        dec.win = torch.zeros(dec.B, dtype=torch.int32, device=dec.dev)
-        dec.active = torch.zeros(dec.B, dtype=torch.int32, device=dec.dev)
-    return dec.active, dec.win
+def _capture(fn, state):
+    """fn() recorded into a hipGraph, which is returned.  state: the tensors fn's launches write that must afterwards read as before (a capture
+    does not execute: they are restored from clones).  The caller has run fn's launches eagerly once before (first window, or _window_pooled's
+    pass with no row active)."""
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    keep = [t.clone() for t in state]
+    pg_alive = torch.distributed.is_available() and torch.distributed.is_initialized()     # RCCL helper threads: see train_gan.GraphedGanStep
+    with torch.cuda.graph(graph, capture_error_mode="thread_local" if pg_alive else "global"):
+        fn()
+    for t, k in zip(state, keep):
+        t.copy_(k)
+    return graph
 
 
-def _window_pooled(dec, state, active, win, draw):
-    """window_pooled of both window decoders; state: the tensors a capture must leave as they were (besides dec.win)."""
-    a_buf, w_buf = _pool_buffers(dec)
-    if active is not None:
-        a_buf.copy_(torch.as_tensor(active, dtype=torch.int32), non_blocking=True)
-    if win is not None:
-        w_buf.copy_(torch.as_tensor(win, dtype=torch.int32), non_blocking=True)
-    if draw is not None:
-        dec.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
-    with torch.no_grad(), dec.frozen:
-        if not dec.use_graph:
-            dec._forward_pooled()
-        else:
-            if dec.graph_pooled is None:
+class _WindowDecoderBase:
+    """What the window decoders share: the static buffers (text, audio, seed, tail, out and -- replay_draws -- draw), the window skeleton
+    (_window: eager on the first window or without a graph, else captured once and replayed), the pooled window of a stream pool, and the
+    check a kept decoder passes before a stream or a synthesis call may use it.  A subclass gives its window() (the copies of ITS inputs into
+    the static buffers, then _window), _model_forward() -- the model on the static buffers, returning the (B, T, D) result or None if it
+    wrote self.out itself -- and, where the seed is not the plain `pre` (B, n_pre, D), seed() and _reseed().
+    self.model is the network (self.gen and self.net: the names the decoders had for it)."""
+
+    def __init__(self, args, model, batch, device, D, graph, seed_shape=None, draw_width=0, text_width=None, audio=True, audio_sr=16000):
+        self.args, self.B, self.dev = args, batch, device
+        self.model = self.gen = self.net = model
+        T, n_pre = self.T, self.n_pre = args.n_poses, args.n_pre_poses
+        self.D = D
+        self.audio_len = int(T / args.motion_resampling_framerate * audio_sr)
+        # replay_draws (parity tests): the per-window eps / random z comes from self.draw, filled by the caller before each window, instead of
+        # the device RNG -- a static buffer, so a captured window replays with new contents
+        self.draw = torch.zeros(batch, draw_width, device=device) if draw_width else None
+        self.text = torch.zeros(batch, text_width or T, dtype=torch.int64, device=device)
+        self.audio = torch.zeros(batch, self.audio_len, device=device) if audio else None
+        self.pre = torch.zeros((batch,) + (seed_shape or (n_pre, D)), device=device)       # the next window's seed
+        self.tail = torch.zeros(batch, n_pre, D, device=device)
+        self.out = torch.zeros(batch, T, D, device=device)
+        self.use_graph, self.graph = graph, None
+        # the weights stand still for the lifetime of a decoder: weight-only operands are formed by the first window and kept
+        # (layers.FrozenWeights) -- a decoder must not outlive a change of the parameters
+        self.frozen = L.FrozenWeights()
+        self.win = self.active = self.graph_pooled = None              # window_pooled's state: made on its first use
+
+    def check_kept(self, model, batch, T, n_pre, replay_draws=False):
+        """Whether this decoder was built for `model` (the same object), `batch` rows, these window sizes and this replay_draws."""
+        return self.model is model and self.B == batch and (self.T, self.n_pre) == (T, n_pre) and bool(replay_draws) == (self.draw is not None)
+
+    def seed(self, seed_seq=None):
+        """`pre` of the first window: zeros, or the seed poses (B, >= n_pre, D) (synthesize.py:46-50)."""
+        self.pre.zero_()
+        if seed_seq is not None:
+            self.pre.copy_(torch.as_tensor(seed_seq, dtype=torch.float32, device=self.dev)[..., :self.n_pre, :])
+
+    def _reseed(self):
+        self.pre.copy_(self.tail)                                # the tail seeds the next window (:122-126)
+
+    def _forward(self, first):
+        res = self._model_forward()
+        if res is not None:
+            ops.copy2d(res.view(self.B * self.T, self.D), self.out.view(self.B * self.T, self.D))
+        if not first:                                            # cross-fade with the previous window's last frames (:145-153)
+            ops.window_blend(self.tail, self.out)
+        # hand-over: the last n_pre frames are kept for the next window's cross-fade (:146-147) and seed it (:122-124)
+        self.tail.copy_(self.out[:, self.T - self.n_pre:, :])    # strided device copy: data movement only
+        self._reseed()
+
+    def _forward_pooled(self):
+        ops.pool_handover(self._model_forward().view(self.B, self.T, self.D), self.out, self.tail, self.pre, self.win, self.active)
+
+    def _window(self, first):
+        with torch.no_grad(), self.frozen:
+            if first or not self.use_graph:
+                self._forward(first)
+            else:
+                if self.graph is None:
+                    self.graph = _capture(lambda: self._forward(False), (self.pre, self.tail, self.out))
+                self.graph.replay()
+        return self.out
+
+    def pool_buffers(self):
+        """(active, win): the static (B,) int32 device buffers window_pooled reads -- the mask of the rows to run and every row's window index."""
+        if self.win is None:
+            self.win = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+            self.active = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        return self.active, self.win
+
+    def window_pooled(self, active=None, win=None, draw=None):
+        """One window for the rows of a stream pool (StreamPool): the forward runs on all B rows, then ops.pool_handover gives every row with
+        active[b] != 0 its output, cross-fade (where the row's window counter win[b] > 0), tail, next seed and win[b] + 1; the other rows'
+        out / tail / seed / win keep every bit.  active, win: B integers copied into the static int32 buffers self.active / self.win
+        (pool_buffers), or None: the buffers as they are -- win counts on the device, so a pool passes it only to reset rows.  A row's first
+        window is like any other: from the first call on the window is ONE captured graph, self.graph_pooled (window() and its graph are
+        not touched).  The inputs are self.text / self.audio (/ self.vid), written in place."""
+        a_buf, w_buf = self.pool_buffers()
+        if active is not None:
+            a_buf.copy_(torch.as_tensor(active, dtype=torch.int32), non_blocking=True)
+        if win is not None:
+            w_buf.copy_(torch.as_tensor(win, dtype=torch.int32), non_blocking=True)
+        if draw is not None:
+            self.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
+        with torch.no_grad(), self.frozen:
+            if self.use_graph and self.graph_pooled is None:
                 # There is no eager first window here, so the one eager pass a capture needs in front of it (the weight-only operands of
                 # layers.FrozenWeights and the kernels' workspaces are made on first use and must stay OUT of the graph) runs with no row
                 # active: the hand-over then writes nothing
                 mask = a_buf.clone()
                 a_buf.zero_()
-                dec._forward_pooled()
+                self._forward_pooled()
                 a_buf.copy_(mask)
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                keep = [t.clone() for t in state + (w_buf,)]
-                pg_alive = torch.distributed.is_available() and torch.distributed.is_initialized()     # RCCL helper threads: see train_gan.GraphedGanStep
-                with torch.cuda.graph(graph, capture_error_mode="thread_local" if pg_alive else "global"):
-                    dec._forward_pooled()
-                for t, k in zip(state + (w_buf,), keep):                   # capture does not execute: restore state
-                    t.copy_(k)
-                dec.graph_pooled = graph
-            dec.graph_pooled.replay()
-    return dec.out
+                self.graph_pooled = _capture(self._forward_pooled, (self.pre, self.tail, self.out, w_buf))
+            if self.use_graph:
+                self.graph_pooled.replay()
+            else:
+                self._forward_pooled()
+        return self.out
 
 
-class WindowDecoder:
-    """Batched window forward with device-side seed hand-over and cross-fade; optional hipGraph capture."""
+class WindowDecoder(_WindowDecoderBase):
+    """Batched window forward of the multimodal_context generator with device-side seed hand-over and cross-fade; optional hipGraph capture.
+    The seed is pre_seq (B, T, D + 1): the seed poses with the constraint bit, zeros behind."""
 
-    def __init__(self, args, pose_decoder, batch, device, graph=True, replay_draws=False):
-        self.args, self.gen, self.B, self.dev = args, pose_decoder, batch, device
-        # replay_draws (parity tests): the per-window eps / random z comes from self.draw (B, 16), filled by the caller before each
-        # window, instead of the device RNG -- a static buffer, so a captured window replays with new contents
-        self.draw = torch.zeros(batch, 16, device=device) if replay_draws else None
-        self.T, self.n_pre = args.n_poses, args.n_pre_poses
-        self.D = pose_decoder.pose_dim
-        self.audio_len = int(self.T / args.motion_resampling_framerate * 16000)
-        self.pre_seq = torch.zeros(batch, self.T, self.D + 1, device=device)
-        self.text = torch.zeros(batch, self.T, dtype=torch.int64, device=device)
-        self.audio = torch.zeros(batch, self.audio_len, device=device)
+    def __init__(self, args, pose_decoder, batch, device, graph=True, replay_draws=False, audio_sr=16000):
+        super().__init__(args, pose_decoder, batch, device, pose_decoder.pose_dim, graph, seed_shape=(args.n_poses, pose_decoder.pose_dim + 1),
+                         draw_width=16 if replay_draws else 0, audio_sr=audio_sr)
+        self.pre_seq = self.pre
         self.vid = torch.zeros(batch, dtype=torch.int64, device=device)
-        self.out = torch.zeros(batch, self.T, self.D, device=device)
-        self.tail = torch.zeros(batch, self.n_pre, self.D, device=device)
         self.seedwin = torch.zeros(batch, self.T, self.D, device=device)
-        self.use_graph, self.graph = graph, None
-        # the generator's weights stand still for the lifetime of a decoder (one synthesis call): weight-only operands are formed by the first
-        # window and kept (layers.FrozenWeights) -- a decoder must not outlive a change of the parameters
-        self.frozen = L.FrozenWeights()
-        self.win = self.active = self.graph_pooled = None              # window_pooled's state: made on its first use
         pose_decoder.train(False)
-
-    def _forward_pooled(self):
-        eng = self.gen.engine
-        eng.rng.advance()
-        inject = None if self.draw is None else {"g.eps": self.draw, "g.z": self.draw}
-        vid = self.vid if eng.z_mode == "speaker" else None
-        res = eng.forward(self.pre_seq, self.text, self.audio, vid, training=False, inject=inject)
-        ops.pool_handover(res["out"].view(self.B, self.T, self.D), self.out, self.tail, self.pre_seq, self.win, self.active)
-
-    def window_pooled(self, active=None, win=None, draw=None):
-        """One window for the rows of a stream pool (StreamPool): the forward runs on all B rows, then ops.pool_handover gives every row with
-        active[b] != 0 its output, cross-fade (where the row's window counter win[b] > 0), tail, next seed and win[b] + 1; the other rows'
-        out / tail / pre_seq / win keep every bit.  active, win: B integers copied into the static int32 buffers self.active / self.win
-        (pool_buffers), or None: the buffers as they are -- win counts on the device, so a pool passes it only to reset rows.  A row's first
-        window is like any other: from the first call on the window is ONE captured graph, self.graph_pooled (window() and its graph are
-        not touched).  The inputs are self.text / self.audio / self.vid, written in place."""
-        return _window_pooled(self, (self.pre_seq, self.tail, self.out), active, win, draw)
-
-    def pool_buffers(self):
-        """(active, win): the static (B,) int32 device buffers window_pooled reads -- the mask of the rows to run and every row's window index."""
-        return _pool_buffers(self)
 
     def seed(self, seed_seq=None):
         """pre_seq of the first window: optional seed poses with the constraint bit (synthesize.py:46-50)."""
@@ -319,19 +377,16 @@ class WindowDecoder:
             self.pre_seq[:, :self.n_pre, :-1] = s[..., :self.n_pre, :]
             self.pre_seq[:, :self.n_pre, -1] = 1
 
-    def _forward(self, first):
+    def _reseed(self):
+        self.seedwin[:, :self.n_pre, :].copy_(self.tail)
+        ops.make_pre_seq(self.seedwin, self.pre_seq, self.n_pre)          # frames < n_pre + constraint bit, zeros elsewhere
+
+    def _model_forward(self):
         eng = self.gen.engine
         eng.rng.advance()                      # reparameterize() draws a fresh eps per window, also at inference
         inject = None if self.draw is None else {"g.eps": self.draw, "g.z": self.draw}
         vid = self.vid if eng.z_mode == "speaker" else None            # synthesize.py:67-74: no speaker input otherwise
-        res = eng.forward(self.pre_seq, self.text, self.audio, vid, training=False, inject=inject)
-        ops.copy2d(res["out"].view(self.B * self.T, self.D), self.out.view(self.B * self.T, self.D))
-        if not first:                                            # cross-fade with the previous window's last frames
-            ops.window_blend(self.tail, self.out)
-        # hand-over: the last n_pre frames are kept for the next window's cross-fade (:146-147) and seed it (:122-124)
-        self.tail.copy_(self.out[:, self.T - self.n_pre:, :])          # strided device copy: data movement only
-        self.seedwin[:, :self.n_pre, :].copy_(self.tail)
-        ops.make_pre_seq(self.seedwin, self.pre_seq, self.n_pre)          # frames < n_pre + constraint bit, zeros elsewhere
+        return eng.forward(self.pre_seq, self.text, self.audio, vid, training=False, inject=inject)["out"]
 
     def window(self, in_text, in_audio, vid, first, draw=None):
         """One window for the whole batch.  Inputs may be CPU or GPU tensors, or None: self.text / self.audio were filled in place
@@ -344,24 +399,10 @@ class WindowDecoder:
             self.vid.copy_(vid, non_blocking=True)
         if draw is not None:
             self.draw.copy_(draw, non_blocking=True)
-        with torch.no_grad(), self.frozen:
-            if not self.use_graph or first:
-                self._forward(first)
-            else:
-                if self.graph is None:
-                    torch.cuda.synchronize()
-                    self.graph = torch.cuda.CUDAGraph()
-                    keep = [t.clone() for t in (self.pre_seq, self.tail, self.out)]
-                    pg_alive = torch.distributed.is_available() and torch.distributed.is_initialized()     # RCCL helper threads: see train_gan.GraphedGanStep
-                    with torch.cuda.graph(self.graph, capture_error_mode="thread_local" if pg_alive else "global"):
-                        self._forward(False)
-                    for t, k in zip((self.pre_seq, self.tail, self.out), keep):   # capture does not execute: restore state
-                        t.copy_(k)
-                self.graph.replay()
-        return self.out
+        return self._window(first)
 
 
-class JointEmbedWindowDecoder:
+class JointEmbedWindowDecoder(_WindowDecoderBase):
     """WindowDecoder's counterpart for the joint-embedding baseline (args.model == 'joint_embedding', at most four utterances in lock-step):
     one window = ContextEncoder -> PoseDecoderGRU.forward_constant -> cross-fade -> tail copy -> `pre` hand-over, on static buffers, on the
     current stream, as one linear chain (nothing forks), so that the non-first window can be captured into a hipGraph once and replayed.
@@ -383,54 +424,14 @@ class JointEmbedWindowDecoder:
                              f"from {dec.pre_pose_net[0].in_features // dec.pose_dim} seed poses")
         if not 1 <= batch <= 4:
             raise ValueError(f"JointEmbedWindowDecoder: 1 to 4 utterances in lock-step (the few-row recurrence kernel's rows), got {batch}")
-        self.args, self.net, self.B, self.dev = args, net, batch, device
-        self.T, self.n_pre, self.D = T, n_pre, dec.pose_dim
-        self.audio_len = int(T / args.motion_resampling_framerate * audio_sr)
-        self.draw = torch.zeros(batch, 32, device=device) if replay_draws else None
-        self.text = torch.zeros(batch, T, dtype=torch.int64, device=device)
-        self.audio = torch.zeros(batch, self.audio_len, device=device)
-        self.pre = torch.zeros(batch, n_pre, self.D, device=device)
-        self.tail = torch.zeros(batch, n_pre, self.D, device=device)
-        self.out = torch.zeros(batch, T, self.D, device=device)
-        self.use_graph, self.graph = graph, None
-        # as WindowDecoder: weight-only operands are formed by the first window and kept -- a decoder must not outlive a change of the parameters
-        self.frozen = L.FrozenWeights()
-        self.win = self.active = self.graph_pooled = None              # window_pooled's state: made on its first use
+        super().__init__(args, net, batch, device, dec.pose_dim, graph, draw_width=32 if replay_draws else 0, audio_sr=audio_sr)
 
-    def _forward_pooled(self):
-        net = self.net
-        net.context_encoder.gru.few_row_eval = True
-        inject = None if self.draw is None else {"c.eps": self.draw}
-        latent, _, _ = net.context_encoder(self.text, self.audio, inject=inject)
-        res = net.decoder.forward_constant(latent, self.pre)
-        ops.pool_handover(res, self.out, self.tail, self.pre, self.win, self.active)
-
-    def window_pooled(self, active=None, win=None, draw=None):
-        """WindowDecoder.window_pooled for this decoder: the forward on all B rows, then ops.pool_handover (seed layout `pre`) for the rows with
-        active[b] != 0; one captured graph, self.graph_pooled, from the first call on.  The inputs are self.text / self.audio, in place."""
-        return _window_pooled(self, (self.pre, self.tail, self.out), active, win, draw)
-
-    def pool_buffers(self):
-        """(active, win): the static (B,) int32 device buffers window_pooled reads."""
-        return _pool_buffers(self)
-
-    def seed(self, seed_seq=None):
-        """`pre` of the first window: zeros, or the seed poses (B, >= n_pre, D) (synthesize.py:46-50)."""
-        self.pre.zero_()
-        if seed_seq is not None:
-            self.pre.copy_(torch.as_tensor(seed_seq, dtype=torch.float32, device=self.dev)[..., :self.n_pre, :])
-
-    def _forward(self, first):
+    def _model_forward(self):
         net = self.net
         net.context_encoder.gru.few_row_eval = True              # one launch per layer (EmbeddingNet.synthesize sets it the same way)
         inject = None if self.draw is None else {"c.eps": self.draw}       # None: the encoder advances its counter RNG on the device
         latent, _, _ = net.context_encoder(self.text, self.audio, inject=inject)
-        res = net.decoder.forward_constant(latent, self.pre)
-        ops.copy2d(res.view(self.B * self.T, self.D), self.out.view(self.B * self.T, self.D))
-        if not first:                                            # cross-fade with the previous window's last frames (:145-153)
-            ops.window_blend(self.tail, self.out)
-        self.tail.copy_(self.out[:, self.T - self.n_pre:, :])    # strided device copy: kept for the next cross-fade ...
-        self.pre.copy_(self.tail)                                # ... and seeds the next window (:122-126)
+        return net.decoder.forward_constant(latent, self.pre)
 
     def window(self, in_text, in_audio, first, draw=None):
         """One window for the whole batch.  Inputs may be CPU or GPU tensors, or None: self.text / self.audio were filled in place
@@ -441,24 +442,10 @@ class JointEmbedWindowDecoder:
             self.audio.copy_(in_audio, non_blocking=True)
         if draw is not None:
             self.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
-        with torch.no_grad(), self.frozen:
-            if not self.use_graph or first:
-                self._forward(first)
-            else:
-                if self.graph is None:
-                    torch.cuda.synchronize()
-                    self.graph = torch.cuda.CUDAGraph()
-                    keep = [t.clone() for t in (self.pre, self.tail, self.out)]
-                    pg_alive = torch.distributed.is_available() and torch.distributed.is_initialized()     # RCCL helper threads: see train_gan.GraphedGanStep
-                    with torch.cuda.graph(self.graph, capture_error_mode="thread_local" if pg_alive else "global"):
-                        self._forward(False)
-                    for t, k in zip((self.pre, self.tail, self.out), keep):       # capture does not execute: restore state
-                        t.copy_(k)
-                self.graph.replay()
-        return self.out
+        return self._window(first)
 
 
-class Seq2SeqWindowDecoder:
+class Seq2SeqWindowDecoder(_WindowDecoderBase):
     """The window decoders' counterpart for the Seq2Seq baseline (args.model == 'seq2seq', at most four utterances in lock-step): one window =
     embedding -> per encoder layer one GEMM entry + the recurrence -> direction sum, h0 = encoder_hidden[:n_layers] -> keys GEMM -> the
     one-launch decoder loop (csrc/seq2seq_decode.hip) -> cross-fade -> tail copy -> `pre` hand-over, on static buffers, on the current
@@ -471,6 +458,7 @@ class Seq2SeqWindowDecoder:
 
     row_local_encoder: the encoder's recurrence as ONE launch per layer (csrc/seq2seq_encode.hip) instead of one launch per time step and
     layer -- Te of them, all but a row's length idle.  Default True: the measured choice at one row.
+    No random draw, no audio buffer (audio_len is the stream's window; the model never sees the samples) and no pooled window in this model.
     Host-side validation raises ValueError before anything touches the GPU."""
 
     def __init__(self, args, net, batch, device, graph=True, max_words=32, row_local_encoder=True, audio_sr=16000):
@@ -492,27 +480,14 @@ class Seq2SeqWindowDecoder:
             raise ValueError(f"Seq2SeqWindowDecoder: 1 to 4 utterances in lock-step (the rows of a stream), got {batch}")
         if not 0 <= max_words <= 126:
             raise ValueError(f"Seq2SeqWindowDecoder: 0 <= max_words <= 126 (the kernels take lists of at most 128 entries), got {max_words}")
-        self.args, self.net, self.B, self.dev = args, net, batch, device
-        self.T, self.n_pre, self.D = T, n_pre, gen.output_size
         self.max_words, self.Te, self.row_local = int(max_words), int(max_words) + 2, bool(row_local_encoder)
-        self.audio_len = int(T / args.motion_resampling_framerate * audio_sr)      # (the stream's window; the model never sees the samples)
-        self.draw = None                                                           # (no random draw in this model)
-        self.text = torch.zeros(batch, self.Te, dtype=torch.int64, device=device)
+        super().__init__(args, net, batch, device, gen.output_size, graph, text_width=self.Te, audio=False, audio_sr=audio_sr)
         self.len = torch.full((batch,), 2, dtype=torch.int64, device=device)
-        self.pre = torch.zeros(batch, n_pre, self.D, device=device)
-        self.tail = torch.zeros(batch, n_pre, self.D, device=device)
-        self.out = torch.zeros(batch, T, self.D, device=device)
-        self.use_graph, self.graph = graph, None
-        # as WindowDecoder: weight-only operands are formed by the first window and kept -- a decoder must not outlive a change of the parameters
-        self.frozen = L.FrozenWeights()
 
-    def seed(self, seed_seq=None):
-        """`pre` of the first window: zeros, or the seed poses (B, >= n_pre, D) (synthesize.py:46-50)."""
-        self.pre.zero_()
-        if seed_seq is not None:
-            self.pre.copy_(torch.as_tensor(seed_seq, dtype=torch.float32, device=self.dev)[..., :self.n_pre, :])
+    def check_kept(self, model, batch, T, n_pre, max_words=32, row_local_encoder=True):
+        return super().check_kept(model, batch, T, n_pre) and self.max_words == max_words and self.row_local == bool(row_local_encoder)
 
-    def _forward(self, first):
+    def _model_forward(self):
         from .rnn import _EmbedFn, _SumHalvesFn
         enc, dec = self.net.encoder, self.net.decoder.decoder
         was = enc.gru.row_local_eval
@@ -523,11 +498,7 @@ class Seq2SeqWindowDecoder:
         finally:
             enc.gru.row_local_eval = was
         enc_bt = _SumHalvesFn.apply(y)                                               # (B, Te, H): exact zeros behind every row's length
-        dec.decode_eval_static(enc_bt, hidden[:dec.n_layers], self.pre, self.T, self.n_pre, self.len, self.out)
-        if not first:                                            # cross-fade with the previous window's last frames (:145-153)
-            ops.window_blend(self.tail, self.out)
-        self.tail.copy_(self.out[:, self.T - self.n_pre:, :])    # strided device copy: kept for the next cross-fade ...
-        self.pre.copy_(self.tail)                                # ... and seeds the next window (:122-126)
+        dec.decode_eval_static(enc_bt, hidden[:dec.n_layers], self.pre, self.T, self.n_pre, self.len, self.out)    # (writes self.out itself)
 
     def window(self, in_text=None, in_len=None, first=False):
         """One window for the whole batch.  in_text (B, Te) / in_len (B,) int64, CPU or GPU tensors, or None: self.text / self.len were
@@ -536,21 +507,16 @@ class Seq2SeqWindowDecoder:
             self.text.copy_(in_text, non_blocking=True)
         if in_len is not None:
             self.len.copy_(in_len, non_blocking=True)
-        with torch.no_grad(), self.frozen:
-            if not self.use_graph or first:
-                self._forward(first)
-            else:
-                if self.graph is None:
-                    torch.cuda.synchronize()
-                    self.graph = torch.cuda.CUDAGraph()
-                    keep = [t.clone() for t in (self.pre, self.tail, self.out)]
-                    pg_alive = torch.distributed.is_available() and torch.distributed.is_initialized()     # RCCL helper threads: see train_gan.GraphedGanStep
-                    with torch.cuda.graph(self.graph, capture_error_mode="thread_local" if pg_alive else "global"):
-                        self._forward(False)
-                    for t, k in zip((self.pre, self.tail, self.out), keep):       # capture does not execute: restore state
-                        t.copy_(k)
-                self.graph.replay()
-        return self.out
+        return self._window(first)
+
+
+def _kept_decoder(who, kind, d, model, batch, T, n_pre, rows="row(s)", **built_for):
+    """The kept window decoder d if `who` may run on it: a `kind` built for this model, row count, window and built_for (check_kept); else
+    ValueError in who's name."""
+    if not (isinstance(d, kind) and d.check_kept(model, batch, T, n_pre, **built_for)):
+        raise ValueError(f"{who}: window_decoder must be a {kind.__name__} built for this model, {batch} {rows}, (n_poses, n_pre_poses) = {(T, n_pre)}"
+                         + "".join(f", {k} = {v}" for k, v in built_for.items()))
+    return d
 
 
 def _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, window_decoder,
@@ -562,15 +528,12 @@ def _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, w
     if B > 4:
         raise ValueError(f"window_decoder runs at most 4 utterances in lock-step, got {B}")
     if isinstance(window_decoder, JointEmbedWindowDecoder):
-        dec = window_decoder
-        if dec.net is not pose_decoder or dec.B != B or (dec.T, dec.n_pre) != (T, n_pre) or (eps_list is not None) != (dec.draw is not None):
-            raise ValueError(f"window_decoder: the decoder was built for another model, {dec.B} utterance(s), (n_poses, n_pre_poses) = "
-                             f"{(dec.T, dec.n_pre)} or replay_draws = {dec.draw is not None}; this call has {B} utterance(s), {(T, n_pre)} and "
-                             f"eps_list {'given' if eps_list is not None else 'absent'}")
+        dec = _kept_decoder("generate_gestures_batch", JointEmbedWindowDecoder, window_decoder, pose_decoder, B, T, n_pre, rows="utterance(s)",
+                            replay_draws=eps_list is not None)
     else:
         dec = JointEmbedWindowDecoder(args, pose_decoder, B, next(pose_decoder.parameters()).device, graph=False, replay_draws=eps_list is not None,
                                       audio_sr=audio_sr)
-    dec.seed(None if seed_seqs is None else np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]))
+    dec.seed(_seed_rows(seed_seqs, n_pre))
     stride = T - n_pre
     n_win = [num_windows(len(a) / audio_sr, T, n_pre, args.motion_resampling_framerate) for a in audios]
     ub = None if device_opts is None else UtteranceBatch(args, lang_model, audios, words_list, dec.dev, audio_sr)
@@ -580,19 +543,14 @@ def _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, w
             ub.stage(i, dec.text, dec.audio)
             t_in = a_in = None
         else:
-            a_np, t_np = [], []
-            for b in range(B):
-                a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], min(i, n_win[b] - 1), audio_sr)   # finished utterances idle
-                a_np.append(a); t_np.append(ids)
-            t_in, a_in = torch.from_numpy(np.stack(t_np)), torch.from_numpy(np.stack(a_np))
+            t_in, a_in = _host_window_batch(args, lang_model, audios, words_list, n_win, i, audio_sr)
         out = dec.window(t_in, a_in, first=(i == 0), draw=None if eps_list is None else eps_list[i])
         for b in range(B):
             if i < n_win[b]:                                                     # an idling utterance's frames are not written
                 total[b, i * stride:i * stride + T, :].copy_(out[b])
     if ub is not None:
         return _device_result(ub, total, *device_opts)
-    res = total.cpu().numpy()
-    return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
+    return _rows_result(total, n_win, stride, n_pre)
 
 
 def spec_slice_length(n_poses=34, fps=15, sr=16000):
@@ -654,6 +612,13 @@ def projection_tables(n_pre):
     starts at frame 0 and is as long as the others') and 'fade' (2 n_pre points, quadratic, weight 5 on both ends: fade_out_to_mean)."""
     w = np.ones(2 * n_pre); w[0] = 5; w[-1] = 5
     return dict(smooth=_projection(3 * n_pre, 3), fade=_projection(2 * n_pre, 2, w))
+
+
+def _projection_device(n_pre, device):
+    """projection_tables(n_pre), 'smooth' then 'fade', as one fp64 device vector: ops.utterance_finish's proj.  Built once per utterance batch,
+    stream or pool, and kept."""
+    t = projection_tables(n_pre)
+    return torch.from_numpy(np.concatenate([t["smooth"].ravel(), t["fade"].ravel()])).to(device)
 
 
 def _fade_start_frame(n_frames, end_padding_samples, args, audio_sr=16000):
@@ -766,8 +731,7 @@ class UtteranceBatch:
             fade_start = torch.tensor(starts, dtype=torch.int32, device=self.dev)
         if (smooth or fade_out) and 1 <= n <= 8:                   # (outside: the library refuses the call and names its envelope)
             if self._tables is None:
-                t = projection_tables(n)
-                self._tables = torch.from_numpy(np.concatenate([t["smooth"].ravel(), t["fade"].ravel()])).to(self.dev)
+                self._tables = _projection_device(n, self.dev)
             tab = self._tables
         if joints:
             mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
@@ -810,7 +774,7 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
     D = pose_decoder.final_out.out_channels
     pre = torch.zeros(B, n_pre, D, device=dev)
     if seed_seqs is not None:                                                   # synthesize.py:46-50
-        pre.copy_(torch.as_tensor(np.stack([np.asarray(s)[:n_pre] for s in seed_seqs]), dtype=torch.float32))
+        pre.copy_(torch.as_tensor(_seed_rows(seed_seqs, n_pre), dtype=torch.float32))
     tail = torch.zeros(B, n_pre, D, device=dev)
     ub = None
     if device_opts is not None:                                                 # the on_device path: slices cut by ops.spec_stage from the packed spectrograms
@@ -845,8 +809,7 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
         pose_decoder.train(was_training)
     if ub is not None:
         return _device_result(ub, total, *device_opts)
-    res = total.cpu().numpy()
-    return [res[b, :n_win[b] * stride + n_pre] for b in range(B)]
+    return _rows_result(total, n_win, stride, n_pre)
 
 
 def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, vids=None, seed_seqs=None, audio_sr=16000,
@@ -879,17 +842,17 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
         outs = generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, vids, seed_seqs, audio_sr, graph, _draws, spec_pad_mode,
                                        eps_list, window_decoder)
         return [fade_out_to_mean(o, end_padding_samples(args, len(a), audio_sr), args, audio_sr) for o, a in zip(outs, audios)]
-    if window_decoder and getattr(args, "model", "multimodal_context") != "joint_embedding":
-        raise ValueError(f"window_decoder=True is the joint_embedding model's window decoder; args.model is {getattr(args, 'model', 'multimodal_context')!r} "
+    if window_decoder and model != "joint_embedding":
+        raise ValueError(f"window_decoder=True is the joint_embedding model's window decoder; args.model is {model!r} "
                          "(the multimodal_context model always runs on its WindowDecoder)")
-    if getattr(args, "model", "multimodal_context") == "speech2gesture":
+    if model == "speech2gesture":
         return _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pad_mode, dopts)
-    if getattr(args, "model", "multimodal_context") == "seq2seq":             # audio matters through its length only; vids, graph unused
+    if model == "seq2seq":             # audio matters through its length only; vids, graph unused
         if on_device:
             return _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, dopts)
         outs, n_win = _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr)
         return [seq2seq_smooth(o, n, args.n_poses, args.n_pre_poses) for o, n in zip(outs, n_win)]
-    if getattr(args, "model", "multimodal_context") == "joint_embedding":
+    if model == "joint_embedding":
         if window_decoder:
             return _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, window_decoder,
                                                       dopts)
@@ -898,7 +861,7 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
     B = len(audios)
     n_win = [num_windows(len(a) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate) for a in audios]
     dec = WindowDecoder(args, pose_decoder, B, dev, graph=graph, replay_draws=_draws is not None)
-    dec.seed(None if seed_seqs is None else np.stack([np.asarray(s)[:args.n_pre_poses] for s in seed_seqs]))
+    dec.seed(_seed_rows(seed_seqs, args.n_pre_poses))
     vid = None
     if args.z_type == "speaker":                                                       # synthesize.py:67-74
         vids = [None] * B if vids is None else list(vids)
@@ -914,20 +877,14 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
             ub.stage(i, dec.text, dec.audio)
             out = dec.window(None, None, vid if i == 0 else None, first=(i == 0), draw=None if _draws is None else _draws[i])
         else:
-            a_np, t_np = [], []
-            for b in range(B):
-                j = min(i, n_win[b] - 1)                               # finished utterances idle on their last window
-                a, ids, _ = window_inputs(args, lang_model, audios[b], words_list[b], j, audio_sr)
-                a_np.append(a); t_np.append(ids)
-            out = dec.window(torch.from_numpy(np.stack(t_np)), torch.from_numpy(np.stack(a_np)), vid, first=(i == 0),
+            out = dec.window(*_host_window_batch(args, lang_model, audios, words_list, n_win, i, audio_sr), vid, first=(i == 0),
                              draw=None if _draws is None else _draws[i])
         # out_list[-1][:-n_pre] + blended window == write the whole window at frame i*stride (its first n_pre frames overwrite
         # the previous window's last n_pre frames with the cross-faded values)
         total[:, i * stride:i * stride + args.n_poses, :].copy_(out)
     if ub is not None:
         return _device_result(ub, total, *dopts)
-    res = total.cpu().numpy()
-    return [res[b, :n_win[b] * stride + args.n_pre_poses] for b in range(B)]
+    return _rows_result(total, n_win, stride, args.n_pre_poses)
 
 
 def fade_out_to_mean(out_dir_vec, end_padding_samples, args, audio_sr=16000):
@@ -1016,7 +973,143 @@ def word_records(args, lang_model, words):
     return out
 
 
-class GestureStream:
+_STREAM_DECODERS = {"multimodal_context": WindowDecoder, "joint_embedding": JointEmbedWindowDecoder, "seq2seq": Seq2SeqWindowDecoder}
+
+
+class _StreamCore:
+    """What the streams (rows on one clock) and the pool (a clock per row) share: the constructor's checks and set-up, a row's word-record
+    bookkeeping, the joints of a push and the closing window.  B rows; per row b, self._n_rec[b] counts the records pushed so far and
+    self._live[b] lists (index in the row's record sequence, window) of the records a window may still need."""
+    _models = ("multimodal_context", "joint_embedding")
+    _rows = "rows"
+    _smooth_closing = False                          # whether close() smooths the window it ran (Seq2SeqGestureStream)
+
+    def _refusal(self, model):
+        return {"seq2seq": "the seq2seq model cannot stream: its smoothing rewrites frames of a window after the next window has run -- in the "
+                           "offline order only: synthesize.Seq2SeqGestureStream smooths every window as it runs",
+                "speech2gesture": "the speech2gesture model cannot stream: its log-mel spectrogram is padded over the whole utterance"
+                }.get(model, f"unknown model {model!r}")
+
+    def __init__(self, args, pose_decoder, lang_model, rows, audio_sr, max_chunk, word_ring, ring, window_decoder, graph, **built_for):
+        """built_for: what the window decoder is built with besides the model, the rows and the window (replay_draws; seq2seq: max_words,
+        row_local_encoder) -- given to a new decoder, checked on a kept one.  Every refusal comes before anything touches the model."""
+        who, model = type(self).__name__, getattr(args, "model", "multimodal_context")
+        if model not in self._models:
+            raise ValueError(f"{who}: {self._refusal(model)}")
+        if not 1 <= rows <= 4:
+            raise ValueError(f"{who}: 1 to 4 {self._rows}, got {rows}")
+        if max_chunk < 1:
+            raise ValueError(f"{who}: max_chunk = {max_chunk}")
+        self.args, self.model, self.lang, self.B, self.audio_sr, self.max_chunk = args, model, lang_model, int(rows), audio_sr, int(max_chunk)
+        T, n_pre = self.T, self.n_pre = args.n_poses, args.n_pre_poses
+        self.stride = T - n_pre
+        self.S, self.A = stream_geometry(args, audio_sr)
+        R = self.A + self.max_chunk if ring is None else int(ring)
+        if R < self.A + self.max_chunk:
+            raise ValueError(f"{who}: a ring of {R} samples; window + max_chunk = {self.A + self.max_chunk} are needed")
+        dev = self.dev = next(pose_decoder.parameters()).device
+        kind = _STREAM_DECODERS[model]
+        if window_decoder is not None:
+            self.dec = _kept_decoder(who, kind, window_decoder, pose_decoder, self.B, T, n_pre, **built_for)
+        else:
+            self.dec = kind(args, pose_decoder, self.B, dev, graph=graph, audio_sr=audio_sr, **built_for)
+        if self.dec.audio_len != self.A:
+            raise ValueError(f"{who}: the window decoder takes {self.dec.audio_len} samples, the stream's window is {self.A} (audio_sr = {audio_sr})")
+        self.D = self.dec.D
+        self.state = ops.stream_state(self.B, R, self.S, self.A, word_ring, T, dev)
+        self.chunk_buf = torch.zeros(self.B, self.max_chunk, device=dev)
+        self._live, self._n_rec = [[] for _ in range(self.B)], [0] * self.B
+        self._ones = torch.ones(self.B, dtype=torch.int32, device=dev)
+        self._mean = self._tables = None                 # the fp64 mean and the projection tables on the device: made once, on first use
+
+    # -------------------------------------------------------------------------------------------------------------- host bookkeeping (integers)
+    def _row_records(self, words, next_window):
+        """One row's word list -> (its records of windows that have not run yet, in word order; how many words are late for a window)."""
+        keep, late = [], 0
+        for w in words or ():
+            rec = word_records(self.args, self.lang, [w])
+            late += any(r[0] < next_window for r in rec)
+            keep += [r for r in rec if r[0] >= next_window]
+        return keep, late
+
+    def _live_slots(self, b):
+        """Word-ring slots of row b from the oldest record a window still needs to the newest."""
+        return self._n_rec[b] - self._live[b][0][0] if self._live[b] else 0
+
+    def _commit_records(self, rows):
+        """rows (per row, the records of _row_records) are on their way to the device: the (B, 1 + 3 m_max) int32 table -- per row a count and
+        that many triples -- uploaded, or None without records; and m_max."""
+        m_max = max(len(r) for r in rows)
+        if m_max == 0:
+            return None, 0
+        table = np.zeros((self.B, 1 + 3 * m_max), dtype=np.int32)
+        for b, r in enumerate(rows):
+            table[b, 0] = len(r)
+            table[b, 1:1 + 3 * len(r)] = np.asarray(r, dtype=np.int32).reshape(-1)
+            self._live[b] += [(self._n_rec[b] + k, rec[0]) for k, rec in enumerate(r)]
+            self._n_rec[b] += len(r)
+        return torch.from_numpy(table).to(self.dev, non_blocking=True), m_max
+
+    def _ran(self, b, next_window):
+        """Row b has run its windows below next_window: their records are no longer needed."""
+        self._live[b] = [r for r in self._live[b] if r[1] >= next_window]
+
+    def _mean_dev(self):
+        if self._mean is None:
+            self._mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
+        return self._mean
+
+    def _joints(self, buf, k):
+        """fp64 joint positions (B, k * stride, 10, 3) of the frames a stacked buffer of k windows finalises."""
+        jt = torch.zeros(self.B, k * self.stride, 10, 3, dtype=torch.float64, device=self.dev)
+        ops.utterance_finish(buf, self._ones, k, self.T, self.n_pre, mean=self._mean_dev(), joints=jt)
+        return jt
+
+    @staticmethod
+    def _result(frames, jt, numpy):
+        if numpy:
+            frames, jt = frames.cpu().numpy(), None if jt is None else jt.cpu().numpy()
+        return frames if jt is None else (frames, jt)
+
+    def _windows_left(self, what, pushed, next_window):
+        """(n_win, k): the reference's window count of `pushed` samples and the k in (0, 1) windows close() still has to run -- windows run as
+        soon as they are complete, so at most the padded last one is left."""
+        n_win = num_windows(pushed / self.audio_sr, self.T, self.n_pre, self.args.motion_resampling_framerate)
+        if n_win - next_window not in (0, 1):
+            raise RuntimeError(f"{what}: {next_window} windows ran, the reference counts {n_win} for {pushed} samples")
+        return n_win, n_win - next_window
+
+    def _closing(self, out, pushed, n_win, closing_window, fade_out, joints, smooth=False):
+        """The finish of a stream's last window: out (b, T, D) -- rows of dec.out, which holds that window whether close() ran it
+        (closing_window) or a push did (then it was complete and its first `stride` frames are out already) -- goes through
+        ops.utterance_finish on a one-window buffer of its own.  Returns the remaining (frames, joint positions or None), device views."""
+        b, T, D, st, n = out.shape[0], self.T, self.D, self.stride, self.n_pre
+        fin = torch.zeros(b, T + 2 * n, D, device=self.dev)
+        ops.copy2d(out.view(b, T * D), fin.view(b, (T + 2 * n) * D)[:, :T * D])
+        length, fade_start, tab, jt = T, None, None, None
+        if fade_out:
+            # the padding is at most a window, so int(pad / sr * fps) <= n_poses and start_frame >= n_win * stride + n_pre - n_poses = (n_win - 1) * stride:
+            # the fade-out starts inside the last window.  That window has been emitted only if it was complete, and then pad = 0 and the fade
+            # starts at the utterance's end: no emitted frame changes
+            start = _fade_start_frame(n_win * st + n, end_padding_samples(self.args, pushed, self.audio_sr), self.args, self.audio_sr)
+            rel = start - (n_win - 1) * st
+            assert 0 <= rel <= T and (closing_window or rel == T)
+            length = max(T, rel + 2 * n)
+            fade_start = torch.tensor([rel] * b, dtype=torch.int32, device=self.dev)
+        if (smooth or fade_out) and 1 <= n <= 8:                    # (outside: the library refuses the call and names its envelope)
+            if self._tables is None:
+                self._tables = _projection_device(n, self.dev)
+            tab = self._tables
+        if joints:
+            jt = torch.zeros(b, T + 2 * n, 10, 3, dtype=torch.float64, device=self.dev)
+        if smooth or fade_out or joints:
+            ops.utterance_finish(fin, self._ones[:b], 1, T, n, smooth=smooth, proj=tab, fade_start=fade_start, mean=self._mean_dev() if joints else None,
+                                 joints=jt)
+        skip = 0 if closing_window else st
+        return fin[:, skip:length], None if jt is None else jt[:, skip:length]
+
+
+class GestureStream(_StreamCore):
     """Gestures window by window while the audio is still arriving (args.model 'multimodal_context' on a WindowDecoder, 'joint_embedding' on a
     JointEmbedWindowDecoder; 1 to 4 rows that share a clock).  push(chunk, words) appends samples and words to device-resident rings
     (csrc/stream.hip), runs every window that has become complete -- window w is complete when w * S + A samples have been pushed -- and returns
@@ -1048,121 +1141,55 @@ class GestureStream:
     push() never reads from the device.  A refused push (ValueError) leaves the stream as it was; a close that raised can be called again."""
 
     def __init__(self, args, pose_decoder, lang_model, batch=1, vids=None, seed_seqs=None, audio_sr=16000, max_chunk=16000, _draws=None, eps_list=None,
-                 window_decoder=None, graph=True, word_ring=256, ring=None):
+                 window_decoder=None, graph=True, word_ring=256, ring=None, _built_for=None):
         model = getattr(args, "model", "multimodal_context")
-        if model == "seq2seq":
-            raise ValueError("GestureStream: the seq2seq model cannot stream: its smoothing rewrites frames of a window after the next window has run"
-                             " -- in the offline order only: synthesize.Seq2SeqGestureStream smooths every window as it runs")
-        if model == "speech2gesture":
-            raise ValueError("GestureStream: the speech2gesture model cannot stream: its log-mel spectrogram is padded over the whole utterance")
-        if model not in ("multimodal_context", "joint_embedding"):
-            raise ValueError(f"GestureStream: unknown model {model!r}")
-        if not 1 <= batch <= 4:
-            raise ValueError(f"GestureStream: 1 to 4 rows, got {batch}")
-        if max_chunk < 1:
-            raise ValueError(f"GestureStream: max_chunk = {max_chunk}")
-        self.args, self.model, self.lang, self.B, self.audio_sr, self.max_chunk = args, model, lang_model, batch, audio_sr, int(max_chunk)
-        self.T, self.n_pre = args.n_poses, args.n_pre_poses
-        self.stride = self.T - self.n_pre
-        self.S, self.A = stream_geometry(args, audio_sr)
-        dev = self.dev = next(pose_decoder.parameters()).device
-        draws = _draws if model == "multimodal_context" else eps_list
-        if window_decoder is not None:
-            kind = WindowDecoder if model == "multimodal_context" else JointEmbedWindowDecoder
-            d = window_decoder
-            if not isinstance(d, kind) or (d.gen if kind is WindowDecoder else d.net) is not pose_decoder or d.B != batch or (d.T, d.n_pre) != (self.T, self.n_pre) \
-                    or (draws is not None) != (d.draw is not None):
-                raise ValueError(f"GestureStream: window_decoder must be a {kind.__name__} built for this model, {batch} row(s), (n_poses, n_pre_poses) = "
-                                 f"{(self.T, self.n_pre)} and replay_draws = {draws is not None}")
-            self.dec = d
-        elif model == "multimodal_context":
-            self.dec = WindowDecoder(args, pose_decoder, batch, dev, graph=graph, replay_draws=draws is not None)
-        else:
-            self.dec = JointEmbedWindowDecoder(args, pose_decoder, batch, dev, graph=graph, replay_draws=draws is not None, audio_sr=audio_sr)
-        if self.dec.audio_len != self.A:
-            raise ValueError(f"GestureStream: the window decoder takes {self.dec.audio_len} samples, the stream's window is {self.A} (audio_sr = {audio_sr})")
-        self.D, self.draws = self.dec.D, draws
-        self.dec.seed(None if seed_seqs is None else np.stack([np.asarray(s)[:self.n_pre] for s in seed_seqs]))
+        self.draws = _draws if model == "multimodal_context" else eps_list
+        super().__init__(args, pose_decoder, lang_model, batch, audio_sr, max_chunk, word_ring, ring, window_decoder, graph,
+                         **(dict(replay_draws=self.draws is not None) if _built_for is None else _built_for))
+        self.dec.seed(_seed_rows(seed_seqs, self.n_pre))
         self.vid = None
         if model == "multimodal_context" and args.z_type == "speaker":                  # synthesize.py:67-74
             vids = [None] * batch if vids is None else list(vids)
             self.vid = torch.as_tensor([v if v else random.randrange(pose_decoder.z_obj.n_words) for v in vids], dtype=torch.int64)
-        R = self.A + self.max_chunk if ring is None else int(ring)
-        if R < self.A + self.max_chunk:
-            raise ValueError(f"GestureStream: a ring of {R} samples; window + max_chunk = {self.A + self.max_chunk} are needed")
-        self.state = ops.stream_state(batch, R, self.S, self.A, word_ring, self.T, dev)
-        self.chunk_buf = torch.zeros(batch, self.max_chunk, device=dev)
         self.pushed = self.next_window = self.late_words = 0
-        self.closed = False
-        self._live = [[] for _ in range(batch)]          # per row: (index of the record in the row's sequence, window) of records a window may still need
-        self._n_rec = [0] * batch
-        self._ones = torch.ones(batch, dtype=torch.int32, device=dev)
-        self._mean, self._closing_window = None, False
+        self.closed = self._closing_window = False
 
-    # -------------------------------------------------------------------------------------------------------------- host bookkeeping (integers)
     def _records(self, words):
         """words (one list per row) -> (recs tensor or None, m_max, words_live): the records of windows that have not run yet."""
         if words is None:
             return None, 0, 0
         if len(words) != self.B:
-            raise ValueError(f"GestureStream.push: words for {len(words)} row(s), the stream has {self.B}")
-        rows, late = [], 0
-        for b, wl in enumerate(words):
-            keep = []
-            for w in wl or ():
-                rec = word_records(self.args, self.lang, [w])
-                late += any(r[0] < self.next_window for r in rec)
-                keep += [r for r in rec if r[0] >= self.next_window]
-            rows.append(keep)
+            raise ValueError(f"{type(self).__name__}.push: words for {len(words)} row(s), the stream has {self.B}")
+        rows, late = zip(*(self._row_records(wl, self.next_window) for wl in words))
         m_max = max(len(r) for r in rows)
-        if m_max == 0:
-            self.late_words += late
-            return None, 0, 0
-        live = max(n - l[0][0] if l else 0 for n, l in zip(self._n_rec, self._live))
+        live = max(self._live_slots(b) for b in range(self.B)) if m_max else 0
         if live + m_max > self.state["W"]:
-            raise ValueError(f"GestureStream.push: {m_max} word record(s) on top of {live} a window still needs exceed the word ring's capacity "
+            raise ValueError(f"{type(self).__name__}.push: {m_max} word record(s) on top of {live} a window still needs exceed the word ring's capacity "
                              f"{self.state['W']} (word_ring=...)")
-        self.late_words += late                                      # (state changes only once the push can no longer be refused here)
-        table = np.zeros((self.B, 1 + 3 * m_max), dtype=np.int32)
-        for b, r in enumerate(rows):
-            table[b, 0] = len(r)
-            table[b, 1:1 + 3 * len(r)] = np.asarray(r, dtype=np.int32).reshape(-1)
-            self._live[b] += [(self._n_rec[b] + k, rec[0]) for k, rec in enumerate(r)]
-            self._n_rec[b] += len(r)
-        return torch.from_numpy(table).to(self.dev, non_blocking=True), m_max, live
+        self.late_words += sum(late)                                 # (state changes only once the push can no longer be refused here)
+        return self._commit_records(rows) + (live,)
 
-    def _run(self, k):
-        """The next k windows, stacked as the offline loop stacks them: (B, k * stride + n_pre, D)."""
+    def _stage_and_run(self, i):
+        """Window i: its inputs cut from the rings straight into the decoder's static buffers, then the decoder."""
+        ops.stream_stage(self.state, self.dec.text, self.dec.audio)
+        draw = None if self.draws is None else self.draws[i]
+        if self.model == "multimodal_context":
+            return self.dec.window(None, None, self.vid if i == 0 else None, first=(i == 0), draw=draw)
+        return self.dec.window(None, None, first=(i == 0), draw=draw)
+
+    def _run(self, k, smooth=False):
+        """The next k windows, stacked as the offline loop stacks them: (B, k * stride + n_pre, D).  (smooth: Seq2SeqGestureStream's post-step.)"""
         B, T, D, st = self.B, self.T, self.D, self.stride
         F = k * st + self.n_pre
         buf = torch.empty(B, F, D, device=self.dev)                 # (the windows tile it)
         for j in range(k):
-            i = self.next_window
-            ops.stream_stage(self.state, self.dec.text, self.dec.audio)               # straight into the decoder's static buffers
-            draw = None if self.draws is None else self.draws[i]
-            if self.model == "multimodal_context":
-                out = self.dec.window(None, None, self.vid if i == 0 else None, first=(i == 0), draw=draw)
-            else:
-                out = self.dec.window(None, None, first=(i == 0), draw=draw)
+            out = self._stage_and_run(self.next_window)
             ops.copy2d(out.view(B, T * D), buf.view(B, F * D)[:, j * st * D:(j * st + T) * D])
             ops.counter_inc(self.state["win"])
             self.next_window += 1
-        self._live = [[r for r in l if r[1] >= self.next_window] for l in self._live]
+        for b in range(B):
+            self._ran(b, self.next_window)
         return buf
-
-    def _joints(self, buf, k, frames):
-        """fp64 joint positions (B, frames, 10, 3) of the first `frames` frames of a stacked buffer of k windows."""
-        if self._mean is None:
-            self._mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
-        jt = torch.zeros(self.B, frames, 10, 3, dtype=torch.float64, device=self.dev)
-        ops.utterance_finish(buf, self._ones, k, self.T, self.n_pre, mean=self._mean, joints=jt)
-        return jt
-
-    @staticmethod
-    def _result(frames, jt, numpy):
-        if numpy:
-            frames, jt = frames.cpu().numpy(), None if jt is None else jt.cpu().numpy()
-        return frames if jt is None else (frames, jt)
 
     # -------------------------------------------------------------------------------------------------------------- the interface
     def push(self, chunk, words=None, numpy=False, joints=False):
@@ -1171,21 +1198,22 @@ class GestureStream:
         view of the frames that became final in this call (frames = 0 if no window completed); numpy=True reads them back; joints=True returns
         (frames, fp64 joint positions (B, frames, 10, 3)).  A word whose window has already run is not applied to that window and counted in
         late_words.  ValueError: closed stream, chunk over max_chunk, dtype other than float32, wrong row count."""
+        who = type(self).__name__
         if self.closed:
-            raise ValueError("GestureStream.push: the stream is closed")
+            raise ValueError(f"{who}.push: the stream is closed")
         if isinstance(chunk, np.ndarray):
             if chunk.dtype != np.float32:
-                raise ValueError(f"GestureStream.push: the chunk must be float32, got {chunk.dtype}")
+                raise ValueError(f"{who}.push: the chunk must be float32, got {chunk.dtype}")
             chunk = torch.from_numpy(np.ascontiguousarray(chunk))
         if not isinstance(chunk, torch.Tensor) or chunk.dtype != torch.float32:
-            raise ValueError(f"GestureStream.push: the chunk must be float32, got {getattr(chunk, 'dtype', type(chunk).__name__)}")
+            raise ValueError(f"{who}.push: the chunk must be float32, got {getattr(chunk, 'dtype', type(chunk).__name__)}")
         if chunk.dim() == 1 and self.B == 1:
             chunk = chunk[None]
         if chunk.dim() != 2 or chunk.shape[0] != self.B or chunk.shape[1] < 1:
-            raise ValueError(f"GestureStream.push: the chunk is {tuple(chunk.shape)}, expected ({self.B}, n >= 1)")
+            raise ValueError(f"{who}.push: the chunk is {tuple(chunk.shape)}, expected ({self.B}, n >= 1)")
         n = chunk.shape[1]
         if n > self.max_chunk:
-            raise ValueError(f"GestureStream.push: a chunk of {n} samples, max_chunk is {self.max_chunk}")
+            raise ValueError(f"{who}.push: a chunk of {n} samples, max_chunk is {self.max_chunk}")
         if words is not None and self.B == 1 and (len(words) == 0 or (len(words[0]) > 0 and isinstance(words[0][0], str))):
             words = [words]                                          # one row: its word list as it is
         recs, m_max, live = self._records(words)
@@ -1199,52 +1227,24 @@ class GestureStream:
         if k <= 0:
             empty = self.chunk_buf.new_zeros(self.B, 0, self.D)
             return self._result(empty, empty.new_zeros(self.B, 0, 10, 3, dtype=torch.float64) if joints else None, numpy)
-        buf = self._run(k)
-        return self._result(buf[:, :k * self.stride], self._joints(buf, k, k * self.stride) if joints else None, numpy)
+        buf = self._run(k, smooth=True)
+        return self._result(buf[:, :k * self.stride], self._joints(buf, k) if joints else None, numpy)
 
     def close(self, fade_out=False, joints=False, numpy=False):
         """Ends the stream: runs the windows the reference's window count (num_windows of the final length) still asks for, zero-padded, and returns
         the remaining frames, the last window's final n_pre_poses among them; fade_out: faded out to the mean pose on the device as
         generate_gestures_batch(on_device=True, fade_out=True) does (the result may grow, as there); joints=True: (frames, joint positions)."""
+        who = type(self).__name__
         if self.closed:
-            raise ValueError("GestureStream.close: the stream is closed")
+            raise ValueError(f"{who}.close: the stream is closed")
         if self.pushed == 0:
-            raise ValueError("GestureStream.close: nothing was pushed")
-        B, T, D, st, n = self.B, self.T, self.D, self.stride, self.n_pre
-        n_win = num_windows(self.pushed / self.audio_sr, T, n, self.args.motion_resampling_framerate)
-        k = n_win - self.next_window
-        if k not in (0, 1):                                         # windows run as soon as they are complete: at most the padded last one is left
-            raise RuntimeError(f"GestureStream.close: {self.next_window} windows ran, the reference counts {n_win} for {self.pushed} samples")
-        # the last window goes through the finish on a one-window buffer of its own; dec.out holds it, whether it runs here or ran in a push
-        # (then it was complete, and its first `stride` frames are out already)
+            raise ValueError(f"{who}.close: nothing was pushed")
+        n_win, k = self._windows_left(f"{who}.close", self.pushed, self.next_window)
         if k:
             self._run(1)
             self._closing_window = True                             # (a close that raises after this point and is called again must not skip its frames)
-        skip = 0 if self._closing_window else st
-        fin = torch.zeros(B, T + 2 * n, D, device=self.dev)
-        ops.copy2d(self.dec.out.view(B, T * D), fin.view(B, (T + 2 * n) * D)[:, :T * D])
-        length, fade_start, tab = T, None, None
-        if fade_out:
-            # the padding is at most a window, so int(pad / sr * fps) <= n_poses and start_frame >= n_win * stride + n_pre - n_poses = (n_win - 1) * stride:
-            # the fade-out starts inside the last window.  That window has been emitted only if it was complete, and then pad = 0 and the fade
-            # starts at the utterance's end: no emitted frame changes
-            start = _fade_start_frame(n_win * st + n, end_padding_samples(self.args, self.pushed, self.audio_sr), self.args, self.audio_sr)
-            rel = start - (n_win - 1) * st
-            assert 0 <= rel <= T and (k > 0 or rel == T)
-            length = max(T, rel + 2 * n)
-            fade_start = torch.tensor([rel] * B, dtype=torch.int32, device=self.dev)
-            if 1 <= n <= 8:                                         # (outside: the library refuses the call and names its envelope)
-                t = projection_tables(n)
-                tab = torch.from_numpy(np.concatenate([t["smooth"].ravel(), t["fade"].ravel()])).to(self.dev)
-        jt = None
-        if joints:
-            if self._mean is None:
-                self._mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
-            jt = torch.zeros(B, T + 2 * n, 10, 3, dtype=torch.float64, device=self.dev)
-        if fade_out or joints:
-            ops.utterance_finish(fin, self._ones, 1, T, n, proj=tab, fade_start=fade_start, mean=self._mean if joints else None, joints=jt)
-        frames, jrows = fin[:, skip:length], None if jt is None else jt[:, skip:length]
-        res = self._result(frames, jrows, numpy)
+        res = self._result(*self._closing(self.dec.out, self.pushed, n_win, self._closing_window, fade_out, joints,
+                                          self._smooth_closing and self._closing_window), numpy)
         self.closed = True                                          # only now: a close that raised can be called again
         return res
 
@@ -1266,58 +1266,31 @@ class Seq2SeqGestureStream(GestureStream):
     row_local_encoder.  Words follow GestureStream's timing rule.  max_words: the most words one window of one row may hold (the text
     buffer has max_words + 2 entries); a push that would give a window more is refused and leaves the stream as it was.
     Refused at construction: 3 n_pre > stride, n_pre outside 1 .. 8, batch outside 1 .. 4, another model, a window_decoder built for something else."""
+    _models = ("seq2seq",)
+    # close(): the padded last window if it has not run -- unsmoothed by _run, so that dec.out keeps the raw window and a close that raises and is
+    # repeated smooths a fresh copy -- then smoothing and fade-out in the offline finish's order on the one-window buffer (a last window that a
+    # push emitted was smoothed there: its remaining n_pre frames are not in a segment)
+    _smooth_closing = True
+
+    def _refusal(self, model):
+        return f"args.model is {model!r}, not 'seq2seq' (GestureStream streams multimodal_context and joint_embedding)"
 
     def __init__(self, args, pose_decoder, lang_model, batch=1, seed_seqs=None, audio_sr=16000, max_chunk=16000, window_decoder=None, graph=True,
                  word_ring=256, ring=None, max_words=32, row_local_encoder=True):
-        model = getattr(args, "model", "multimodal_context")
-        if model != "seq2seq":
-            raise ValueError(f"Seq2SeqGestureStream: args.model is {model!r}, not 'seq2seq' (GestureStream streams multimodal_context and joint_embedding)")
-        self.T, self.n_pre = args.n_poses, args.n_pre_poses
-        self.stride = self.T - self.n_pre
-        if not 1 <= self.n_pre <= 8:
-            raise ValueError(f"Seq2SeqGestureStream: 1 <= n_pre_poses <= 8 (the smoothing kernel's tables), got {self.n_pre}")
-        if 3 * self.n_pre > self.stride:
-            raise ValueError(f"Seq2SeqGestureStream: a window's smoothing segment of 3 n_pre = {3 * self.n_pre} frames must lie inside its first "
-                             f"n_poses - n_pre_poses = {self.stride} frames, else it would rewrite frames the next window has handed out")
-        if not 1 <= batch <= 4:
-            raise ValueError(f"Seq2SeqGestureStream: 1 to 4 rows, got {batch}")
-        if max_chunk < 1:
-            raise ValueError(f"Seq2SeqGestureStream: max_chunk = {max_chunk}")
-        self.args, self.model, self.lang, self.B, self.audio_sr, self.max_chunk = args, model, lang_model, batch, audio_sr, int(max_chunk)
-        self.S, self.A = stream_geometry(args, audio_sr)
-        dev = self.dev = next(pose_decoder.parameters()).device
-        if window_decoder is not None:
-            d = window_decoder
-            if not isinstance(d, Seq2SeqWindowDecoder) or d.net is not pose_decoder or d.B != batch or (d.T, d.n_pre) != (self.T, self.n_pre) \
-                    or d.max_words != max_words or d.row_local != bool(row_local_encoder):
-                raise ValueError(f"Seq2SeqGestureStream: window_decoder must be a Seq2SeqWindowDecoder built for this model, {batch} row(s), (n_poses, "
-                                 f"n_pre_poses) = {(self.T, self.n_pre)}, max_words = {max_words} and row_local_encoder = {bool(row_local_encoder)}")
-            self.dec = d
-        else:
-            self.dec = Seq2SeqWindowDecoder(args, pose_decoder, batch, dev, graph=graph, max_words=max_words, row_local_encoder=row_local_encoder,
-                                            audio_sr=audio_sr)
-        if self.dec.audio_len != self.A:
-            raise ValueError(f"Seq2SeqGestureStream: the window decoder counts {self.dec.audio_len} samples, the stream's window is {self.A} (audio_sr = {audio_sr})")
-        self.D, self.draws, self.vid, self.max_words = self.dec.D, None, None, self.dec.max_words
-        self.dec.seed(None if seed_seqs is None else np.stack([np.asarray(s)[:self.n_pre] for s in seed_seqs]))
-        R = self.A + self.max_chunk if ring is None else int(ring)
-        if R < self.A + self.max_chunk:
-            raise ValueError(f"Seq2SeqGestureStream: a ring of {R} samples; window + max_chunk = {self.A + self.max_chunk} are needed")
-        self.state = ops.stream_state(batch, R, self.S, self.A, word_ring, self.T, dev)
-        self.chunk_buf = torch.zeros(batch, self.max_chunk, device=dev)
-        self.pushed = self.next_window = self.late_words = 0
-        self.closed = False
-        self._live = [[] for _ in range(batch)]
-        self._n_rec = [0] * batch
+        n_pre, stride = args.n_pre_poses, args.n_poses - args.n_pre_poses
+        if not 1 <= n_pre <= 8:
+            raise ValueError(f"Seq2SeqGestureStream: 1 <= n_pre_poses <= 8 (the smoothing kernel's tables), got {n_pre}")
+        if 3 * n_pre > stride:
+            raise ValueError(f"Seq2SeqGestureStream: a window's smoothing segment of 3 n_pre = {3 * n_pre} frames must lie inside its first "
+                             f"n_poses - n_pre_poses = {stride} frames, else it would rewrite frames the next window has handed out")
+        super().__init__(args, pose_decoder, lang_model, batch, None, seed_seqs, audio_sr, max_chunk, None, None, window_decoder, graph, word_ring,
+                         ring, _built_for=dict(max_words=max_words, row_local_encoder=bool(row_local_encoder)))
+        self.max_words = self.dec.max_words
         self._win_words = [{} for _ in range(batch)]     # per row: window -> words pushed for it so far (windows that have not run)
-        self._ones = torch.ones(batch, dtype=torch.int32, device=dev)
         self._k_dev = {1: self._ones}                    # (B,) int32 window counts of a push's buffer, by k
-        t = projection_tables(self.n_pre)
-        self._tables = torch.from_numpy(np.concatenate([t["smooth"].ravel(), t["fade"].ravel()])).to(dev)
+        self._tables = _projection_device(self.n_pre, self.dev)
         self._sos, self._eos = int(lang_model.SOS_token), int(lang_model.EOS_token)
-        self._mean, self._closing_window = None, False
 
-    # -------------------------------------------------------------------------------------------------------------- host bookkeeping (integers)
     def _records(self, words):
         """GestureStream._records behind one more refusal: no window of a row may hold more than max_words words."""
         add = None
@@ -1340,65 +1313,20 @@ class Seq2SeqGestureStream(GestureStream):
                 self._win_words[b][win] = self._win_words[b].get(win, 0) + c
         return res
 
-    def _run(self, k, smooth=True):
-        """The next k windows, stacked as the offline loop stacks them, (B, k * stride + n_pre, D), and -- smooth -- smoothed as its finish
-        smooths them: the k segments lie inside the buffer and are final."""
-        B, T, D, st = self.B, self.T, self.D, self.stride
-        F = k * st + self.n_pre
-        buf = torch.empty(B, F, D, device=self.dev)                 # (the windows tile it)
-        for j in range(k):
-            i = self.next_window
-            ops.stream_stage_text(self.state, self._sos, self._eos, self.dec.text, self.dec.len)     # straight into the decoder's static buffers
-            out = self.dec.window(first=(i == 0))
-            ops.copy2d(out.view(B, T * D), buf.view(B, F * D)[:, j * st * D:(j * st + T) * D])
-            ops.counter_inc(self.state["win"])
-            self.next_window += 1
-        self._live = [[r for r in l if r[1] >= self.next_window] for l in self._live]
+    def _stage_and_run(self, i):
+        ops.stream_stage_text(self.state, self._sos, self._eos, self.dec.text, self.dec.len)     # straight into the decoder's static buffers
+        return self.dec.window(first=(i == 0))
+
+    def _run(self, k, smooth=False):
+        """GestureStream._run and -- smooth -- the k windows smoothed as the offline finish smooths them: the k segments lie inside the buffer
+        and are final."""
+        buf = super()._run(k)
         self._win_words = [{w: c for w, c in d.items() if w >= self.next_window} for d in self._win_words]
         if smooth:
             if k not in self._k_dev:
-                self._k_dev[k] = torch.full((B,), k, dtype=torch.int32, device=self.dev)
-            ops.utterance_finish(buf, self._k_dev[k], k, T, self.n_pre, smooth=True, proj=self._tables)
+                self._k_dev[k] = torch.full((self.B,), k, dtype=torch.int32, device=self.dev)
+            ops.utterance_finish(buf, self._k_dev[k], k, self.T, self.n_pre, smooth=True, proj=self._tables)
         return buf
-
-    # -------------------------------------------------------------------------------------------------------------- the interface
-    def close(self, fade_out=False, joints=False, numpy=False):
-        """GestureStream.close for this model: the padded last window if it has not run, then smoothing and fade-out in the offline finish's
-        order on the one-window buffer (a last window that a push emitted was smoothed there: its remaining n_pre frames are not in a segment)."""
-        if self.closed:
-            raise ValueError("Seq2SeqGestureStream.close: the stream is closed")
-        if self.pushed == 0:
-            raise ValueError("Seq2SeqGestureStream.close: nothing was pushed")
-        B, T, D, st, n = self.B, self.T, self.D, self.stride, self.n_pre
-        n_win = num_windows(self.pushed / self.audio_sr, T, n, self.args.motion_resampling_framerate)
-        k = n_win - self.next_window
-        if k not in (0, 1):                                         # windows run as soon as they are complete: at most the padded last one is left
-            raise RuntimeError(f"Seq2SeqGestureStream.close: {self.next_window} windows ran, the reference counts {n_win} for {self.pushed} samples")
-        if k:
-            self._run(1, smooth=False)                              # (dec.out keeps the raw window: a close that raises and is repeated smooths a fresh copy)
-            self._closing_window = True
-        skip = 0 if self._closing_window else st
-        fin = torch.zeros(B, T + 2 * n, D, device=self.dev)
-        ops.copy2d(self.dec.out.view(B, T * D), fin.view(B, (T + 2 * n) * D)[:, :T * D])
-        length, fade_start = T, None
-        if fade_out:                                                # (GestureStream.close: the fade-out starts inside the last window)
-            start = _fade_start_frame(n_win * st + n, end_padding_samples(self.args, self.pushed, self.audio_sr), self.args, self.audio_sr)
-            rel = start - (n_win - 1) * st
-            assert 0 <= rel <= T and (self._closing_window or rel == T)
-            length = max(T, rel + 2 * n)
-            fade_start = torch.tensor([rel] * B, dtype=torch.int32, device=self.dev)
-        jt = None
-        if joints:
-            if self._mean is None:
-                self._mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
-            jt = torch.zeros(B, T + 2 * n, 10, 3, dtype=torch.float64, device=self.dev)
-        if self._closing_window or fade_out or joints:
-            ops.utterance_finish(fin, self._ones, 1, T, n, smooth=self._closing_window, proj=self._tables, fade_start=fade_start,
-                                 mean=self._mean if joints else None, joints=jt)
-        res = self._result(fin[:, skip:length], None if jt is None else jt[:, skip:length], numpy)
-        self.closed = True                                          # only now: a close that raised can be called again
-        return res
-
 
 # ------------------------------------------------------------------------------------------------------------------ stream pool
 def pool_rounds(pushed, next_window, S, A):
@@ -1409,7 +1337,7 @@ def pool_rounds(pushed, next_window, S, A):
     return [[int(kb > j) for kb in k] for j in range(max(k, default=0))]
 
 
-class StreamPool:
+class StreamPool(_StreamCore):
     """GestureStream for independent sessions: `slots` (1 to 4) rows on ONE window decoder, each row a session with a clock of its own.
     open() takes a free row and returns its index, push({slot: chunk or (chunk, words)}) appends ragged chunks to any of the open rows and
     returns, per pushed slot, the frames that became final, close(slot) ends one session and frees its row; sessions join and leave while the
@@ -1427,56 +1355,20 @@ class StreamPool:
     _replay_draws (parity tests): every open() then brings the session's per-window draws ((16,) multimodal_context, (32,) joint_embedding).
     window_decoder: a kept decoder of the model's kind built for `slots` rows; its graph_pooled is captured once and replayed by every pool
     that uses it, one pool at a time.  push() never reads from the device.  A refused call (ValueError) leaves the pool as it was."""
+    _rows = "slots"
 
     def __init__(self, args, pose_decoder, lang_model, slots=4, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, ring=None,
                  window_decoder=None, _replay_draws=False):
-        model = getattr(args, "model", "multimodal_context")
-        if model == "seq2seq":
-            raise ValueError("StreamPool: the seq2seq model cannot stream: its smoothing rewrites frames of a window after the next window has run")
-        if model == "speech2gesture":
-            raise ValueError("StreamPool: the speech2gesture model cannot stream: its log-mel spectrogram is padded over the whole utterance")
-        if model not in ("multimodal_context", "joint_embedding"):
-            raise ValueError(f"StreamPool: unknown model {model!r}")
-        if not 1 <= slots <= 4:
-            raise ValueError(f"StreamPool: 1 to 4 slots, got {slots}")
-        if max_chunk < 1:
-            raise ValueError(f"StreamPool: max_chunk = {max_chunk}")
-        self.args, self.model, self.lang, self.B, self.audio_sr, self.max_chunk = args, model, lang_model, int(slots), audio_sr, int(max_chunk)
-        self.T, self.n_pre = args.n_poses, args.n_pre_poses
-        self.stride = self.T - self.n_pre
-        self.S, self.A = stream_geometry(args, audio_sr)
-        R = self.A + self.max_chunk if ring is None else int(ring)
-        if R < self.A + self.max_chunk:
-            raise ValueError(f"StreamPool: a ring of {R} samples; window + max_chunk = {self.A + self.max_chunk} are needed")
-        B = self.B
+        self.replay = bool(_replay_draws)
+        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, word_ring, ring, window_decoder, graph, replay_draws=self.replay)
+        B = self.B                                                  # (the state's one-entry `win` is not used: the rows' counters are dec.win)
         self.open_slots = [False] * B
         self.pushed, self.next_window, self.late_words = [0] * B, [0] * B, [0] * B
-        self._live, self._n_rec, self._draws, self._closing_window = [[] for _ in range(B)], [0] * B, [None] * B, [False] * B
-        self.replay = bool(_replay_draws)
-        dev = self.dev = next(pose_decoder.parameters()).device
-        if window_decoder is not None:
-            kind = WindowDecoder if model == "multimodal_context" else JointEmbedWindowDecoder
-            d = window_decoder
-            if not isinstance(d, kind) or (d.gen if kind is WindowDecoder else d.net) is not pose_decoder or d.B != B or (d.T, d.n_pre) != (self.T, self.n_pre) \
-                    or self.replay != (d.draw is not None):
-                raise ValueError(f"StreamPool: window_decoder must be a {kind.__name__} built for this model, {B} row(s), (n_poses, n_pre_poses) = "
-                                 f"{(self.T, self.n_pre)} and replay_draws = {self.replay}")
-            self.dec = d
-        elif model == "multimodal_context":
-            self.dec = WindowDecoder(args, pose_decoder, B, dev, graph=graph, replay_draws=self.replay)
-        else:
-            self.dec = JointEmbedWindowDecoder(args, pose_decoder, B, dev, graph=graph, replay_draws=self.replay, audio_sr=audio_sr)
-        if self.dec.audio_len != self.A:
-            raise ValueError(f"StreamPool: the window decoder takes {self.dec.audio_len} samples, the pool's window is {self.A} (audio_sr = {audio_sr})")
-        self.D = self.dec.D
-        self.speakers = model == "multimodal_context" and args.z_type == "speaker"
-        self.state = ops.stream_state(B, R, self.S, self.A, word_ring, self.T, dev)      # (its one-entry `win` is not used: the rows' counters are dec.win)
+        self._draws, self._closing_window = [None] * B, [False] * B
+        self.speakers = self.model == "multimodal_context" and args.z_type == "speaker"
         self.active, self.win = self.dec.pool_buffers()
         self.active.zero_(); self.win.zero_()
-        self.chunk_buf = torch.zeros(B, self.max_chunk, device=dev)
         self._draw_host = None if self.dec.draw is None else torch.zeros(tuple(self.dec.draw.shape))
-        self._ones = torch.ones(B, dtype=torch.int32, device=dev)
-        self._mean = None
 
     # -------------------------------------------------------------------------------------------------------------- sessions
     def _slot(self, slot, what):
@@ -1497,19 +1389,16 @@ class StreamPool:
         seed = None if seed_seq is None else torch.as_tensor(np.asarray(seed_seq)[:n], dtype=torch.float32).to(self.dev)
         if seed is not None and tuple(seed.shape) != (n, self.D):
             raise ValueError(f"StreamPool.open: seed_seq gives {tuple(seed.shape)} seed poses, expected {(n, self.D)}")
-        for t in (self.state["written"], self.state["n_words"], self.win, dec.tail):
+        for t in (self.state["written"], self.state["n_words"], self.win, dec.tail, dec.pre):
             t[b:b + 1].zero_()
         if self.model == "multimodal_context":
-            dec.pre_seq[b:b + 1].zero_()
             if seed is not None:
                 dec.pre_seq[b, :n, :-1] = seed
                 dec.pre_seq[b, :n, -1] = 1
             if self.speakers:                                                   # synthesize.py:67-74
                 dec.vid[b:b + 1].copy_(torch.tensor([vid if vid else random.randrange(dec.gen.z_obj.n_words)], dtype=torch.int64))
-        else:
-            dec.pre[b:b + 1].zero_()
-            if seed is not None:
-                dec.pre[b].copy_(seed)
+        elif seed is not None:
+            dec.pre[b].copy_(seed)
         self.pushed[b] = self.next_window[b] = self.late_words[b] = self._n_rec[b] = 0
         self._live[b], self._draws[b], self._closing_window[b] = [], _draws, False
         self.open_slots[b] = True
@@ -1517,19 +1406,15 @@ class StreamPool:
 
     # -------------------------------------------------------------------------------------------------------------- host bookkeeping (integers)
     def _records(self, words):
-        """{slot: word list} -> (per-row records of windows that have not run yet, per-row late counts), GestureStream._records per row: each row
-        against its own next_window.  ValueError if a row's word ring would overflow; nothing is changed here."""
+        """{slot: word list} -> (per-row records of windows that have not run yet, per-row late counts): each row against its own next_window.
+        ValueError if a row's word ring would overflow; nothing is changed here."""
         rows, late = [[] for _ in range(self.B)], [0] * self.B
         for b, wl in words.items():
-            for w in wl or ():
-                rec = word_records(self.args, self.lang, [w])
-                late[b] += any(r[0] < self.next_window[b] for r in rec)
-                rows[b] += [r for r in rec if r[0] >= self.next_window[b]]
+            rows[b], late[b] = self._row_records(wl, self.next_window[b])
         for b, r in enumerate(rows):
-            live = self._n_rec[b] - self._live[b][0][0] if self._live[b] else 0
-            if r and live + len(r) > self.state["W"]:
-                raise ValueError(f"StreamPool.push: slot {b}: {len(r)} word record(s) on top of {live} a window still needs exceed the word ring's "
-                                 f"capacity {self.state['W']} (word_ring=...)")
+            if r and self._live_slots(b) + len(r) > self.state["W"]:
+                raise ValueError(f"StreamPool.push: slot {b}: {len(r)} word record(s) on top of {self._live_slots(b)} a window still needs exceed the "
+                                 f"word ring's capacity {self.state['W']} (word_ring=...)")
         return rows, late
 
     def _round(self, mask):
@@ -1544,13 +1429,8 @@ class StreamPool:
         for b, a in enumerate(mask):
             if a:
                 self.next_window[b] += 1
-                self._live[b] = [r for r in self._live[b] if r[1] >= self.next_window[b]]
+                self._ran(b, self.next_window[b])
         return out
-
-    def _mean_dev(self):
-        if self._mean is None:
-            self._mean = torch.as_tensor(np.asarray(self.args.mean_dir_vec, dtype=np.float64).reshape(-1), device=self.dev)
-        return self._mean
 
     # -------------------------------------------------------------------------------------------------------------- the interface
     def push(self, chunks, numpy=False, joints=False):
@@ -1582,22 +1462,12 @@ class StreamPool:
             host[b, :n[b]] = c
         dst = self.chunk_buf[:, :max(n)]
         dst.copy_(torch.from_numpy(host), non_blocking=True)
-        m = [len(r) for r in recs]
-        m_max, table, fullest = max(m), None, 0
-        if m_max:
-            tab = np.zeros((B, 1 + 3 * m_max), dtype=np.int32)
-            for b, r in enumerate(recs):
-                if r:
-                    tab[b, 0] = len(r)
-                    tab[b, 1:1 + 3 * len(r)] = np.asarray(r, dtype=np.int32).reshape(-1)
-                    fullest = max(fullest, (self._n_rec[b] - self._live[b][0][0] if self._live[b] else 0) + len(r))
-            table = torch.from_numpy(tab).to(self.dev, non_blocking=True)
+        fullest = max((self._live_slots(b) + len(r) for b, r in enumerate(recs) if r), default=0)      # slots of the fullest word ring after the push
+        table, m_max = self._commit_records(recs)
         ops.pool_push(self.state, dst, n, table, m_max, max(0, fullest - m_max))
         for b in range(B):
             self.pushed[b] += n[b]
             self.late_words[b] += late[b]
-            self._live[b] += [(self._n_rec[b] + k, rec[0]) for k, rec in enumerate(recs[b])]
-            self._n_rec[b] += len(recs[b])
         masks = pool_rounds(self.pushed, self.next_window, self.S, self.A)
         k = [sum(mk[b] for mk in masks) for b in range(B)]
         buf = jt = None
@@ -1608,13 +1478,12 @@ class StreamPool:
                 out = self._round(mask)
                 ops.copy2d(out.view(B, T * D), buf.view(B, F * D)[:, j * st * D:(j * st + T) * D])
             if joints:
-                jt = torch.zeros(B, len(masks) * st, 10, 3, dtype=torch.float64, device=self.dev)
-                ops.utterance_finish(buf, self._ones, len(masks), T, self.n_pre, mean=self._mean_dev(), joints=jt)
+                jt = self._joints(buf, len(masks))
         res = {}
         for b in rows:
             frames = buf[b, :k[b] * st] if k[b] else self.chunk_buf.new_zeros(0, D)
             jrows = None if not joints else (jt[b, :k[b] * st] if k[b] else torch.zeros(0, 10, 3, dtype=torch.float64, device=self.dev))
-            res[b] = GestureStream._result(frames, jrows, numpy)
+            res[b] = self._result(frames, jrows, numpy)
         return res
 
     def close(self, slot, fade_out=False, joints=False, numpy=False):
@@ -1624,33 +1493,12 @@ class StreamPool:
         b = self._slot(slot, "close")
         if self.pushed[b] == 0:
             raise ValueError(f"StreamPool.close: nothing was pushed to slot {b}")
-        T, D, st, n = self.T, self.D, self.stride, self.n_pre
-        n_win = num_windows(self.pushed[b] / self.audio_sr, T, n, self.args.motion_resampling_framerate)
-        k = n_win - self.next_window[b]
-        if k not in (0, 1):                                         # windows run as soon as they are complete: at most the padded last one is left
-            raise RuntimeError(f"StreamPool.close: slot {b}: {self.next_window[b]} windows ran, the reference counts {n_win} for {self.pushed[b]} samples")
+        n_win, k = self._windows_left(f"StreamPool.close: slot {b}", self.pushed[b], self.next_window[b])
         if k:
             self._round([int(r == b) for r in range(self.B)])
             self._closing_window[b] = True                          # (a close that raises after this point and is called again must not skip its frames)
-        skip = 0 if self._closing_window[b] else st
-        fin = torch.zeros(1, T + 2 * n, D, device=self.dev)
-        ops.copy2d(self.dec.out[b:b + 1].view(1, T * D), fin.view(1, (T + 2 * n) * D)[:, :T * D])
-        length, fade_start, tab = T, None, None
-        if fade_out:                                                # (GestureStream.close: the fade-out starts inside the last window)
-            start = _fade_start_frame(n_win * st + n, end_padding_samples(self.args, self.pushed[b], self.audio_sr), self.args, self.audio_sr)
-            rel = start - (n_win - 1) * st
-            assert 0 <= rel <= T and (k > 0 or self._closing_window[b] or rel == T)
-            length = max(T, rel + 2 * n)
-            fade_start = torch.tensor([rel], dtype=torch.int32, device=self.dev)
-            if 1 <= n <= 8:                                         # (outside: the library refuses the call and names its envelope)
-                t = projection_tables(n)
-                tab = torch.from_numpy(np.concatenate([t["smooth"].ravel(), t["fade"].ravel()])).to(self.dev)
-        jt = None
-        if joints:
-            jt = torch.zeros(1, T + 2 * n, 10, 3, dtype=torch.float64, device=self.dev)
-        if fade_out or joints:
-            ops.utterance_finish(fin, self._ones[:1], 1, T, n, proj=tab, fade_start=fade_start, mean=self._mean_dev() if joints else None, joints=jt)
-        res = GestureStream._result(fin[0, skip:length], None if jt is None else jt[0, skip:length], numpy)
+        frames, jrows = self._closing(self.dec.out[b:b + 1], self.pushed[b], n_win, self._closing_window[b], fade_out, joints)
+        res = self._result(frames[0], None if jrows is None else jrows[0], numpy)
         self.open_slots[b] = False                                  # only now: a close that raised can be called again
         self.pushed[b] = self.next_window[b] = 0                    # (a free row has no windows to run)
         return res
