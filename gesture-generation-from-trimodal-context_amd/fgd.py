@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .modules import _need_cuda_variational
 from .optim import FusedAdam
 
 
@@ -309,7 +310,6 @@ def train_iter(args, epoch, target_data, net, optim, *, variational_encoding=Fal
     target = target_data.float().contiguous()
     if variational_encoding:
         from .joint_embed import unpack_scalars
-        from .modules import _need_cuda_variational
         _need_cuda_variational(target, "train_iter: target_data")
         inject = net._replay_draws.pop(0) if net._replay_draws else None
         _, packed = _vae_step(E, optim, target, epoch, inject)

@@ -21,14 +21,12 @@ import torch.nn as nn
 
 from . import layers as L
 from . import ops
+from .autograd_fns import L1MeanFn, LinearFn, RepeatRowsFn
 from .engine import AutoencoderEngine, DeviceRNG, GeneratorEngine
+from .layers import need_cuda
+from .modules import EmbeddingNet, _need_cuda_variational, _TextEncoderParams, _WavEncoderParams
+from .optim import ParamAdam, adopt
 from .rnn import GRU, _SumHalvesFn
-
-
-def _need_cuda(t, name, dtype=torch.float32):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype):
-        raise TypeError(f"{name} must be a CUDA {dtype} tensor, got {getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}: there is no "
-                        "torch fallback")
 
 
 # ------------------------------------------------------------------------------------------------------------------ engine stages
@@ -165,38 +163,6 @@ class _LatentHeadFn(torch.autograd.Function):
         return (None, dx_full, dcat) + tuple(G[k] if ctx.needs_input_grad[3 + i] else None for i, k in enumerate(order))
 
 
-class _RepeatFn(torch.autograd.Function):
-    """feat (B, C) -> (B, T, C), every step the same row (embedding_net.py:155); backward: the sum over the steps."""
-
-    @staticmethod
-    def forward(ctx, feat, T):
-        B, C = feat.shape
-        out = L.empty(B, T, C, like=feat)
-        ops.repeat_rows(feat.contiguous(), out.view(B * T, C), B, T)
-        ctx.dims = (B, T, C)
-        return out
-
-    @staticmethod
-    def backward(ctx, dout):
-        B, T, C = ctx.dims
-        return ops.sum_rows(dout.contiguous().view(B * T, C), L.empty(B, C, like=dout), B, T), None
-
-
-class _LinearFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, W, b):
-        ctx.saved = (x, W)
-        return L.linear_fwd(x, W, b)
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, W = ctx.saved
-        dy = dy.contiguous()
-        dW, db = ops.zeros_like(W), ops.zeros(W.shape[0], device=W.device)
-        dx = L.linear_bwd(dy, x, W, dW, db, need_dx=ctx.needs_input_grad[0])
-        return dx, dW if ctx.needs_input_grad[1] else None, db if ctx.needs_input_grad[2] else None
-
-
 # ------------------------------------------------------------------------------------------------------------------------ modules
 def _head_params(seq, mu=None, logvar=None):
     ps = [seq[0].weight, seq[0].bias, seq[1].weight, seq[1].bias, seq[3].weight, seq[3].bias]
@@ -212,7 +178,6 @@ class ContextEncoder(nn.Module):
 
     def __init__(self, args, n_frames, n_words, word_embed_size, word_embeddings):
         super().__init__()
-        from .modules import _TextEncoderParams, _WavEncoderParams
         self.text_encoder = _TextEncoderParams(args, n_words, word_embed_size, word_embeddings, 0.3)
         self.audio_encoder = _WavEncoderParams()
         self.gru = GRU(32 + 32, hidden_size=256, num_layers=2, bidirectional=False, batch_first=True)
@@ -234,7 +199,7 @@ class ContextEncoder(nn.Module):
         return names
 
     def forward(self, in_text, in_spec, inject=None):
-        _need_cuda(in_text, "ContextEncoder: in_text", torch.int64); _need_cuda(in_spec, "ContextEncoder: in_spec")
+        need_cuda(in_text, "ContextEncoder: in_text", torch.int64); need_cuda(in_spec, "ContextEncoder: in_spec")
         if in_text.dim() != 2 or in_spec.dim() != 2 or in_spec.shape[0] != in_text.shape[0]:
             raise ValueError(f"ContextEncoder: in_text (B, T) and in_spec (B, samples) expected, got {tuple(in_text.shape)} and {tuple(in_spec.shape)}")
         B, T = in_text.shape
@@ -280,7 +245,7 @@ class PoseDecoderGRU(nn.Module):
         self.out = nn.Sequential(nn.Linear(self.hidden_size, self.hidden_size // 2), nn.LeakyReLU(True), nn.Linear(self.hidden_size // 2, pose_dim))
 
     def forward(self, latent_code, pre_poses):
-        _need_cuda(latent_code, "PoseDecoderGRU: latent_code"); _need_cuda(pre_poses, "PoseDecoderGRU: pre_poses")
+        need_cuda(latent_code, "PoseDecoderGRU: latent_code"); need_cuda(pre_poses, "PoseDecoderGRU: pre_poses")
         B = pre_poses.shape[0]
         if self.training and B == 1:
             raise ValueError("PoseDecoderGRU: BatchNorm in train mode needs more than one clip")
@@ -289,9 +254,9 @@ class PoseDecoderGRU(nn.Module):
             raise ValueError(f"PoseDecoderGRU: pre_poses {tuple(pre_poses.shape)} / latent_code {tuple(latent_code.shape)} do not match the network")
         hcfg = (self.pre_pose_net[1], self.training, 0.0, False, False, None, None)
         feat = _LatentHeadFn.apply(hcfg, pre, latent_code, *_head_params(self.pre_pose_net))          # (B, 64) = [pre_pose_feat | latent]
-        output, _ = self.gru(_RepeatFn.apply(feat, self.gen_length))
+        output, _ = self.gru(RepeatRowsFn.apply(feat, self.gen_length))
         o = _SumHalvesFn.apply(output).view(B * self.gen_length, self.hidden_size)
-        o = _LinearFn.apply(_LinearFn.apply(o, self.out[0].weight, self.out[0].bias), self.out[2].weight, self.out[2].bias)
+        o = LinearFn.apply(LinearFn.apply(o, self.out[0].weight, self.out[0].bias), self.out[2].weight, self.out[2].bias)
         return o.view(B, self.gen_length, -1)
 
     def forward_constant(self, latent_code, pre_poses):
@@ -300,7 +265,7 @@ class PoseDecoderGRU(nn.Module):
         no tg_repeat_rows launch.  Same head, direction sum and output MLP as forward.  Raises ValueError where forward_constant does."""
         if self.training:
             raise ValueError("PoseDecoderGRU.forward_constant runs in eval mode only: call .eval() first")
-        _need_cuda(latent_code, "PoseDecoderGRU: latent_code"); _need_cuda(pre_poses, "PoseDecoderGRU: pre_poses")
+        need_cuda(latent_code, "PoseDecoderGRU: latent_code"); need_cuda(pre_poses, "PoseDecoderGRU: pre_poses")
         B = pre_poses.shape[0]
         pre = pre_poses.reshape(B, -1).contiguous()
         if pre.shape[1] != self.pre_pose_net[0].in_features or tuple(latent_code.shape) != (B, 32):
@@ -310,14 +275,13 @@ class PoseDecoderGRU(nn.Module):
             feat = _LatentHeadFn.apply(hcfg, pre, latent_code, *_head_params(self.pre_pose_net))      # (B, 64) = [pre_pose_feat | latent]
             output, _ = self.gru.forward_constant(feat, self.gen_length)
             o = _SumHalvesFn.apply(output).view(B * self.gen_length, self.hidden_size)
-            o = _LinearFn.apply(_LinearFn.apply(o, self.out[0].weight, self.out[0].bias), self.out[2].weight, self.out[2].bias)
+            o = LinearFn.apply(LinearFn.apply(o, self.out[0].weight, self.out[0].bias), self.out[2].weight, self.out[2].bias)
         return o.view(B, self.gen_length, -1)
 
 
 def embedding_forward(net, in_text, in_audio, pre_poses, poses, input_mode=None, variational_encoding=False):
     """EmbeddingNet.forward of the speech / random modes (embedding_net.py:276-308)."""
     if variational_encoding and poses is not None:
-        from .modules import _need_cuda_variational
         _need_cuda_variational(poses, "EmbeddingNet: poses")
     if input_mode is None:
         assert net.mode is not None
@@ -332,7 +296,7 @@ def embedding_forward(net, in_text, in_audio, pre_poses, poses, input_mode=None,
         context_feat, context_mu, context_logvar = net.context_encoder(in_text, in_audio.float(), inject=inject)
     poses_feat = pose_mu = pose_logvar = None
     if poses is not None:
-        _need_cuda(poses, "EmbeddingNet: poses")
+        need_cuda(poses, "EmbeddingNet: poses")
         if net.training and poses.shape[0] == 1:
             raise ValueError("EmbeddingNet: BatchNorm in train mode needs more than one clip")
         enc = net.pose_encoder
@@ -390,41 +354,18 @@ def embedding_synthesize(net, in_text, in_audio, pre_poses, inject=None, constan
 
 
 # ----------------------------------------------------------------------------------------------------------------------- training
-class _L1SumFn(torch.autograd.Function):
-    """sum over clips of mean_{t,d} |recon - target| (train_joint_embed.py:20-28; clips have equal size: B x the mean over everything)."""
-
-    @staticmethod
-    def forward(ctx, recon, target, bscale, out=None):
-        # out: an optional one-element LIST holding the float [1] tensor to write the loss into (a slot of a packed result buffer; a
-        # list, because autograd forbids an input tensor that comes back as an output)
-        loss = ops.l1_mean(recon, target, L.empty(1, like=recon) if out is None else out[0])
-        ops.scale_by(loss, bscale)
-        ctx.saved = (recon, target, bscale)
-        return loss
-
-    @staticmethod
-    def backward(ctx, g):
-        recon, target, bscale = ctx.saved
-        d = ops.s2g_l1_grad(recon, target, torch.empty_like(recon))
-        ops.scale_by(d, bscale)
-        return ops.scale_by(d, g.contiguous()), None, None, None
-
-
 class JointEmbedTrainer:
-    """train_iter_embed with the device Adam (torch.optim.Adam semantics, tg_adam_step): forward (both encoders), the summed per-clip L1,
+    """train_iter_embed with the device Adam (optim.ParamAdam): forward (both encoders), the summed per-clip L1 (L1MeanFn times B),
     backward, Adam on every parameter that received a gradient."""
 
     def __init__(self, net, lr=5e-4, betas=(0.5, 0.999), eps=1e-8):
         self.net = net
-        self.params = [p for p in net.parameters()]
-        dev = self.params[0].device
-        self.m, self.v = [torch.zeros_like(p) for p in self.params], [torch.zeros_like(p) for p in self.params]
-        self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32)
-        self.lr, self.betas, self.eps = lr, tuple(betas), eps
+        self.adam = ParamAdam(net.parameters(), lr, betas, eps)
+        self.step_dev = self.adam.step_dev
         self._bscale = {}                    # device constants by (value, device, dtype)
 
     def set_hparams(self, lr, betas, eps):
-        self.lr, self.betas, self.eps = lr, tuple(betas), eps
+        self.adam.set_hparams(lr, betas, eps)
 
     def _const(self, value, dev, dtype=torch.float32):
         key = (float(value), dev, dtype)
@@ -437,17 +378,16 @@ class JointEmbedTrainer:
         (slot 0: the fp32 loss in its first four bytes, slot 1: the fp64 KLD) -- read with unpack_scalars, one copy to the host."""
         target = target_data.float().contiguous()
         B, dev = target.shape[0], target.device
-        for p in self.params:
-            p.grad = None
+        self.adam.zero_grad()
         pre_seq = target[:, 0:args.n_pre_poses]
         out = self.net(in_text, in_audio, pre_seq, target, mode, variational_encoding=variational_encoding)
         if not variational_encoding:
-            loss = _L1SumFn.apply(out[6].contiguous(), target, self._const(B, dev))
+            loss = L1MeanFn.apply(out[6].contiguous(), target, self._const(B, dev))
             loss.backward()
             packed = loss.detach()
         else:
             packed = torch.empty(2, device=dev, dtype=torch.float64)
-            loss = _L1SumFn.apply(out[6].contiguous(), target, self._const(B, dev), [packed[0:1].view(torch.float32)[0:1]])
+            loss = L1MeanFn.apply(out[6].contiguous(), target, self._const(B, dev), [packed[0:1].view(torch.float32)[0:1]])
             # train_joint_embed.py:30-40: the context latent's KL term when the NET's mode is 'speech', the pose latent's otherwise
             mu, logvar = (out[1], out[2]) if self.net.mode == "speech" else (out[4], out[5])
             if mu is None:
@@ -457,13 +397,7 @@ class JointEmbedTrainer:
             torch.autograd.backward([loss, kld], [self._const(args.loss_regression_weight, dev),
                                                   self._const(embed_kld_weight(epoch, args.loss_kld_weight), dev, torch.float64)])
             packed = packed.detach()
-        ops.counter_inc(self.step_dev)
-        for p, m, v in zip(self.params, self.m, self.v):
-            if p.grad is None:
-                continue
-            if not p.grad.is_contiguous():
-                p.grad = p.grad.contiguous()
-            ops.adam_step(p.data, p.grad, m, v, self.lr, self.betas[0], self.betas[1], self.eps, self.step_dev)
+        self.adam.step()
         return packed
 
 
@@ -480,7 +414,7 @@ def unpack_scalars(packed):
 
 class _KldFn(torch.autograd.Function):
     """KLD = -0.5 sum(1 + logvar - mu^2 - exp(logvar)) of a latent (fp64 device scalar, written into out[0]: a one-element list, as
-    _L1SumFn's), value and gradient from ONE launch (ops.vae_kld); the backward scales the stored gradient by the incoming one (a device
+    L1MeanFn's), value and gradient from ONE launch (ops.vae_kld); the backward scales the stored gradient by the incoming one (a device
     scalar: no host read)."""
 
     @staticmethod
@@ -500,19 +434,10 @@ def train_iter_embed(args, epoch, in_text, in_audio, target_data, net, optim, mo
     """The reference's signature and return dict (train_joint_embed.py:5-51).  variational_encoding is False on both of the reference's
     branches, so by default there is no KLD term; True (keyword only) is the reference with that literal flipped:
     loss = args.loss_regression_weight * recon + KLD_weight * KLD, KLD_weight = embed_kld_weight(epoch, args.loss_kld_weight), and the dict
-    is {'loss': recon, 'KLD': KLD}, both unweighted as there.  The device Adam moments live in a JointEmbedTrainer kept on `optim`; lr,
-    betas and eps are read from optim.param_groups on every call.  One host read: the returned float (the packed pair with the KL term).
-    As in train_iter_seq2seq, `optim` is a torch.optim.Adam whose hyper-parameters are used and whose own step() and state are NOT: every
-    parameter of `net` that received a gradient is stepped (as Adam over net.parameters() does, which skips parameters without one).
-    Anything else -- another optimiser class, several parameter groups, weight_decay, amsgrad -- raises."""
-    g0 = optim.param_groups[0]
-    if not isinstance(optim, torch.optim.Adam) or len(optim.param_groups) != 1 or g0.get("weight_decay", 0) or g0.get("amsgrad", False):
-        raise NotImplementedError("train_iter_embed steps with the device Adam: pass a torch.optim.Adam with one parameter group, no weight_decay, no amsgrad")
-    tr = getattr(optim, "_joint_embed_trainer", None)
-    if tr is None or tr.net is not net:
-        tr = JointEmbedTrainer(net)
-        optim._joint_embed_trainer = tr
-    g = optim.param_groups[0]
+    is {'loss': recon, 'KLD': KLD}, both unweighted as there.  One host read: the returned float (the packed pair with the KL term).
+    The JointEmbedTrainer is kept on `optim` (optim.adopt: a plain torch.optim.Adam, whose hyper-parameters alone are used): every parameter
+    of `net` that received a gradient is stepped (as Adam over net.parameters() does, which skips parameters without one)."""
+    tr, g = adopt(optim, "_joint_embed_trainer", "train_iter_embed", lambda: JointEmbedTrainer(net), lambda t: t.net is net)
     tr.set_hparams(g["lr"], g["betas"], g["eps"])
     if not variational_encoding:
         return {"loss": tr.step(args, epoch, in_text, in_audio, target_data, mode).item()}
@@ -523,7 +448,6 @@ def train_iter_embed(args, epoch, in_text, in_audio, target_data, net, optim, mo
 # -------------------------------------------------------------------------------------------------------------------- checkpoints
 def build_model(args, lang_model, pose_dim, device):
     """train.py:41-44 for model == 'joint_embedding': (EmbeddingNet(mode='random'), None, None)."""
-    from .modules import EmbeddingNet
     generator = EmbeddingNet(args, pose_dim, args.n_poses, lang_model.n_words, args.wordembed_dim, lang_model.word_embedding_weights,
                              mode="random").to(device)
     return generator, None, None

@@ -16,6 +16,13 @@ def empty(*shape, like=None, device=None, dtype=torch.float32):
     return torch.empty(*shape, device=like.device if like is not None else device, dtype=dtype)
 
 
+def need_cuda(t, name, dtype=torch.float32, error=TypeError, why="there is no torch fallback"):
+    """The one "must be a CUDA tensor" check of the module layer; dtype=None checks the device only."""
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and (dtype is None or t.dtype == dtype)):
+        kind = "tensor" if dtype is None else f"{dtype} tensor"
+        raise error(f"{name} must be a CUDA {kind}, got {getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}: {why}")
+
+
 # ----------------------------------------------------------------------------------------------- weights that stand still
 _FROZEN = None          # the memo of the active FrozenWeights scope
 

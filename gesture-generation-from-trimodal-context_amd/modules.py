@@ -17,6 +17,7 @@ import torch.nn as nn
 from . import vocab
 from . import ops
 from .engine import AutoencoderEngine, DiscriminatorEngine, GeneratorEngine
+from .layers import need_cuda
 
 
 def _wn_conv(cin, cout, k, dilation):
@@ -75,9 +76,8 @@ class CpuVariationalError(TypeError, NotImplementedError):
 
 
 def _need_cuda_variational(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda):
-        raise CpuVariationalError(f"{name} must be a CUDA tensor for variational_encoding=True, got {getattr(t, 'device', None)}: the "
-                                  "reparameterised latent runs in csrc/vae_latent.hip only, there is no torch fallback")
+    need_cuda(t, name, None, CpuVariationalError,
+              "variational_encoding=True runs the reparameterised latent in csrc/vae_latent.hip only, there is no torch fallback")
 
 
 class _Bridge(torch.autograd.Function):

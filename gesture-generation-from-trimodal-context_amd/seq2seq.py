@@ -18,7 +18,9 @@ import torch.nn as nn
 
 from . import layers as L
 from . import ops
+from .layers import need_cuda
 from .ops import Win
+from .optim import ParamAdam, adopt
 from .rnn import GRU, EncoderRNN, _EmbedFn
 
 
@@ -41,7 +43,7 @@ class Attn(nn.Module):
         self.v.data.normal_(mean=0, std=stdv)
 
     def forward(self, hidden, encoder_outputs):
-        _need_cuda(hidden, "Attn: hidden"); _need_cuda(encoder_outputs, "Attn: encoder_outputs")
+        need_cuda(hidden, "Attn: hidden"); need_cuda(encoder_outputs, "Attn: encoder_outputs")
         H = self.hidden_size
         with torch.no_grad():
             enc = encoder_outputs.transpose(0, 1).contiguous()
@@ -52,12 +54,6 @@ class Attn(nn.Module):
             q = ops.gemm_nt(Win.plain(hidden.contiguous()), wa[:, :H], None, L.empty(B, H, like=enc))
             w, _ = ops.attn_step_forward(q, keys, enc, self.v.detach(), L.empty(B, Te, like=enc), L.empty(B, H, like=enc))
         return w.unsqueeze(1)
-
-
-def _need_cuda(t, name):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
-        raise TypeError(f"{name} must be a CUDA float32 tensor, got {getattr(t, 'dtype', None)} on {getattr(t, 'device', None)}: there is no "
-                        "torch fallback")
 
 
 def _need_attn(B, Te, H):
@@ -305,7 +301,7 @@ class BahdanauAttnDecoderRNN(nn.Module):
         return h_n
 
     def forward(self, motion_input, last_hidden, encoder_outputs, vid_indices=None):
-        _need_cuda(motion_input, "BahdanauAttnDecoderRNN: motion_input")
+        need_cuda(motion_input, "BahdanauAttnDecoderRNN: motion_input")
         with torch.no_grad():
             enc = encoder_outputs.transpose(0, 1).contiguous()
             out, hidden, w = self.decode(enc, last_hidden, motion_input.unsqueeze(1), 2, 1, None, vid_indices)
@@ -349,9 +345,8 @@ class Seq2SeqNet(nn.Module):
         return self._run(in_text, in_lengths, poses, vid_indices, z, None)
 
     def _run(self, in_text, in_lengths, poses, vid_indices, z, enc_lengths):
-        _need_cuda(poses, "Seq2SeqNet: poses")
-        if not (isinstance(in_text, torch.Tensor) and in_text.is_cuda):
-            raise TypeError("Seq2SeqNet: in_text must be a CUDA int64 tensor: there is no torch fallback")
+        need_cuda(poses, "Seq2SeqNet: poses")
+        need_cuda(in_text, "Seq2SeqNet: in_text", None)
         if poses.dim() != 3 or poses.shape[1] < max(self.n_pre_poses, 1) or poses.shape[2] != self.decoder.output_size:
             raise ValueError(f"Seq2SeqNet: poses must be (B, >= {max(self.n_pre_poses, 1)}, {self.decoder.output_size}), got {tuple(poses.shape)}")
         encoder_outputs, encoder_hidden = self.encoder(in_text.transpose(0, 1), in_lengths, None)
@@ -397,22 +392,20 @@ def custom_loss(output, target, args, epoch=None):
 
 
 class Seq2SeqTrainer:
-    """train_iter_seq2seq with the device Adam (torch.optim.Adam semantics, tg_adam_step): zero_grad, forward, custom_loss, backward,
-    clip_grad_norm_(parameters, 5) by a device scale (no host read between the backward and the optimiser), Adam."""
+    """train_iter_seq2seq with the device Adam (optim.ParamAdam): zero_grad, forward, custom_loss, backward, clip_grad_norm_(parameters, 5)
+    by a device scale (no host read between the backward and the optimiser), Adam on every parameter that received a gradient."""
 
     def __init__(self, net, lr=1e-3, betas=(0.5, 0.999), eps=1e-8, max_norm=5.0):
-        self.net = net
-        self.params = [p for p in net.parameters()]
-        dev = self.params[0].device
-        self.m, self.v = [torch.zeros_like(p) for p in self.params], [torch.zeros_like(p) for p in self.params]
-        self.step_dev = torch.zeros(1, device=dev, dtype=torch.int32)
-        self.lr, self.betas, self.eps, self.max_norm = lr, tuple(betas), eps, max_norm
+        self.net, self.max_norm = net, max_norm
+        self.adam = ParamAdam(net.parameters(), lr, betas, eps)
+        self.step_dev = self.adam.step_dev
+        dev = self.step_dev.device
         self.total = torch.zeros(1, device=dev, dtype=torch.float64)
         self.ws = torch.empty(256, device=dev, dtype=torch.float64)
         self.scale = torch.zeros(2, device=dev, dtype=torch.float32)
 
     def set_hparams(self, lr, betas, eps):
-        self.lr, self.betas, self.eps = lr, tuple(betas), eps
+        self.adam.set_hparams(lr, betas, eps)
 
     def clip(self, grads):
         ops.zero_(self.total)
@@ -423,30 +416,19 @@ class Seq2SeqTrainer:
             ops.scale_by(g, self.scale)
 
     def step(self, args, epoch, in_text, in_lengths, target_poses):
-        for p in self.params:
-            p.grad = None
+        self.adam.zero_grad()
         outputs = self.net(in_text, in_lengths, target_poses, None)
         loss = custom_loss(outputs, target_poses, args, epoch)
         loss.backward()
-        live = [(p, m, v) for p, m, v in zip(self.params, self.m, self.v) if p.grad is not None]
-        for p, _, _ in live:
-            if not p.grad.is_contiguous():
-                p.grad = p.grad.contiguous()
-        self.clip([p.grad for p, _, _ in live])
-        ops.counter_inc(self.step_dev)
-        for p, m, v in live:
-            ops.adam_step(p.data, p.grad, m, v, self.lr, self.betas[0], self.betas[1], self.eps, self.step_dev)
+        self.clip(self.adam.live_grads())
+        self.adam.step()
         return loss.detach()
 
 
 def train_iter_seq2seq(args, epoch, in_text, in_lengths, target_poses, net, optim):
-    """The reference's signature and return dict (train_seq2seq.py:36-51).  The device Adam moments live in a Seq2SeqTrainer kept on `optim`;
-    lr, betas and eps are read from optim.param_groups on every call, so schedules apply.  The torch optimiser's own state is not used."""
-    tr = getattr(optim, "_seq2seq_trainer", None)
-    if tr is None or tr.net is not net:
-        tr = Seq2SeqTrainer(net)
-        optim._seq2seq_trainer = tr
-    g = optim.param_groups[0]
+    """The reference's signature and return dict (train_seq2seq.py:36-51).  The Seq2SeqTrainer is kept on `optim` (optim.adopt: a plain
+    torch.optim.Adam, whose hyper-parameters alone are used)."""
+    tr, g = adopt(optim, "_seq2seq_trainer", "train_iter_seq2seq", lambda: Seq2SeqTrainer(net), lambda t: t.net is net)
     tr.set_hparams(g["lr"], g["betas"], g["eps"])
     return {"loss": tr.step(args, epoch, in_text, in_lengths, target_poses).item()}
 

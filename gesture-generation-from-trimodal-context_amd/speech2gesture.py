@@ -16,6 +16,9 @@ import torch.nn as nn
 from torch.autograd import Function
 
 from . import layers, ops
+from .autograd_fns import L1MeanFn, LinearFn
+from .layers import need_cuda
+from .optim import ParamAdam, adam_group, adopt
 
 N_MELS = 128
 MAKE_1D_COL = 3           # Upsample((n_poses, 1)) from W = 7: source column (0 + 0.5) * 7 - 0.5 = 3 exactly
@@ -157,25 +160,9 @@ class _BNActFn(Function):
         if not ctx.training:
             raise RuntimeError("speech2gesture: backward through an eval-mode BatchNorm is not supported (the reference trains in train mode)")
         gamma, beta = ctx.saved_tensors
-        dg, dbt = torch.zeros_like(gamma), torch.zeros_like(beta)
+        dg, dbt = ops.zeros_like(gamma), ops.zeros_like(beta)
         dx = layers.bn_bwd(dy.contiguous(), ctx.st, gamma.detach(), beta.detach(), dg, dbt)    # (one launch forms all three)
         return dx, dg if ctx.needs_input_grad[1] else None, dbt if ctx.needs_input_grad[2] else None, None, None, None
-
-
-class _LinearFn(Function):
-    @staticmethod
-    def forward(ctx, x, w, b):
-        x = x.contiguous()
-        y = layers.linear_fwd(x, w.detach(), b.detach())
-        ctx.save_for_backward(x, w)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, w = ctx.saved_tensors
-        dw, db = torch.zeros_like(w), torch.zeros(w.shape[0], device=w.device, dtype=torch.float32)
-        dx = layers.linear_bwd(dy.contiguous(), x, w.detach(), dw, db, need_dx=ctx.needs_input_grad[0])
-        return dx, dw, db
 
 
 class _RowsInterpFn(Function):
@@ -291,12 +278,6 @@ def _block2d(seq, x):
     return _BNActFn.apply(y, bn.weight, bn.bias, bn, bn.training, 0.2)
 
 
-def _cuda_check(mod, *xs):
-    for x in xs:
-        if not x.is_cuda:
-            raise RuntimeError(f"{type(mod).__name__}: inputs must be on the GPU (there is no CPU path)")
-
-
 # ------------------------------------------------------------------------------------------------- modules
 class Generator(nn.Module):
     def __init__(self, n_poses, pose_dim, n_pre_poses):
@@ -327,15 +308,16 @@ class Generator(nn.Module):
         return x
 
     def forward(self, in_spec, pre_poses):
-        _cuda_check(self, in_spec, pre_poses)
+        for t, name in ((in_spec, "in_spec"), (pre_poses, "pre_poses")):
+            need_cuda(t, "Generator: " + name, None, RuntimeError, "there is no CPU path")
         if in_spec.dtype not in (torch.float16, torch.float32):
             in_spec = in_spec.float()
         audio = self.audio_features(in_spec)
         B = pre_poses.shape[0]
         pe = self.pre_pose_encoder
-        h = _LinearFn.apply(pre_poses.reshape(B, -1).float(), pe[0].weight, pe[0].bias)
+        h = LinearFn.apply(pre_poses.reshape(B, -1).float(), pe[0].weight, pe[0].bias)
         h = _BNActFn.apply(h, pe[1].weight, pe[1].bias, pe[1], pe[1].training, 0.0)
-        pp = _LinearFn.apply(h, pe[3].weight, pe[3].bias)
+        pp = LinearFn.apply(h, pe[3].weight, pe[3].bias)
         x = _CatRepeatFn.apply(audio, pp)
         for blk in self.decoder:
             x = _block1d(blk, x)
@@ -350,7 +332,7 @@ class Discriminator(nn.Module):
 
     def forward(self, x):
         """x (B, T, pose_dim) -> logits (B, 1, T') as the reference returns them (T' = ceil((T - 1) / 4))."""
-        _cuda_check(self, x)
+        need_cuda(x, "Discriminator: x", None, RuntimeError, "there is no CPU path")
         x = first_difference(x.float())
         c0 = self.net[0]
         rows, left = _tf_geom(c0, x.shape[1], 0)
@@ -366,67 +348,36 @@ class Discriminator(nn.Module):
 # ------------------------------------------------------------------------------------------------- training iteration
 def l1_loss(out, target):
     """mean |out - target| (tg_l1_mean) with its gradient sign(out - target) / n as an autograd node."""
-    return _L1Fn.apply(out, target)
-
-
-class _L1Fn(Function):
-    @staticmethod
-    def forward(ctx, a, b):
-        a, b = a.contiguous(), b.contiguous()
-        loss = torch.empty(1, device=a.device, dtype=torch.float32)
-        ops.l1_mean(a, b, loss)
-        ctx.save_for_backward(a, b)
-        return loss.view(())
-
-    @staticmethod
-    def backward(ctx, g):
-        a, b = ctx.saved_tensors
-        d = torch.empty_like(a)
-        ops.s2g_l1_grad(a, b, d)
-        return d * g, None
+    return L1MeanFn.apply(out.contiguous(), target.contiguous()).view(())
 
 
 class S2GTrainer:
-    """train_iter_speech2gesture with the device Adam (torch.optim.Adam semantics, tg_adam_step) owning one moment pair per parameter.
+    """train_iter_speech2gesture with the device Adam (optim.ParamAdam, one per network: adam_g, adam_d).
     G: Adam(lr, betas), D: Adam(lr * 0.2, betas) -- train.py:104-109 for this model."""
 
     def __init__(self, generator, discriminator, lr=1e-3, betas=(0.5, 0.999), eps=1e-8, dis_lr_scale=0.2, regression_weight=100.0,
                  gan_weight=10.0, n_pre_poses=4):
         self.g, self.d = generator, discriminator
-        dev = next(generator.parameters()).device
-        self.opt = {}
-        for name, mod, rate in (("g", generator, lr), ("d", discriminator, lr * dis_lr_scale)):
-            ps = [p for p in mod.parameters()]
-            self.opt[name] = dict(params=ps, m=[torch.zeros_like(p) for p in ps], v=[torch.zeros_like(p) for p in ps],
-                                  step=torch.zeros(1, device=dev, dtype=torch.int32), lr=rate)
-        self.betas, self.eps = betas, eps
+        self.adam_g = ParamAdam(generator.parameters(), lr, betas, eps)
+        self.adam_d = ParamAdam(discriminator.parameters(), lr * dis_lr_scale, betas, eps)
         self.w_reg, self.w_gan, self.n_pre = regression_weight, gan_weight, n_pre_poses
 
     def set_hparams(self, lr, betas, eps, dis_lr_scale):
         """Learning rates / betas / eps of both optimisers (read again on every train_iter_speech2gesture call)."""
-        self.opt["g"]["lr"], self.opt["d"]["lr"] = lr, lr * dis_lr_scale
-        self.betas, self.eps = tuple(betas), eps
-
-    def _adam(self, name):
-        o = self.opt[name]
-        ops.counter_inc(o["step"])
-        for p, m, v in zip(o["params"], o["m"], o["v"]):
-            g = p.grad if p.grad is not None else torch.zeros_like(p)
-            ops.adam_step(p.data, g.contiguous(), m, v, o["lr"], self.betas[0], self.betas[1], self.eps, o["step"])
+        self.adam_g.set_hparams(lr, betas, eps)
+        self.adam_d.set_hparams(lr * dis_lr_scale, betas, eps)
 
     def step(self, in_spec, target_poses):
         """One iteration; returns device scalars (loss = w_reg L1, gen = w_gan mse(1, D(G)), dis)."""
         g, d = self.g, self.d
-        for p in list(g.parameters()) + list(d.parameters()):
-            p.grad = None
+        self.adam_g.zero_grad(); self.adam_d.zero_grad()
         out = g(in_spec, target_poses[:, :self.n_pre])
         target_motion = first_difference(target_poses)
         out_motion = first_difference(out)
         dis_error = mse_to_const(d(target_motion), 1.0) + mse_to_const(d(out_motion.detach()), 0.0)
         dis_error.backward()
-        self._adam("d")
-        for p in g.parameters():
-            p.grad = None
+        self.adam_d.step()
+        self.adam_g.zero_grad()
         l1 = l1_loss(out, target_poses)
         for p in d.parameters():            # the G step takes no D gradient: frozen BEFORE D's forward, so its backward skips them
             p.requires_grad_(False)
@@ -437,20 +388,21 @@ class S2GTrainer:
         finally:
             for p in d.parameters():
                 p.requires_grad_(True)
-        self._adam("g")
+        self.adam_g.step()
         return dict(loss=self.w_reg * l1.detach(), gen=self.w_gan * gen_error.detach(), dis=dis_error.detach())
 
 
 def train_iter_speech2gesture(args, in_spec, target_poses, pose_decoder, discriminator, pose_dec_optim, dis_optim, loss_fn):
-    """The reference's signature and return dict.  The device Adam moments live in an S2GTrainer kept on `pose_dec_optim` (so they go
-    with the optimiser); lr, betas and eps are read from the two torch optimisers' param_groups on every call, so schedules apply.  The
-    torch optimisers' own state is not used."""
-    tr = getattr(pose_dec_optim, "_s2g_trainer", None)
-    if tr is None or tr.g is not pose_decoder or tr.d is not discriminator:
-        tr = S2GTrainer(pose_decoder, discriminator, regression_weight=args.loss_regression_weight, gan_weight=args.loss_gan_weight,
-                        n_pre_poses=args.n_pre_poses)
-        pose_dec_optim._s2g_trainer = tr
-    gg, dg = pose_dec_optim.param_groups[0], dis_optim.param_groups[0]
+    """The reference's signature and return dict.  The S2GTrainer is kept on `pose_dec_optim` (optim.adopt: both optimisers are plain
+    torch.optim.Adams, whose hyper-parameters alone are used; the discriminator's is checked first, so either refusal comes before the
+    trainer is built).  betas and eps of BOTH networks come from `pose_dec_optim`; of `dis_optim` only lr is read (train.py:104-109 gives
+    the two the same betas), and the refusal does not look at its betas / eps."""
+    who = "train_iter_speech2gesture"
+    dg = adam_group(dis_optim, who)
+    tr, gg = adopt(pose_dec_optim, "_s2g_trainer", who,
+                   lambda: S2GTrainer(pose_decoder, discriminator, regression_weight=args.loss_regression_weight,
+                                      gan_weight=args.loss_gan_weight, n_pre_poses=args.n_pre_poses),
+                   lambda t: t.g is pose_decoder and t.d is discriminator)
     tr.set_hparams(gg["lr"], gg["betas"], gg["eps"], dg["lr"] / gg["lr"])
     r = tr.step(in_spec, target_poses)
     return {"loss": r["loss"].item(), "gen": r["gen"].item(), "dis": r["dis"].item()}
