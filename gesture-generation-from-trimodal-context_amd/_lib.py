@@ -229,6 +229,10 @@ def load():
     lib.tg_gemm_nt_variant.argtypes = [C.POINTER(NtProblem), I32, C.POINTER(C.c_int32)]
     lib.tg_gemm_tn_split_plan.restype = C.c_int32
     lib.tg_gemm_tn_split_plan.argtypes = [C.POINTER(TnProblem), I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.tg_gemm_nt_split_variant.restype = C.c_int32
+    lib.tg_gemm_nt_split_variant.argtypes = [C.POINTER(NtProblem), I32, C.POINTER(C.c_int32)]
+    lib.tg_gemm_tn_split_tile.restype = C.c_int32
+    lib.tg_gemm_tn_split_tile.argtypes = [C.POINTER(TnProblem), I32, C.POINTER(C.c_int32)]
     lib.tg_bn_fused_supported.restype = C.c_int32
     lib.tg_bn_fused_supported.argtypes = [I32, I32, I32]
     lib.tg_set_math_mode.restype = C.c_int

@@ -911,6 +911,20 @@ extern "C" int32_t tg_gemm_nt_variant(const tg_gemm_nt_problem* problems, int32_
     return fam;
 }
 
+void tg_gemm_nt_split_pick(const NtGroup& g, int out[4]);
+extern "C" int32_t tg_gemm_nt_split_variant(const tg_gemm_nt_problem* problems, int32_t n, int32_t out[4]) {
+    if (tg_gemm_nt_kernel_plan(problems, n, nullptr, nullptr) != 1) return -1;        // (also: null, bad sizes, mixed families)
+    NtGroup g;
+    g.n = n;
+    for (int i = 0; i < n; ++i)
+        if (nt_fill(g.p[i], problems[i], i)) return -1;
+    for (int i = n; i < TG_MAX_GROUP; ++i) g.p[i] = g.p[0];
+    int v[4];
+    tg_gemm_nt_split_pick(g, v);
+    if (out) { out[0] = v[0]; out[1] = v[1]; out[2] = v[2]; out[3] = v[3]; }
+    return 1;
+}
+
 extern "C" int tg_gemm_nt_group(const tg_gemm_nt_problem* problems, int32_t n, void* stream) {
     TG_REQUIRE(problems && n >= 1 && n <= TG_MAX_GROUP, "tg_gemm_nt_group: 1..%d problems", TG_MAX_GROUP);
     NtGroup g;
@@ -1019,7 +1033,7 @@ static int tn_fill(TnProb& p, const tg_gemm_tn_problem& q, int idx, int group_ti
 
 // plan_only != nullptr: decide the kernel (0 f32-MFMA, 1 bf16 x 3 staged slabs, 2 bf16 x 3 mover waves) and return without launching;
 // split_plan (with plan_only, plans 0 and 1): also report every problem's row splits, rows per split and combine (tn_reduce_kind)
-struct TnSplitPlanOut { int32_t *splits, *rows_per_split, *reduce_kind; };
+struct TnSplitPlanOut { int32_t *splits, *rows_per_split, *reduce_kind, *tile; };       // tile: {tnw, tkw} of gemm_tn_split_kernel, plan 1 only
 extern "C" int tg_get_tn_workgroup_cap(void);
 static int tn_group_impl(const tg_gemm_tn_problem* problems, int32_t n, void* stream, int32_t* plan_only, const TnSplitPlanOut* split_plan = nullptr) {
     TG_REQUIRE(problems && n >= 1 && n <= TG_MAX_GROUP, "tg_gemm_tn_group: 1..%d problems", TG_MAX_GROUP);
@@ -1093,6 +1107,7 @@ static int tn_group_impl(const tg_gemm_tn_problem* problems, int32_t n, void* st
             if (split_plan->rows_per_split) split_plan->rows_per_split[i] = g.p[i].rows_per_split;
             if (split_plan->reduce_kind) split_plan->reduce_kind[i] = tn_reduce_kind(g.p[i].partial != nullptr, splits[i]);
         }
+        if (split_plan && split_plan->tile && x3) { split_plan->tile[0] = tnw; split_plan->tile[1] = tkw; }
         return 0;
     }
     // tg_set_tn_workgroup_cap promises a launch that occupies at most that many CUs (it runs beside a cluster-synchronised recurrence whose
@@ -1128,8 +1143,20 @@ extern "C" int32_t tg_gemm_tn_split_plan(const tg_gemm_tn_problem* problems, int
     if (!problems || n < 1 || n > TG_MAX_GROUP) return -1;
     for (int i = 0; i < n; ++i)
         if (!problems[i].dY || !problems[i].dW || !problems[i].A.ptr) return -1;
-    const TnSplitPlanOut out = {splits, rows_per_split, reduce_kind};
+    const TnSplitPlanOut out = {splits, rows_per_split, reduce_kind, nullptr};
     return tn_group_impl(problems, n, nullptr, &plan, &out) == 0 ? plan : -1;
+}
+
+extern "C" int32_t tg_gemm_tn_split_tile(const tg_gemm_tn_problem* problems, int32_t n, int32_t out[2]) {
+    int32_t plan = -1;
+    if (!problems || n < 1 || n > TG_MAX_GROUP) return -1;
+    for (int i = 0; i < n; ++i)
+        if (!problems[i].dY || !problems[i].dW || !problems[i].A.ptr) return -1;
+    int32_t tile[2] = {0, 0};
+    const TnSplitPlanOut po = {nullptr, nullptr, nullptr, tile};
+    if (tn_group_impl(problems, n, nullptr, &plan, &po) != 0 || plan != 1) return -1;
+    if (out) { out[0] = tile[0]; out[1] = tile[1]; }
+    return 1;
 }
 
 extern "C" int tg_gemm_tn(const float* dY, int64_t ldy, const tg_window* A, float* dW, int64_t ldw, int32_t M, int32_t N,

@@ -623,6 +623,25 @@ static SplitTile split_pick_tile(int M, int N) {
 bool tg_gemm_nt_mw_eligible(NtGroup& g, int* tm, int* tn);
 int tg_gemm_nt_mw_launch(NtGroup& g, int tm, int tn, int splits, hipStream_t s);
 
+// The instantiation of gemm_nt_split_kernel a big-product group runs on once the mover-wave kernel has declined it -- the ONE place that
+// decides (tg_gemm_nt_split_launch switches on it, tg_gemm_nt_split_variant reports it): the tile of the group's largest M times its problem
+// count and largest N, and fast addressing (see the kernel's FAST note) for the group as a whole -- fp32-accurate mode only.
+struct SplitVariant { int tm, tn, db, fast; };
+static SplitVariant split_pick_variant(const NtGroup& g) {
+    int Mx = 0, Nx = 0;
+    for (int i = 0; i < g.n; ++i) { Mx = Mx > g.p[i].M ? Mx : g.p[i].M; Nx = Nx > g.p[i].N ? Nx : g.p[i].N; }
+    const SplitTile tl = split_pick_tile(Mx * g.n, Nx);
+    static const int fast_on = [] { const char* e = getenv("TG_NT_FAST"); return e ? atoi(e) : 1; }();
+    bool fast = fast_on != 0 && g_math_mode == 0;
+    for (int i = 0; i < g.n && fast; ++i) fast = nt_fast_ok(g.p[i]);
+    return {tl.tm, tl.tn, tl.db, fast ? 1 : 0};
+}
+// (for tg_gemm_nt_split_variant, gemm.hip)
+void tg_gemm_nt_split_pick(const NtGroup& g, int out[4]) {
+    const SplitVariant v = split_pick_variant(g);
+    out[0] = 32 * v.tm; out[1] = 32 * v.tn; out[2] = v.db; out[3] = v.fast;
+}
+
 int tg_gemm_nt_split_launch(NtGroup& g, hipStream_t s) {
     {   // many-row products whose big tiles fill the chip: mover-wave kernel (gemm_mw.hip)
         int tm = 0, tn = 0;
@@ -636,9 +655,7 @@ int tg_gemm_nt_split_launch(NtGroup& g, hipStream_t s) {
     for (int i = 0; i < g.n; ++i)
         TG_REQUIRE(g.p[i].drop_state == nullptr || g.p[i].vec_c, "tg_gemm_nt: regenerated dropout needs a vectorisable C (N %% 4 == 0, strides %% 4 == 0, "
                    "16-byte aligned; problem %d)", i);
-    int Mx = 0, Nx = 0;
-    for (int i = 0; i < g.n; ++i) { Mx = Mx > g.p[i].M ? Mx : g.p[i].M; Nx = Nx > g.p[i].N ? Nx : g.p[i].N; }
-    const SplitTile tl = split_pick_tile(Mx * g.n, Nx);
+    const SplitVariant tl = split_pick_variant(g);
     const int bm = 32 * tl.tm, bn = 32 * tl.tn;
     int wg = 0;
     for (int i = 0; i < g.n; ++i) {             // every problem's range starts at a multiple of 8 (XCD mapping, see gemm.hip nt_layout)
@@ -662,11 +679,7 @@ int tg_gemm_nt_split_launch(NtGroup& g, hipStream_t s) {
         else if (tl.tm == 2 && tl.tn == 3) TG_SPLIT(2, 3, SP_, 1);      \
         else TG_SPLIT(2, 2, SP_, 1);                                    \
     } while (0)
-    // fast addressing (see the kernel's FAST note): decided for the group as a whole
-    static const int fast_on = [] { const char* e = getenv("TG_NT_FAST"); return e ? atoi(e) : 1; }();
-    bool fast = fast_on != 0 && g_math_mode == 0;
-    for (int i = 0; i < g.n && fast; ++i) fast = nt_fast_ok(g.p[i]);
-    if (fast) {
+    if (tl.fast) {
 #define TG_FAST(TM_, TN_, DB_, R_, O_) hipLaunchKernelGGL((gemm_nt_split_kernel<TM_, TN_, 3, DB_, R_, O_, 0, true>), grid, dim3(256), 0, s, g)
         if (tl.tm == 4 && tl.tn == 3) TG_FAST(4, 3, 0, 1, 3);
         else if (tl.tm == 4 && tl.tn == 2) TG_FAST(4, 2, 0, 1, 4);

@@ -229,6 +229,18 @@ def nt_variant(problems):
     return tuple(out) if fam > 0 else (0,)
 
 
+def nt_split_variant(problems):
+    """(tile_m, tile_n, db, fast): the instantiation of the staged-slab bf16 x 3 kernel (csrc/gemm_split.hip) a big-product group given as
+    gemm_nt_group's list of dicts runs on -- tile 128 / 64 x 96 / 64, double-buffered LDS, fast (maskless) addressing -- as the launcher itself
+    decides it.  Raises for a group nt_kernel_plan does not answer with 1."""
+    qs = [_nt_problem(**p) for p in problems]
+    arr = (_lib.NtProblem * len(qs))(*qs)
+    out = (C.c_int32 * 4)()
+    if int(_lib.load().tg_gemm_nt_split_variant(arr, len(qs), out)) != 1:
+        raise ValueError("nt_split_variant: not a group of the staged-slab bf16 x 3 kernel (nt_kernel_plan != 1)")
+    return tuple(out)
+
+
 def gemm_nt(A: Win, W, bias, out, **kw):
     """out(m, :) = act(A(m, :) @ W^T + bias) [+ out].  W: [N, K] (row stride may exceed K).
     out: 2-D view [M, N] (unit inner stride) unless explicit C addressing is given."""
@@ -626,6 +638,18 @@ def tn_split_plan(problems):
     if plan not in (0, 1):
         raise ValueError(f"tn_split_plan: plan {plan} (invalid group, or the mover-wave kernel's)")
     return [(splits[i], rows[i], kind[i]) for i in range(n)]
+
+
+def tn_split_tile(problems):
+    """(tnw, tkw): the dW tile (32 tnw x 32 tkw) of the staged-slab bf16 x 3 weight-gradient kernel for a group given as gemm_tn_group's list of
+    dicts, as the launcher chooses it.  Raises for a group tn_kernel_plan does not answer with 1."""
+    keep = []
+    n = len(problems)
+    arr = (_lib.TnProblem * n)(*[_tn_problem(keep=keep, **p)[0] for p in problems])
+    out = (C.c_int32 * 2)()
+    if int(_lib.load().tg_gemm_tn_split_tile(arr, n, out)) != 1:
+        raise ValueError("tn_split_tile: not a group of the staged-slab bf16 x 3 kernel (tn_kernel_plan != 1)")
+    return tuple(out)
 
 
 def colsum(X, out, *, accumulate=True):

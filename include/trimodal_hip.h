@@ -175,6 +175,11 @@ int32_t tg_gemm_nt_kernel_plan(const tg_gemm_nt_problem* problems, int32_t n, in
  * workgroup: tile 32 wm x 32 wn), ring (k-steps of operands in flight), ks (waves splitting K: 1 or 4)}; family 0 fills nothing.
  * Test aid like tg_gemm_nt_kernel_plan: a parity test asserts which kernel it covered. */
 int32_t tg_gemm_nt_variant(const tg_gemm_nt_problem* problems, int32_t n, int32_t out[6]);
+/* Which instantiation of the staged-slab bf16 x 3 kernel (gemm_split.hip: gemm_nt_split_kernel) a big-product group would run on, without
+ * launching -- the choice tg_gemm_nt_group itself makes.  Returns 1 and fills out = {tile rows (128 / 64), tile columns (96 / 64), db (1: two
+ * LDS buffers), fast (1: the addressing form without row masks, every window of the group free of padding)} for a group that
+ * tg_gemm_nt_kernel_plan answers with 1; -1 for any other plan or an invalid group (out untouched).  Test aid like tg_gemm_nt_variant. */
+int32_t tg_gemm_nt_split_variant(const tg_gemm_nt_problem* problems, int32_t n, int32_t out[4]);
 /* Process-wide switch of the mover-wave kernel: 1 on, 0 off (every big product on gemm_split.hip), -1 back to the environment default
  * (TG_NT_MW, on).  For same-process A/B timing (tools/nt_mw_probe.py) and tests; results are equal within the fp32 tolerance either way. */
 int tg_set_nt_mover_waves(int32_t on);
@@ -245,6 +250,10 @@ int32_t tg_gemm_tn_kernel_plan(const tg_gemm_tn_problem* problems, int32_t n);
  * splits, rows_per_split (a multiple of 32; the last split may be shorter) and reduce_kind -- 0: float atomics (ws == NULL), 16 / 256: the
  * fixed-order fp64 combine with that many threads per output entry (256 from 512 splits on).  Plan 2 fills nothing.  Test aid. */
 int32_t tg_gemm_tn_split_plan(const tg_gemm_tn_problem* problems, int32_t n, int32_t* splits, int32_t* rows_per_split, int32_t* reduce_kind);
+/* The dW tile of the staged-slab bf16 x 3 weight-gradient kernel (gemm_split.hip: gemm_tn_split_kernel<tnw, tkw>, tile 32 tnw x 32 tkw) as
+ * tg_gemm_tn_group chooses it: returns 1 and fills out = {tnw, tkw} for a group tg_gemm_tn_kernel_plan answers with 1, -1 otherwise (out
+ * untouched).  Test aid. */
+int32_t tg_gemm_tn_split_tile(const tg_gemm_tn_problem* problems, int32_t n, int32_t out[2]);
 int tg_gemm_tn(const float* dY, int64_t ldy, const tg_window* A, float* dW, int64_t ldw, int32_t M, int32_t N,
                int32_t out_kw, float* dbias, float* ws, int64_t ws_floats, void* stream);
 

@@ -625,8 +625,10 @@ def test_gemm_nt_big_tile_path_with_conv_window(pkg, dev):
 @pytest.mark.parametrize("M,N,K", [(13056, 300, 600), (4352, 600, 900), (1030, 49, 68), (2049, 97, 108), (1500, 161, 1024), (1024, 48, 64)])
 def test_gemm_nt_split_bf16x3_path_is_fp32_accurate(pkg, dev, M, N, K):
     """The big-product path (csrc/gemm_split.hip: fp32 operands split exactly into three bf16 terms, six partial products on the bf16
-    matrix cores) against fp64 at the fp32 tolerance, every tile of its menu, ragged edges in M, N and K, bias + activation,
-    accumulate, strided output -- and full-range operands (8 decades of magnitude) so that lost low-order terms would show."""
+    matrix cores) against fp64 at the fp32 tolerance, ragged edges in M, N and K, bias + activation, a column slice as output -- and
+    full-range operands (8 decades of magnitude) so that lost low-order terms would show.  By split_pick_tile the shapes land on the
+    128 x 64 tile for (13056, 300, 600), on 64 x 96 for (4352, 600, 900) and on 64 x 64 for the other four, all with fast addressing; the
+    128 x 96 tile, the general addressing form and a per-element gate are tests/test_gemm_split_envelope_gpu.py's."""
     ops, Win = pkg.ops, pkg.ops.Win
     g = torch.Generator().manual_seed(M + N + K)
     x = torch.randn(M, K, generator=g) * torch.pow(10.0, torch.randint(-4, 4, (M, 1), generator=g).float())
