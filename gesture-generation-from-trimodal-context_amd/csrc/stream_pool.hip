@@ -12,11 +12,9 @@
 // stream.hip (whose kernels serve every stream that shares a clock), and so are the bounds: here a row brings its own chunk length and
 // window index, and a row that is idle leaves before the body.
 #include "stream_rows.hpp"
+#include "window_rows.hpp"
 
 namespace tg {
-
-constexpr int PL_MAX_PRE = 8;           // tg_utterance_finish's n_pre and D
-constexpr int PL_MAX_DIM = 64;
 
 struct PoolLens {
     int n[ST_MAX_ROWS];
@@ -56,10 +54,7 @@ __global__ __launch_bounds__(256) void pool_handover_kernel(const float* __restr
     const int nD = n * D;
     for (int i = threadIdx.x; i < T * D; i += 256) {
         float v = r[i];
-        if (w > 0 && i < nD) {
-            const int j = i / D;                                      // tg_window_blend (losses.hip), with *p = v
-            v = tl[i] * (float)(n - j) / (float)(n + 1) + v * (float)(j + 1) / (float)(n + 1);
-        }
+        if (w > 0 && i < nD) v = blend_head(tl[i], v, i / D, n);      // tg_window_blend (losses.hip), with *p = v
         o[i] = v;
     }
     __syncthreads();                                                  // the old tail has been read, the window is whole

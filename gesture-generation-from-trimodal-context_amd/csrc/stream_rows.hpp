@@ -1,7 +1,7 @@
 // The row bodies of the stream kernels: what one row of the stream state -- sample ring [R], counter `written`, word ring [W][3], counter
 // n_words -- does in a push and in the staging of a window.  stream.hip runs them for rows that share a clock (one chunk length, one window
-// index), stream_pool.hip for rows with clocks of their own (a length and a window index per row, idle rows skipped); stream_seq.hip reads the
-// same word ring.  The bounds are the three files' bounds.
+// index), stream_pool.hip for rows with clocks of their own (a length and a window index per row, idle rows skipped); stream_seq.hip and
+// stream_pool_seq.hip stage the Seq2Seq model's word list from the same word ring, in the same two ways.  The bounds are the files' bounds.
 // As in utterance.hip the device sees integers only and samples and ids move as bits: plain loads and stores.
 #pragma once
 #include "common.hpp"
@@ -103,6 +103,66 @@ __device__ __forceinline__ void ring_stage_row(int b, int w, const float* __rest
     } else {
         for (int q = i; q < A; ++q) dst[q] = at(q);
     }
+}
+
+constexpr int SQ_MAX_TE = 128;          // longest list (the encoder's and the decoder's envelope)
+constexpr int SQ_THREADS = ST_MAX_WORDS / 4;   // four records of the word ring per thread
+
+// Row b of the Seq2Seq model's text of window w, by a workgroup of SQ_THREADS threads: out_text[b] = [sos, the ids of EVERY record of window w
+// in push order, eos, 0 ...] (Te entries), out_len[b] = count + 2.  The ring's live records are read oldest to newest, four per thread,
+// flagged, and an integer prefix sum over the workgroup gives every kept record its place -- an order-preserving compaction without atomics;
+// ids move as bits.  The count is clamped to Te - 2 so that no index can leave the row.  stream_seq.hip runs it for rows that share a window
+// index, stream_pool_seq.hip with an index per row; the whole workgroup comes here or none of it does (barriers).
+__device__ __forceinline__ void ring_stage_text_row(int b, int w, const int32_t* __restrict__ word_ring, const int64_t* __restrict__ n_words, int W,
+                                                    int Te, long long sos, long long eos, long long* __restrict__ out_text,
+                                                    long long* __restrict__ out_len) {
+    __shared__ int s_scan[SQ_THREADS];
+    const int tid = threadIdx.x;
+    const long cnt = n_words[b];
+    const long lo = cnt > W ? cnt - W : 0;                            // the ring holds the last W records, slot = index mod W
+    const int live = cnt < 0 ? 0 : (int)(cnt - lo);
+    const int s0 = (int)(lo % W);
+    const int32_t* __restrict__ ring = word_ring + (long)b * W * 3;
+    long long* __restrict__ row = out_text + (long)b * Te;
+    int32_t id[4];
+    bool hit[4];
+    int c = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int j = 4 * tid + q;                                    // age order: j = 0 is the oldest live record
+        hit[q] = false;
+        id[q] = 0;
+        if (j < live) {
+            int slot = s0 + j;                                        // live <= W: one subtraction wraps
+            if (slot >= W) slot -= W;
+            hit[q] = ring[3 * slot] == w;
+            id[q] = ring[3 * slot + 2];
+        }
+        c += hit[q] ? 1 : 0;
+    }
+    s_scan[tid] = c;
+    __syncthreads();
+    for (int o = 1; o < SQ_THREADS; o <<= 1) {
+        const int v = tid >= o ? s_scan[tid - o] : 0;
+        __syncthreads();
+        s_scan[tid] += v;
+        __syncthreads();
+    }
+    const int total = s_scan[SQ_THREADS - 1];
+    const int kept = total < Te - 2 ? total : Te - 2;                 // (Te >= 2)
+    int pos = s_scan[tid] - c;                                        // records kept in front of this thread's
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+        if (hit[q]) {
+            if (pos < kept) row[1 + pos] = (long long)id[q];
+            ++pos;
+        }
+    if (tid == 0) {
+        row[0] = sos;
+        row[1 + kept] = eos;
+        out_len[b] = kept + 2;
+    }
+    for (int p = kept + 2 + tid; p < Te; p += SQ_THREADS) row[p] = 0;
 }
 
 }  // namespace tg

@@ -11,12 +11,12 @@
 //                        fit on the fixed abscissae 0 .. n-1 is a projection y -> P y: the host builds the n x n matrices from n_pre in fp64,
 //                        the kernels accumulate P y in fp64 and round once to fp32, as numpy does when it assigns into the fp32 array.
 // Plain loads and stores; no workgroup depends on another.  Compiled with -ffp-contract=off (multiply, then add, like numpy's doubles).
-#include "common.hpp"
+#include "window_rows.hpp"
 
 namespace tg {
 
 constexpr int UT_PLAN_COLS = 4;        // plan_win row: audio_start, n_valid, spec_start, text length
-constexpr int UT_MAX_PRE = 8;
+constexpr int UT_MAX_PRE = PL_MAX_PRE; // (the fits' tables: window_rows.hpp)
 
 // window of row b: its scheduled index clamped to the utterance's own windows (a finished utterance idles on its last one)
 __device__ __forceinline__ long plan_row(const int32_t* __restrict__ win_off, const int32_t* __restrict__ win_idx, int b) {
@@ -83,16 +83,7 @@ __global__ __launch_bounds__(64) void utterance_smooth_kernel(float* __restrict_
                                                               int stride, int n_pre, const double* __restrict__ proj) {
     const int b = blockIdx.x, i = blockIdx.y, d = threadIdx.x;
     if (d >= D || i >= n_win[b]) return;
-    const int n = 3 * n_pre;
-    const double* __restrict__ P = proj;
-    float* __restrict__ y = total + ((long)b * F + (long)i * stride) * D + d;
-    double v[3 * UT_MAX_PRE];
-    for (int k = 0; k < n; ++k) v[k] = (double)y[(long)k * D];
-    for (int r = 0; r < n; ++r) {
-        double acc = 0.0;
-        for (int k = 0; k < n; ++k) acc += P[r * n + k] * v[k];
-        y[(long)r * D] = (float)acc;
-    }
+    project_segment(total + ((long)b * F + (long)i * stride) * D + d, D, 3 * n_pre, proj);     // (window_rows.hpp: shared with the pool's hand-over)
 }
 
 // (b) one thread per (row, dimension)

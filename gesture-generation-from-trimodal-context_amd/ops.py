@@ -2140,6 +2140,38 @@ def pool_handover(res, out, tail, seed, win, active):
     call("tg_pool_handover", _p(res), _p(out), _p(tail), _p(seed), layout, _p(win), _p(active), B, T, D, n_pre, _stream())
 
 
+# ------------------------------------------------------------------------------------------------- seq2seq stream pool (csrc/stream_pool_seq.hip)
+def pool_stage_text(st, win, active, sos, eos, text_out, len_out):
+    """stream_stage_text per row: row b with active[b] != 0 gets the Seq2Seq text of its own window win[b] (win, active: (B,) int32 on the device)
+    in text_out[b] (B, Te) int64 and its length in len_out[b] (B,) int64; the other rows of both buffers are left as they are."""
+    _stream_check(st)
+    _dev_int(win, torch.int32, st["B"], "win"); _dev_int(active, torch.int32, st["B"], "active")
+    _i64(text_out, "text_out")
+    if text_out.dim() != 2 or text_out.shape[0] != st["B"] or not text_out.is_contiguous():
+        raise ValueError(f"text_out is {tuple(text_out.shape)}, expected ({st['B']}, Te), contiguous")
+    _dev_int(len_out, torch.int64, st["B"], "len_out")
+    call("tg_pool_stage_text", _p(st["words"]), _p(st["n_words"]), _p(win), _p(active), st["B"], st["W"], int(text_out.shape[1]), int(sos), int(eos),
+         _p(text_out), _p(len_out), _stream())
+
+
+def pool_handover_smooth(res, out, tail, seed, win, active, proj):
+    """pool_handover for the plain seed (B, n_pre, D) with the Seq2Seq model's smoothing of the window it hands over: per row with active[b] != 0
+    out = res, cross-faded with tail where win[b] > 0, frames [0, 3 n_pre) of out replaced by their cubic fit (proj: the fp64 tables of
+    synthesize.projection_tables(n_pre); utterance_finish(smooth)'s bits on that window), tail = seed = out's last n_pre frames, win[b] += 1.
+    Nothing of an inactive row is written.  3 n_pre > T - n_pre is refused by the library (RuntimeError naming the envelope), nothing is launched."""
+    for t, name in ((res, "res"), (out, "out"), (tail, "tail"), (seed, "seed")):
+        _flat(t, name)
+        if t.dim() != 3:
+            raise ValueError(f"{name}: expected three dimensions, got {tuple(t.shape)}")
+    B, T, D = out.shape
+    n_pre = tail.shape[1]
+    if tuple(res.shape) != (B, T, D) or tuple(tail.shape) != (B, n_pre, D) or tuple(seed.shape) != (B, n_pre, D):
+        raise ValueError(f"res {tuple(res.shape)} / tail {tuple(tail.shape)} / seed {tuple(seed.shape)} do not belong to out {tuple(out.shape)}")
+    _dev_int(win, torch.int32, B, "win"); _dev_int(active, torch.int32, B, "active")
+    assert proj.is_cuda and proj.dtype == torch.float64 and proj.is_contiguous() and proj.numel() >= 9 * n_pre * n_pre
+    call("tg_pool_handover_smooth", _p(res), _p(out), _p(tail), _p(seed), _p(win), _p(active), _p(proj), B, T, D, n_pre, _stream())
+
+
 def pose_metrics(out, target, mean_dir_vec, n_pre, sums):
     _same(out, target); _flat(mean_dir_vec, "mean"); B, T, D = out.shape
     assert D == 27 and mean_dir_vec.numel() == 27 and sums.dtype == torch.float64 and sums.numel() >= 3 and sums.is_cuda

@@ -44,6 +44,10 @@ StreamPool is GestureStream for independent sessions: the 1 to 4 rows of ONE win
 counters on the device), opened, pushed to (ragged chunks) and closed on their own; the windows that have become complete run together, and
 the hand-over kernel (csrc/stream_pool.hip) leaves the rows that did not run untouched.  One graph serves first and later windows.
 
+Seq2SeqStreamPool is StreamPool for the seq2seq model (StreamPool itself keeps refusing it): every active row's word list of its own window
+comes out of the word ring per row, the decoder's forward goes into a result buffer of its own and the hand-over kernel
+(csrc/stream_pool_seq.hip) also smooths the window it hands over -- the smoothing segment is window-local.
+
 Structure: the three window decoders are subclasses of _WindowDecoderBase (buffers, the eager / capture-once / replay skeleton, the pooled
 window, check_kept; _capture is the one place a graph is captured); the streams and the pool are subclasses of _StreamCore (constructor checks,
 a row's word records, the closing window); the five offline loops stay separate and share _seed_rows, _host_window_batch and _rows_result.
@@ -458,7 +462,14 @@ class Seq2SeqWindowDecoder(_WindowDecoderBase):
 
     row_local_encoder: the encoder's recurrence as ONE launch per layer (csrc/seq2seq_encode.hip) instead of one launch per time step and
     layer -- Te of them, all but a row's length idle.  Default True: the measured choice at one row.
-    No random draw, no audio buffer (audio_len is the stream's window; the model never sees the samples) and no pooled window in this model.
+    No random draw and no audio buffer (audio_len is the stream's window; the model never sees the samples).
+
+    The pooled window (window_pooled, for Seq2SeqStreamPool: rows with window counters of their own) is the same chain into a result buffer of
+    the decoder's own, self.res -- the one-launch decoder loop writes its output buffer itself, so if it wrote self.out a row that does not run
+    would lose its window -- followed by ops.pool_handover_smooth, which gives the active rows their output, cross-fade, smoothed segment, tail,
+    seed and counter and leaves the other rows' bits alone.  It is the base class's skeleton: ONE captured graph (graph_pooled) for first and
+    later windows, an eager pass with no row active in front of the capture; window() and its graph are not touched.  Every row of self.text /
+    self.len must hold a valid list at all times (idle rows: [SOS, EOS], length 2): the forward runs on all B rows.
     Host-side validation raises ValueError before anything touches the GPU."""
 
     def __init__(self, args, net, batch, device, graph=True, max_words=32, row_local_encoder=True, audio_sr=16000):
@@ -483,11 +494,22 @@ class Seq2SeqWindowDecoder(_WindowDecoderBase):
         self.max_words, self.Te, self.row_local = int(max_words), int(max_words) + 2, bool(row_local_encoder)
         super().__init__(args, net, batch, device, gen.output_size, graph, text_width=self.Te, audio=False, audio_sr=audio_sr)
         self.len = torch.full((batch,), 2, dtype=torch.int64, device=device)
+        self.res = self.proj = None                                    # the pooled window's result buffer and smoothing table: made on its first use
 
     def check_kept(self, model, batch, T, n_pre, max_words=32, row_local_encoder=True):
         return super().check_kept(model, batch, T, n_pre) and self.max_words == max_words and self.row_local == bool(row_local_encoder)
 
-    def _model_forward(self):
+    def pool_buffers(self):
+        if self.res is None:
+            self.res = torch.zeros(self.B, self.T, self.D, device=self.dev)
+            self.proj = _projection_device(self.n_pre, self.dev)
+        return super().pool_buffers()
+
+    def _forward_pooled(self):
+        self._model_forward(self.res)
+        ops.pool_handover_smooth(self.res, self.out, self.tail, self.pre, self.win, self.active, self.proj)
+
+    def _model_forward(self, out=None):
         from .rnn import _EmbedFn, _SumHalvesFn
         enc, dec = self.net.encoder, self.net.decoder.decoder
         was = enc.gru.row_local_eval
@@ -498,7 +520,8 @@ class Seq2SeqWindowDecoder(_WindowDecoderBase):
         finally:
             enc.gru.row_local_eval = was
         enc_bt = _SumHalvesFn.apply(y)                                               # (B, Te, H): exact zeros behind every row's length
-        dec.decode_eval_static(enc_bt, hidden[:dec.n_layers], self.pre, self.T, self.n_pre, self.len, self.out)    # (writes self.out itself)
+        # (writes its output buffer itself: self.out for window(), self.res for the pooled window)
+        dec.decode_eval_static(enc_bt, hidden[:dec.n_layers], self.pre, self.T, self.n_pre, self.len, self.out if out is None else out)
 
     def window(self, in_text=None, in_len=None, first=False):
         """One window for the whole batch.  in_text (B, Te) / in_len (B,) int64, CPU or GPU tensors, or None: self.text / self.len were
@@ -1358,9 +1381,10 @@ class StreamPool(_StreamCore):
     _rows = "slots"
 
     def __init__(self, args, pose_decoder, lang_model, slots=4, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, ring=None,
-                 window_decoder=None, _replay_draws=False):
+                 window_decoder=None, _replay_draws=False, _built_for=None):
         self.replay = bool(_replay_draws)
-        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, word_ring, ring, window_decoder, graph, replay_draws=self.replay)
+        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, word_ring, ring, window_decoder, graph,
+                         **(dict(replay_draws=self.replay) if _built_for is None else _built_for))
         B = self.B                                                  # (the state's one-entry `win` is not used: the rows' counters are dec.win)
         self.open_slots = [False] * B
         self.pushed, self.next_window, self.late_words = [0] * B, [0] * B, [0] * B
@@ -1373,7 +1397,7 @@ class StreamPool(_StreamCore):
     # -------------------------------------------------------------------------------------------------------------- sessions
     def _slot(self, slot, what):
         if not (isinstance(slot, (int, np.integer)) and 0 <= slot < self.B and self.open_slots[slot]):
-            raise ValueError(f"StreamPool.{what}: slot {slot!r} is not open")
+            raise ValueError(f"{type(self).__name__}.{what}: slot {slot!r} is not open")
         return slot
 
     def open(self, vid=None, seed_seq=None, _draws=None):
@@ -1382,13 +1406,13 @@ class StreamPool(_StreamCore):
         tail and seed on the device; no other row is touched."""
         free = [b for b in range(self.B) if not self.open_slots[b]]
         if not free:
-            raise ValueError(f"StreamPool.open: all {self.B} slot(s) are taken")
+            raise ValueError(f"{type(self).__name__}.open: all {self.B} slot(s) are taken")
         if self.replay and _draws is None:
-            raise ValueError("StreamPool.open: a pool with _replay_draws needs the session's _draws")
+            raise ValueError(f"{type(self).__name__}.open: a pool with _replay_draws needs the session's _draws")
         b, dec, n = free[0], self.dec, self.n_pre
         seed = None if seed_seq is None else torch.as_tensor(np.asarray(seed_seq)[:n], dtype=torch.float32).to(self.dev)
         if seed is not None and tuple(seed.shape) != (n, self.D):
-            raise ValueError(f"StreamPool.open: seed_seq gives {tuple(seed.shape)} seed poses, expected {(n, self.D)}")
+            raise ValueError(f"{type(self).__name__}.open: seed_seq gives {tuple(seed.shape)} seed poses, expected {(n, self.D)}")
         for t in (self.state["written"], self.state["n_words"], self.win, dec.tail, dec.pre):
             t[b:b + 1].zero_()
         if self.model == "multimodal_context":
@@ -1413,9 +1437,13 @@ class StreamPool(_StreamCore):
             rows[b], late[b] = self._row_records(wl, self.next_window[b])
         for b, r in enumerate(rows):
             if r and self._live_slots(b) + len(r) > self.state["W"]:
-                raise ValueError(f"StreamPool.push: slot {b}: {len(r)} word record(s) on top of {self._live_slots(b)} a window still needs exceed the "
+                raise ValueError(f"{type(self).__name__}.push: slot {b}: {len(r)} word record(s) on top of {self._live_slots(b)} a window still needs exceed the "
                                  f"word ring's capacity {self.state['W']} (word_ring=...)")
         return rows, late
+
+    def _stage(self):
+        """The active rows' inputs of their own windows, straight into the decoder's static buffers."""
+        ops.pool_stage(self.state, self.win, self.active, self.dec.text, self.dec.audio)
 
     def _round(self, mask):
         """One window for the rows of `mask`: the mask (and the rows' draws) go up by a small copy, then stage -> window_pooled."""
@@ -1424,7 +1452,7 @@ class StreamPool(_StreamCore):
                 if a:
                     self._draw_host[b] = torch.as_tensor(self._draws[b][self.next_window[b]], dtype=torch.float32).reshape(-1)
         self.active.copy_(torch.tensor(mask, dtype=torch.int32), non_blocking=True)
-        ops.pool_stage(self.state, self.win, self.active, self.dec.text, self.dec.audio)     # straight into the decoder's static buffers
+        self._stage()
         out = self.dec.window_pooled(draw=None if self._draw_host is None else self._draw_host.clone())
         for b, a in enumerate(mask):
             if a:
@@ -1441,19 +1469,19 @@ class StreamPool(_StreamCore):
         joints=True gives (frames, fp64 joint positions (k * stride, 10, 3))."""
         B, st, T, D = self.B, self.stride, self.T, self.D
         if not isinstance(chunks, dict) or not chunks:
-            raise ValueError("StreamPool.push: expected a non-empty {slot: chunk} dict")
+            raise ValueError(f"{type(self).__name__}.push: expected a non-empty {{slot: chunk}} dict")
         rows, words = {}, {}
         for slot, c in chunks.items():
             b = self._slot(slot, "push")
             c, w = c if isinstance(c, tuple) else (c, None)
             if isinstance(c, torch.Tensor):
                 if c.is_cuda:
-                    raise ValueError("StreamPool.push: chunks are host arrays (one upload per push)")
+                    raise ValueError(f"{type(self).__name__}.push: chunks are host arrays (one upload per push)")
                 c = c.numpy()
             if not isinstance(c, np.ndarray) or c.dtype != np.float32:
-                raise ValueError(f"StreamPool.push: the chunk must be float32, got {getattr(c, 'dtype', type(c).__name__)}")
+                raise ValueError(f"{type(self).__name__}.push: the chunk must be float32, got {getattr(c, 'dtype', type(c).__name__)}")
             if c.ndim != 1 or not 1 <= c.shape[0] <= self.max_chunk:
-                raise ValueError(f"StreamPool.push: slot {b}: a chunk of shape {c.shape}; expected 1-D with 1 <= len <= max_chunk = {self.max_chunk}")
+                raise ValueError(f"{type(self).__name__}.push: slot {b}: a chunk of shape {c.shape}; expected 1-D with 1 <= len <= max_chunk = {self.max_chunk}")
             rows[b], words[b] = c, w
         recs, late = self._records(words)                                   # (may refuse; nothing has changed yet)
         n = [len(rows[b]) if b in rows else 0 for b in range(B)]
@@ -1492,8 +1520,8 @@ class StreamPool(_StreamCore):
         is free again.  Returns the session's remaining frames (frames, D), or (frames, joint positions)."""
         b = self._slot(slot, "close")
         if self.pushed[b] == 0:
-            raise ValueError(f"StreamPool.close: nothing was pushed to slot {b}")
-        n_win, k = self._windows_left(f"StreamPool.close: slot {b}", self.pushed[b], self.next_window[b])
+            raise ValueError(f"{type(self).__name__}.close: nothing was pushed to slot {b}")
+        n_win, k = self._windows_left(f"{type(self).__name__}.close: slot {b}", self.pushed[b], self.next_window[b])
         if k:
             self._round([int(r == b) for r in range(self.B)])
             self._closing_window[b] = True                          # (a close that raises after this point and is called again must not skip its frames)
@@ -1502,3 +1530,91 @@ class StreamPool(_StreamCore):
         self.open_slots[b] = False                                  # only now: a close that raised can be called again
         self.pushed[b] = self.next_window[b] = 0                    # (a free row has no windows to run)
         return res
+
+
+class Seq2SeqStreamPool(StreamPool):
+    """StreamPool for the Seq2Seq baseline (args.model == 'seq2seq') on ONE Seq2SeqWindowDecoder: the same interface -- open(seed_seq=...),
+    push({slot: chunk or (chunk, words)}), close(slot, fade_out=..., joints=...), 1 to 4 slots, join and leave while the others run,
+    late_words per slot, window_decoder= reuse, no device read in push -- and the same host bookkeeping.  The audio chunks drive each row's
+    clock as in Seq2SeqGestureStream (window w of a row is complete at w * S + A of ITS samples; the model ignores the samples).  A round
+    (pool_rounds) is ops.pool_stage_text -- every active row's word list of its own window and the list's length, straight into the decoder's
+    static buffers; the idle rows keep the valid list they hold -- and the decoder's pooled window: the forward on all rows into the decoder's
+    result buffer, then ops.pool_handover_smooth, which gives only the active rows their output, cross-fade, SMOOTHED segment, tail, seed and
+    counter.
+
+    StreamPool refuses this model because scripts/synthesize.py smooths after all windows are stacked.  The smoothing is window-local all the
+    same (GestureStream's docstring has the argument; n_smooth == n_pre): window i's segment is its own local frames [0, 3 n_pre), window 0's
+    too; it lies inside the window's first `stride` frames when 3 n_pre <= stride; its values before the fit are final once the window has been
+    cross-faded; and the next window's seed and cross-fade take the raw frames [T - n_pre, T), which no segment touches.  So it runs in the
+    window's own hand-over launch, per row, whatever window each row is at.  (Speech2Gesture stays refused: power_to_db(ref=np.max) needs the
+    whole utterance.)  close() runs the padded last window if it has not run -- the hand-over has smoothed it -- and applies the fade-out with
+    ops.utterance_finish on the one-window buffer: smoothing, then fade-out, the offline finish's order.
+
+    Everything push() and close() returned for the session in slot b, concatenated, equals row b of generate_gestures_batch(args, ...,
+    on_device=True, fade_out=...) on a batch of `slots` utterances with that utterance in row b, bit for bit, whatever the other rows hold and
+    whenever they joined or left, for lengths where stream_matches_offline holds and with the encoder's row_local_eval set to the decoder's
+    row_local_encoder.  max_words: the most words one window of one slot may hold; a push that would give a window more is refused, names
+    the slot and the window, and leaves the pool as it was.  Refused at construction: 3 n_pre > stride, n_pre outside 1 .. 8, slots outside
+    1 .. 4, another model, a decoder with a speaker model, a window_decoder built for something else."""
+    _models = ("seq2seq",)
+
+    def _refusal(self, model):
+        return f"args.model is {model!r}, not 'seq2seq' (StreamPool pools multimodal_context and joint_embedding)"
+
+    def __init__(self, args, pose_decoder, lang_model, slots=4, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, ring=None,
+                 window_decoder=None, max_words=32, row_local_encoder=True):
+        n_pre, stride = args.n_pre_poses, args.n_poses - args.n_pre_poses
+        if not 1 <= n_pre <= 8:
+            raise ValueError(f"Seq2SeqStreamPool: 1 <= n_pre_poses <= 8 (the smoothing kernel's tables), got {n_pre}")
+        if 3 * n_pre > stride:
+            raise ValueError(f"Seq2SeqStreamPool: a window's smoothing segment of 3 n_pre = {3 * n_pre} frames must lie inside its first "
+                             f"n_poses - n_pre_poses = {stride} frames, else it would rewrite frames the next window has handed out")
+        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, graph, word_ring, ring, window_decoder,
+                         _built_for=dict(max_words=max_words, row_local_encoder=bool(row_local_encoder)))
+        self.max_words = self.dec.max_words
+        self._win_words = [{} for _ in range(self.B)]   # per slot: window -> words pushed for it so far (windows that have not run)
+        self._sos, self._eos = int(lang_model.SOS_token), int(lang_model.EOS_token)
+        for b in range(self.B):
+            self._idle_text(b)
+
+    def _idle_text(self, b):
+        """Row b holds [SOS, EOS, 0 ...], length 2: the forward runs on every row, open or not."""
+        text, ln = self.dec.text, self.dec.len
+        text[b:b + 1].zero_()
+        text[b:b + 1, 0:1].fill_(self._sos)
+        text[b:b + 1, 1:2].fill_(self._eos)
+        ln[b:b + 1].fill_(2)
+
+    def open(self, seed_seq=None):
+        """Starts a session on the lowest free row and returns its index; ValueError if every row is taken.  seed_seq: (>= n_pre, D) seed poses.
+        Resets the row's counters, tail, seed and word list on the device; no other row is touched."""
+        b = super().open(seed_seq=seed_seq)
+        self._win_words[b] = {}
+        self._idle_text(b)
+        return b
+
+    def _records(self, words):
+        """StreamPool._records behind one more refusal: no window of a slot may hold more than max_words words.  Nothing is changed here."""
+        rows, late = super()._records(words)
+        for b, r in enumerate(rows):
+            cnt = {}
+            for rec in r:                                                # one record per (word, window it falls in)
+                cnt[rec[0]] = cnt.get(rec[0], 0) + 1
+            for win, c in cnt.items():
+                have = self._win_words[b].get(win, 0)
+                if have + c > self.max_words:
+                    raise ValueError(f"Seq2SeqStreamPool.push: slot {b}: window {win} would hold {have + c} words, max_words is {self.max_words}")
+        return rows, late
+
+    def _commit_records(self, rows):
+        for b, r in enumerate(rows):                                     # (the push can no longer be refused)
+            for rec in r:
+                self._win_words[b][rec[0]] = self._win_words[b].get(rec[0], 0) + 1
+        return super()._commit_records(rows)
+
+    def _ran(self, b, next_window):
+        super()._ran(b, next_window)
+        self._win_words[b] = {w: c for w, c in self._win_words[b].items() if w >= next_window}
+
+    def _stage(self):
+        ops.pool_stage_text(self.state, self.win, self.active, self._sos, self._eos, self.dec.text, self.dec.len)

@@ -763,6 +763,22 @@ int tg_pool_stage(const float* ring, const int64_t* written, const int32_t* word
 int tg_pool_handover(const float* res, float* out, float* tail, float* seed, int32_t seed_layout, int32_t* win, const int32_t* active, int32_t B,
                      int32_t T, int32_t D, int32_t n_pre, void* stream);
 
+/* Stream pool of the Seq2Seq model (csrc/stream_pool_seq.hip; synthesize.Seq2SeqStreamPool): the same per-row state, one workgroup per row, no
+ * atomics, nothing waits on another workgroup; a row with active[b] == 0 leaves before any barrier and keeps every bit of what it owns.
+ * tg_pool_stage_text is tg_stream_stage_text per row: row b with active[b] != 0 gets [sos, every record of ITS window win[b] in push order, eos,
+ * 0 ...] in out_text[b] and count + 2 in out_len[b] (the count clamped to Te - 2); the other rows of out_text / out_len are not written.
+ * Envelope: tg_stream_stage_text's, active and win [B] int32 non-null. */
+int tg_pool_stage_text(const int32_t* word_ring, const int64_t* n_words, const int32_t* win, const int32_t* active, int32_t B, int32_t W, int32_t Te,
+                       int64_t sos, int64_t eos, int64_t* out_text, int64_t* out_len, void* stream);
+/* tg_pool_handover for the seed layout pre [B][n_pre][D], with the Seq2Seq model's smoothing of the window it hands over: per active row
+ * out[b] = res[b], cross-faded with tail[b] where win[b] > 0; then frames [0, 3 n_pre) of out[b] are replaced by their cubic least-squares
+ * fit -- proj: the (3 n_pre)^2 fp64 projection tg_utterance_finish takes, applied in the same order, so the bits are those of
+ * tg_utterance_finish(smooth) on that window --; tail[b] = out[b][T - n_pre ..], seed[b] = tail[b], win[b] += 1.  The segment must lie inside
+ * the window's first T - n_pre frames: the tail is then raw decoder output, as the next window's cross-fade and seed need it.
+ * Envelope: 1 <= B <= 4, 1 <= n_pre <= 8, 1 <= D <= 64, 3 n_pre <= T - n_pre, T <= 1024; refused otherwise, nothing is launched. */
+int tg_pool_handover_smooth(const float* res, float* out, float* tail, float* seed, int32_t* win, const int32_t* active, const double* proj,
+                            int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream);
+
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over
  * T-2 frames, sums[2] = sum |out - target|.  (joint_mae = sums[0]/(B*(T-n_pre)*30), accel = sums[1]/(B*(T-2)*30), l1 = sums[2]/(B*T*27).) */
