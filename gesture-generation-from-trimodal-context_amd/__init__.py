@@ -16,7 +16,7 @@ from .rnn import GRU, EncoderRNN  # noqa: F401
 from .seq2seq import Attn, BahdanauAttnDecoderRNN, Generator, Seq2SeqNet, train_iter_seq2seq  # noqa: F401
 from .joint_embed import ContextEncoder, JointEmbedTrainer, PoseDecoderGRU, train_iter_embed  # noqa: F401
 from .synthesize import generate_gestures, generate_gestures_batch  # noqa: F401
-from . import checkpoint, config, data, ddp, eval_metrics, fgd, h36m, joint_embed, layers, melspec, ops, preprocess, rnn, seq2seq, synthesize  # noqa: F401,E402  (hip.fgd, hip.config, ... as INTEGRATION.md uses them)
+from . import checkpoint, config, data, ddp, eval_metrics, fgd, h36m, joint_embed, layers, melspec, ops, preprocess, resample, rnn, seq2seq, synthesize  # noqa: F401,E402  (hip.fgd, hip.config, ... as INTEGRATION.md uses them)
 
 __all__ = ["PoseGenerator", "ConvDiscriminator", "EmbeddingNet", "FusedAdam", "ParamAdam", "GanTrainer", "GraphedGanStep", "StepLosses",
            "Vocab", "extract_melspectrogram", "DataPreprocessor", "calculate_data_mean", "resample_pose_seq", "Human36M", "GRU", "EncoderRNN",

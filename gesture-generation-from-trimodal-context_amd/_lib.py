@@ -149,6 +149,8 @@ SIGNATURES = {
     "tg_pool_handover": [P, P, P, P, I32, P, P, I32, I32, I32, I32, P],
     "tg_pool_stage_text": [P, P, P, P, I32, I32, I32, I64, I64, P, P, P],
     "tg_pool_handover_smooth": [P, P, P, P, P, P, P, I32, I32, I32, I32, P],
+    "tg_resample": [P, P, P, I32, I64, P, I32, I32, I32, P, P],
+    "tg_resample_stream": [P, I64, I32, I32, I32, I32, I32, P, I32, I32, I32, P, P, P, P, I64, I32, P],
     "tg_pose_metrics": [P, P, P, I32, I32, I32, P, P],
     "tg_ae_loss": [P, P, I32, I32, I32, P, P, P],
     "tg_counter_inc": [P, P],

@@ -2172,6 +2172,76 @@ def pool_handover_smooth(res, out, tail, seed, win, active, proj):
     call("tg_pool_handover_smooth", _p(res), _p(out), _p(tail), _p(seed), _p(win), _p(active), _p(proj), B, T, D, n_pre, _stream())
 
 
+# ------------------------------------------------------------------------------------------------- resampling to 16 kHz (csrc/resample.hip)
+def _taps_check(taps, L, M, K):
+    _flat(taps, "taps")
+    if taps.numel() != L * K or L < 1 or M < 1 or K < 2 or K % 2:
+        raise ValueError(f"taps: expected the (L, K) = {(L, K)} table with K even, got {tuple(taps.shape)}")
+
+
+def resample(x, lengths, taps, L, M, K):
+    """B signals packed in x (device fp32, numel == sum(lengths), every length >= 1) -> (y, out_lengths): their resampled versions packed in
+    one new device buffer, signal b at y[sum(out_lengths[:b]):][:out_lengths[b]], out_lengths[b] = ceil(lengths[b] L / M) (host integers).  One
+    launch; taps: the (L, K) fp32 table of resample.device_taps.  Outside the kernel's envelope the library refuses (RuntimeError naming the
+    envelope); nothing is launched."""
+    _flat(x, "x"); _taps_check(taps, L, M, K)
+    lengths = [int(v) for v in lengths]
+    if not lengths or min(lengths) < 1 or x.numel() != sum(lengths):
+        raise ValueError(f"resample: {len(lengths)} signal(s) of lengths {lengths[:8]} in a buffer of {x.numel()} samples")
+    out_lengths = [(n * L + M - 1) // M for n in lengths]
+    off = torch.zeros(2, len(lengths) + 1, dtype=torch.int64)
+    off[0, 1:] = torch.cumsum(torch.tensor(lengths, dtype=torch.int64), 0)
+    off[1, 1:] = torch.cumsum(torch.tensor(out_lengths, dtype=torch.int64), 0)
+    off = off.to(x.device, non_blocking=True)
+    y = torch.empty(sum(out_lengths), device=x.device, dtype=torch.float32)
+    call("tg_resample", _p(x), _p(off[0]), _p(off[1]), len(lengths), max(out_lengths), _p(taps), L, M, K, _p(y), _stream())
+    return y, out_lengths
+
+
+def resample_state(B, taps, L, M, K, max_chunk, device):
+    """The device-resident state of a streaming resampler of B rows: per row the carry of the last K - 1 input samples (zeros: the signal has
+    not begun) and the int64 counters `consumed` (input samples) and `produced` (output samples); `stage` (B, max_chunk): where a host chunk
+    is uploaded.  out_stride: the most output samples one call can write per row -- ceil(max_chunk L / M) + 1, or what a flush adds."""
+    _taps_check(taps, L, M, K)
+    out_stride = max((int(max_chunk) * L + M - 1) // M, ((K // 2) * L + M - 1) // M) + 1
+    return dict(B=int(B), L=int(L), M=int(M), K=int(K), taps=taps, max_chunk=int(max_chunk), out_stride=out_stride,
+                carry=torch.zeros(B, K - 1, device=device), consumed=torch.zeros(B, dtype=torch.int64, device=device),
+                produced=torch.zeros(B, dtype=torch.int64, device=device), stage=torch.zeros(B, int(max_chunk), device=device))
+
+
+def resample_stream(rs, chunk, n, out, flush=()):
+    """Row b of the resampler state rs takes chunk[b, :n[b]] (chunk (B, >= max n) fp32, device, unit inner stride; None if every n[b] is 0; n: B
+    host integers in [0, max_chunk]) and writes the output samples that became final to out[b, 0:...] (out (B, >= rs['out_stride']) fp32, device,
+    contiguous); flush: the rows whose input has ended -- they also produce what is left, zeros past the end.  How many samples a row got
+    is the host's to compute (synthesize.resampled_ready / resampled_length on its own counts); a row with n[b] == 0 that is not flushed keeps
+    every bit.  Outside the envelope the library refuses (RuntimeError naming the envelope); nothing is launched."""
+    B = rs["B"]
+    n = [int(v) for v in n]
+    n_max = max(n, default=0)
+    if len(n) != B or min(n) < 0 or n_max > rs["max_chunk"]:
+        raise ValueError(f"n: chunk lengths {n} for {B} row(s) of at most {rs['max_chunk']} samples")
+    mask = 0
+    for b in flush:
+        if not 0 <= int(b) < B:
+            raise ValueError(f"flush: row {b} of {B}")
+        mask |= 1 << int(b)
+    cs = 0
+    if n_max > 0:
+        _f32(chunk, "chunk")
+        if chunk.dim() != 2 or chunk.shape[0] != B or chunk.shape[1] < n_max or (chunk.shape[1] > 1 and chunk.stride(1) != 1):
+            raise ValueError(f"chunk: expected ({B}, >= {n_max}) with unit inner stride, got {tuple(chunk.shape)} strides {chunk.stride()}")
+        cs = chunk.stride(0) if B > 1 else max(chunk.shape[1], 1)
+        if cs < n_max or (B - 1) * cs + n_max > _room(chunk):
+            raise ValueError("chunk: rows overlap or exceed the tensor")
+    _flat(out, "out")
+    if out.dim() != 2 or out.shape[0] != B or out.shape[1] < rs["out_stride"]:
+        raise ValueError(f"out: expected a contiguous ({B}, >= {rs['out_stride']}) tensor, got {tuple(out.shape)}")
+    _flat(rs["carry"], "carry"); _dev_int(rs["consumed"], torch.int64, B, "consumed"); _dev_int(rs["produced"], torch.int64, B, "produced")
+    assert rs["carry"].numel() == B * (rs["K"] - 1)
+    call("tg_resample_stream", _p(chunk if n_max > 0 else None), cs, *(n + [0] * 4)[:4], mask, _p(rs["taps"]), rs["L"], rs["M"], rs["K"], _p(rs["carry"]),
+         _p(rs["consumed"]), _p(rs["produced"]), _p(out), out.shape[1], B, _stream())      # (B > 4: refused by the library)
+
+
 def pose_metrics(out, target, mean_dir_vec, n_pre, sums):
     _same(out, target); _flat(mean_dir_vec, "mean"); B, T, D = out.shape
     assert D == 27 and mean_dir_vec.numel() == 27 and sums.dtype == torch.float64 and sums.numel() >= 3 and sums.is_cuda

@@ -52,6 +52,10 @@ Structure: the three window decoders are subclasses of _WindowDecoderBase (buffe
 window, check_kept; _capture is the one place a graph is captured); the streams and the pool are subclasses of _StreamCore (constructor checks,
 a row's word records, the closing window); the five offline loops stay separate and share _seed_rows, _host_window_batch and _rows_result.
 
+Audio that is not 16 kHz (input_sr= on every entry point above; resample_audio on its own): resampled on the device by csrc/resample.hip, the
+counterpart of the script's librosa.load(..., sr=16000) -- offline by one launch per batch, in the streams chunk by chunk with a carry and two
+counters per row in device memory.  resample.py has the definition; None or 16000 keeps every launch and every bit.
+
 TTS / Gentle alignment / LMDB front-ends of the reference script are network services and out of scope; `words` is the
 reference's word list [[word, start_s, end_s], ...].
 """
@@ -61,7 +65,7 @@ import random
 import numpy as np
 import torch
 
-from . import melspec, ops, layers as L
+from . import melspec, ops, resample, layers as L
 from .speech2gesture import spectrogram_length
 
 
@@ -656,7 +660,11 @@ class UtteranceBatch:
     seq2seq's smoothing, the fade-out and the joint integration on the stacked windows (ops.utterance_finish).  Every slice is checked against
     its utterance here, on the host, before anything is uploaded."""
 
-    def __init__(self, args, lang_model, audios, words_list, device, audio_sr=16000):
+    def __init__(self, args, lang_model, audios, words_list, device, audio_sr=16000, input_sr=None):
+        """audios: numpy arrays, or device tensors (packed on the device, no host visit).  input_sr: the audios' rate if it is not 16 kHz --
+        they are uploaded once at that rate and resampled by one launch (resample_audio); the plans are built from the resampled lengths."""
+        if _resampling("UtteranceBatch", input_sr, audio_sr) is not None:
+            audios = resample_audio(list(audios), input_sr, device=device, return_device=True)
         self.args, self.dev, self.audio_sr = args, device, audio_sr
         self.model = getattr(args, "model", "multimodal_context")
         self.T, self.n_pre = args.n_poses, args.n_pre_poses
@@ -691,8 +699,11 @@ class UtteranceBatch:
                          text=torch.from_numpy(np.ascontiguousarray(text)).to(device), audio=None, audio_off=None, audio_total=0)
         if self.model in ("multimodal_context", "joint_embedding"):                    # the other two models never see the samples
             off = np.concatenate([[0], np.cumsum([len(a) for a in audios])]).astype(np.int64)
-            packed = np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1) for a in audios])
-            self.plan.update(audio=torch.from_numpy(packed).to(device), audio_off=torch.from_numpy(off).to(device), audio_total=int(off[-1]))
+            if all(isinstance(a, torch.Tensor) and a.is_cuda for a in audios):         # (resampled on the device: packed there)
+                packed = torch.cat([a.reshape(-1).to(device=device, dtype=torch.float32) for a in audios])
+            else:
+                packed = torch.from_numpy(np.concatenate([np.asarray(a, dtype=np.float32).reshape(-1) for a in audios])).to(device)
+            self.plan.update(audio=packed, audio_off=torch.from_numpy(off).to(device), audio_total=int(off[-1]))
         # row b's window in lock-step step i: min(i, n_win[b] - 1), for every step, uploaded once
         idx = np.minimum(np.arange(self.max_win)[:, None], np.array(self.n_win)[None, :] - 1).astype(np.int32)
         self.win_idx = torch.from_numpy(np.ascontiguousarray(idx)).to(device)
@@ -793,7 +804,8 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
                              f"for its last window, the generator needs {need}; the minimum is {(melspec.N_MELS + need - 2) * melspec.HOP} samples "
                              f"({(melspec.N_MELS + need - 2) * melspec.HOP / audio_sr:.3f} s)")
     # one spectrogram per utterance, on the device, once
-    specs = [melspec.extract_melspectrogram(np.asarray(a, dtype=np.float32), melspec.SR, pad_mode=spec_pad_mode, device=dev) for a in audios]
+    specs = [melspec.extract_melspectrogram(a if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float32), melspec.SR, pad_mode=spec_pad_mode,
+                                            device=dev) for a in audios]               # (a device tensor: audio resampled on the device)
     D = pose_decoder.final_out.out_channels
     pre = torch.zeros(B, n_pre, D, device=dev)
     if seed_seqs is not None:                                                   # synthesize.py:46-50
@@ -837,7 +849,7 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
 
 def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, vids=None, seed_seqs=None, audio_sr=16000,
                             graph=True, _draws=None, spec_pad_mode="reflect", eps_list=None, window_decoder=False, on_device=False,
-                            return_device=False, joints=False, fade_out=False):
+                            return_device=False, joints=False, fade_out=False, input_sr=None):
     """Lock-step synthesis of several utterances.  Returns a list of (n_i * 30 + 4, D) numpy arrays (mean-subtracted direction
     vectors, like the reference's return value without fade-out).  vids: one speaker id per utterance, or None / a falsy entry to
     draw it like the reference (synthesize.py:67-74; ignored unless args.z_type == 'speaker').  _draws (parity tests): per window,
@@ -856,8 +868,14 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
     forward's results are; the fitted frames agree with the numpy fits to one fp32 rounding.  With it: return_device=True returns device
     tensors (row views of one buffer; nothing is read back) and joints=True returns (rows, joint_rows), joint_rows[b] the fp64
     (frames, 10, 3) joint positions of rows[b] + args.mean_dir_vec.  fade_out: every utterance faded out to the mean pose
-    (fade_out_to_mean), on either path."""
+    (fade_out_to_mean), on either path.
+    input_sr (every model; None or 16000: nothing changes): the audios' sample rate.  They are uploaded once at that rate and resampled to 16 kHz
+    by one launch (resample_audio); everything downstream is the 16 kHz path on the resampled audio -- window plans from the resampled
+    lengths, speech2gesture's spectrogram from the resampled samples -- and with on_device=True that audio never visits the host.  audio_sr
+    keeps its meaning (it rescales sample counts) and must be 16000 next to input_sr."""
     model = getattr(args, "model", "multimodal_context")
+    if _resampling("generate_gestures_batch", input_sr, audio_sr) is not None:
+        audios = resample_audio(list(audios), input_sr, device=next(pose_decoder.parameters()).device, return_device=bool(on_device))
     if (return_device or joints) and not on_device:
         raise ValueError("return_device and joints belong to the on_device path: pass on_device=True")
     dopts = (bool(fade_out), bool(joints), bool(return_device)) if on_device else None
@@ -929,10 +947,13 @@ def fade_out_to_mean(out_dir_vec, end_padding_samples, args, audio_sr=16000):
 
 
 def generate_gestures(args, pose_decoder, lang_model, audio, words, audio_sr=16000, vid=None, seed_seq=None, fade_out=False,
-                      _draws=None, spec_pad_mode="reflect", eps_list=None, window_decoder=False, on_device=False, return_device=False, joints=False):
+                      _draws=None, spec_pad_mode="reflect", eps_list=None, window_decoder=False, on_device=False, return_device=False, joints=False,
+                      input_sr=None):
     """Single-utterance API of the reference (synthesize.py:36-209; multimodal_context, speech2gesture, seq2seq and joint_embedding models).
     window_decoder, on_device, return_device, joints: see generate_gestures_batch (with on_device the fade-out runs on the device too;
-    joints=True returns (out, joint positions))."""
+    joints=True returns (out, joint positions)).  input_sr: the audio's sample rate if it is not 16 kHz (resampled on the device first)."""
+    if _resampling("generate_gestures", input_sr, audio_sr) is not None:
+        audio = resample_audio(audio, input_sr, device=next(pose_decoder.parameters()).device, return_device=bool(on_device))
     if on_device or return_device or joints:
         res = generate_gestures_batch(args, pose_decoder, lang_model, [audio], [words], [vid], None if seed_seq is None else [seed_seq], audio_sr,
                                       graph=True, _draws=_draws, spec_pad_mode=spec_pad_mode, eps_list=eps_list, window_decoder=window_decoder,
@@ -975,6 +996,67 @@ def complete_windows(pushed, S, A):
     return 0 if pushed < A else (pushed - A) // S + 1
 
 
+def resampled_length(n_in, L, M):
+    """Output samples of n_in input samples resampled by L / M: ceil(n_in L / M) -- the outputs whose position n M / L lies before the end."""
+    return 0 if n_in <= 0 else (int(n_in) * L + M - 1) // M
+
+
+def resampled_ready(p, L, M, K):
+    """Output samples that are final after p input samples: those whose whole tap span -- input samples i_n - K/2 + 1 .. i_n + K/2 with
+    i_n = (n M) // L -- lies at or before sample p - 1, i.e. n M < (p - K/2) L (integers; the device computes the same expression)."""
+    q = int(p) - K // 2
+    return 0 if q <= 0 else (q * L - 1) // M + 1
+
+
+def _resampling(who, input_sr, audio_sr):
+    """The rate to resample from, or None where nothing is to be done (input_sr None or 16000: every call keeps its launches and its bits).
+    ValueError -- before anything is launched -- for a rate outside the resampler's envelope and for audio_sr != 16000 next to input_sr
+    (audio_sr keeps its meaning: it rescales sample counts and never resamples)."""
+    if input_sr is None:
+        return None
+    if audio_sr != resample.TARGET_SR:
+        raise ValueError(f"{who}: input_sr = {input_sr} resamples to {resample.TARGET_SR} Hz, so audio_sr must be {resample.TARGET_SR}, got {audio_sr}")
+    resample.geometry(input_sr)
+    return None if int(input_sr) == resample.TARGET_SR else int(input_sr)
+
+
+def resample_audio(audio, input_sr, device=None, return_device=False):
+    """audio at input_sr -> 16 kHz on the device (resample.py has the definition, csrc/resample.hip the arithmetic).  audio: one 1-D signal
+    or a list of them (numpy, host or device tensors; ragged), uploaded once, packed, and resampled by ONE launch.  Returns float32 numpy
+    arrays -- or, return_device=True, device tensors (views of one buffer; nothing is read back) -- of ceil(n L / M) samples each, a list
+    for a list.  input_sr == 16000 is the identity and launches nothing.  ValueError for a rate outside the envelope (an integer in
+    [8000, 192000] with at most 640 phases and 512 taps per phase) or an empty signal."""
+    single = not isinstance(audio, (list, tuple))
+    audios = [audio] if single else list(audio)
+    rate = _resampling("resample_audio", input_sr, resample.TARGET_SR)
+    rows = [a.detach().reshape(-1) if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float32).reshape(-1) for a in audios]
+    if not rows or min(len(r) for r in rows) < 1:
+        raise ValueError("resample_audio: an empty signal")
+    if device is None and (rate is not None or return_device):
+        dev_in = [r.device for r in rows if isinstance(r, torch.Tensor) and r.is_cuda]
+        device = dev_in[0] if dev_in else torch.device("cuda", torch.cuda.current_device())
+    on_dev = all(isinstance(r, torch.Tensor) and r.is_cuda for r in rows)
+    host = lambda r: r.cpu().numpy().astype(np.float32) if isinstance(r, torch.Tensor) else r
+    if rate is None:                                                             # the identity
+        if return_device:
+            outs = [(r if isinstance(r, torch.Tensor) else torch.from_numpy(r)).to(device=device, dtype=torch.float32) for r in rows]
+        else:
+            outs = [host(r) for r in rows]
+        return outs[0] if single else outs
+    taps, L_, M_, K_ = resample.device_taps(rate, device)
+    if on_dev:
+        packed = torch.cat([r.to(device=device, dtype=torch.float32) for r in rows])
+    else:
+        packed = torch.from_numpy(np.concatenate([host(r) for r in rows])).to(device)          # one upload
+    y, out_len = ops.resample(packed, [len(r) for r in rows], taps, L_, M_, K_)
+    if return_device:
+        outs = list(torch.split(y, out_len))
+    else:
+        res, off = y.cpu().numpy(), np.concatenate([[0], np.cumsum(out_len)])
+        outs = [res[off[b]:off[b + 1]] for b in range(len(rows))]
+    return outs[0] if single else outs
+
+
 def word_records(args, lang_model, words):
     """The integer records (window, frame, word id) of a word list, in word order: one record per window a word falls in (overlapping windows
     share words), by the expressions of words_in_time_range and _window_geometry: the word is in window i if w[1] < end_time and w[2] >
@@ -1013,9 +1095,11 @@ class _StreamCore:
                 "speech2gesture": "the speech2gesture model cannot stream: its log-mel spectrogram is padded over the whole utterance"
                 }.get(model, f"unknown model {model!r}")
 
-    def __init__(self, args, pose_decoder, lang_model, rows, audio_sr, max_chunk, word_ring, ring, window_decoder, graph, **built_for):
+    def __init__(self, args, pose_decoder, lang_model, rows, audio_sr, max_chunk, word_ring, ring, window_decoder, graph, input_sr=None, **built_for):
         """built_for: what the window decoder is built with besides the model, the rows and the window (replay_draws; seq2seq: max_words,
-        row_local_encoder) -- given to a new decoder, checked on a kept one.  Every refusal comes before anything touches the model."""
+        row_local_encoder) -- given to a new decoder, checked on a kept one.  Every refusal comes before anything touches the model.
+        input_sr: the rate of the pushed audio if it is not 16 kHz -- max_chunk then counts INPUT samples, every push goes through the
+        streaming resampler (ops.resample_stream, state self.rs) into chunk_buf, and the ring takes the 16 kHz samples that became final."""
         who, model = type(self).__name__, getattr(args, "model", "multimodal_context")
         if model not in self._models:
             raise ValueError(f"{who}: {self._refusal(model)}")
@@ -1023,13 +1107,19 @@ class _StreamCore:
             raise ValueError(f"{who}: 1 to 4 {self._rows}, got {rows}")
         if max_chunk < 1:
             raise ValueError(f"{who}: max_chunk = {max_chunk}")
+        self.input_sr = _resampling(who, input_sr, audio_sr)
         self.args, self.model, self.lang, self.B, self.audio_sr, self.max_chunk = args, model, lang_model, int(rows), audio_sr, int(max_chunk)
         T, n_pre = self.T, self.n_pre = args.n_poses, args.n_pre_poses
         self.stride = T - n_pre
         self.S, self.A = stream_geometry(args, audio_sr)
-        R = self.A + self.max_chunk if ring is None else int(ring)
-        if R < self.A + self.max_chunk:
-            raise ValueError(f"{who}: a ring of {R} samples; window + max_chunk = {self.A + self.max_chunk} are needed")
+        # 16 kHz samples one push can add to the ring: the chunk itself, or what the resampler can make final in one call (a flush included)
+        chunk16 = self.max_chunk
+        if self.input_sr is not None:
+            L_, M_, K_, _ = resample.geometry(self.input_sr)
+            chunk16 = max(resampled_length(self.max_chunk, L_, M_), resampled_length(K_ // 2, L_, M_)) + 1
+        R = self.A + chunk16 if ring is None else int(ring)
+        if R < self.A + chunk16:
+            raise ValueError(f"{who}: a ring of {R} samples; window + max_chunk = {self.A + chunk16} (at 16 kHz) are needed")
         dev = self.dev = next(pose_decoder.parameters()).device
         kind = _STREAM_DECODERS[model]
         if window_decoder is not None:
@@ -1040,7 +1130,10 @@ class _StreamCore:
             raise ValueError(f"{who}: the window decoder takes {self.dec.audio_len} samples, the stream's window is {self.A} (audio_sr = {audio_sr})")
         self.D = self.dec.D
         self.state = ops.stream_state(self.B, R, self.S, self.A, word_ring, T, dev)
-        self.chunk_buf = torch.zeros(self.B, self.max_chunk, device=dev)
+        self.chunk_buf = torch.zeros(self.B, chunk16, device=dev)
+        # the streaming resampler: device state (carry, counters) and the host's mirror of both counters per row, plain integers
+        self.rs = None if self.input_sr is None else ops.resample_state(self.B, *resample.device_taps(self.input_sr, dev), self.max_chunk, dev)
+        self._rs_in, self._rs_out = [0] * self.B, [0] * self.B
         self._live, self._n_rec = [[] for _ in range(self.B)], [0] * self.B
         self._ones = torch.ones(self.B, dtype=torch.int32, device=dev)
         self._mean = self._tables = None                 # the fp64 mean and the projection tables on the device: made once, on first use
@@ -1076,6 +1169,20 @@ class _StreamCore:
     def _ran(self, b, next_window):
         """Row b has run its windows below next_window: their records are no longer needed."""
         self._live[b] = [r for r in self._live[b] if r[1] >= next_window]
+
+    def _resample(self, chunk, n, flush=()):
+        """One launch of the streaming resampler: row b takes chunk[b, :n[b]] (input_sr samples, device) and -- flush: the rows whose input
+        has ended -- writes its new 16 kHz samples to chunk_buf[b].  Returns their counts per row, from the host's own counters by the
+        integer expressions the kernel evaluates on the device's (resampled_ready / resampled_length); nothing is read back."""
+        L_, M_, K_ = self.rs["L"], self.rs["M"], self.rs["K"]
+        ops.resample_stream(self.rs, chunk, n, self.chunk_buf, flush)
+        got = [0] * self.B
+        for b in range(self.B):
+            if n[b] or b in flush:
+                self._rs_in[b] += n[b]
+                made = resampled_length(self._rs_in[b], L_, M_) if b in flush else resampled_ready(self._rs_in[b], L_, M_, K_)
+                got[b], self._rs_out[b] = made - self._rs_out[b], made
+        return got
 
     def _mean_dev(self):
         if self._mean is None:
@@ -1161,14 +1268,22 @@ class GestureStream(_StreamCore):
     _draws / eps_list (parity tests): per window the (B, 16) / (B, 32) draws to replay; window_decoder: a kept decoder of the model's kind
     (its window graph is captured once and replayed by every stream that uses it; the constructor re-seeds it and the stream writes its
     static buffers, so a kept decoder serves ONE stream at a time -- start the next stream on it after the previous one was closed).
-    push() never reads from the device.  A refused push (ValueError) leaves the stream as it was; a close that raised can be called again."""
+    push() never reads from the device.  A refused push (ValueError) leaves the stream as it was; a close that raised can be called again.
+
+    input_sr (None or 16000: nothing changes): the rate of the pushed audio.  max_chunk then counts input samples; a push uploads the chunk to a
+    staging buffer, ops.resample_stream (csrc/resample.hip: a carry of K - 1 samples and two counters per row on the device, mirrored here in
+    integers) writes the 16 kHz samples that became final into chunk_buf, and the unchanged ops.stream_push appends the host's count of them --
+    a push that yields none still advances the carry.  close() flushes the resampler first (zeros past the end); a window those last samples
+    complete runs like a push's, in front of the closing frames.  The stream then equals generate_gestures_batch(on_device=True) on
+    resample_audio's output bit for bit where stream_matches_offline holds for the RESAMPLED length; words are in seconds and unaffected."""
 
     def __init__(self, args, pose_decoder, lang_model, batch=1, vids=None, seed_seqs=None, audio_sr=16000, max_chunk=16000, _draws=None, eps_list=None,
-                 window_decoder=None, graph=True, word_ring=256, ring=None, _built_for=None):
+                 window_decoder=None, graph=True, word_ring=256, ring=None, _built_for=None, input_sr=None):
         model = getattr(args, "model", "multimodal_context")
         self.draws = _draws if model == "multimodal_context" else eps_list
-        super().__init__(args, pose_decoder, lang_model, batch, audio_sr, max_chunk, word_ring, ring, window_decoder, graph,
+        super().__init__(args, pose_decoder, lang_model, batch, audio_sr, max_chunk, word_ring, ring, window_decoder, graph, input_sr=input_sr,
                          **(dict(replay_draws=self.draws is not None) if _built_for is None else _built_for))
+        self._head = None                                # close(): the frames of the windows the resampler's flush completed
         self.dec.seed(_seed_rows(seed_seqs, self.n_pre))
         self.vid = None
         if model == "multimodal_context" and args.z_type == "speaker":                  # synthesize.py:67-74
@@ -1241,17 +1356,32 @@ class GestureStream(_StreamCore):
             words = [words]                                          # one row: its word list as it is
         recs, m_max, live = self._records(words)
         if not (chunk.is_cuda and chunk.stride(1) == 1 and (self.B == 1 or chunk.stride(0) >= n)):
-            dst = self.chunk_buf[:, :n]
+            dst = (self.chunk_buf if self.rs is None else self.rs["stage"])[:, :n]
             dst.copy_(chunk, non_blocking=True)                      # pinned host memory: asynchronous
             chunk = dst
-        ops.stream_push(self.state, chunk, recs, m_max, live)
+        if self.rs is not None:                                      # input_sr samples -> the 16 kHz samples that became final, in chunk_buf
+            n = self._resample(chunk, [n] * self.B)[0]               # (rows share a clock: one count)
+            chunk = self.chunk_buf[:, :n]
+        self._feed(chunk, n, recs, m_max, live)
+        return self._result(*self._emit(joints), numpy)
+
+    def _feed(self, chunk, n, recs, m_max, live):
+        """n 16 kHz samples per row and the push's records go to the rings.  n == 0 (a resampled push that made no sample final): the records
+        alone, by the per-row push with every length 0 -- the same row body -- or nothing at all."""
+        if n > 0:
+            ops.stream_push(self.state, chunk, recs, m_max, live)
+        elif m_max > 0:
+            ops.pool_push(self.state, self.chunk_buf, [0] * self.B, recs, m_max, live)
         self.pushed += n
+
+    def _emit(self, joints):
+        """Runs the windows that have become complete; (frames (B, k * stride, D), joint positions or None) of what became final, device views."""
         k = complete_windows(self.pushed, self.S, self.A) - self.next_window
         if k <= 0:
             empty = self.chunk_buf.new_zeros(self.B, 0, self.D)
-            return self._result(empty, empty.new_zeros(self.B, 0, 10, 3, dtype=torch.float64) if joints else None, numpy)
+            return empty, empty.new_zeros(self.B, 0, 10, 3, dtype=torch.float64) if joints else None
         buf = self._run(k, smooth=True)
-        return self._result(buf[:, :k * self.stride], self._joints(buf, k) if joints else None, numpy)
+        return buf[:, :k * self.stride], self._joints(buf, k) if joints else None
 
     def close(self, fade_out=False, joints=False, numpy=False):
         """Ends the stream: runs the windows the reference's window count (num_windows of the final length) still asks for, zero-padded, and returns
@@ -1260,14 +1390,25 @@ class GestureStream(_StreamCore):
         who = type(self).__name__
         if self.closed:
             raise ValueError(f"{who}.close: the stream is closed")
-        if self.pushed == 0:
+        if self.pushed == 0 and self._rs_in[0] == 0:
             raise ValueError(f"{who}.close: nothing was pushed")
+        if self.rs is not None and self._head is None:
+            # the input has ended: the resampler's remaining outputs (zeros past the end) go to the ring like a push, and the windows they
+            # complete run like a push's; their frames go in front of the closing frames (kept: a close that raises later does not flush twice)
+            n = self._resample(None, [0] * self.B, flush=range(self.B))[0]
+            self._feed(self.chunk_buf[:, :n], n, None, 0, 0)
+            self._head = self._emit(joints)
         n_win, k = self._windows_left(f"{who}.close", self.pushed, self.next_window)
         if k:
             self._run(1)
             self._closing_window = True                             # (a close that raises after this point and is called again must not skip its frames)
-        res = self._result(*self._closing(self.dec.out, self.pushed, n_win, self._closing_window, fade_out, joints,
-                                          self._smooth_closing and self._closing_window), numpy)
+        frames, jt = self._closing(self.dec.out, self.pushed, n_win, self._closing_window, fade_out, joints,
+                                   self._smooth_closing and self._closing_window)
+        if self._head is not None and self._head[0].shape[1]:
+            if jt is not None and self._head[1] is None:
+                raise ValueError(f"{who}.close: repeated with joints=True after a close without them had run the last complete windows")
+            frames, jt = torch.cat([self._head[0], frames], 1), None if jt is None else torch.cat([self._head[1], jt], 1)
+        res = self._result(frames, jt, numpy)
         self.closed = True                                          # only now: a close that raised can be called again
         return res
 
@@ -1299,7 +1440,7 @@ class Seq2SeqGestureStream(GestureStream):
         return f"args.model is {model!r}, not 'seq2seq' (GestureStream streams multimodal_context and joint_embedding)"
 
     def __init__(self, args, pose_decoder, lang_model, batch=1, seed_seqs=None, audio_sr=16000, max_chunk=16000, window_decoder=None, graph=True,
-                 word_ring=256, ring=None, max_words=32, row_local_encoder=True):
+                 word_ring=256, ring=None, max_words=32, row_local_encoder=True, input_sr=None):
         n_pre, stride = args.n_pre_poses, args.n_poses - args.n_pre_poses
         if not 1 <= n_pre <= 8:
             raise ValueError(f"Seq2SeqGestureStream: 1 <= n_pre_poses <= 8 (the smoothing kernel's tables), got {n_pre}")
@@ -1307,7 +1448,7 @@ class Seq2SeqGestureStream(GestureStream):
             raise ValueError(f"Seq2SeqGestureStream: a window's smoothing segment of 3 n_pre = {3 * n_pre} frames must lie inside its first "
                              f"n_poses - n_pre_poses = {stride} frames, else it would rewrite frames the next window has handed out")
         super().__init__(args, pose_decoder, lang_model, batch, None, seed_seqs, audio_sr, max_chunk, None, None, window_decoder, graph, word_ring,
-                         ring, _built_for=dict(max_words=max_words, row_local_encoder=bool(row_local_encoder)))
+                         ring, _built_for=dict(max_words=max_words, row_local_encoder=bool(row_local_encoder)), input_sr=input_sr)
         self.max_words = self.dec.max_words
         self._win_words = [{} for _ in range(batch)]     # per row: window -> words pushed for it so far (windows that have not run)
         self._k_dev = {1: self._ones}                    # (B,) int32 window counts of a push's buffer, by k
@@ -1377,15 +1518,18 @@ class StreamPool(_StreamCore):
     max_chunk: the largest chunk of one row in one push; ring: samples per row (default and minimum A + max_chunk); word_ring: records per row.
     _replay_draws (parity tests): every open() then brings the session's per-window draws ((16,) multimodal_context, (32,) joint_embedding).
     window_decoder: a kept decoder of the model's kind built for `slots` rows; its graph_pooled is captured once and replayed by every pool
-    that uses it, one pool at a time.  push() never reads from the device.  A refused call (ValueError) leaves the pool as it was."""
+    that uses it, one pool at a time.  push() never reads from the device.  A refused call (ValueError) leaves the pool as it was.
+    input_sr: as for GestureStream, per row -- every slot has a resampler row of its own (carry and counters, reset by open(), flushed by
+    close(slot)); the chunks of one push are resampled by one launch, lengths by value."""
     _rows = "slots"
 
     def __init__(self, args, pose_decoder, lang_model, slots=4, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, ring=None,
-                 window_decoder=None, _replay_draws=False, _built_for=None):
+                 window_decoder=None, _replay_draws=False, _built_for=None, input_sr=None):
         self.replay = bool(_replay_draws)
-        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, word_ring, ring, window_decoder, graph,
+        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, word_ring, ring, window_decoder, graph, input_sr=input_sr,
                          **(dict(replay_draws=self.replay) if _built_for is None else _built_for))
         B = self.B                                                  # (the state's one-entry `win` is not used: the rows' counters are dec.win)
+        self._head = [None] * B                                     # close(slot): the frames of the windows the resampler's flush completed
         self.open_slots = [False] * B
         self.pushed, self.next_window, self.late_words = [0] * B, [0] * B, [0] * B
         self._draws, self._closing_window = [None] * B, [False] * B
@@ -1415,6 +1559,11 @@ class StreamPool(_StreamCore):
             raise ValueError(f"{type(self).__name__}.open: seed_seq gives {tuple(seed.shape)} seed poses, expected {(n, self.D)}")
         for t in (self.state["written"], self.state["n_words"], self.win, dec.tail, dec.pre):
             t[b:b + 1].zero_()
+        if self.rs is not None:                                                 # the resampler's row: its carry and both counters, nothing else
+            for t in (self.rs["carry"], self.rs["consumed"], self.rs["produced"]):
+                t[b:b + 1].zero_()
+            self._rs_in[b] = self._rs_out[b] = 0
+            self._head[b] = None
         if self.model == "multimodal_context":
             if seed is not None:
                 dec.pre_seq[b, :n, :-1] = seed
@@ -1488,14 +1637,29 @@ class StreamPool(_StreamCore):
         host = np.zeros((B, max(n)), np.float32)
         for b, c in rows.items():
             host[b, :n[b]] = c
-        dst = self.chunk_buf[:, :max(n)]
+        dst = (self.chunk_buf if self.rs is None else self.rs["stage"])[:, :max(n)]
         dst.copy_(torch.from_numpy(host), non_blocking=True)
         fullest = max((self._live_slots(b) + len(r) for b, r in enumerate(recs) if r), default=0)      # slots of the fullest word ring after the push
         table, m_max = self._commit_records(recs)
-        ops.pool_push(self.state, dst, n, table, m_max, max(0, fullest - m_max))
+        if self.rs is not None:                                             # input_sr samples -> every row's new 16 kHz samples, in chunk_buf
+            n, dst = self._resample(dst, n), self.chunk_buf
+        self._feed(dst, n, table, m_max, max(0, fullest - m_max))
         for b in range(B):
-            self.pushed[b] += n[b]
             self.late_words[b] += late[b]
+        return {b: self._result(*fr, numpy) for b, fr in self._emit(list(rows), joints).items()}
+
+    def _feed(self, chunk, n, table, m_max, words_live):
+        """n[b] 16 kHz samples of chunk row b and the push's records go to row b's rings (nothing to do if a resampled push made no sample
+        final and brought no records)."""
+        if max(n) > 0 or m_max > 0:
+            ops.pool_push(self.state, chunk, n, table, m_max, words_live)
+        for b in range(self.B):
+            self.pushed[b] += n[b]
+
+    def _emit(self, slots, joints):
+        """Runs the rounds of the windows that have become complete; {slot: (frames (k * stride, D), joint positions or None)} for `slots`:
+        device views of what became final."""
+        B, st, T, D = self.B, self.stride, self.T, self.D
         masks = pool_rounds(self.pushed, self.next_window, self.S, self.A)
         k = [sum(mk[b] for mk in masks) for b in range(B)]
         buf = jt = None
@@ -1508,10 +1672,10 @@ class StreamPool(_StreamCore):
             if joints:
                 jt = self._joints(buf, len(masks))
         res = {}
-        for b in rows:
+        for b in slots:
             frames = buf[b, :k[b] * st] if k[b] else self.chunk_buf.new_zeros(0, D)
             jrows = None if not joints else (jt[b, :k[b] * st] if k[b] else torch.zeros(0, 10, 3, dtype=torch.float64, device=self.dev))
-            res[b] = self._result(frames, jrows, numpy)
+            res[b] = (frames, jrows)
         return res
 
     def close(self, slot, fade_out=False, joints=False, numpy=False):
@@ -1519,14 +1683,25 @@ class StreamPool(_StreamCore):
         runs as a round with only this row active, the finish (fade_out, joints) runs on a one-row copy of the row's last window, and the row
         is free again.  Returns the session's remaining frames (frames, D), or (frames, joint positions)."""
         b = self._slot(slot, "close")
-        if self.pushed[b] == 0:
+        if self.pushed[b] == 0 and self._rs_in[b] == 0:
             raise ValueError(f"{type(self).__name__}.close: nothing was pushed to slot {b}")
+        if self.rs is not None and self._head[b] is None:
+            # the session's input has ended: the resampler's remaining outputs of this row (zeros past the end) go to its ring like a push,
+            # and the windows they complete run like a push's -- the other rows have none pending -- in front of the closing frames
+            n = self._resample(None, [0] * self.B, flush=(b,))
+            self._feed(self.chunk_buf, n, None, 0, 0)
+            self._head[b] = self._emit([b], joints)[b]
         n_win, k = self._windows_left(f"{type(self).__name__}.close: slot {b}", self.pushed[b], self.next_window[b])
         if k:
             self._round([int(r == b) for r in range(self.B)])
             self._closing_window[b] = True                          # (a close that raises after this point and is called again must not skip its frames)
         frames, jrows = self._closing(self.dec.out[b:b + 1], self.pushed[b], n_win, self._closing_window[b], fade_out, joints)
-        res = self._result(frames[0], None if jrows is None else jrows[0], numpy)
+        frames, jrows = frames[0], None if jrows is None else jrows[0]
+        if self._head[b] is not None and self._head[b][0].shape[0]:
+            if jrows is not None and self._head[b][1] is None:
+                raise ValueError(f"{type(self).__name__}.close: repeated with joints=True after a close without them had run the last complete windows")
+            frames, jrows = torch.cat([self._head[b][0], frames]), None if jrows is None else torch.cat([self._head[b][1], jrows])
+        res = self._result(frames, jrows, numpy)
         self.open_slots[b] = False                                  # only now: a close that raised can be called again
         self.pushed[b] = self.next_window[b] = 0                    # (a free row has no windows to run)
         return res
@@ -1562,7 +1737,7 @@ class Seq2SeqStreamPool(StreamPool):
         return f"args.model is {model!r}, not 'seq2seq' (StreamPool pools multimodal_context and joint_embedding)"
 
     def __init__(self, args, pose_decoder, lang_model, slots=4, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, ring=None,
-                 window_decoder=None, max_words=32, row_local_encoder=True):
+                 window_decoder=None, max_words=32, row_local_encoder=True, input_sr=None):
         n_pre, stride = args.n_pre_poses, args.n_poses - args.n_pre_poses
         if not 1 <= n_pre <= 8:
             raise ValueError(f"Seq2SeqStreamPool: 1 <= n_pre_poses <= 8 (the smoothing kernel's tables), got {n_pre}")
@@ -1570,7 +1745,7 @@ class Seq2SeqStreamPool(StreamPool):
             raise ValueError(f"Seq2SeqStreamPool: a window's smoothing segment of 3 n_pre = {3 * n_pre} frames must lie inside its first "
                              f"n_poses - n_pre_poses = {stride} frames, else it would rewrite frames the next window has handed out")
         super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, graph, word_ring, ring, window_decoder,
-                         _built_for=dict(max_words=max_words, row_local_encoder=bool(row_local_encoder)))
+                         _built_for=dict(max_words=max_words, row_local_encoder=bool(row_local_encoder)), input_sr=input_sr)
         self.max_words = self.dec.max_words
         self._win_words = [{} for _ in range(self.B)]   # per slot: window -> words pushed for it so far (windows that have not run)
         self._sos, self._eos = int(lang_model.SOS_token), int(lang_model.EOS_token)

@@ -779,6 +779,29 @@ int tg_pool_stage_text(const int32_t* word_ring, const int64_t* n_words, const i
 int tg_pool_handover_smooth(const float* res, float* out, float* tail, float* seed, int32_t* win, const int32_t* active, const double* proj,
                             int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream);
 
+/* Sample-rate conversion to 16 kHz (csrc/resample.hip; the counterpart of scripts/synthesize.py's librosa.load(..., sr=16000); added under
+ * ABI 11 -- new symbols only).  Rational polyphase resampling by L / M, L = 16000 / g, M = input_sr / g, g = gcd(16000, input_sr), with the
+ * caller's tap table taps [L][K] fp32 (K even):  y[n] = sum_{k < K} x[(n M) div L - K/2 + 1 + k] * taps[(n M) mod L][k],  samples outside the
+ * signal exact zeros, fp32 fused multiply-adds in increasing k.  A signal of n_in samples gives ceil(n_in L / M) outputs.
+ * tg_resample: B signals packed in x, signal b = x[in_off[b] .. in_off[b+1]) -> y[out_off[b] ..), at most out_off[b+1] - out_off[b] samples
+ * (in_off, out_off [B + 1] int64, device memory); max_out: the longest output, which sizes the grid.
+ * Envelope: 1 <= B <= 65535, max_out >= 1, 1 <= L <= 640, M >= 1, K even in [2, 512]; refused otherwise, nothing is launched.  (A tile is
+ * the largest power of two of outputs, at most 256, whose tap rows and input span fit the LDS: 256 at 48 kHz, 64 at 44.1 kHz.) */
+int tg_resample(const float* x, const int64_t* in_off, const int64_t* out_off, int32_t B, int64_t max_out, const float* taps, int32_t L, int32_t M,
+                int32_t K, float* y, void* stream);
+/* The same conversion for 1 to 4 rows whose input arrives in chunks: row b appends chunk[b][0 .. n[b]) (n0 .. n3 by value, 0 for b >= B; rows
+ * chunk_stride floats apart).  Per row, in device memory: carry [B][K - 1] (the last K - 1 input samples; zeros when the row is opened),
+ * consumed [B] and produced [B] int64 (input samples taken, output samples written so far).  The call writes to out[b][0 ..) the outputs that
+ * became final -- those whose whole tap span lies at or before the last input sample: produced becomes ((consumed - K/2) L - 1) div M + 1, or 0
+ * while consumed <= K/2 -- and, for a row whose bit of flush_mask is set, everything up to ceil(consumed L / M) with zeros past the end of
+ * the input.  Concatenated, a row's outputs are tg_resample's of the whole signal bit for bit.  A row with n[b] == 0 and no flush bit is not
+ * touched.  The host mirrors both counters with the same integer expressions; nothing here is read back.
+ * Envelope: 1 <= B <= 4, n[b] >= 0, some n[b] >= 1 or a flush bit, tg_resample's L, M, K, chunk_stride >= max n,
+ * out_stride >= ceil((max n + (K/2 on a flush)) L / M) + 1. */
+int tg_resample_stream(const float* chunk, int64_t chunk_stride, int32_t n0, int32_t n1, int32_t n2, int32_t n3, int32_t flush_mask, const float* taps,
+                       int32_t L, int32_t M, int32_t K, float* carry, int64_t* consumed, int64_t* produced, float* out, int64_t out_stride, int32_t B,
+                       void* stream);
+
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over
  * T-2 frames, sums[2] = sum |out - target|.  (joint_mae = sums[0]/(B*(T-n_pre)*30), accel = sums[1]/(B*(T-2)*30), l1 = sums[2]/(B*T*27).) */
