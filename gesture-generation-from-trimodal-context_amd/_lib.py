@@ -151,6 +151,9 @@ SIGNATURES = {
     "tg_pool_handover_smooth": [P, P, P, P, P, P, P, I32, I32, I32, I32, P],
     "tg_resample": [P, P, P, I32, I64, P, I32, I32, I32, P, P],
     "tg_resample_stream": [P, I64, I32, I32, I32, I32, I32, P, I32, I32, I32, P, P, P, P, I64, I32, P],
+    "tg_resample_stream_peek": [I32, P, I32, I32, I32, P, P, P, P, I64, I32, P],
+    "tg_stream_stage_preview": [P, P, P, P, P, I32, P, P, I64, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P, P],
+    "tg_preview_handover": [P, P, P, I32, P, I32, I32, I32, I32, P, P],
     "tg_pose_metrics": [P, P, P, I32, I32, I32, P, P],
     "tg_ae_loss": [P, P, I32, I32, I32, P, P, P],
     "tg_counter_inc": [P, P],

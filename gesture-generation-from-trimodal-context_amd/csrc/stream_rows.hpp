@@ -47,9 +47,14 @@ __device__ __forceinline__ void ring_push_row(int b, int n, int m, long wr, long
 // out_text[b][f] = the id of the LAST pushed record with window w and frame f, else 0 (the reference's loop overwrites in word order: the
 // records are scanned oldest to newest by the one thread that owns the frame).  Either output may be null.  The whole workgroup comes here
 // or none of it does: the text part has a barrier.
+// EXTRA (stream_preview.hip): the row counts as written[b] + extra_n samples long, and the samples at positions written[b] <= p < written[b] +
+// extra_n come from the side buffer extra_row[p - written[b]] -- what a push of them would have put into the ring, without the push.  The
+// kernels that stage real windows instantiate EXTRA = false: for them nothing here changes.
+template <bool EXTRA = false>
 __device__ __forceinline__ void ring_stage_row(int b, int w, const float* __restrict__ ring, const int64_t* __restrict__ written,
                                                const int32_t* __restrict__ word_ring, const int64_t* __restrict__ n_words, int R, int S, int A,
-                                               int W, int T, float* __restrict__ out_audio, int64_t* __restrict__ out_text) {
+                                               int W, int T, float* __restrict__ out_audio, int64_t* __restrict__ out_text,
+                                               const float* __restrict__ extra_row = nullptr, int extra_n = 0) {
     __shared__ int32_t rec[ST_MAX_WORDS * 3];
     if (out_text && blockIdx.y == 0) {
         const long cnt = n_words[b];
@@ -72,14 +77,18 @@ __device__ __forceinline__ void ring_stage_row(int b, int w, const float* __rest
     const long base = (long)w * S, wr = written[b];
     // samples [base + lost, base + nv) of the stream are in the ring; lost > 0 only if the host ran the window too late (older samples were
     // overwritten): those read as zeros, like everything from nv on
-    long nv = wr - base, lost = wr - R - base;
+    const long gap = wr - base;                                       // EXTRA: window offsets from gap on are the side buffer's [0, extra_n)
+    long nv = gap + (EXTRA ? extra_n : 0), lost = wr - R - base;
     nv = (nv < 0 || w < 0) ? 0 : (nv > A ? A : nv);                   // (a negative window index stages silence)
     lost = lost < 0 ? 0 : (lost > A ? A : lost);
+    long nr = nv;                                                     // offsets below nr are in the ring (EXTRA = false: all of them)
+    if (EXTRA) nr = gap < 0 ? 0 : (gap < nv ? gap : nv);
     const int p0 = (int)(base % R);
     const float* __restrict__ src = ring + (long)b * R;
     float* __restrict__ dst = out_audio + (long)b * A;
     auto at = [&](int k) -> float {                                   // A < R: one subtraction wraps
         if (k < lost || k >= nv) return 0.f;
+        if (EXTRA && k >= nr) return extra_row[k - gap];              // 0 <= k - gap < extra_n: nr <= k < nv <= gap + extra_n
         int p = p0 + k;
         if (p >= R) p -= R;
         return src[p];
@@ -93,7 +102,7 @@ __device__ __forceinline__ void ring_stage_row(int b, int w, const float* __rest
         f32x4 v;
         int p = p0 + i;
         if (p >= R) p -= R;
-        if (i >= lost && i + 3 < nv && p + 3 < R && (reinterpret_cast<uintptr_t>(src + p) & 15u) == 0) {
+        if (i >= lost && i + 3 < nr && p + 3 < R && (reinterpret_cast<uintptr_t>(src + p) & 15u) == 0) {
             v = *reinterpret_cast<const f32x4*>(src + p);
         } else {
 #pragma unroll

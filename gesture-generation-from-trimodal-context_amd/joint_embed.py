@@ -198,6 +198,12 @@ class ContextEncoder(nn.Module):
                 seen.add(id(p)); names.append(n)
         return names
 
+    def rng(self, device):
+        """The encoder's counter RNG on `device`, made on first use (forward's own): the one object forward advances and draws from."""
+        if self._rng is None or self._rng.state.device != device:
+            self._rng = DeviceRNG(self.seed, device)
+        return self._rng
+
     def forward(self, in_text, in_spec, inject=None):
         need_cuda(in_text, "ContextEncoder: in_text", torch.int64); need_cuda(in_spec, "ContextEncoder: in_spec")
         if in_text.dim() != 2 or in_spec.dim() != 2 or in_spec.shape[0] != in_text.shape[0]:
@@ -205,8 +211,7 @@ class ContextEncoder(nn.Module):
         B, T = in_text.shape
         if self.training and B == 1:
             raise ValueError("ContextEncoder: BatchNorm in train mode needs more than one clip")
-        if self._rng is None or self._rng.state.device != in_spec.device:
-            self._rng = DeviceRNG(self.seed, in_spec.device)
+        self.rng(in_spec.device)
         if inject is None:
             self._rng.advance()
         inject = dict(inject or {})

@@ -2242,6 +2242,83 @@ def resample_stream(rs, chunk, n, out, flush=()):
          _p(rs["consumed"]), _p(rs["produced"]), _p(out), out.shape[1], B, _stream())      # (B > 4: refused by the library)
 
 
+# ------------------------------------------------------------------------------------------------- stream preview (csrc/stream_preview.hip)
+def resample_stream_peek(rs, extra, rows):
+    """What a flush of `rows` of the resampler state rs would append, WITHOUT the flush: extra[b, 0:...] (extra (B, >= ceil((K/2) L / M) + 1)
+    fp32, device, contiguous) = the outputs from produced[b] up to ceil(consumed[b] L / M), zeros past the end of the input; rs keeps every
+    bit.  The count is the host's to compute (synthesize.resampled_length on its own counters)."""
+    B = rs["B"]
+    mask = 0
+    for b in rows:
+        if not 0 <= int(b) < B:
+            raise ValueError(f"rows: row {b} of {B}")
+        mask |= 1 << int(b)
+    _flat(extra, "extra")
+    if extra.dim() != 2 or extra.shape[0] != B:
+        raise ValueError(f"extra: expected a contiguous ({B}, n) tensor, got {tuple(extra.shape)}")
+    _flat(rs["carry"], "carry"); _dev_int(rs["consumed"], torch.int64, B, "consumed"); _dev_int(rs["produced"], torch.int64, B, "produced")
+    assert rs["carry"].numel() == B * (rs["K"] - 1)
+    call("tg_resample_stream_peek", mask, _p(rs["taps"]), rs["L"], rs["M"], rs["K"], _p(rs["carry"]), _p(rs["consumed"]), _p(rs["produced"]),
+         _p(extra), extra.shape[1], B, _stream())
+
+
+def stream_stage_preview(st, win, active, extra, extra_n, text_out=None, audio_out=None):
+    """stream_stage / pool_stage on rows that count as written[b] + extra_n[b] samples long, the samples behind written[b] read from extra[b]
+    (extra (B, >= max extra_n) fp32, device, contiguous, or None if every extra_n[b] is 0; extra_n: B host integers >= 0).  win: (B,) int32 on
+    the device -- row b stages its window win[b] -- or a host integer: every row stages that window; active: (B,) int32 on the device or
+    None (every row).  The state st is only read."""
+    _stream_check(st)
+    B = st["B"]
+    extra_n = [int(v) for v in extra_n]
+    if len(extra_n) != B:
+        raise ValueError(f"extra_n: {len(extra_n)} counts for {B} rows")
+    es = 0
+    if max(extra_n) > 0:
+        _flat(extra, "extra")
+        if extra.dim() != 2 or extra.shape[0] != B or extra.shape[1] < max(extra_n):
+            raise ValueError(f"extra: expected a contiguous ({B}, >= {max(extra_n)}) tensor, got {tuple(extra.shape)}")
+        es = extra.shape[1]
+    w_value = 0
+    if not isinstance(win, torch.Tensor):
+        win, w_value = None, int(win)
+    else:
+        _dev_int(win, torch.int32, B, "win")
+    if active is not None:
+        _dev_int(active, torch.int32, B, "active")
+    if audio_out is not None:
+        _flat(audio_out, "audio_out")
+        if tuple(audio_out.shape) != (B, st["A"]):
+            raise ValueError(f"audio_out is {tuple(audio_out.shape)}, a window is {(B, st['A'])}")
+    if text_out is not None:
+        _i64(text_out, "text_out")
+        if tuple(text_out.shape) != (B, st["T"]) or not text_out.is_contiguous():
+            raise ValueError(f"text_out is {tuple(text_out.shape)}, a window's text is {(B, st['T'])}, contiguous")
+    call("tg_stream_stage_preview", _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(win), w_value, _p(active),
+         _p(extra if es else None), es, *(extra_n + [0] * 4)[:4], B, st["R"], st["S"], st["A"], st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
+
+
+def preview_handover(res, tail, win, active, preview_out):
+    """pool_handover's first half and nothing else: for the rows with active[b] != 0 (active None: every row) preview_out = res (B, T, D),
+    cross-faded with tail (B, n_pre, D) where the row's window index -- win[b], (B,) int32 on the device, or one host integer for every row --
+    is > 0 (window_blend's arithmetic).  tail, the seeds and win are only read."""
+    for t, name in ((res, "res"), (tail, "tail"), (preview_out, "preview_out")):
+        _flat(t, name)
+        if t.dim() != 3:
+            raise ValueError(f"{name}: expected three dimensions, got {tuple(t.shape)}")
+    B, T, D = preview_out.shape
+    n_pre = tail.shape[1]
+    if tuple(res.shape) != (B, T, D) or tail.shape[0] != B or tail.shape[2] != D:
+        raise ValueError(f"res {tuple(res.shape)} / tail {tuple(tail.shape)} do not belong to preview_out {tuple(preview_out.shape)}")
+    w_value = 0
+    if not isinstance(win, torch.Tensor):
+        win, w_value = None, int(win)
+    else:
+        _dev_int(win, torch.int32, B, "win")
+    if active is not None:
+        _dev_int(active, torch.int32, B, "active")
+    call("tg_preview_handover", _p(res), _p(tail), _p(win), w_value, _p(active), B, T, D, n_pre, _p(preview_out), _stream())
+
+
 def pose_metrics(out, target, mean_dir_vec, n_pre, sums):
     _same(out, target); _flat(mean_dir_vec, "mean"); B, T, D = out.shape
     assert D == 27 and mean_dir_vec.numel() == 27 and sums.dtype == torch.float64 and sums.numel() >= 3 and sums.is_cuda

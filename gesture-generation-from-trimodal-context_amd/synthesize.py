@@ -48,6 +48,9 @@ Seq2SeqStreamPool is StreamPool for the seq2seq model (StreamPool itself keeps r
 comes out of the word ring per row, the decoder's forward goes into a result buffer of its own and the hand-over kernel
 (csrc/stream_pool_seq.hip) also smooths the window it hands over -- the smoothing segment is window-local.
 
+preview() (GestureStream, StreamPool): what close() would return now -- the window still filling, zero-padded -- computed
+beside the stream by csrc/stream_preview.hip and the decoders' preview chain; the stream, its device state and its RNG counter keep every bit.
+
 Structure: the three window decoders are subclasses of _WindowDecoderBase (buffers, the eager / capture-once / replay skeleton, the pooled
 window, check_kept; _capture is the one place a graph is captured); the streams and the pool are subclasses of _StreamCore (constructor checks,
 a row's word records, the closing window); the five offline loops stay separate and share _seed_rows, _host_window_batch and _rows_result.
@@ -290,6 +293,7 @@ class _WindowDecoderBase:
         # (layers.FrozenWeights) -- a decoder must not outlive a change of the parameters
         self.frozen = L.FrozenWeights()
         self.win = self.active = self.graph_pooled = None              # window_pooled's state: made on its first use
+        self.pv = self.graph_preview = None                            # preview()'s buffers and graph: made on its first use
 
     def check_kept(self, model, batch, T, n_pre, replay_draws=False):
         """Whether this decoder was built for `model` (the same object), `batch` rows, these window sizes and this replay_draws."""
@@ -364,6 +368,90 @@ class _WindowDecoderBase:
                 self._forward_pooled()
         return self.out
 
+    # -------------------------------------------------------------------------------------------------------------- preview
+    _seed_names = ("pre",)                                          # the attributes _model_forward reads the seed from
+
+    def _rng(self):
+        """The DeviceRNG _model_forward advances (made here if no window has run yet)."""
+        raise ValueError(f"{type(self).__name__}: this decoder has no preview")
+
+    def _seed_from(self, frames, seed):
+        seed.copy_(frames)                                       # _reseed's copy, into a seed buffer of the preview's own
+
+    def preview_buffers(self):
+        """The preview's static buffers, made on first use: out (B, T, D) -- what preview() returns --, win and active (B,) int32 -- every
+        row's window index and the mask of the rows to hand over, read by the staging (ops.stream_stage_preview) and by the hand-over --, and
+        the keep of the RNG counter."""
+        if self.pv is None:
+            self.pv = dict(out=torch.zeros_like(self.out), win=torch.zeros(self.B, dtype=torch.int32, device=self.dev),
+                           active=torch.ones(self.B, dtype=torch.int32, device=self.dev), rng=self._rng().state.clone(), seed=None)
+        return self.pv
+
+    def _forward_preview(self, skip=0):
+        """window()'s / window_pooled()'s forward chain into the same result buffer, then ONE launch, ops.preview_handover, in place of the
+        hand-over chain: pv['out'] = the result cross-faded with the tail; out, tail, the seed and win are only read.  The forward advances
+        the model's RNG counter (a device tensor): it is saved in front and put back behind -- two small device copies, captured with the
+        chain --, so the window that runs next draws what it would have drawn, and a preview draws what that window will draw.  skip: the
+        previewed windows in front of this one (a window that follows a previewed one): the counter is advanced past their draws first,
+        so this window draws what close() would give it."""
+        pv, rng = self.pv, self._rng()
+        state = rng.state
+        pv["rng"].copy_(state)
+        for _ in range(skip):
+            rng.advance()
+        ops.preview_handover(self._model_forward().view(self.B, self.T, self.D), self.tail, pv["win"], pv["active"], pv["out"])
+        state.copy_(pv["rng"])
+
+    def _preview(self, win, active, draw, after):
+        pv = self.preview_buffers()
+        for buf, val in ((pv["win"], win), (pv["active"], active)):
+            if val is not None:
+                buf.copy_(torch.as_tensor(val, dtype=torch.int32).expand(self.B), non_blocking=True)
+        if draw is not None:
+            self.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
+        with torch.no_grad(), self.frozen:
+            if after is not None:
+                # the window FOLLOWS a previewed one (a resampler flush that completes a window and leaves a rest): its seed and tail are that
+                # preview's last frames, in buffers of the preview's own that stand in for self.pre / self.tail while the chain runs -- eagerly,
+                # the graph has the real ones' addresses.  The real seed and tail are not written.
+                if pv["seed"] is None:
+                    pv["seed"] = (torch.zeros_like(self.pre), torch.zeros_like(self.tail))
+                seed, tail = pv["seed"]
+                real = [getattr(self, n) for n in self._seed_names], self.tail
+                tail.copy_(after[:, self.T - self.n_pre:, :])
+                self._seed_from(tail, seed)
+                try:
+                    for n in self._seed_names:
+                        setattr(self, n, seed)
+                    self.tail = tail
+                    self._forward_preview(skip=1)
+                finally:
+                    for n, t in zip(self._seed_names, real[0]):
+                        setattr(self, n, t)
+                    self.tail = real[1]
+            elif self.use_graph:
+                if self.graph_preview is None:
+                    self._forward_preview()                      # the eager pass a capture needs in front of it (see window_pooled); it writes what a preview may
+                    self.graph_preview = _capture(self._forward_preview, ())
+                self.graph_preview.replay()
+            else:
+                self._forward_preview()
+        return pv["out"]
+
+    def preview(self, win=None, draw=None, after=None):
+        """The window `win` (an integer, or one per row; None: pv['win'] as it is) of every row as window() would run it now -- the inputs are
+        self.text / self.audio (/ self.vid), written in place -- WITHOUT the hand-over: returns pv['out'] (B, T, D), the result cross-faded
+        with self.tail where the index is > 0 (overwritten by the next preview).  out, tail, the seed, win / active and the RNG counter keep
+        every bit; text, audio, draw and the result buffer are the preview's to overwrite.  From the first call on the chain is ONE captured
+        graph, self.graph_preview (graph and graph_pooled are not touched).  after: a (B, T, D) copy of an earlier preview that this window
+        follows (its last n_pre frames are the tail and the seed); that one runs eagerly."""
+        return self._preview(win, [1] * self.B, draw, after)
+
+    def preview_pooled(self, active, win=None, draw=None, after=None):
+        """preview() for the rows of a stream pool: only the rows with active[b] != 0 get their pv['out'] row; the others' keep every bit.
+        active None: pv['active'] as it is (the caller wrote it in place, for the staging)."""
+        return self._preview(win, active, draw, after)
+
 
 class WindowDecoder(_WindowDecoderBase):
     """Batched window forward of the multimodal_context generator with device-side seed hand-over and cross-fade; optional hipGraph capture.
@@ -388,6 +476,16 @@ class WindowDecoder(_WindowDecoderBase):
     def _reseed(self):
         self.seedwin[:, :self.n_pre, :].copy_(self.tail)
         ops.make_pre_seq(self.seedwin, self.pre_seq, self.n_pre)          # frames < n_pre + constraint bit, zeros elsewhere
+
+    _seed_names = ("pre", "pre_seq")
+
+    def _rng(self):
+        return self.gen.engine.rng
+
+    def _seed_from(self, frames, seed):
+        win = torch.zeros_like(self.seedwin)                     # _reseed's two steps, on buffers of the preview's own
+        win[:, :self.n_pre, :].copy_(frames)
+        ops.make_pre_seq(win, seed, self.n_pre)
 
     def _model_forward(self):
         eng = self.gen.engine
@@ -433,6 +531,9 @@ class JointEmbedWindowDecoder(_WindowDecoderBase):
         if not 1 <= batch <= 4:
             raise ValueError(f"JointEmbedWindowDecoder: 1 to 4 utterances in lock-step (the few-row recurrence kernel's rows), got {batch}")
         super().__init__(args, net, batch, device, dec.pose_dim, graph, draw_width=32 if replay_draws else 0, audio_sr=audio_sr)
+
+    def _rng(self):
+        return self.net.context_encoder.rng(self.out.device)
 
     def _model_forward(self):
         net = self.net
@@ -1137,6 +1238,7 @@ class _StreamCore:
         self._live, self._n_rec = [[] for _ in range(self.B)], [0] * self.B
         self._ones = torch.ones(self.B, dtype=torch.int32, device=dev)
         self._mean = self._tables = None                 # the fp64 mean and the projection tables on the device: made once, on first use
+        self._extra = None                               # preview(): where the resampler's flush is peeked at, made on first use
 
     # -------------------------------------------------------------------------------------------------------------- host bookkeeping (integers)
     def _row_records(self, words, next_window):
@@ -1174,15 +1276,29 @@ class _StreamCore:
         """One launch of the streaming resampler: row b takes chunk[b, :n[b]] (input_sr samples, device) and -- flush: the rows whose input
         has ended -- writes its new 16 kHz samples to chunk_buf[b].  Returns their counts per row, from the host's own counters by the
         integer expressions the kernel evaluates on the device's (resampled_ready / resampled_length); nothing is read back."""
-        L_, M_, K_ = self.rs["L"], self.rs["M"], self.rs["K"]
         ops.resample_stream(self.rs, chunk, n, self.chunk_buf, flush)
         got = [0] * self.B
         for b in range(self.B):
             if n[b] or b in flush:
                 self._rs_in[b] += n[b]
-                made = resampled_length(self._rs_in[b], L_, M_) if b in flush else resampled_ready(self._rs_in[b], L_, M_, K_)
+                made = self._made(self._rs_in[b], b in flush)
                 got[b], self._rs_out[b] = made - self._rs_out[b], made
         return got
+
+    def _made(self, n_in, flushed):
+        """The 16 kHz samples the resampler has written after n_in input samples: the final ones, or -- flushed -- all of them."""
+        L_, M_, K_ = self.rs["L"], self.rs["M"], self.rs["K"]
+        return resampled_length(n_in, L_, M_) if flushed else resampled_ready(n_in, L_, M_, K_)
+
+    @staticmethod
+    def _prepend(what, head, frames, jt, dim=1):
+        """head (frames, joint positions or None) or None, put in front of (frames, jt) along `dim`: the windows a flush completed in front of
+        the closing frames."""
+        if head is None or not head[0].shape[dim]:
+            return frames, jt
+        if jt is not None and head[1] is None:
+            raise ValueError(f"{what}: repeated with joints=True after a close without them had run the last complete windows")
+        return torch.cat([head[0], frames], dim), None if jt is None else torch.cat([head[1], jt], dim)
 
     def _mean_dev(self):
         if self._mean is None:
@@ -1237,6 +1353,52 @@ class _StreamCore:
                                  joints=jt)
         skip = 0 if closing_window else st
         return fin[:, skip:length], None if jt is None else jt[:, skip:length]
+
+    # -------------------------------------------------------------------------------------------------------------- preview
+    def _flush_count(self, b):
+        """The 16 kHz samples a flush of row b's resampler would still append: close()'s count, from the host's counters, not committed."""
+        if self.rs is None:
+            return 0
+        return self._made(self._rs_in[b], True) - self._rs_out[b]
+
+    def _preview_plan(self, what, pushed, next_window):
+        """close()'s integers for a row of `pushed` 16 kHz samples (the flush's included) whose windows below next_window have run:
+        (n_win, head, k) -- the reference's window count, the head in (0, 1) windows the flush's samples complete (they run like a push's, in
+        front of the closing frames) and the k in (0, 1) padded windows behind them.  Nothing is committed."""
+        head = max(0, complete_windows(pushed, self.S, self.A) - next_window)
+        n_win, k = self._windows_left(what, pushed, next_window + head)
+        return n_win, head, k
+
+    def _preview_rows(self, what, sel, mask, pushed, next_window, e, draw_of, ran_closing, held, fade_out, joints):
+        """What close() would return now for the rows `sel` (a slice; mask: the pool's 0 / 1 list of them, None: every row), computed beside the
+        stream: the resampler's flush is peeked at (ops.resample_stream_peek: e samples per row into a side buffer), the windows close() would
+        still run are staged from the rings plus that buffer (ops.stream_stage_preview) and run by the decoder's preview chain, and the finish
+        is close()'s own (_closing) on the previewed window.  pushed: the rows' sample count with the flush's e; draw_of(i): the draw to replay
+        for window i, or None; ran_closing / held: a close() that raised may have run the closing window / kept the flush's frames already.
+        No host field and no device state of the stream changes."""
+        B, st, dec = self.B, self.stride, self.dec
+        n_win, head_k, k = self._preview_plan(what, pushed, next_window)
+        last, head, after = dec.out, None, None
+        if head_k + k:
+            pv = dec.preview_buffers()
+            on = [1] * B if mask is None else [int(bool(a)) for a in mask]
+            extra, extra_n = None, [e * a for a in on]
+            if e:
+                if self._extra is None:
+                    self._extra = torch.zeros(B, self.rs["out_stride"], device=self.dev)
+                extra = self._extra
+                ops.resample_stream_peek(self.rs, extra, [b for b in range(B) if on[b]])
+            pv["active"].copy_(torch.tensor(on, dtype=torch.int32), non_blocking=True)
+        for j in range(head_k + k):
+            i = next_window + j
+            pv["win"].copy_(torch.tensor([i] * B, dtype=torch.int32), non_blocking=True)
+            ops.stream_stage_preview(self.state, pv["win"], pv["active"], extra, extra_n, dec.text, dec.audio)
+            last = dec.preview_pooled(None, draw=None if draw_of is None else draw_of(i), after=after)
+            if j < head_k:                                           # a complete window: its first `stride` frames, as a push emits them
+                last = after = last.clone()
+                head = (last[sel, :st], self._joints(last, 1)[sel] if joints else None)
+        frames, jt = self._closing(last[sel], pushed, n_win, bool(k) or ran_closing, fade_out, joints)
+        return self._prepend(what, held, *self._prepend(what, head, frames, jt))      # (held: in front of everything else, as close() puts it)
 
 
 class GestureStream(_StreamCore):
@@ -1404,13 +1566,31 @@ class GestureStream(_StreamCore):
             self._closing_window = True                             # (a close that raises after this point and is called again must not skip its frames)
         frames, jt = self._closing(self.dec.out, self.pushed, n_win, self._closing_window, fade_out, joints,
                                    self._smooth_closing and self._closing_window)
-        if self._head is not None and self._head[0].shape[1]:
-            if jt is not None and self._head[1] is None:
-                raise ValueError(f"{who}.close: repeated with joints=True after a close without them had run the last complete windows")
-            frames, jt = torch.cat([self._head[0], frames], 1), None if jt is None else torch.cat([self._head[1], jt], 1)
+        frames, jt = self._prepend(f"{who}.close", self._head, frames, jt)
         res = self._result(frames, jt, numpy)
         self.closed = True                                          # only now: a close that raised can be called again
         return res
+
+    def preview(self, fade_out=False, joints=False, numpy=False):
+        """What close(fade_out, joints, numpy) would return NOW, without ending the stream and without changing it: the frames not yet
+        emitted -- the window that is still filling run as the reference runs an utterance's last window: its audio zero-padded, the words
+        that have arrived, cross-faded with the kept tail -- or, where the last complete window has been emitted, its n_pre_poses tail frames
+        (more under fade_out, as at close()).  Provisional: the frames a later push() or close() returns replace them, and those are bit for
+        bit what a stream that was never previewed returns.  Any number of previews may follow one another and interleave with pushes.
+        Nothing is read from the device unless numpy=True.  The draw: with _draws / eps_list the entry the closing window would use (nothing
+        is consumed); else the device RNG's next draw -- what the window that runs next will draw; where two windows are previewed, the
+        second draws the step behind it, as close() would --, its counter saved and put back around the preview.  ValueError: closed stream, nothing pushed."""
+        who = type(self).__name__
+        if self.closed:
+            raise ValueError(f"{who}.preview: the stream is closed")
+        if self.pushed == 0 and self._rs_in[0] == 0:
+            raise ValueError(f"{who}.preview: nothing was pushed")
+        if self.vid is not None and self.next_window == 0:
+            self.dec.vid.copy_(self.vid, non_blocking=True)        # window 0 has not run: the speaker ids it will copy itself, the same values
+        e = self._flush_count(0)                                    # (rows share a clock: one count)
+        draw_of = None if self.draws is None else (lambda i: self.draws[i])
+        return self._result(*self._preview_rows(f"{who}.preview", slice(None), None, self.pushed + e, self.next_window, e, draw_of,
+                                                self._closing_window, self._head, fade_out, joints), numpy)
 
 
 class Seq2SeqGestureStream(GestureStream):
@@ -1454,6 +1634,10 @@ class Seq2SeqGestureStream(GestureStream):
         self._k_dev = {1: self._ones}                    # (B,) int32 window counts of a push's buffer, by k
         self._tables = _projection_device(self.n_pre, self.dev)
         self._sos, self._eos = int(lang_model.SOS_token), int(lang_model.EOS_token)
+
+    def preview(self, fade_out=False, joints=False, numpy=False):
+        raise ValueError("Seq2SeqGestureStream.preview: the seq2seq model has no preview -- its closing path smooths the window it ran and "
+                         "stages a word list, which the preview chain does not do")
 
     def _records(self, words):
         """GestureStream._records behind one more refusal: no window of a row may hold more than max_words words."""
@@ -1697,14 +1881,31 @@ class StreamPool(_StreamCore):
             self._closing_window[b] = True                          # (a close that raises after this point and is called again must not skip its frames)
         frames, jrows = self._closing(self.dec.out[b:b + 1], self.pushed[b], n_win, self._closing_window[b], fade_out, joints)
         frames, jrows = frames[0], None if jrows is None else jrows[0]
-        if self._head[b] is not None and self._head[b][0].shape[0]:
-            if jrows is not None and self._head[b][1] is None:
-                raise ValueError(f"{type(self).__name__}.close: repeated with joints=True after a close without them had run the last complete windows")
-            frames, jrows = torch.cat([self._head[b][0], frames]), None if jrows is None else torch.cat([self._head[b][1], jrows])
+        frames, jrows = self._prepend(f"{type(self).__name__}.close", self._head[b], frames, jrows, dim=0)
         res = self._result(frames, jrows, numpy)
         self.open_slots[b] = False                                  # only now: a close that raised can be called again
         self.pushed[b] = self.next_window[b] = 0                    # (a free row has no windows to run)
         return res
+
+    def preview(self, slot, fade_out=False, joints=False, numpy=False):
+        """What close(slot, fade_out, joints, numpy) would return NOW (GestureStream.preview has the definition), for that row alone and
+        without ending its session: the slot stays open, and neither its state nor any other row's changes -- the preview chain hands over
+        this row only, into a buffer of its own.  ValueError: a slot that is not open, nothing pushed to it."""
+        who = type(self).__name__
+        b = self._slot(slot, "preview")
+        if self.pushed[b] == 0 and self._rs_in[b] == 0:
+            raise ValueError(f"{who}.preview: nothing was pushed to slot {b}")
+        e = self._flush_count(b)
+        draw_of = None
+        if self._draw_host is not None:
+            def draw_of(i):                                          # _round's rows, with this row's draw of window i; _draw_host itself is kept
+                d = self._draw_host.clone()
+                d[b] = torch.as_tensor(self._draws[b][i], dtype=torch.float32).reshape(-1)
+                return d
+        held = None if self._head[b] is None else tuple(None if t is None else t[None] for t in self._head[b])
+        frames, jrows = self._preview_rows(f"{who}.preview: slot {b}", slice(b, b + 1), [int(r == b) for r in range(self.B)], self.pushed[b] + e,
+                                           self.next_window[b], e, draw_of, self._closing_window[b], held, fade_out, joints)
+        return self._result(frames[0], None if jrows is None else jrows[0], numpy)
 
 
 class Seq2SeqStreamPool(StreamPool):
@@ -1751,6 +1952,10 @@ class Seq2SeqStreamPool(StreamPool):
         self._sos, self._eos = int(lang_model.SOS_token), int(lang_model.EOS_token)
         for b in range(self.B):
             self._idle_text(b)
+
+    def preview(self, slot, fade_out=False, joints=False, numpy=False):
+        raise ValueError("Seq2SeqStreamPool.preview: the seq2seq model has no preview -- its closing path smooths the window it ran and "
+                         "stages a word list, which the preview chain does not do")
 
     def _idle_text(self, b):
         """Row b holds [SOS, EOS, 0 ...], length 2: the forward runs on every row, open or not."""

@@ -802,6 +802,32 @@ int tg_resample_stream(const float* chunk, int64_t chunk_stride, int32_t n0, int
                        int32_t L, int32_t M, int32_t K, float* carry, int64_t* consumed, int64_t* produced, float* out, int64_t out_stride, int32_t B,
                        void* stream);
 
+/* Stream preview (csrc/stream_preview.hip; synthesize.GestureStream.preview / StreamPool.preview; added under ABI 11 -- new symbols only): the
+ * window that is still filling, as the closing window of the utterance truncated now would run it, without touching the stream.  None of the
+ * three stores to a ring, a counter, tail, a seed, win, active, the resampler's carry or the decoder's out.  One workgroup (or grid column)
+ * per row, a row that is not selected leaves before any store, no atomics, nothing waits on another workgroup.
+ * tg_resample_stream_peek: tg_resample_stream's flush of the rows in row_mask WITHOUT its stores to carry / consumed / produced: extra[b][0 ..)
+ * (rows extra_stride floats apart) = the outputs from produced[b] up to ceil(consumed[b] L / M) out of [carry | zeros], the same tile body and
+ * chain of fused multiply-adds, so the bits a flush would append.  The host knows the count: ceil(consumed L / M) - produced.
+ * Envelope: 1 <= B <= 4, 1 <= row_mask < 2^B, tg_resample's L, M, K, extra_stride >= ceil((K/2) L / M) + 1. */
+int tg_resample_stream_peek(int32_t row_mask, const float* taps, int32_t L, int32_t M, int32_t K, const float* carry, const int64_t* consumed,
+                            const int64_t* produced, float* extra, int64_t extra_stride, int32_t B, void* stream);
+/* tg_stream_stage / tg_pool_stage on rows that count as written[b] + extra_n[b] samples long: stream positions written[b] <= p < written[b] +
+ * extra_n[b] read extra[b][p - written[b]] (rows extra_stride floats apart; e0 .. e3 by value, 0 for b >= B), zeros behind.  The window index
+ * of row b is win[b] (int32 [B], device memory) or, win == null, w_value for every row; active (int32 [B]) may be null: every row.  With
+ * every extra_n 0 the outputs are tg_stream_stage's / tg_pool_stage's bit for bit (one row body, stream_rows.hpp).  Writes out_audio and
+ * out_text only.  Envelope: tg_stream_stage's, extra_n[b] >= 0, extra_stride >= max extra_n, extra and out_audio non-null if any extra_n > 0. */
+int tg_stream_stage_preview(const float* ring, const int64_t* written, const int32_t* word_ring, const int64_t* n_words, const int32_t* win,
+                            int32_t w_value, const int32_t* active, const float* extra, int64_t extra_stride, int32_t e0, int32_t e1, int32_t e2,
+                            int32_t e3, int32_t B, int32_t R, int32_t S, int32_t A, int32_t W, int32_t T, float* out_audio, int64_t* out_text,
+                            void* stream);
+/* tg_pool_handover's first half and nothing else: for every row with active[b] != 0 (active == null: every row) preview_out[b] = res[b]
+ * ([B][T][D], contiguous), its first n_pre frames cross-faded with tail[b] exactly as tg_window_blend does where the row's window index --
+ * win[b], or w_value if win == null -- is > 0.  tail, the seeds and win are not written; the preview_out rows of the other rows neither.
+ * Envelope: tg_pool_handover's (1 <= B <= 4, 1 <= n_pre <= 8, 1 <= D <= 64, n_pre < T <= 1024). */
+int tg_preview_handover(const float* res, const float* tail, const int32_t* win, int32_t w_value, const int32_t* active, int32_t B, int32_t T,
+                        int32_t D, int32_t n_pre, float* preview_out, void* stream);
+
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over
  * T-2 frames, sums[2] = sum |out - target|.  (joint_mae = sums[0]/(B*(T-n_pre)*30), accel = sums[1]/(B*(T-2)*30), l1 = sums[2]/(B*T*27).) */
