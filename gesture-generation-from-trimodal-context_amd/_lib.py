@@ -1,14 +1,21 @@
 """ctypes binding of libtrimodal_hip.so (the C ABI declared in include/trimodal_hip.h).
 
+The header is the table: it is parsed once at import (text only; the library is not opened before load()) and every prototype's restype /
+argtypes, and ABI_VERSION, come from it.  A new entry point needs its declaration there and nothing here; only the struct mirrors below are
+written by hand (tests/test_abi_cpu.py pins their layout against the C compiler's).  A declaration outside the header's "plain C types
+only" convention fails the import, naming it.
+
 There is no CPU fallback: if the library is missing or a symbol is absent the import fails loudly.
 """
 import ctypes as C
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (TG_LIB_PATH: another build of the same library -- same-box A/B timing against an older build, tools/ab_bench.sh; the lab library of the
 # ablation tools.  Unset in every test and in bench.py's default run.)
 LIB_PATH = os.environ.get("TG_LIB_PATH") or os.path.join(_HERE, "libtrimodal_hip.so")
+HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "trimodal_hip.h")
 
 
 class Window(C.Structure):
@@ -46,167 +53,85 @@ class AeStepArgs(C.Structure):
 
 MAX_GROUP = 8
 
-# name -> argtypes (all return int); mirrors include/trimodal_hip.h one to one
-SIGNATURES = {
-    "tg_gemm_nt": [WP, P, I64, P, P, I64, I64, I32, I32, I32, F32, I32, P],
-    "tg_gemm_nt_group": [C.POINTER(NtProblem), I32, P],
-    "tg_gemm_tn_group": [C.POINTER(TnProblem), I32, P],
-    "tg_ae_train_step": [C.POINTER(AeStepArgs), P],
-    "tg_split3_planes": [P, I64, I32, I32, P, I32, I64, P],
-    "tg_split2h_planes": [P, I64, I32, I32, P, I32, I64, P, P],
-    "tg_split2h_planes_tcat": [P, P, I32, I32, P, I32, I64, P, P],
-    "tg_win_row_absmax": [WP, I32, P, P],
-    "tg_h2_row_scales": [WP, I32, P, P, P],
-    "tg_absmax_rows_cols": [P, I64, I32, I32, I32, P, P, P],
-    "tg_gemm_tn": [P, I64, WP, P, I64, I32, I32, I32, P, P, I64, P],
-    "tg_colsum": [P, I64, I32, I32, P, I32, P],
-    "tg_gru_forward": [P, I64, P, P, P, P, P, P, I64, I32, I32, I32, P],
-    "tg_gru_backward": [P, P, P, I64, P, P, P, P, I64, P, I32, I32, I32, P],
-    "tg_gru_h64_forward": [P, I64, P, P, P, P, P, P, I64, P, P, I32, I32, P],
-    "tg_gru_h64_backward": [P, P, P, P, I64, P, P, P, P, I64, I32, I32, P],
-    "tg_gru_forward_cluster": [P, I64, P, P, P, P, P, P, I64, P, P, P, I64, I32, I32, I32, P],
-    "tg_gru_forward_cluster_rows": [P, I64, P, P, P, P, P, P, I64, P, P, P, I64, I32, I32, I32, I32, I32, P],
-    "tg_gru_forward_vec": [P, I64, P, P, P, P, P, P, I64, I32, I32, I32, P],
-    "tg_gru_vec1_supported": [I32, I32, P],
-    "tg_gru_forward_vec1": [P, P, P, P, P, I64, I32, I32, I32, P],
-    "tg_gru_vec_const_supported": [I32, I32, I32, P],
-    "tg_gru_forward_vec_const": [P, I64, P, P, P, P, P, P, I64, I32, I32, I32, I32, P],
-    "tg_gru_backward_cluster": [P, P, P, P, I64, P, P, P, P, I64, P, I64, I32, I32, I32, P],
-    "tg_gru_backward_cluster_stats": [P, P, P, P, I64, P, P, P, P, I64, P, I64, I32, I32, I32, P, I64, P, P, P],
-    "tg_bn_train_stats": [P, I32, I32, I32, P, P, P, P, P, P, F32, F32, I32, P],
-    "tg_bn_eval_stats": [P, P, I32, F32, P, P, P],
-    "tg_bn_train_fused": [P, P, I32, I32, I32, P, P, P, P, P, P, P, F32, F32, F32, I32, P],
-    "tg_bn_apply": [P, P, I32, I32, I32, P, P, P, P, F32, P],
-    "tg_bn2_train": [P, P, I32, I32, I32, P, I64, P, P, P, P, P, P, P, F32, F32, F32, I32, P],
-    "tg_bn2_backward": [P, P, P, I32, I32, I32, P, P, P, P, F32, P, I64, P, P, P],
-    "tg_bn_backward": [P, P, P, I32, I32, P, P, P, P, F32, P, P, P, P],
-    "tg_wav_front_stats": [P, I64, I32, I32, P, P, I32, I32, I32, P, I64, P, P, P, P, P, P, F32, F32, I32, P],
-    "tg_wav_front_apply": [P, I64, I32, I32, P, P, I32, I32, I32, P, P, P, P, F32, P, P, P],
-    "tg_wav_front_backward": [P, P, P, I64, I32, I32, P, P, I32, I32, I32, P, P, P, P, F32, P, I64, P, P, P, P, P],
-    "tg_wav_front_backward_fused": [P, I32, P, P, P, I64, I32, I32, P, P, I32, I32, I32, P, P, P, P, F32, P, I64, P, P, P, P, P],
-    "tg_speaker_fwd": [P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, I32, P, I64, I32, P, U32, P],
-    "tg_speaker_bwd": [P, P, P, P, P, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, I32, P],
-    "tg_wav_conv2_wgrad": [P, P, I32, I32, I32, P, I64, P, P, P],
-    "tg_out_mlp_compose": [P, P, P, P, I32, I32, I32, I32, P, P, P, P],
-    "tg_out_mlp_param_grads": [P, P, P, P, P, I32, I32, I32, I32, P, P, P, P, P],
-    "tg_zero": [P, I64, P],
-    "tg_permute3_batch": [P, I32, I32, P],
-    "tg_add_relu": [P, P, P, I64, P],
-    "tg_act_mask_bwd": [P, P, P, F32, P, I64, P],
-    "tg_act_mask_bwd2": [P, P, P, P, F32, P, P, I64, P],
-    "tg_embed_gather_drop": [P, P, P, I32, I32, I32, F32, P, U32, P],
-    "tg_tcn_fwd_fused": [P, P, I64, I32, P, C.POINTER(P), P, P, P, U32, F32, I32, I32, I32, I32, P, P, P, I32, I32, P, I64, P],
-    "tg_d_preconv_bwd": [P] * 26 + [I32, P, I64, I32, I32, P],
-    "tg_d_preconv_fwd": [P] * 27 + [I64, I32, I32, F32, F32, P],
-    "tg_iter_head": [P, P, P, P, P, P, I64, I32, I32, I32, I32, I32, P, P, P, P, I32, P, U32, P, P, P],
-    "tg_act_mask_bwd_drop": [P, P, F32, P, U32, I64, F32, P, I64, P],
-    "tg_act_mask_bwd2_drop": [P, P, P, F32, P, U32, I64, F32, P, P, I64, P],
-    "tg_mul": [P, P, P, I64, P],
-    "tg_axpy": [P, P, F32, I32, I64, P],
-    "tg_copy2d": [P, I64, P, I64, I32, I32, I32, P],
-    "tg_repeat_rows": [P, I64, P, I64, I32, I32, I32, P],
-    "tg_sum_rows": [P, I64, P, I64, I32, I32, I32, I32, P],
-    "tg_add_halves": [P, P, I32, I32, P],
-    "tg_sum_parts": [P, I64, I32, P, I64, P],
-    "tg_narrow8_pair": [P, P, P, P, P, I32, I32, P],
-    "tg_dup_halves": [P, P, I32, I32, P],
-    "tg_make_pre_seq": [P, P, I32, I32, I32, I32, P],
-    "tg_embed_gather": [P, P, P, I32, I32, I32, P],
-    "tg_assemble_batch": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, P, P, P, P, P],
-    "tg_embed_scatter_add": [P, P, P, I32, I32, I32, P],
-    "tg_permute3": [P, P, I32, I32, I32, I32, I32, I32, P],
-    "tg_conv_dgrad_pack": [P, P, I32, I32, I32, I32, P],
-    "tg_weight_norm_fwd": [P, P, P, I32, I32, I32, P],
-    "tg_weight_norm_fwd_batch": [I32, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), I32, I32, I32, P],
-    "tg_weight_norm_bwd": [P, P, P, P, P, I32, I32, I32, P],
-    "tg_weight_norm_bwd_batch": [I32, C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), C.POINTER(P), I32, I32, I32, P],
-    "tg_rng_advance": [P, P],
-    "tg_iter_begin": [P, P, P, P, P],
-    "tg_dropout_mask": [P, I64, F32, P, U32, P],
-    "tg_dropout_apply": [P, P, P, I64, F32, P, U32, P],
-    "tg_normal": [P, I64, P, U32, P],
-    "tg_randperm": [P, I32, P, U32, P],
-    "tg_gather_i64": [P, P, P, I32, P],
-    "tg_reparam_fwd": [P, P, P, P, I64, P],
-    "tg_reparam_bwd": [P, P, P, P, P, I64, P],
-    "tg_gan_d_loss": [P, P, I32, P, P, P, P],
-    "tg_gan_g_loss": [P, P, P, P, P, P, P, P, I32, I32, I32, F32, F32, F32, F32, I32, P, P, P, P, P, P, P],
-    "tg_d_head_fwd": [P, P, P, P, P, P, P, P, I32, I32, I32, P],
-    "tg_d_head_bwd": [P, P, P, P, P, P, P, P, P, P, I32, I32, I32, P],
-    "tg_d_head_step": [P] * 17 + [I32, I32, F32, F32, I32, I32, P],
-    "tg_l1_mean": [P, P, I64, P, P],
-    "tg_sigmoid": [P, P, I64, P],
-    "tg_sigmoid_bwd": [P, P, P, I64, P],
-    "tg_window_blend": [P, P, I32, I32, I32, I32, P],
-    "tg_window_stage": [P, P, P, P, P, P, I32, I32, I32, I32, P, P, P],
-    "tg_spec_stage": [P, P, P, P, P, I32, I32, I32, I32, P, P],
-    "tg_utterance_finish": [P, I64, I32, I32, P, I32, I32, I32, I32, P, P, P, P, I64, P],
-    "tg_stream_push": [P, I64, I32, P, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, P],
-    "tg_stream_stage": [P, P, P, P, P, I32, I32, I32, I32, I32, I32, P, P, P],
-    "tg_stream_stage_text": [P, P, P, I32, I32, I32, I64, I64, P, P, P],
-    "tg_pool_push": [P, I64, I32, I32, I32, I32, P, I32, I32, I32, P, P, P, P, I32, I32, I32, I32, P],
-    "tg_pool_stage": [P, P, P, P, P, P, I32, I32, I32, I32, I32, I32, P, P, P],
-    "tg_pool_handover": [P, P, P, P, I32, P, P, I32, I32, I32, I32, P],
-    "tg_pool_stage_text": [P, P, P, P, I32, I32, I32, I64, I64, P, P, P],
-    "tg_pool_handover_smooth": [P, P, P, P, P, P, P, I32, I32, I32, I32, P],
-    "tg_resample": [P, P, P, I32, I64, P, I32, I32, I32, P, P],
-    "tg_resample_stream": [P, I64, I32, I32, I32, I32, I32, P, I32, I32, I32, P, P, P, P, I64, I32, P],
-    "tg_resample_stream_peek": [I32, P, I32, I32, I32, P, P, P, P, I64, I32, P],
-    "tg_stream_stage_preview": [P, P, P, P, P, I32, P, P, I64, I32, I32, I32, I32, I32, I32, I32, I32, I32, I32, P, P, P],
-    "tg_preview_handover": [P, P, P, I32, P, I32, I32, I32, I32, P, P],
-    "tg_pose_metrics": [P, P, P, I32, I32, I32, P, P],
-    "tg_ae_loss": [P, P, I32, I32, I32, P, P, P],
-    "tg_counter_inc": [P, P],
-    "tg_adam_step": [P, P, P, P, I64, F32, F32, F32, F32, P, P],
-    "tg_conv2d_fwd": [P, I32, P, P, P] + [I32] * 12 + [P],
-    "tg_conv2d_dgrad": [P, P, P, I32] + [I32] * 12 + [P],
-    "tg_conv2d_wgrad_ws_bytes": [I32] * 12 + [P],
-    "tg_conv2d_wgrad": [P, P, I32, P, I32, P, I64] + [I32] * 12 + [P],
-    "tg_s2g_rows_interp": [P, P, I32, I32, I32, I32, I32, I32, P],
-    "tg_s2g_rows_interp_bwd": [P, P, I32, I32, I32, I32, I32, I32, P],
-    "tg_s2g_up_add": [P, P, P, I32, I32, I32, I32, P],
-    "tg_s2g_up_add_bwd": [P, P, I32, I32, I32, I32, I32, P],
-    "tg_s2g_diff": [P, P, I32, I32, I32, P],
-    "tg_s2g_diff_bwd": [P, P, I32, I32, I32, I32, P],
-    "tg_s2g_mse_const": [P, I64, F32, F32, P, P, P],
-    "tg_s2g_l1_grad": [P, P, P, I64, P],
-    "tg_logmel_query": [I32, I32, P],
-    "tg_logmel": [P, I64, I32, I32, I32, P, I64, P, I64, P, I32, P],
-    "tg_pose_resample": [P, I64, I32, P, I64, I32, P, I64, P],
-    "tg_clip_windows": [P, I64, I32, P, I64, I32, I32, P, I64, P, P, P, P, P],
-    "tg_clip_slices": [P, I64, I32, I32, P, I64, I32, I32, P, P],
-    "tg_motion_stats_query": [I64, P],
-    "tg_motion_stats": [P, I64, I32, P, I64, P, P],
-    "tg_h36m_normalize": [P, I64, I32, P, P],
-    "tg_h36m_samples": [P, I64, P, I64, I32, I32, I32, P, I64, P, I64, P, U32, U32, F32, F32, F32, P, P, P, P],
-    "tg_fgd_state_doubles": [I32, P],
-    "tg_fgd_reset": [P, I32, P],
-    "tg_fgd_push": [P, P, P, I32, I32, P, P, P],
-    "tg_fgd_scores": [P, I32, P, P],
-    "tg_fgd_from_stats": [P, P, P, P, I32, P, P],
-    "tg_gru_seq_supported": [I32, I32, I32, I32, P],
-    "tg_gru_seq_forward": [P] * 11 + [I32, I32, I32, I32, P],
-    "tg_gru_seq_backward": [P] * 10 + [I32, I32, I32, I32, P],
-    "tg_attn_step_supported": [I32, I32, I32, P],
-    "tg_attn_step_forward": [P, P, P, P, P, P, I64, I32, I32, I32, P],
-    "tg_attn_step_backward": [P, I64] + [P] * 9 + [I32, I32, I32, P],
-    "tg_seq2seq_decode_supported": [I32] * 10 + [P],
-    "tg_seq2seq_decode_eval": [P, P, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, F32, C.POINTER(P), P, P, P, P, P] + [I32] * 10 + [P],
-    "tg_seq2seq_encode_supported": [I32, I32, I32, I32, P],
-    "tg_seq2seq_encode_eval": [P] * 10 + [I32, I32, I32, I32, P],
-    "tg_seq2seq_loss": [P, P, I32, I32, I32, F32, F32, F32, P, P, P, P],
-    "tg_sumsq_accumulate": [P, I64, P, P, P],
-    "tg_clip_scale": [P, F32, P, P],
-    "tg_scale_by": [P, I64, P, P],
-    "tg_latent_head_supported": [I32, I32, I32, I32, I32, P],
-    "tg_latent_head_fwd": [P, I64] + [P] * 15 + [U32, P, I64] + [P] * 6 + [I32] * 5 + [F32, F32, F32, P],
-    "tg_latent_head_bwd": [P, I64, P, P, P, I64] + [P] * 23 + [I64] + [I32] * 5 + [F32, P],
-    "tg_vae_latent_fwd": [P] * 7 + [U32] + [P] * 4 + [I32, P],
-    "tg_vae_latent_bwd": [P] * 9 + [F32] + [P] * 6 + [I32, P],
-    "tg_vae_kld": [P, P, I32, I32, F32, P, P, P, P],
-}
+STRUCTS = {"tg_window": Window, "tg_gemm_nt_problem": NtProblem, "tg_gemm_tn_problem": TnProblem, "tg_ae_step_args": AeStepArgs}
+_BY_VALUE = {"int32_t": I32, "int64_t": I64, "uint32_t": U32, "float": F32}
+# C return type -> restype.  c_int32 IS c_int here, so "returns a status" (int) is told from "returns a number" (int32_t) by the spelling
+RESTYPES = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "const char *": C.c_char_p}
+_POINTEES = {"void", "char", "int", "float", "double"} | {f"{u}int{n}_t" for u in ("", "u") for n in (8, 16, 32, 64)}
 
-ABI_VERSION = 11
+
+def strip_comments(text):
+    """The header's comments hold parentheses, semicolons and text that looks like a prototype: they go first."""
+    return re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+
+# one parameter: [const] TYPE [const] {* [const]} [name] [[n]]
+_PARAM = re.compile(r"\s*(?:const\s+)?(\w+)(?:\s+const\b)?((?:\s*\*(?:\s*const\b)?)*)\s*(?:(?<=[\s*])(?!const\b)\w+)?\s*(\[[^\]]*\])?\s*")
+
+
+def _argtype(arg, decl):
+    """One parameter of `decl` -> its ctypes type; ValueError for anything but the forms the header's conventions allow."""
+    m = _PARAM.fullmatch(arg)
+    base, stars, array = m.groups() if m else ("", "", None)
+    ptr = "".join(stars.split()) + ("*" if array else "")             # `int32_t out[6]` is `int32_t* out`
+    if base not in _POINTEES and base not in STRUCTS:
+        raise ValueError(f"{decl}: unknown type in parameter `{arg}`")
+    if not ptr and base in _BY_VALUE:
+        return _BY_VALUE[base]
+    if ptr.count("*") == 1:
+        return P if base not in STRUCTS else WP if base == "tg_window" else C.POINTER(STRUCTS[base])
+    if ptr in ("*const*", "*const*const") and base not in STRUCTS:
+        return C.POINTER(P)
+    raise ValueError(f"{decl}: parameter `{arg}` is outside the plain-C convention of the header")
+
+
+def parse_header(text):
+    """Every `RET tg_name(ARGS);` of a header text -> {name: (RET as spelled, [argtypes])}, in declaration order.  Comments, preprocessor lines,
+    the extern "C" bracket and typedef struct blocks are skipped; any other statement, return type or parameter raises ValueError."""
+    text = re.sub(r"#\s*ifdef\s+__cplusplus.*?#\s*endif", " ", strip_comments(text), flags=re.S)
+    text = re.sub(r"^[ \t]*#[^\n]*", " ", text, flags=re.M)
+    text = re.sub(r"\btypedef\s+struct\b[^{;]*\{[^{}]*\}\s*\w+\s*;", " ", text)
+    out = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.*?)\b(tg_\w+) ?\((.*)\)", stmt)
+        if not m:
+            raise ValueError(f"not a tg_* prototype: `{stmt[:120]}`")
+        ret, name, args = " ".join(re.findall(r"\w+|\S", m.group(1))), m.group(2), m.group(3).strip()
+        if ret not in RESTYPES:
+            raise ValueError(f"{name}: return type `{ret}` is outside the plain-C convention of the header")
+        if name in out:
+            raise ValueError(f"{name}: declared twice")
+        if not args:
+            raise ValueError(f"{name}: empty parameter list; write (void)")
+        out[name] = (ret, [] if args == "void" else [_argtype(a, name) for a in args.split(",")])
+    return out
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            text = f.read()
+    except OSError as e:
+        raise ImportError(f"{HEADER_PATH} not readable ({e}): the binding is derived from the C header, which ships beside the package "
+                          "(<package>/../include/trimodal_hip.h)") from None
+    m = re.search(r"^#define\s+TG_ABI_VERSION\s+(\d+)\s*$", text, flags=re.M)
+    if not m:
+        raise ImportError(f"{HEADER_PATH} has no #define TG_ABI_VERSION")
+    return int(m.group(1)), parse_header(text)
+
+
+# name -> (C return type as spelled, argtypes) of every declared function, and the same with the restype: what load() sets
+ABI_VERSION, DECLARED = _read_header()
+PROTOTYPES = {n: (RESTYPES[r], a) for n, (r, a) in DECLARED.items()}
+# the process-wide getters and setters: they return int as well, but give or take a plain value (a zero argument is valid), so they are
+# not among the entries that must refuse null / zero arguments (tests/abi_fuzz.py)
+GETTERS_SETTERS = ("tg_version", "tg_set_deterministic", "tg_get_deterministic", "tg_set_tn_workgroup_cap", "tg_get_tn_workgroup_cap",
+                   "tg_set_math_mode", "tg_get_math_mode", "tg_set_nt_mover_waves")
+# name -> argtypes of the status-returning entry points (0 on success, message in tg_last_error): what call() is for
+SIGNATURES = {n: a for n, (r, a) in DECLARED.items() if r == "int" and n not in GETTERS_SETTERS}
 _lib = None
 
 
@@ -220,74 +145,10 @@ def load():
             f"{LIB_PATH} not found: the HIP extension is not built. Run `python -c 'import __graft_entry__ as g; g.build()'` "
             "(or `make -C gesture-generation-from-trimodal-context_amd/csrc`). There is no CPU fallback.")
     lib = C.CDLL(LIB_PATH)
-    lib.tg_version.restype = C.c_int
-    lib.tg_last_error.restype = C.c_char_p
-    lib.tg_gemm_tn_ws_floats.restype = C.c_int64
-    lib.tg_gemm_tn_ws_floats.argtypes = [I32, I32, I32]
-    lib.tg_gemm_nt_family.restype = C.c_int32
-    lib.tg_gemm_nt_family.argtypes = [C.POINTER(NtProblem)]
-    lib.tg_gemm_nt_ext_supported.restype = C.c_int32
-    lib.tg_gemm_nt_ext_supported.argtypes = [C.POINTER(NtProblem)]
-    lib.tg_gemm_nt_kernel_plan.restype = C.c_int32
-    lib.tg_gemm_nt_kernel_plan.argtypes = [C.POINTER(NtProblem), I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.tg_gemm_tn_kernel_plan.restype = C.c_int32
-    lib.tg_gemm_tn_kernel_plan.argtypes = [C.POINTER(TnProblem), I32]
-    lib.tg_gemm_nt_variant.restype = C.c_int32
-    lib.tg_gemm_nt_variant.argtypes = [C.POINTER(NtProblem), I32, C.POINTER(C.c_int32)]
-    lib.tg_gemm_tn_split_plan.restype = C.c_int32
-    lib.tg_gemm_tn_split_plan.argtypes = [C.POINTER(TnProblem), I32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    lib.tg_gemm_nt_split_variant.restype = C.c_int32
-    lib.tg_gemm_nt_split_variant.argtypes = [C.POINTER(NtProblem), I32, C.POINTER(C.c_int32)]
-    lib.tg_gemm_tn_split_tile.restype = C.c_int32
-    lib.tg_gemm_tn_split_tile.argtypes = [C.POINTER(TnProblem), I32, C.POINTER(C.c_int32)]
-    lib.tg_bn_fused_supported.restype = C.c_int32
-    lib.tg_bn_fused_supported.argtypes = [I32, I32, I32]
-    lib.tg_set_math_mode.restype = C.c_int
-    lib.tg_set_math_mode.argtypes = [I32]
-    lib.tg_get_math_mode.restype = C.c_int
-    lib.tg_set_deterministic.restype = C.c_int
-    lib.tg_set_deterministic.argtypes = [I32]
-    lib.tg_get_deterministic.restype = C.c_int
-    lib.tg_set_tn_workgroup_cap.restype = C.c_int
-    lib.tg_set_tn_workgroup_cap.argtypes = [I32]
-    lib.tg_get_tn_workgroup_cap.restype = C.c_int
-    lib.tg_set_nt_mover_waves.restype = C.c_int
-    lib.tg_set_nt_mover_waves.argtypes = [I32]
-    lib.tg_gru_cluster_fused_dropout.restype = C.c_int32
-    lib.tg_gru_cluster_supported.restype = C.c_int32
-    lib.tg_gru_cluster_supported.argtypes = [I32, I32]
-    lib.tg_gru_cluster_ws_bytes.restype = C.c_int64
-    lib.tg_gru_cluster_ws_bytes.argtypes = [I32, I32]
-    lib.tg_gru_vec_supported.restype = C.c_int32
-    lib.tg_gru_vec_supported.argtypes = [I32, I32]
-    lib.tg_gru_vec_ws_bytes.restype = C.c_int64
-    lib.tg_gru_vec_ws_bytes.argtypes = [I32]
-    lib.tg_gru_vec_ws_header_bytes.restype = C.c_int32
-    lib.tg_gru_vec_ws_header_bytes.argtypes = []
-    lib.tg_gru_cluster_bwd_supported.restype = C.c_int32
-    lib.tg_gru_cluster_bwd_supported.argtypes = [I32, I32]
-    lib.tg_gru_cluster_bwd_ws_bytes.restype = C.c_int64
-    lib.tg_gru_cluster_bwd_ws_bytes.argtypes = [I32, I32]
-    lib.tg_speaker_bwd_max_rows.restype = C.c_int32
-    lib.tg_bn2_supported.restype = C.c_int32
-    lib.tg_bn2_supported.argtypes = [I32, I32]
-    lib.tg_bn2_ws_doubles.restype = C.c_int64
-    lib.tg_bn2_ws_doubles.argtypes = [I32, I32, I32]
-    lib.tg_d_preconv_fwd_supported.restype = C.c_int32
-    lib.tg_d_preconv_fwd_supported.argtypes = [I32, I32]
-    lib.tg_d_preconv_ws_bytes.restype = C.c_int64
-    lib.tg_d_preconv_ws_bytes.argtypes = [I32]
-    lib.tg_ae_step_supported.restype = C.c_int32
-    lib.tg_ae_step_supported.argtypes = [I32]
-    lib.tg_ae_step_ws_bytes.restype = C.c_int64
-    lib.tg_ae_step_ws_bytes.argtypes = [I32]
-    for q, at in (("tg_wav_conv2_wgrad_ws_floats", []), ("tg_wav_front_ws_doubles", []), ("tg_wav_front_fstat_doubles", []), ("tg_wav_front_gate_words", [I32, I32])):
-        getattr(lib, q).restype = C.c_int64
-        getattr(lib, q).argtypes = at
-    for name, argtypes in SIGNATURES.items():
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(lib, name)          # AttributeError if the symbol is missing: intended
         fn.argtypes = argtypes
-        fn.restype = C.c_int
+        fn.restype = restype
     if lib.tg_version() != ABI_VERSION:
         raise RuntimeError(f"libtrimodal_hip.so ABI {lib.tg_version()} != expected {ABI_VERSION}; rebuild")
     _lib = lib

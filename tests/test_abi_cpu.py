@@ -1,5 +1,6 @@
-"""CPU-side checks of the drop-in boundary: the C-ABI library loads and exports every declared symbol, the host
-mirror has the reference's state_dict key set, and the product package never touches oracle/ or /root/reference."""
+"""CPU-side checks of the drop-in boundary: the binding's header parser maps what it knows and refuses the rest, the ctypes struct mirrors
+have the C compiler's layout, the C-ABI library loads and exports every declared symbol, the host mirror has the reference's state_dict key
+set, and the product package never touches oracle/ or /root/reference."""
 import ctypes
 import os
 import re
@@ -21,21 +22,139 @@ def _build_if_needed():
 
 
 def test_library_exports_every_declared_symbol(pkg):
-    lib_path = _build_if_needed()
-    header = open(os.path.join(ROOT, "include", "trimodal_hip.h")).read()
-    declared = set(re.findall(r"\b(tg_[a-z0-9_]+)\s*\(", header))
-    declared.discard("tg_window")
-    lib = ctypes.CDLL(lib_path)
-    missing = [n for n in sorted(declared) if not hasattr(lib, n)]
+    L = pkg._lib
+    lib = ctypes.CDLL(_build_if_needed())
+    missing = [n for n in L.PROTOTYPES if not hasattr(lib, n)]
     assert not missing, missing
-    bound = set(pkg._lib.SIGNATURES) | {"tg_version", "tg_last_error", "tg_gemm_tn_ws_floats", "tg_set_math_mode", "tg_get_math_mode", "tg_set_deterministic", "tg_get_deterministic", "tg_set_tn_workgroup_cap", "tg_get_tn_workgroup_cap",
-                                         "tg_gru_cluster_supported", "tg_gru_cluster_ws_bytes", "tg_gru_cluster_bwd_supported",
-                                         "tg_gru_cluster_bwd_ws_bytes", "tg_gemm_nt_family", "tg_gemm_nt_ext_supported", "tg_gemm_nt_kernel_plan", "tg_gemm_nt_variant", "tg_gemm_nt_split_variant", "tg_gemm_tn_kernel_plan", "tg_gemm_tn_split_plan", "tg_gemm_tn_split_tile", "tg_set_nt_mover_waves", "tg_bn_fused_supported", "tg_gru_cluster_fused_dropout", "tg_ae_step_ws_bytes", "tg_ae_step_supported",
-                                         "tg_wav_front_ws_doubles", "tg_wav_front_fstat_doubles", "tg_wav_front_gate_words", "tg_bn2_supported", "tg_bn2_ws_doubles", "tg_speaker_bwd_max_rows", "tg_wav_conv2_wgrad_ws_floats", "tg_d_preconv_fwd_supported", "tg_d_preconv_ws_bytes",
-                                         "tg_gru_vec_supported", "tg_gru_vec_ws_bytes", "tg_gru_vec_ws_header_bytes"}
-    assert declared == bound, declared ^ bound
+    other = {n for n, (ret, _) in L.DECLARED.items() if ret != "int"}             # by C spelling: ctypes.c_int32 is ctypes.c_int
+    assert len(L.PROTOTYPES) >= 194 and "tg_last_error" in other and not other & set(L.SIGNATURES)
+    assert set(L.SIGNATURES) | set(L.GETTERS_SETTERS) | other == set(L.PROTOTYPES)
+    assert all(L.PROTOTYPES[n][1] is L.SIGNATURES[n] for n in L.SIGNATURES) and not set(L.GETTERS_SETTERS) & set(L.SIGNATURES)
     lib.tg_version.restype = ctypes.c_int
-    assert lib.tg_version() == pkg._lib.ABI_VERSION
+    assert lib.tg_version() == L.ABI_VERSION
+
+
+SYNTHETIC = """
+/* int tg_fake(int32_t x); an unbalanced ( and a ; in a block comment
+ * int tg_fake2(void);  )) */
+#ifndef SYN_H
+#define SYN_H
+#include <stdint.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define TG_ABI_VERSION 3      // int tg_fake3(void); (
+typedef struct tg_window {
+    const float* ptr;         /* ; ( */
+    int64_t batch_stride, row_stride;
+} tg_window;
+typedef struct { int32_t off[44]; float* p[8]; } tg_ae_step_args;
+int tg_version(void);
+const char* tg_last_error(void);
+int64_t tg_ws_bytes(int32_t B,
+                    int32_t H);            // ) ; int tg_fake4(float y);
+int32_t tg_plan(const tg_gemm_nt_problem* problems, int32_t n, int32_t out[6], int32_t* tile_m);
+int tg_many(const tg_window* A, const float* x, int64_t ldx, uint32_t site, float slope,
+            const float* const* v, float* const* w, const void* const* params,
+            const uint64_t* s, double* ws, const tg_gemm_tn_problem* q, tg_ae_step_args* args,
+            void* stream);
+int tg_unnamed(int32_t, const float*, float *const *);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_parser_maps_a_synthetic_header_exactly(pkg):
+    L = pkg._lib
+    P, I32, I64, F32, U32, PP = L.P, L.I32, L.I64, L.F32, L.U32, ctypes.POINTER(L.P)
+    got = L.parse_header(SYNTHETIC)
+    assert got == {
+        "tg_version": ("int", []),
+        "tg_last_error": ("const char *", []),
+        "tg_ws_bytes": ("int64_t", [I32, I32]),
+        "tg_plan": ("int32_t", [ctypes.POINTER(L.NtProblem), I32, P, P]),
+        "tg_many": ("int", [L.WP, P, I64, U32, F32, PP, PP, PP, P, P, ctypes.POINTER(L.TnProblem), ctypes.POINTER(L.AeStepArgs), P]),
+        "tg_unnamed": ("int", [I32, P, PP]),
+    }
+    assert list(got) == ["tg_version", "tg_last_error", "tg_ws_bytes", "tg_plan", "tg_many", "tg_unnamed"]       # declaration order
+    assert [L.RESTYPES[got[n][0]] for n in got] == [ctypes.c_int, ctypes.c_char_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int, ctypes.c_int]
+    assert L.I32 is not L.I64 and L.F32 is not L.U32 and L.P is not PP                      # the equality above tells the types apart
+
+
+@pytest.mark.parametrize("decl", [
+    "int tg_bad(tg_window w);",                       # a struct by value
+    "int tg_bad(int32_t n, void (*cb)(int32_t));",    # a function pointer
+    "int tg_bad(const char* fmt, ...);",
+    "int tg_bad(double x);",
+    "int tg_bad(int n);",                             # sizes are int32_t / int64_t
+    "int tg_bad(size_t n);",                          # an unknown type name
+    "int tg_bad(unsigned int n);",
+    "int tg_bad(tg_thing* t);",
+    "int tg_bad(float** v);",                         # only T* const* is a pointer table
+    "int tg_bad(const tg_window* const* w);",
+    "int tg_bad(float* v[4]);",
+    "int tg_bad();",
+    "void tg_bad(int32_t n);",
+    "float tg_bad(void);",
+    "tg_window tg_bad(void);",
+    "float* tg_bad(void);",
+    "static int tg_bad(void);",
+    "int tg_bad(void); int tg_bad(int32_t n);",       # declared twice
+])
+def test_parser_refuses_what_it_does_not_know_and_names_the_declaration(pkg, decl):
+    with pytest.raises(ValueError, match="tg_bad"):
+        pkg._lib.parse_header("int tg_ok(int32_t n);\n" + decl + "\nint tg_after(void);\n")
+
+
+@pytest.mark.parametrize("text", ["int helper(int32_t n);", "struct tg_s { int32_t a; };", "typedef int32_t tg_i;", "extern int tg_flag;"])
+def test_parser_refuses_statements_that_are_no_tg_prototype(pkg, text):
+    with pytest.raises(ValueError, match="not a tg_\\* prototype"):
+        pkg._lib.parse_header("int tg_ok(int32_t n);\n" + text + "\n")
+
+
+def test_missing_header_fails_at_import_with_a_plain_message(pkg, monkeypatch):
+    monkeypatch.setattr(pkg._lib, "HEADER_PATH", "/nonexistent/include/trimodal_hip.h")
+    with pytest.raises(ImportError, match="derived from the C header"):
+        pkg._lib._read_header()
+
+
+def _struct_bodies(L):
+    """name -> the declarators of every typedef struct of the header, e.g. `int32_t M, N, out_kw, reserved;` gives four."""
+    text = L.strip_comments(open(os.path.join(ROOT, "include", "trimodal_hip.h")).read())
+    return {m.group(2): [d for stmt in m.group(1).split(";") if stmt.strip() for d in stmt.split(",")]
+            for m in re.finditer(r"typedef\s+struct\s*\w*\s*\{([^{}]*)\}\s*(\w+)\s*;", text)}
+
+
+def test_struct_mirrors_have_the_layout_the_c_compiler_gives_the_header(pkg, tmp_path):
+    """sizeof, and offsetof / sizeof of every field the ctypes classes name, from a host program compiled against the real header; the field
+    counts against the declarators of the struct bodies, so a field added to the header alone fails even where it lands in tail padding."""
+    import shutil
+    import subprocess
+    cc = shutil.which("cc") or shutil.which("gcc")
+    if cc is None:
+        pytest.skip("no host C compiler")
+    L = pkg._lib
+    bodies = _struct_bodies(L)
+    assert set(bodies) == set(L.STRUCTS) and len(bodies) == 4
+    lines = ['#include <stddef.h>', '#include <stdio.h>', '#include "trimodal_hip.h"', 'int main(void) {']
+    for cname, cls in L.STRUCTS.items():
+        lines.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'    printf("{cname}.{f} %zu %zu\\n", offsetof({cname}, {f}), sizeof((({cname}*)0)->{f}));' for f, _ in cls._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines + ["    return 0;", "}", ""]))
+    exe = str(tmp_path / "layout")
+    r = subprocess.run([cc, "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src), "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]                          # a ctypes field the C struct does not have stops here
+    c = {k: tuple(int(x) for x in v) for k, *v in (ln.split() for ln in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.splitlines())}
+    for cname, cls in L.STRUCTS.items():
+        assert c[cname] == (ctypes.sizeof(cls),), (cname, c[cname], ctypes.sizeof(cls))
+        assert len(cls._fields_) == len(bodies[cname]), (cname, len(cls._fields_), len(bodies[cname]))
+        for f, _ in cls._fields_:
+            d = getattr(cls, f)
+            assert c[f"{cname}.{f}"] == (d.offset, d.size), (cname, f, c[f"{cname}.{f}"], (d.offset, d.size))
+    assert [c[n][0] for n in L.STRUCTS] == [56, 288, 144, 488]
 
 
 def test_argument_checks_fail_loudly_without_gpu(pkg):

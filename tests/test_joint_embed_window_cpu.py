@@ -4,7 +4,6 @@ PoseDecoderGRU.forward_constant, synthesize.JointEmbedWindowDecoder, the window_
 GPU call."""
 import inspect
 import os
-import re
 from types import SimpleNamespace
 
 import pytest
@@ -16,8 +15,6 @@ from conftest import ROOT
 def test_header_and_library_declare_the_constant_input_entries(pkg):
     header = open(os.path.join(ROOT, "include", "trimodal_hip.h")).read()
     for name, nargs in (("tg_gru_vec_const_supported", 4), ("tg_gru_forward_vec_const", 14)):
-        m = re.search(r"\bint " + name + r"\s*\(([^;]*)\);", header)
-        assert m and len(m.group(1).split(",")) == nargs, name
         assert len(pkg._lib.SIGNATURES[name]) == nargs
     assert "MAY SHARE" in header and "ONE DIRECTION COUNT" in header            # the workspace rule and its extension are documented
     assert pkg._lib.ABI_VERSION == 11

@@ -2,7 +2,6 @@
 refusal StreamPool keeps for this model, the per-slot, per-window max_words bookkeeping against a brute-force count, the numpy restatement of
 the text staging against the one-clock host model, and the entries' envelope checks (argument validation precedes any launch)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -13,7 +12,6 @@ import seq2seq_stream_ref as SR
 import stream_ref as R
 import test_stream_pool_cpu as SP
 import utterance_ref as U
-from conftest import ROOT
 
 
 @pytest.fixture(scope="module")
@@ -158,8 +156,7 @@ def test_the_compaction_gives_the_one_clock_host_model_and_seq2seq_window_text(s
 
 def test_entries_are_declared_and_refuse_calls_outside_their_envelope(pkg):
     lib = pkg._lib.load()
-    header = open(os.path.join(ROOT, "include", "trimodal_hip.h")).read()
-    assert all(f"int {e}(" in header for e in ("tg_pool_stage_text", "tg_pool_handover_smooth")) and "#define TG_ABI_VERSION 11" in header
+    assert all(e in pkg._lib.SIGNATURES for e in ("tg_pool_stage_text", "tg_pool_handover_smooth")) and pkg._lib.ABI_VERSION == 11
     buf = (C.c_double * 64)()
     p = C.cast(buf, C.c_void_p)
     for B, W, Te in ((5, 16, 34), (0, 16, 34), (1, 0, 34), (1, 1025, 34), (1, 16, 1), (1, 16, 129)):

@@ -3,7 +3,6 @@ window when it runs equals the offline smoothing bit for bit, the host model of 
 seq2seq_window_text, and the new entries refuse calls outside their envelopes before any launch."""
 import ctypes as C
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -11,7 +10,6 @@ import pytest
 import seq2seq_stream_ref as SR
 import stream_ref as R
 import utterance_ref as U
-from conftest import ROOT
 
 
 @pytest.fixture(scope="module")
@@ -119,6 +117,5 @@ def test_entries_refuse_calls_outside_their_envelope(pkg):
         assert lib.tg_seq2seq_encode_supported(*dims, C.cast(C.byref(ok), C.c_void_p)) == 0 and ok.value == want, dims
     assert lib.tg_seq2seq_encode_supported(0, 5, 200, 2, C.cast(C.byref(ok), C.c_void_p)) != 0
     assert pkg.ops.seq2seq_encode_supported(3, 34, 200, 2) and not pkg.ops.seq2seq_encode_supported(3, 200, 200, 2)
-    header = open(os.path.join(ROOT, "include", "trimodal_hip.h")).read()
-    assert all(f"int {e}(" in header for e in ("tg_stream_stage_text", "tg_seq2seq_encode_supported", "tg_seq2seq_encode_eval"))
-    assert "#define TG_ABI_VERSION 11" in header
+    assert all(e in pkg._lib.SIGNATURES for e in ("tg_stream_stage_text", "tg_seq2seq_encode_supported", "tg_seq2seq_encode_eval"))
+    assert pkg._lib.ABI_VERSION == 11

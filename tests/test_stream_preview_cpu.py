@@ -1,14 +1,11 @@
 """Stream preview, host side (no GPU): the integers preview() shares with close() against a brute-force replay of close()'s flow over a grid
 of (pushed, next_window) states -- resampled ones at 44.1 and 48 kHz included --, the refusals, and the C ABI's new entries."""
 import argparse
-import os
 
 import pytest
 
 import stream_ref as R
 import utterance_ref as U
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -89,10 +86,9 @@ def test_refusals(syn):
 
 
 def test_the_abi_has_the_new_entries_and_they_refuse_before_any_launch(pkg):
-    header = open(os.path.join(ROOT, "include", "trimodal_hip.h")).read()
     names = ("tg_preview_handover", "tg_stream_stage_preview", "tg_resample_stream_peek")
-    assert all(f"int {e}(" in header for e in names) and all(e in pkg._lib.SIGNATURES for e in names)
-    assert "#define TG_ABI_VERSION 11" in header
+    assert all(e in pkg._lib.SIGNATURES for e in names)
+    assert pkg._lib.ABI_VERSION == 11
     lib = pkg._lib.load()
     p = 16                                                          # a non-null pointer that is never dereferenced: every call below is refused
     for B, T, D, n in ((5, 34, 27, 4), (0, 34, 27, 4), (3, 34, 65, 4), (3, 34, 27, 9), (3, 4, 27, 4), (3, 1025, 27, 4)):
