@@ -48,28 +48,9 @@ __global__ __launch_bounds__(256) void pool_handover_kernel(const float* __restr
     const int b = blockIdx.x;
     if (active[b] == 0) return;                                       // (the whole workgroup)
     const int w = win[b];
-    const float* __restrict__ r = res + (long)b * T * D;
-    float* o = out + (long)b * T * D;
-    float* tl = tail + (long)b * n * D;
-    const int nD = n * D;
-    for (int i = threadIdx.x; i < T * D; i += 256) {
-        float v = r[i];
-        if (w > 0 && i < nD) v = blend_head(tl[i], v, i / D, n);      // tg_window_blend (losses.hip), with *p = v
-        o[i] = v;
-    }
-    __syncthreads();                                                  // the old tail has been read, the window is whole
-    const float* last = o + (long)(T - n) * D;
-    for (int i = threadIdx.x; i < nD; i += 256) tl[i] = last[i];
-    if (seed_bit) {
-        float* __restrict__ pre = seed + (long)b * T * (D + 1);
-        for (int i = threadIdx.x; i < T * (D + 1); i += 256) {        // tg_make_pre_seq on a window whose first n frames are `last`
-            const int c = i % (D + 1), t = i / (D + 1);
-            pre[i] = t < n ? (c < D ? last[t * D + c] : 1.f) : 0.f;
-        }
-    } else {
-        float* __restrict__ pre = seed + (long)b * nD;
-        for (int i = threadIdx.x; i < nD; i += 256) pre[i] = last[i];
-    }
+    // (window_rows.hpp: the row body, shared with the synthesis queue's hand-over)
+    handover_row(res + (long)b * T * D, out + (long)b * T * D, tail + (long)b * n * D, seed + (long)b * (seed_bit ? T * (D + 1) : n * D), seed_bit, w > 0,
+                 T, D, n);
     if (threadIdx.x == 0) win[b] = w + 1;                             // every thread read w before the barrier above
 }
 

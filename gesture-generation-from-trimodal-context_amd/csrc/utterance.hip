@@ -36,31 +36,9 @@ __global__ __launch_bounds__(256) void window_stage_kernel(const float* __restri
     if (out_text && blockIdx.y == 0)
         for (int t = threadIdx.x; t < text_w; t += 256) out_text[(long)b * text_w + t] = plan_text[g * text_stride + t];
     if (!out_audio) return;
-    // the slice [a0, a0 + nv) of the utterance, clamped to its samples (the plan is the host's; the clamp keeps a wrong one inside the buffer)
-    const long len = audio_off[b + 1] - audio_off[b];
-    long a0 = plan_win[g * UT_PLAN_COLS + 0], nv = plan_win[g * UT_PLAN_COLS + 1];
-    a0 = a0 < 0 ? 0 : (a0 > len ? len : a0);
-    nv = nv < 0 ? 0 : (nv > len - a0 ? len - a0 : nv);
-    if (nv > L) nv = L;
-    const float* __restrict__ src = audio + audio_off[b] + a0;
-    float* __restrict__ dst = out_audio + (long)b * L;
-    // head: the elements before dst's first 16-byte boundary; body: 16-byte stores, 16-byte loads where src is aligned with dst and the four
-    // samples are all valid; tail: what is left of the row
-    const int head = min((int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(dst) & 15u)) & 15u) >> 2), L);
-    if (blockIdx.y == 0 && (int)threadIdx.x < head) dst[threadIdx.x] = (long)threadIdx.x < nv ? src[threadIdx.x] : 0.f;
-    const int i = head + 4 * (int)(blockIdx.y * 256 + threadIdx.x);
-    if (i + 3 < L) {
-        f32x4 v;
-        if (i + 3 < nv && (reinterpret_cast<uintptr_t>(src + i) & 15u) == 0) {
-            v = *reinterpret_cast<const f32x4*>(src + i);
-        } else {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = i + q < nv ? src[i + q] : 0.f;
-        }
-        *reinterpret_cast<f32x4*>(dst + i) = v;
-    } else {
-        for (int q = i; q < L; ++q) dst[q] = q < nv ? src[q] : 0.f;
-    }
+    // (window_rows.hpp: the row body, shared with the synthesis queue's staging)
+    stage_audio_row(audio + audio_off[b], audio_off[b + 1] - audio_off[b], plan_win[g * UT_PLAN_COLS + 0], plan_win[g * UT_PLAN_COLS + 1],
+                    out_audio + (long)b * L, L);
 }
 
 // E: the spectrogram's element as an integer of its width (fp16 -- the reference's cast -- or fp32): a copy moves bits

@@ -2172,6 +2172,94 @@ def pool_handover_smooth(res, out, tail, seed, win, active, proj):
     call("tg_pool_handover_smooth", _p(res), _p(out), _p(tail), _p(seed), _p(win), _p(active), _p(proj), B, T, D, n_pre, _stream())
 
 
+# ------------------------------------------------------------------------------------------------- synthesis queue (csrc/queue.hip)
+def _queue_check(q, plan):
+    """q: the device side of a queued synthesis call (synthesize._queue_state builds and validates it): sched (rounds, R, 2) int32, rnd (R,)
+    int32, and per utterance of the plan vids (N,) int64 / draws (G, 16 | 32) fp32 / seeds (N, n_pre, D) fp32 / seed_on (N,) int32, each or None."""
+    rounds, R, N = q["rounds"], q["R"], q["N"]
+    if plan["B"] != N:
+        raise ValueError(f"the queue was made for {N} utterance(s), the plan holds {plan['B']}")
+    _dev_int(q["sched"], torch.int32, rounds * R * 2, "sched"); _dev_int(q["rnd"], torch.int32, R, "rnd")
+    _dev_int(plan["win_off"], torch.int32, N + 1, "win_off"); _dev_int(plan["win"], torch.int64, 4 * plan["G"], "plan_win")
+    return rounds, R, N
+
+
+def _seed_layout(seed, R, T, D, n_pre):
+    if tuple(seed.shape) == (R, T, D + 1):
+        return 0
+    if tuple(seed.shape) == (R, n_pre, D):
+        return 1
+    raise ValueError(f"seed is {tuple(seed.shape)}: expected {(R, T, D + 1)} (pre_seq) or {(R, n_pre, D)} (pre)")
+
+
+def queue_stage(plan, q, T, D, n_pre, *, text_out=None, audio_out=None, len_out=None, vid_out=None, draw_out=None, seed_out=None):
+    """window_stage with the indirection row -> utterance: row b, whose entry sched[rnd[b]][b] is (u, i), gets window i of utterance u --
+    audio_out (R, L) fp32, text_out (R, W) int64 (with len_out (R,) int64: the Seq2Seq list, zeros behind, and its length), vid_out (R,) int64 =
+    q['vids'][u], draw_out (R, w) = q['draws'][win_off[u] + i], and on i == 0 seed_out ((R, T, D + 1) or (R, n_pre, D)) = the utterance's seed
+    (q['seeds'], q['seed_on']; none: zeros).  A row whose entry is idle keeps every bit of every buffer."""
+    rounds, R, N = _queue_check(q, plan)
+    G, L, W, dw, layout = plan["G"], 0, 0, 0, 1
+    if audio_out is not None:
+        _flat(audio_out, "audio_out"); _f32(plan["audio"], "audio"); _dev_int(plan["audio_off"], torch.int64, N + 1, "audio_off")
+        if audio_out.dim() != 2 or audio_out.shape[0] != R or plan["audio"].numel() < plan["audio_total"]:
+            raise ValueError(f"audio_out is {tuple(audio_out.shape)}, expected ({R}, L)")
+        L = audio_out.shape[1]
+    if text_out is not None:
+        _i64(text_out, "text_out")
+        if text_out.dim() != 2 or text_out.shape[0] != R or not text_out.is_contiguous():
+            raise ValueError(f"text_out is {tuple(text_out.shape)}, expected ({R}, W), contiguous")
+        _dev_int(plan["text"], torch.int64, G * plan["text_stride"], "plan_text")
+        W = text_out.shape[1]
+    if len_out is not None:
+        _dev_int(len_out, torch.int64, R, "len_out")
+    if (vid_out is None) != (q["vids"] is None) or (draw_out is None) != (q["draws"] is None):
+        raise ValueError("queue_stage: speaker ids / replayed draws and the rows' buffers for them come together")
+    if vid_out is not None:
+        _dev_int(vid_out, torch.int64, R, "vid_out"); _dev_int(q["vids"], torch.int64, N, "vids")
+    if draw_out is not None:
+        _flat(draw_out, "draw_out"); _flat(q["draws"], "draws")
+        dw = draw_out.shape[-1]
+        if tuple(draw_out.shape) != (R, dw) or tuple(q["draws"].shape) != (G, dw):
+            raise ValueError(f"draw_out is {tuple(draw_out.shape)} and draws {tuple(q['draws'].shape)}: expected ({R}, w) and ({G}, w)")
+    if seed_out is not None:
+        _flat(seed_out, "seed_out")
+        layout = _seed_layout(seed_out, R, T, D, n_pre)
+        if q["seeds"] is not None:
+            _flat(q["seeds"], "seeds")
+            if tuple(q["seeds"].shape) != (N, n_pre, D):
+                raise ValueError(f"seeds is {tuple(q['seeds'].shape)}, expected {(N, n_pre, D)}")
+        if q["seed_on"] is not None:
+            _dev_int(q["seed_on"], torch.int32, N, "seed_on")
+    elif q["seeds"] is not None:
+        raise ValueError("queue_stage: seeds without the rows' seed buffer")
+    call("tg_queue_stage", _p(q["sched"]), _p(q["rnd"]), rounds, R, N, _p(plan["audio"] if audio_out is not None else None),
+         _p(plan["audio_off"] if audio_out is not None else None), _p(plan["win_off"]), _p(plan["win"]),
+         _p(plan["text"] if text_out is not None else None), plan["text_stride"], L, W, _p(audio_out), _p(text_out), _p(len_out), _p(q["vids"]),
+         _p(vid_out), _p(q["draws"]), _p(draw_out), dw, _p(q["seeds"]), _p(q["seed_on"] if q["seeds"] is not None else None), _p(seed_out), layout,
+         T, D, n_pre, _stream())
+
+
+def queue_handover(res, total, tail, seed, plan, q):
+    """pool_handover into the stacked result: row b, whose entry sched[rnd[b]][b] is (u, i), writes total[u, i stride : i stride + T] = res[b]
+    (R, T, D), cross-faded with tail[b] (R, n_pre, D) where i > 0 (window_blend's arithmetic), tail[b] = its last n_pre frames, seed[b] = the next
+    window's seed ((R, T, D + 1): make_pre_seq's layout, (R, n_pre, D): the frames themselves); every row's rnd[b] += 1.  total: (N, F, D) with
+    room for every window of every utterance.  Nothing else of an idle row is written."""
+    rounds, R, N = _queue_check(q, plan)
+    for t, name in ((res, "res"), (total, "total"), (tail, "tail"), (seed, "seed")):
+        _flat(t, name)
+        if t.dim() != 3:
+            raise ValueError(f"{name}: expected three dimensions, got {tuple(t.shape)}")
+    _, T, D = res.shape
+    n_pre = tail.shape[1]
+    if res.shape[0] != R or tuple(tail.shape) != (R, n_pre, D) or total.shape[0] != N or total.shape[2] != D:
+        raise ValueError(f"res {tuple(res.shape)} / tail {tuple(tail.shape)} / total {tuple(total.shape)} do not belong to {R} rows and {N} utterances")
+    F = total.shape[1]
+    if F < q["max_win"] * (T - n_pre) + n_pre:
+        raise ValueError(f"total holds {F} frames per utterance, the longest needs {q['max_win'] * (T - n_pre) + n_pre}")
+    call("tg_queue_handover", _p(res), _p(total), F, _p(tail), _p(seed), _seed_layout(seed, R, T, D, n_pre), _p(q["sched"]), _p(q["rnd"]), rounds,
+         _p(plan["win_off"]), R, N, T, D, n_pre, _stream())
+
+
 # ------------------------------------------------------------------------------------------------- resampling to 16 kHz (csrc/resample.hip)
 def _taps_check(taps, L, M, K):
     _flat(taps, "taps")

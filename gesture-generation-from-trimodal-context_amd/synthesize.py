@@ -51,6 +51,10 @@ comes out of the word ring per row, the decoder's forward goes into a result buf
 preview() (GestureStream, StreamPool): what close() would return now -- the window still filling, zero-padded -- computed
 beside the stream by csrc/stream_preview.hip and the decoders' preview chain; the stream, its device state and its RNG counter keep every bit.
 
+generate_gestures_queue is the offline counterpart of the pools: N utterances on the R rows of one window decoder, a row
+taking the next utterance the moment its own ends on an integer schedule computed once (queue_schedule); per-row round counters on the device,
+csrc/queue.hip's two row-local kernels around one captured graph of the forward (window_queued), the same launches every round.
+
 Structure: the three window decoders are subclasses of _WindowDecoderBase (buffers, the eager / capture-once / replay skeleton, the pooled
 window, check_kept; _capture is the one place a graph is captured); the streams and the pool are subclasses of _StreamCore (constructor checks,
 a row's word records, the closing window); the five offline loops stay separate and share _seed_rows, _host_window_batch and _rows_result.
@@ -294,6 +298,7 @@ class _WindowDecoderBase:
         self.frozen = L.FrozenWeights()
         self.win = self.active = self.graph_pooled = None              # window_pooled's state: made on its first use
         self.pv = self.graph_preview = None                            # preview()'s buffers and graph: made on its first use
+        self.rnd = self.res = self.graph_queue = None                  # window_queued's state: made on its first use
 
     def check_kept(self, model, batch, T, n_pre, replay_draws=False):
         """Whether this decoder was built for `model` (the same object), `batch` rows, these window sizes and this replay_draws."""
@@ -367,6 +372,45 @@ class _WindowDecoderBase:
             else:
                 self._forward_pooled()
         return self.out
+
+    # -------------------------------------------------------------------------------------------------------------- queue
+    def queue_buffers(self):
+        """(rnd, res): the static device buffers window_queued works on -- every row's round counter (B,) int32 and the forward's result
+        (B, T, D), which the hand-over reads (the Seq2Seq decoder shares it with its pooled window)."""
+        if self.rnd is None:
+            self.rnd = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+        if self.res is None:
+            self.res = torch.zeros(self.B, self.T, self.D, device=self.dev)
+        return self.rnd, self.res
+
+    def _forward_queue(self):
+        """The forward alone, into self.res: nothing of a row's output, tail or seed is written here."""
+        res = self._model_forward()
+        ops.copy2d(res.view(self.B * self.T, self.D), self.res.view(self.B * self.T, self.D))
+
+    def _queue_stage(self, q):
+        ops.queue_stage(q.plan, q.dev, self.T, self.D, self.n_pre, text_out=self.text, audio_out=self.audio, len_out=getattr(self, "len", None),
+                        vid_out=getattr(self, "vid", None) if q.dev["vids"] is not None else None,
+                        draw_out=self.draw if q.dev["draws"] is not None else None, seed_out=self.pre)
+
+    def window_queued(self, q):
+        """One round of a synthesis queue (generate_gestures_queue; q: its _QueueState): three calls, the same every round.  ops.queue_stage
+        (eager: the plan's pointers belong to the call) gives row b, whose entry of its own round self.rnd[b] is (utterance u, window i), u's
+        window i in self.text / self.audio (/ self.vid / self.draw / self.len) and, on i == 0, u's seed; the forward runs on all B rows into
+        self.res -- from the first call on ONE captured graph, self.graph_queue, with one eager pass in front of the capture (graph,
+        graph_pooled and graph_preview are not touched) --; ops.queue_handover (eager) writes the window into q.total[u], cross-faded with the
+        row's tail where i > 0, hands tail and seed over and advances every row's counter.  An idle row's buffers keep every bit."""
+        self.queue_buffers()
+        self._queue_stage(q)
+        with torch.no_grad(), self.frozen:
+            if self.use_graph:
+                if self.graph_queue is None:
+                    self._forward_queue()                        # the eager pass a capture needs in front of it (see window_pooled); it writes self.res only
+                    self.graph_queue = _capture(self._forward_queue, (self.res,))
+                self.graph_queue.replay()
+            else:
+                self._forward_queue()
+        ops.queue_handover(self.res, q.total, self.tail, self.pre, q.plan, q.dev)
 
     # -------------------------------------------------------------------------------------------------------------- preview (DESIGN.md section 32)
     _seed_names = ("pre",)                                          # the attributes _model_forward reads the seed from
@@ -605,10 +649,14 @@ class Seq2SeqWindowDecoder(_WindowDecoderBase):
         return super().check_kept(model, batch, T, n_pre) and self.max_words == max_words and self.row_local == bool(row_local_encoder)
 
     def pool_buffers(self):
-        if self.res is None:
+        if self.res is None:                                           # (window_queued may have made it first: queue_buffers)
             self.res = torch.zeros(self.B, self.T, self.D, device=self.dev)
+        if self.proj is None:
             self.proj = _projection_device(self.n_pre, self.dev)
         return super().pool_buffers()
+
+    def _forward_queue(self):
+        self._model_forward(self.res)                                  # (the one-launch decoder loop writes its output buffer itself)
 
     def _forward_pooled(self):
         self._model_forward(self.res)
@@ -1027,6 +1075,184 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
     if ub is not None:
         return _device_result(ub, total, *dopts)
     return _rows_result(total, n_win, stride, args.n_pre_poses)
+
+
+# ------------------------------------------------------------------------------------------------------------------ queue
+QUEUE_MAX_ROWS = 128                                                  # csrc/queue.hip's QU_MAX_ROWS
+QUEUE_ORDERS = ("longest_first", "given")
+
+
+def queue_schedule(n_win, rows, order="longest_first"):
+    """N utterances of n_win[u] windows on `rows` decoder rows, as integers: list scheduling.  The utterances are taken in `order` --
+    'longest_first': by descending window count, ties by index; 'given': by index -- and each goes to the row that frees earliest, ties to the
+    lowest row, where its windows occupy CONSECUTIVE rounds (its tail and seed live in that row).  Returns (rounds, table, row, first): the
+    round count (the fullest row's load), table (rounds, rows, 2) int32 = (utterance, window) of every row in every round, (-1, -1) where
+    the row idles, and per utterance its row and its first round ((N,) int32 each).  rows may exceed N: the surplus rows idle throughout.
+    rounds <= sum(n_win) / rows + (1 - 1 / rows) max(n_win) (Graham's bound for list scheduling, any order)."""
+    n = [int(v) for v in n_win]
+    if not n or min(n) < 1 or any(v != w for v, w in zip(n, n_win)):
+        raise ValueError(f"queue_schedule: n_win must be a non-empty list of window counts >= 1, got {list(n_win)!r}")
+    if isinstance(rows, bool) or int(rows) != rows or rows < 1:
+        raise ValueError(f"queue_schedule: rows must be an integer >= 1, got {rows!r}")
+    if order not in QUEUE_ORDERS:
+        raise ValueError(f"queue_schedule: order must be one of {QUEUE_ORDERS}, got {order!r}")
+    rows = int(rows)
+    taken = sorted(range(len(n)), key=lambda u: (-n[u], u)) if order == "longest_first" else range(len(n))
+    free = [0] * rows                                                 # every row's next free round
+    row, first = np.zeros(len(n), dtype=np.int32), np.zeros(len(n), dtype=np.int32)
+    for u in taken:
+        b = min(range(rows), key=lambda r: (free[r], r))
+        row[u], first[u] = b, free[b]
+        free[b] += n[u]
+    rounds = max(free)
+    table = np.full((rounds, rows, 2), -1, dtype=np.int32)
+    for u, k in enumerate(n):
+        table[first[u]:first[u] + k, row[u], 0] = u
+        table[first[u]:first[u] + k, row[u], 1] = np.arange(k)
+    return rounds, table, row, first
+
+
+def _check_schedule(table, n_win, rows):
+    """What the queue kernels rely on, checked on the host before the upload: every window of every utterance exactly once, an utterance's
+    windows in ONE row in consecutive rounds in order, so that no two rows ever write the same utterance."""
+    rounds = table.shape[0]
+    if table.shape != (rounds, rows, 2) or table.dtype != np.int32:
+        raise ValueError(f"queue schedule: table is {table.shape} {table.dtype}, expected ({rounds}, {rows}, 2) int32")
+    last = {}                                                         # utterance -> (row, round, window) of its latest entry
+    for r in range(rounds):
+        for b in range(rows):
+            u, i = int(table[r, b, 0]), int(table[r, b, 1])
+            if (u, i) == (-1, -1):
+                continue
+            if not (0 <= u < len(n_win) and 0 <= i < n_win[u] and (last.get(u) == (b, r - 1, i - 1) if i > 0 else u not in last)):
+                raise ValueError(f"queue schedule: entry ({u}, {i}) of round {r}, row {b} does not continue its utterance's run of consecutive "
+                                 "rounds in one row")
+            last[u] = (b, r, i)
+    if any(last.get(u, (0, 0, -1))[2] != n_win[u] - 1 for u in range(len(n_win))):
+        raise ValueError("queue schedule: not every window of every utterance is scheduled")
+
+
+class _QueueState:
+    """What a queued synthesis call keeps on the device, uploaded once: the utterance batch's plan (plan), the stacked result total
+    (N, frames, D), and dev -- the schedule, the rows' round counters (the decoder's rnd) and, per utterance, speaker ids, replayed draws, seeds."""
+
+    def __init__(self, ub, dec, rounds, table, total, vids, draws, seeds, seed_on):
+        d = dec.dev
+        up = lambda a, dt: None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(d)
+        self.plan, self.total, self.rounds = ub.plan, total, rounds
+        self.dev = dict(rounds=rounds, R=dec.B, N=ub.B, max_win=ub.max_win, sched=up(table, np.int32), rnd=dec.queue_buffers()[0],
+                        vids=up(vids, np.int64), draws=up(draws, np.float32), seeds=up(seeds, np.float32), seed_on=up(seed_on, np.int32))
+
+
+def generate_gestures_queue(args, pose_decoder, lang_model, audios, words_list, rows, vids=None, seed_seqs=None, audio_sr=16000, input_sr=None,
+                            order="longest_first", window_decoder=None, graph=True, _draws=None, eps_list=None, max_words=32, fade_out=False,
+                            joints=False, return_device=False):
+    """N utterances on the `rows` rows of ONE window decoder: a row takes the next utterance the moment its own ends, on a schedule computed
+    once as integers (queue_schedule(order=...)); generate_gestures_batch(on_device=True)'s return value, in input order.  Device only: one
+    UtteranceBatch of all N utterances holds the audio and the plans (input_sr: as there), the schedule, speaker ids, seeds and draws go up
+    once, and a round is three launches-or-replays that are the same every round (window_queued: no host arithmetic, no upload, no read-back);
+    rounds = the fullest row's load, against lock-step's max(n_win) per group of `rows`.  Then UtteranceBatch.finish as in lock-step (seq2seq's
+    smoothing, fade_out, joints, return_device).
+    args.model: 'multimodal_context' -- 1 <= rows <= 128, the caller picks the row count and with it the recurrence kernels every window
+    runs on --; 'joint_embedding' and 'seq2seq' -- rows <= 4, their window decoders' limit (N is not limited); 'speech2gesture' is refused.
+    vids, seed_seqs: one entry per utterance; a seed_seqs entry may be None (that utterance starts from zeros, without the constraint bit).
+    window_decoder: a kept WindowDecoder / JointEmbedWindowDecoder / Seq2SeqWindowDecoder built for this model and `rows` rows (and, with
+    replayed draws, replay_draws=True; seq2seq: this max_words), whose graph_queue is captured once and replayed by later calls; None builds
+    one for this call.  max_words (seq2seq): the longest window list is max_words + 2 ids.
+    Draws: with the device RNG a row draws per ROUND, so a window's draw depends on the schedule: the result is as valid as lock-step's and
+    not equal to it.  _draws (multimodal_context) / eps_list (joint_embedding): one (n_win[u], 16 | 32) array per utterance, window i of
+    utterance u replays row i -- then utterance u, scheduled on row b, is bit-equal to row b of generate_gestures_batch(on_device=True) on
+    `rows` utterances with u in row b and the same draws, wherever a row's eval forward does not depend on its neighbours (pinned for up to
+    four rows; DESIGN.md section 33 for more).  Every refusal is a ValueError raised on the host before anything touches the GPU."""
+    who = "generate_gestures_queue"
+    model = getattr(args, "model", "multimodal_context")
+    if model == "speech2gesture":
+        raise ValueError(f"{who}: the speech2gesture model has no window decoder -- its generator runs on fresh tensors, and the rows of a window are "
+                         "grouped by the width of their spectrogram slice, so the launches differ from round to round; use generate_gestures_batch")
+    if model not in ("multimodal_context", "joint_embedding", "seq2seq"):
+        raise ValueError(f"{who}: args.model is {model!r}")
+    kind = {"multimodal_context": WindowDecoder, "joint_embedding": JointEmbedWindowDecoder, "seq2seq": Seq2SeqWindowDecoder}[model]
+    limit = QUEUE_MAX_ROWS if model == "multimodal_context" else 4
+    if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= limit:
+        raise ValueError(f"{who}: 1 <= rows <= {limit} for the {model} model" + ("" if limit == QUEUE_MAX_ROWS else " (its window decoder's rows)")
+                         + f", got {rows!r}")
+    rows, N = int(rows), len(audios)
+    if N < 1:
+        raise ValueError(f"{who}: no utterance")
+    if order not in QUEUE_ORDERS:
+        raise ValueError(f"{who}: order must be one of {QUEUE_ORDERS}, got {order!r}")
+    if words_list is not None and len(words_list) != N:
+        raise ValueError(f"{who}: {N} utterance(s), {len(words_list)} word list(s)")
+    T, n_pre = args.n_poses, args.n_pre_poses
+    dev = next(pose_decoder.parameters()).device
+    rate = _resampling(who, input_sr, audio_sr)
+    draws = {"multimodal_context": _draws, "joint_embedding": eps_list, "seq2seq": None}[model]
+    if (_draws is not None or eps_list is not None) and draws is None:
+        raise ValueError(f"{who}: the {model} model takes " + ("no draws" if model == "seq2seq" else "_draws" if model == "multimodal_context" else "eps_list"))
+    # the plan of every utterance on the host first (lengths after resampling are integers the host knows): the window counts, and the refusals
+    if rate is not None:
+        Lr, Mr = resample.geometry(rate)[:2]
+    lengths = [len(a) if rate is None else resampled_length(len(a), Lr, Mr) for a in audios]
+    if min(lengths) < 1:
+        raise ValueError(f"{who}: an empty utterance")
+    n_win = [num_windows(n / audio_sr, T, n_pre, args.motion_resampling_framerate) for n in lengths]
+    if model == "seq2seq":
+        if not 0 <= max_words <= 126:
+            raise ValueError(f"{who}: 0 <= max_words <= 126, got {max_words}")
+        for u in range(N):
+            for i in range(n_win[u]):
+                k = len(seq2seq_window_text(lang_model, words_list[u] if words_list is not None else [], i, T, n_pre, args.motion_resampling_framerate))
+                if k > max_words + 2:
+                    raise ValueError(f"{who}: window {i} of utterance {u} holds {k - 2} words, the decoder's text buffer {max_words} (max_words)")
+    for name, per in (("vids", vids), ("seed_seqs", seed_seqs), ("_draws / eps_list", draws)):
+        if per is not None and len(per) != N:
+            raise ValueError(f"{who}: {name} holds {len(per)} entries for {N} utterance(s)")
+    built_for = dict(max_words=max_words) if model == "seq2seq" else dict(replay_draws=draws is not None)
+    if window_decoder is not None:
+        dec = _kept_decoder(who, kind, window_decoder, pose_decoder, rows, T, n_pre, **built_for)
+    D = pose_decoder.pose_dim if model == "multimodal_context" else pose_decoder.decoder.pose_dim if model == "joint_embedding" else pose_decoder.decoder.output_size
+    draw_tab = None
+    if draws is not None:
+        w = 16 if model == "multimodal_context" else 32
+        draws = [np.asarray(d.cpu() if isinstance(d, torch.Tensor) else d, dtype=np.float32) for d in draws]
+        for u, d in enumerate(draws):
+            if d.shape != (n_win[u], w):
+                raise ValueError(f"{who}: the draws of utterance {u} are {d.shape}, expected one row per window: {(n_win[u], w)}")
+        draw_tab = np.concatenate(draws)
+    seeds = seed_on = None
+    if seed_seqs is not None and any(s is not None for s in seed_seqs):
+        seeds, seed_on = np.zeros((N, n_pre, D), dtype=np.float32), np.zeros(N, dtype=np.int32)
+        for u, s in enumerate(seed_seqs):
+            if s is not None:
+                s = np.asarray(s.cpu() if isinstance(s, torch.Tensor) else s, dtype=np.float32)
+                if s.ndim != 2 or s.shape[0] < n_pre or s.shape[1] != D:
+                    raise ValueError(f"{who}: the seed of utterance {u} is {s.shape}, expected (>= {n_pre}, {D})")
+                seeds[u], seed_on[u] = s[:n_pre], 1
+    rounds, table, _, _ = queue_schedule(n_win, rows, order)
+    _check_schedule(table, n_win, rows)
+    # ---- from here on the GPU
+    if window_decoder is None:
+        opts = dict(max_words=max_words) if model == "seq2seq" else dict(replay_draws=draws is not None)
+        dec = kind(args, pose_decoder, rows, dev, graph=graph, audio_sr=audio_sr, **opts)
+    vid_tab = None
+    if model == "multimodal_context" and args.z_type == "speaker":                   # synthesize.py:67-74
+        vid_tab = [None] * N if vids is None else list(vids)
+        for u in range(N):
+            if not vid_tab[u]:
+                vid_tab[u] = random.randrange(pose_decoder.z_obj.n_words)
+    ub = UtteranceBatch(args, lang_model, audios, words_list, dev, audio_sr, input_sr=input_sr)
+    if ub.n_win != n_win:
+        raise RuntimeError(f"{who}: the utterance batch counts {ub.n_win} windows, the schedule was made for {n_win}")
+    total = torch.zeros(N, ub.frames(fade_out), D, device=dev)
+    q = _QueueState(ub, dec, rounds, table, total, vid_tab, draw_tab, seeds, seed_on)
+    dec.rnd.zero_()
+    if model == "seq2seq":                                                           # every row holds a valid list at all times: idle rows keep [SOS, EOS]
+        dec.text.zero_()
+        dec.text[:, 0], dec.text[:, 1] = lang_model.SOS_token, lang_model.EOS_token
+        dec.len.fill_(2)
+    for _ in range(rounds):
+        dec.window_queued(q)
+    return _device_result(ub, total, bool(fade_out), bool(joints), bool(return_device))
 
 
 def fade_out_to_mean(out_dir_vec, end_padding_samples, args, audio_sr=16000):

@@ -828,6 +828,33 @@ int tg_stream_stage_preview(const float* ring, const int64_t* written, const int
 int tg_preview_handover(const float* res, const float* tail, const int32_t* win, int32_t w_value, const int32_t* active, int32_t B, int32_t T,
                         int32_t D, int32_t n_pre, float* preview_out, void* stream);
 
+/* Synthesis queue (csrc/queue.hip; synthesize.generate_gestures_queue; added under ABI 11 -- new symbols only): N utterances on the R rows of
+ * one window decoder.  sched [rounds][R][2] int32 (device memory) = (utterance, window) of every row in every round, (-1, -1) where the row
+ * idles; rnd [R] int32 (device memory) counts each row's rounds, and row b reads its entry sched[rnd[b]][b]: no round number is passed, the
+ * launches of every round are the same.  The plan tables are tg_window_stage's, of all N utterances (win_off [N + 1], plan_win [G][4],
+ * plan_text [G][text_stride], audio_off [N + 1]).  One workgroup (or grid column) per row, plain loads and stores, no atomics, nothing waits
+ * on another workgroup; an idle row -- an entry that names no window of an utterance, or rnd[b] outside [0, rounds) -- leaves before any
+ * store.  The host guarantees that no two rows of a round run the same utterance.
+ * tg_queue_stage, for row b running (u, i), with g = win_off[u] + i: out_audio[b] [L] = tg_window_stage's slice of utterance u (null: no
+ * audio); out_text[b] [text_w] int64 = the first min(text_w, text_stride) ids of plan_text[g], zeros behind (null: no text) -- with out_len
+ * non-null (the Seq2Seq model, 2 <= text_w = Te <= 128) the list's plan_win[g][3] ids, zeros behind, and out_len[b] = that length --;
+ * vid[b] = vids[u] (int64; both null or neither); draw[b] [draw_w] = draws[g] (draws [G][draw_w], draw_w 16 or 32; both null or neither); and
+ * where i == 0 the row's seed buffer (null: none) = utterance u's seed: seed_layout 0: pre_seq [R][T][D + 1], the n_pre frames of
+ * seeds[u] ([N][n_pre][D]) with the constraint bit, zeros elsewhere; seed_layout 1: pre [R][n_pre][D] = seeds[u].  seeds == null, or
+ * seed_on[u] == 0 (int32 [N]; null: every utterance has a seed): all zeros, no constraint bit.  Copies are bit-exact.
+ * tg_queue_handover, for row b running (u, i): total[u][i (T - n_pre) .. + T) = res[b] ([R][T][D]), its first n_pre frames cross-faded with
+ * tail[b] exactly as tg_window_blend does where i > 0 (total: [N][F][D]); tail[b] = the window's last n_pre frames; the next window's seed in
+ * tg_pool_handover's seed_layout; then rnd[b] += 1.  An idle row with rnd[b] in [0, rounds) only has its counter advanced.
+ * Envelope of both: rounds >= 1, 1 <= R <= 128, N >= 1, 1 <= n_pre <= 8, 1 <= D <= 64, n_pre < T <= 1024 (F >= T); refused otherwise,
+ * nothing is launched. */
+int tg_queue_stage(const int32_t* sched, const int32_t* rnd, int32_t rounds, int32_t R, int32_t N, const float* audio, const int64_t* audio_off,
+                   const int32_t* win_off, const int64_t* plan_win, const int64_t* plan_text, int32_t text_stride, int32_t L, int32_t text_w,
+                   float* out_audio, int64_t* out_text, int64_t* out_len, const int64_t* vids, int64_t* vid, const float* draws, float* draw,
+                   int32_t draw_w, const float* seeds, const int32_t* seed_on, float* seed, int32_t seed_layout, int32_t T, int32_t D, int32_t n_pre,
+                   void* stream);
+int tg_queue_handover(const float* res, float* total, int64_t F, float* tail, float* seed, int32_t seed_layout, const int32_t* sched, int32_t* rnd,
+                      int32_t rounds, const int32_t* win_off, int32_t R, int32_t N, int32_t T, int32_t D, int32_t n_pre, void* stream);
+
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over
  * T-2 frames, sums[2] = sum |out - target|.  (joint_mae = sums[0]/(B*(T-n_pre)*30), accel = sums[1]/(B*(T-2)*30), l1 = sums[2]/(B*T*27).) */
