@@ -9,6 +9,7 @@
 namespace tg {
 
 constexpr int ST_MAX_ROWS = 4;          // rows of a stream (the few-row decoders' lock-step limit)
+constexpr int ST_MAX_WIDE_ROWS = 128;   // rows of a wide pool (stream_pool_wide.hip): the multimodal window decoder's and the queue's row limit
 constexpr int ST_MAX_WORDS = 1024;      // largest word ring per row: 12 KB of LDS in the stage kernels
 constexpr int ST_MAX_FRAMES = 1024;     // frames of a window: one thread each
 constexpr int ST_MAX_RING = 1 << 30;    // samples of a row's ring: positions and their sums stay inside an int
@@ -18,13 +19,15 @@ constexpr int ST_MAX_WINDOW = 1 << 25;  // samples of a window: the stage kernel
 // m records of recs row b (behind its count) to the word ring at cnt mod W, then thread 0 advances both counters.  wr = written[b] and
 // cnt = n_words[b] were read by EVERY thread of the workgroup before it came here: the barrier below is what lets thread 0 move them.
 // written and n_words are read (by the caller) and written (here): no __restrict__ on them.
-__device__ __forceinline__ void ring_push_row(int b, int n, int m, long wr, long cnt, const float* __restrict__ chunk, long chunk_stride,
-                                              const int32_t* __restrict__ recs, int rec_stride, float* __restrict__ ring, int64_t* written,
-                                              int32_t* __restrict__ word_ring, int64_t* n_words, int R, int W) {
+// ring_push_row_from is the body: the row's samples are src[0 .. n) and its records' 3 m integers trip[0 .. 3 m), wherever the caller keeps them --
+// a dense chunk and a table with a count per row (ring_push_row: stream.hip, stream_pool.hip) or slices of one packed buffer
+// (stream_pool_wide.hip).
+__device__ __forceinline__ void ring_push_row_from(int b, int n, int m, long wr, long cnt, const float* __restrict__ src,
+                                                   const int32_t* __restrict__ trip, float* __restrict__ ring, int64_t* written,
+                                                   int32_t* __restrict__ word_ring, int64_t* n_words, int R, int W) {
     __syncthreads();                                                  // every thread has the counters before thread 0 moves them
     const int p0 = (int)(wr % R);
     float* __restrict__ row = ring + (long)b * R;
-    const float* __restrict__ src = chunk + (long)b * chunk_stride;
     for (int k = threadIdx.x; k < n; k += 1024) {
         int p = p0 + k;                                               // n < R: one subtraction wraps
         if (p >= R) p -= R;
@@ -34,12 +37,19 @@ __device__ __forceinline__ void ring_push_row(int b, int n, int m, long wr, long
     for (int t = threadIdx.x; t < 3 * m; t += 1024) {
         int slot = s0 + t / 3;                                        // m <= W
         if (slot >= W) slot -= W;
-        word_ring[((long)b * W + slot) * 3 + t % 3] = recs[(long)b * rec_stride + 1 + t];
+        word_ring[((long)b * W + slot) * 3 + t % 3] = trip[t];
     }
     if (threadIdx.x == 0) {
         written[b] = wr + n;
         n_words[b] = cnt + m;
     }
+}
+
+__device__ __forceinline__ void ring_push_row(int b, int n, int m, long wr, long cnt, const float* __restrict__ chunk, long chunk_stride,
+                                              const int32_t* __restrict__ recs, int rec_stride, float* __restrict__ ring, int64_t* written,
+                                              int32_t* __restrict__ word_ring, int64_t* n_words, int R, int W) {
+    ring_push_row_from(b, n, m, wr, cnt, chunk + (long)b * chunk_stride, recs ? recs + (long)b * rec_stride + 1 : nullptr, ring, written, word_ring,
+                       n_words, R, W);
 }
 
 // Row b of the staging of window w, by the 256-thread workgroups (b, blockIdx.y) of a grid with cdiv(A, 1024) + 1 columns (one without audio):

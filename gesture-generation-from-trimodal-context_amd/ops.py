@@ -2101,7 +2101,7 @@ def pool_push(st, chunk, n, recs=None, m_max=0, words_live=0):
          _p(st["written"]), _p(st["words"]), _p(st["n_words"]), B, st["R"], st["A"], st["W"], _stream())      # (B > 4: refused by the library)
 
 
-def pool_stage(st, win, active, text_out=None, audio_out=None):
+def pool_stage(st, win, active, text_out=None, audio_out=None, entry="tg_pool_stage"):
     """stream_stage per row: row b with active[b] != 0 gets the inputs of its own window win[b] (win, active: (B,) int32 on the device); the rows of
     audio_out / text_out that belong to the other rows are left as they are."""
     _stream_check(st)
@@ -2114,11 +2114,11 @@ def pool_stage(st, win, active, text_out=None, audio_out=None):
         _i64(text_out, "text_out")
         if tuple(text_out.shape) != (st["B"], st["T"]) or not text_out.is_contiguous():
             raise ValueError(f"text_out is {tuple(text_out.shape)}, a window's text is {(st['B'], st['T'])}, contiguous")
-    call("tg_pool_stage", _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(win), _p(active), st["B"], st["R"], st["S"], st["A"],
+    call(entry, _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(win), _p(active), st["B"], st["R"], st["S"], st["A"],
          st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
 
 
-def pool_handover(res, out, tail, seed, win, active):
+def pool_handover(res, out, tail, seed, win, active, entry="tg_pool_handover"):
     """The tail of a window for the rows with active[b] != 0, one launch: out = res (B, T, D), cross-faded with tail (B, n_pre, D) where win[b] > 0
     (window_blend's arithmetic), tail = out's last n_pre frames, seed = the next window's seed -- (B, T, D + 1): make_pre_seq's layout, (B, n_pre,
     D): the frames themselves -- and win[b] += 1.  Nothing of an inactive row is written."""
@@ -2137,7 +2137,36 @@ def pool_handover(res, out, tail, seed, win, active):
     else:
         raise ValueError(f"seed is {tuple(seed.shape)}: expected {(B, T, D + 1)} (pre_seq) or {(B, n_pre, D)} (pre)")
     _dev_int(win, torch.int32, B, "win"); _dev_int(active, torch.int32, B, "active")
-    call("tg_pool_handover", _p(res), _p(out), _p(tail), _p(seed), layout, _p(win), _p(active), B, T, D, n_pre, _stream())
+    call(entry, _p(res), _p(out), _p(tail), _p(seed), layout, _p(win), _p(active), B, T, D, n_pre, _stream())
+
+
+# ------------------------------------------------------------------------------------------------- wide stream pool (csrc/stream_pool_wide.hip)
+def wide_pool_push(st, packed, lay, words_live=0):
+    """pool_push for up to 128 rows from ONE packed device buffer: packed (flat uint8, device) holds, at the byte offsets of lay
+    (synthesize.wide_push_layout), the header (B, 4) int32 = per row (n samples, sample offset, record count, record offset), the rows' chunks
+    concatenated and their (window, frame, word id) records concatenated.  Row b appends its slice of both; a row with neither keeps every bit.
+    words_live + the largest record count: the slot count of the fullest word ring after the push.  Outside the envelope (1 <= B <= 128, a row
+    with samples or records, R >= A + the longest chunk) the library refuses (RuntimeError naming the envelope); nothing is launched."""
+    _stream_check(st)
+    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 1 and packed.is_contiguous()):
+        raise TypeError("packed: expected a flat contiguous CUDA uint8 tensor")
+    if lay["B"] != st["B"] or packed.numel() < lay["total"] or packed.data_ptr() % 16:
+        raise ValueError(f"packed: {packed.numel()} bytes for a layout of {lay['B']} rows and {lay['total']} bytes on a state of {st['B']} rows")
+    base = packed.data_ptr()
+    n_s, n_r = lay["n_samples"], lay["n_records"]
+    call("tg_wide_pool_push", base + lay["hdr"], base + lay["samples"] if n_s else None, n_s, base + lay["records"] if n_r else None, n_r,
+         lay["n_max"], lay["m_max"], int(words_live), _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), st["B"], st["R"], st["A"],
+         st["W"], _stream())
+
+
+def wide_pool_stage(st, win, active, text_out=None, audio_out=None):
+    """pool_stage for up to 128 rows (the same row body: for B <= 4 the same bits)."""
+    pool_stage(st, win, active, text_out, audio_out, entry="tg_wide_pool_stage")
+
+
+def wide_pool_handover(res, out, tail, seed, win, active):
+    """pool_handover for up to 128 rows (the same row body: for B <= 4 the same bits)."""
+    pool_handover(res, out, tail, seed, win, active, entry="tg_wide_pool_handover")
 
 
 # ------------------------------------------------------------------------------------------------- seq2seq stream pool (csrc/stream_pool_seq.hip)

@@ -286,7 +286,9 @@ class _WindowDecoderBase:
         self.audio_len = int(T / args.motion_resampling_framerate * audio_sr)
         # replay_draws (parity tests): the per-window eps / random z comes from self.draw, filled by the caller before each window, instead of
         # the device RNG -- a static buffer, so a captured window replays with new contents
-        self.draw = torch.zeros(batch, draw_width, device=device) if draw_width else None
+        # (draw and window_pooled's mask `active` are views of ONE buffer, round_buf = [draw | active]: a pool can send both up as one copy)
+        self.round_buf = torch.zeros(batch * draw_width + batch, device=device)
+        self.draw = self.round_buf[:batch * draw_width].view(batch, draw_width) if draw_width else None
         self.text = torch.zeros(batch, text_width or T, dtype=torch.int64, device=device)
         self.audio = torch.zeros(batch, self.audio_len, device=device) if audio else None
         self.pre = torch.zeros((batch,) + (seed_shape or (n_pre, D)), device=device)       # the next window's seed
@@ -324,7 +326,8 @@ class _WindowDecoderBase:
         self._reseed()
 
     def _forward_pooled(self):
-        ops.pool_handover(self._model_forward().view(self.B, self.T, self.D), self.out, self.tail, self.pre, self.win, self.active)
+        handover = ops.pool_handover if self.B <= 4 else ops.wide_pool_handover           # (more than four rows: WideStreamPool)
+        handover(self._model_forward().view(self.B, self.T, self.D), self.out, self.tail, self.pre, self.win, self.active)
 
     def _window(self, first):
         with torch.no_grad(), self.frozen:
@@ -340,7 +343,7 @@ class _WindowDecoderBase:
         """(active, win): the static (B,) int32 device buffers window_pooled reads -- the mask of the rows to run and every row's window index."""
         if self.win is None:
             self.win = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
-            self.active = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+            self.active = self.round_buf[self.round_buf.numel() - self.B:].view(torch.int32)       # (zeros so far: nothing else writes them)
         return self.active, self.win
 
     def window_pooled(self, active=None, win=None, draw=None):
@@ -1414,6 +1417,8 @@ class _StreamCore:
     self._live[b] lists (index in the row's record sequence, window) of the records a window may still need."""
     _models = ("multimodal_context", "joint_embedding")
     _rows = "rows"
+    _max_rows = 4                                    # the few-row decoders' and the by-value kernels' limit (WideStreamPool: 128)
+    _dense_chunks = True                             # whether a push goes through the dense (B, max_chunk) device buffer chunk_buf
     _smooth_closing = False                          # whether close() smooths the window it ran (Seq2SeqGestureStream)
 
     def _refusal(self, model):
@@ -1430,8 +1435,8 @@ class _StreamCore:
         who, model = type(self).__name__, getattr(args, "model", "multimodal_context")
         if model not in self._models:
             raise ValueError(f"{who}: {self._refusal(model)}")
-        if not 1 <= rows <= 4:
-            raise ValueError(f"{who}: 1 to 4 {self._rows}, got {rows}")
+        if not 1 <= rows <= self._max_rows:
+            raise ValueError(f"{who}: 1 to {self._max_rows} {self._rows}, got {rows}")
         if max_chunk < 1:
             raise ValueError(f"{who}: max_chunk = {max_chunk}")
         self.input_sr = _resampling(who, input_sr, audio_sr)
@@ -1457,7 +1462,7 @@ class _StreamCore:
             raise ValueError(f"{who}: the window decoder takes {self.dec.audio_len} samples, the stream's window is {self.A} (audio_sr = {audio_sr})")
         self.D = self.dec.D
         self.state = ops.stream_state(self.B, R, self.S, self.A, word_ring, T, dev)
-        self.chunk_buf = torch.zeros(self.B, chunk16, device=dev)
+        self.chunk_buf = torch.zeros(self.B, chunk16 if self._dense_chunks else 0, device=dev)
         # the streaming resampler: device state (carry, counters) and the host's mirror of both counters per row, plain integers
         self.rs = None if self.input_sr is None else ops.resample_state(self.B, *resample.device_taps(self.input_sr, dev), self.max_chunk, dev)
         self._rs_in, self._rs_out = [0] * self.B, [0] * self.B
@@ -1490,9 +1495,14 @@ class _StreamCore:
         for b, r in enumerate(rows):
             table[b, 0] = len(r)
             table[b, 1:1 + 3 * len(r)] = np.asarray(r, dtype=np.int32).reshape(-1)
+        self._note_records(rows)
+        return torch.from_numpy(table).to(self.dev, non_blocking=True), m_max
+
+    def _note_records(self, rows):
+        """The host's count of the records `rows` (per row) that are on their way to the device."""
+        for b, r in enumerate(rows):
             self._live[b] += [(self._n_rec[b] + k, rec[0]) for k, rec in enumerate(r)]
             self._n_rec[b] += len(r)
-        return torch.from_numpy(table).to(self.dev, non_blocking=True), m_max
 
     def _ran(self, b, next_window):
         """Row b has run its windows below next_window: their records are no longer needed."""
@@ -2020,13 +2030,8 @@ class StreamPool(_StreamCore):
         return out
 
     # -------------------------------------------------------------------------------------------------------------- the interface
-    def push(self, chunks, numpy=False, joints=False):
-        """chunks: {slot: chunk} or {slot: (chunk, words)} for any non-empty subset of the open slots; chunk: 1-D float32 (numpy or a host
-        tensor), 1 <= len <= max_chunk, the lengths need not agree; words: a list of (word, start, end), absolute seconds of that session.
-        One upload, one ops.pool_push, then the rounds of pool_rounds.  Returns {slot: frames} for the pushed slots: the (k * stride, D) device
-        view of the frames that became final (k windows of that slot completed; k = 0: an empty result); numpy=True reads them back;
-        joints=True gives (frames, fp64 joint positions (k * stride, 10, 3))."""
-        B, st, T, D = self.B, self.stride, self.T, self.D
+    def _take(self, chunks):
+        """push()'s argument, checked: ({row: chunk as a float32 numpy array}, {row: word list or None}).  Nothing is changed here."""
         if not isinstance(chunks, dict) or not chunks:
             raise ValueError(f"{type(self).__name__}.push: expected a non-empty {{slot: chunk}} dict")
         rows, words = {}, {}
@@ -2042,6 +2047,16 @@ class StreamPool(_StreamCore):
             if c.ndim != 1 or not 1 <= c.shape[0] <= self.max_chunk:
                 raise ValueError(f"{type(self).__name__}.push: slot {b}: a chunk of shape {c.shape}; expected 1-D with 1 <= len <= max_chunk = {self.max_chunk}")
             rows[b], words[b] = c, w
+        return rows, words
+
+    def push(self, chunks, numpy=False, joints=False):
+        """chunks: {slot: chunk} or {slot: (chunk, words)} for any non-empty subset of the open slots; chunk: 1-D float32 (numpy or a host
+        tensor), 1 <= len <= max_chunk, the lengths need not agree; words: a list of (word, start, end), absolute seconds of that session.
+        One upload, one ops.pool_push, then the rounds of pool_rounds.  Returns {slot: frames} for the pushed slots: the (k * stride, D) device
+        view of the frames that became final (k windows of that slot completed; k = 0: an empty result); numpy=True reads them back;
+        joints=True gives (frames, fp64 joint positions (k * stride, 10, 3))."""
+        B = self.B
+        rows, words = self._take(chunks)
         recs, late = self._records(words)                                   # (may refuse; nothing has changed yet)
         n = [len(rows[b]) if b in rows else 0 for b in range(B)]
         host = np.zeros((B, max(n)), np.float32)
@@ -2224,3 +2239,135 @@ class Seq2SeqStreamPool(StreamPool):
 
     def _stage(self):
         ops.pool_stage_text(self.state, self.win, self.active, self._sos, self._eos, self.dec.text, self.dec.len)
+
+
+# ------------------------------------------------------------------------------------------------------------------ wide stream pool
+def wide_push_layout(n, m):
+    """Where the pieces of one push of a wide pool lie in its packed buffer, integers only.  n, m: per row the chunk length in samples and the
+    number of word records (>= 0; a row may have neither, or records without samples).  The pieces -- the header (B, 4) int32 = per row
+    (n, sample offset, m, record offset), the chunks concatenated (fp32, no padding), the records concatenated ((window, frame, id) int32) --
+    start on 256-byte boundaries, like data.packed_like's.  Returns a dict: the byte offsets hdr, samples, records and the byte size total;
+    sample_off / record_off: per row the first sample / record of its slice, in samples / records; n_samples, n_records: the slices' sums;
+    n_max, m_max; B."""
+    n, m = [int(v) for v in n], [int(v) for v in m]
+    if len(n) != len(m) or not n or min(n) < 0 or min(m) < 0:
+        raise ValueError(f"wide_push_layout: {len(n)} chunk lengths and {len(m)} record counts; expected one of each per row, none negative")
+    up = lambda v: (v + 255) // 256 * 256
+    B, n_samples, n_records = len(n), sum(n), sum(m)
+    samples = up(16 * B)
+    records = samples + up(4 * n_samples)
+    return dict(B=B, hdr=0, samples=samples, records=records, total=records + up(12 * n_records), n_samples=n_samples, n_records=n_records,
+                sample_off=[sum(n[:b]) for b in range(B)], record_off=[sum(m[:b]) for b in range(B)], n_max=max(n), m_max=max(m))
+
+
+class WideStreamPool(StreamPool):
+    """StreamPool for up to 128 sessions: `slots` (1 to 128) rows on ONE multimodal WindowDecoder, the same interface -- open(vid, seed_seq),
+    push({slot: chunk or (chunk, words)}), close(slot, fade_out, joints, numpy), late_words, window_decoder= -- and the same contract:
+    everything push() and close() returned for the session in slot b, concatenated, is row b of generate_gestures_batch(on_device=True) on a
+    batch of `slots` utterances with that session's utterance in row b and the same draws, bit for bit, whatever the other rows hold or do,
+    for lengths where stream_matches_offline holds.  The forward always runs `slots` rows: one open session on 128 rows pays the 128-row window.
+
+    What differs from StreamPool is how a tick travels (csrc/stream_pool_wide.hip): a push packs the header, the ragged chunks and the word
+    records of all its rows into ONE pinned host buffer (wide_push_layout; two slots, a slot is reused only after the event behind its copy),
+    sends it up with one copy and appends every row by one launch, ops.wide_pool_push; a round's active mask and replayed draws go up as one
+    small copy into the decoder's round_buf.  push() never reads from the device.  A refused call (ValueError) leaves the pool as it was.
+
+    args.model 'multimodal_context' only, 16 kHz input only and no preview(): the other models' window decoders, the stream resampler and the
+    preview chain are built for four rows (each refusal says so)."""
+    _max_rows = 128
+    _models = ("multimodal_context",)
+    _dense_chunks = False
+
+    def _refusal(self, model):
+        few = "its window decoder holds four rows: use {} (1 to 4 slots)"
+        return {"joint_embedding": "the joint_embedding model has no wide pool -- " + few.format("StreamPool"),
+                "seq2seq": "the seq2seq model has no wide pool -- " + few.format("Seq2SeqStreamPool")}.get(model) or super()._refusal(model)
+
+    def __init__(self, args, pose_decoder, lang_model, slots=128, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, ring=None,
+                 window_decoder=None, _replay_draws=False, input_sr=None):
+        if input_sr is not None and int(input_sr) != resample.TARGET_SR:
+            raise ValueError(f"WideStreamPool: input_sr = {input_sr}: the stream resampler takes its chunk lengths by value for four rows -- push "
+                             f"{resample.TARGET_SR} Hz audio (resample_audio converts whole signals)")
+        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, graph, word_ring, ring, window_decoder, _replay_draws, input_sr=None)
+        B, pin = self.B, self.dev.type == "cuda"
+        host = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, pin_memory=pin)
+        # a push: two pinned slots of the worst-case size (every row a full chunk and a full word ring) and a device buffer behind each
+        size = wide_push_layout([self.max_chunk] * B, [self.state["W"]] * B)["total"]
+        self._push_host = [host(size) for _ in range(2)]
+        self._push_dev = [torch.zeros(size, dtype=torch.uint8, device=self.dev) for _ in range(2)]
+        # a round: the decoder's round_buf = [draws | active mask], two pinned twins
+        self._round_host = [host(4 * self.dec.round_buf.numel()).view(torch.float32) for _ in range(2)]
+        self._copied = {"push": [None, None], "round": [None, None]}            # per slot: the event behind its last host -> device copy
+        self._turn = {"push": 0, "round": 0}
+        self._draw_host = None                                                  # (StreamPool's staging of the draws: the round slots replace it)
+
+    def _slot_to_fill(self, kind):
+        """The pinned slot of `kind` whose turn it is, safe to overwrite: its previous copy has finished."""
+        i = self._turn[kind]
+        self._turn[kind] = i ^ 1
+        if self._copied[kind][i] is not None:
+            self._copied[kind][i].synchronize()
+        return i
+
+    def _sent(self, kind, i):
+        if self.dev.type == "cuda":
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.dev))
+            self._copied[kind][i] = ev
+
+    def preview(self, slot, fade_out=False, joints=False, numpy=False):
+        raise ValueError("WideStreamPool.preview: a wide pool has no preview -- the preview chain's kernels take their lengths by value for four "
+                         "rows (StreamPool.preview)")
+
+    def _stage(self):
+        ops.wide_pool_stage(self.state, self.win, self.active, self.dec.text, self.dec.audio)
+
+    def _round(self, mask):
+        """One window for the rows of `mask`: the mask and the active rows' draws go up as ONE small copy, then stage -> window_pooled."""
+        B, dec = self.B, self.dec
+        i = self._slot_to_fill("round")
+        host = self._round_host[i].numpy()
+        if dec.draw is not None:
+            draws = host[:dec.draw.numel()].reshape(tuple(dec.draw.shape))
+            for b, a in enumerate(mask):
+                if a:
+                    draws[b] = np.asarray(self._draws[b][self.next_window[b]], dtype=np.float32).reshape(-1)
+        host[host.size - B:].view(np.int32)[:] = mask
+        dec.round_buf.copy_(self._round_host[i], non_blocking=True)
+        self._sent("round", i)
+        self._stage()
+        out = dec.window_pooled()
+        for b, a in enumerate(mask):
+            if a:
+                self.next_window[b] += 1
+                self._ran(b, self.next_window[b])
+        return out
+
+    def push(self, chunks, numpy=False, joints=False):
+        """StreamPool.push's arguments and result.  The header, the chunks and the records of every pushed row are packed into a pinned slot
+        (numpy copies), go up as one copy, and ops.wide_pool_push appends all rows in one launch; then the rounds of pool_rounds."""
+        B = self.B
+        rows, words = self._take(chunks)
+        recs, late = self._records(words)                                   # (may refuse; nothing has changed yet)
+        n, m = [len(rows[b]) if b in rows else 0 for b in range(B)], [len(r) for r in recs]
+        lay = wide_push_layout(n, m)
+        i = self._slot_to_fill("push")
+        host = self._push_host[i].numpy()
+        hdr = host[lay["hdr"]:lay["hdr"] + 16 * B].view(np.int32).reshape(B, 4)
+        hdr[:, 0], hdr[:, 1], hdr[:, 2], hdr[:, 3] = n, lay["sample_off"], m, lay["record_off"]
+        samples = host[lay["samples"]:lay["samples"] + 4 * lay["n_samples"]].view(np.float32)
+        for b, c in rows.items():
+            samples[lay["sample_off"][b]:lay["sample_off"][b] + n[b]] = c
+        table = host[lay["records"]:lay["records"] + 12 * lay["n_records"]].view(np.int32)
+        for b, r in enumerate(recs):
+            if r:
+                table[3 * lay["record_off"][b]:3 * (lay["record_off"][b] + m[b])] = np.asarray(r, dtype=np.int32).reshape(-1)
+        self._push_dev[i][:lay["total"]].copy_(self._push_host[i][:lay["total"]], non_blocking=True)
+        self._sent("push", i)
+        fullest = max((self._live_slots(b) + len(r) for b, r in enumerate(recs) if r), default=0)      # slots of the fullest word ring after the push
+        self._note_records(recs)
+        ops.wide_pool_push(self.state, self._push_dev[i], lay, max(0, fullest - lay["m_max"]))
+        for b in range(B):
+            self.pushed[b] += n[b]
+            self.late_words[b] += late[b]
+        return {b: self._result(*fr, numpy) for b, fr in self._emit(list(rows), joints).items()}

@@ -855,6 +855,32 @@ int tg_queue_stage(const int32_t* sched, const int32_t* rnd, int32_t rounds, int
 int tg_queue_handover(const float* res, float* total, int64_t F, float* tail, float* seed, int32_t seed_layout, const int32_t* sched, int32_t* rnd,
                       int32_t rounds, const int32_t* win_off, int32_t R, int32_t N, int32_t T, int32_t D, int32_t n_pre, void* stream);
 
+/* Wide stream pool (csrc/stream_pool_wide.hip; synthesize.WideStreamPool; added under ABI 11 -- new symbols only): the stream pool's three
+ * launches for 1 <= B <= 128 rows, with everything per row in device memory.  The state, the row bodies and every other bound are
+ * tg_pool_*'s; for B <= 4 each entry writes what its tg_pool_* counterpart writes, bit for bit.  One workgroup (or grid column) per row, plain
+ * loads and stores, no atomics, nothing waits on another workgroup; a row that is not selected leaves before any store and before any
+ * barrier and keeps every bit it owns.
+ * tg_wide_pool_push: the push as slices of one packed device buffer.  hdr [B][4] int32 = per row (n samples, sample offset, record count,
+ * record offset); samples [samples_len] fp32 = the rows' chunks concatenated, no padding; recs [recs_len][3] int32 = the rows' records
+ * (window, frame, word id) concatenated.  Row b appends samples[off_b .. off_b + n_b) to its ring and recs[roff_b .. roff_b + m_b) to its word
+ * ring exactly as tg_pool_push's row does; a row with n_b == 0 and m_b == 0 is skipped.  n_max / m_max: the largest n_b / m_b (they size
+ * nothing but the envelope check); words_live as for tg_pool_push.  The host validates the header before it uploads it; the kernel clamps
+ * n_b to [0, n_max], m_b to [0, m_max] and both slices into samples / recs, so that no index leaves them.
+ * Envelope: 1 <= B <= 128, n_max >= 0, m_max >= 0, n_max >= 1 or m_max >= 1, A + n_max <= R <= 2^30, A < R, 1 <= W <= 1024,
+ * words_live + m_max <= W, n_max <= samples_len <= B n_max, m_max <= recs_len <= B m_max; samples (recs) may be null if n_max (m_max) is 0. */
+int tg_wide_pool_push(const int32_t* hdr, const float* samples, int64_t samples_len, const int32_t* recs, int64_t recs_len, int32_t n_max,
+                      int32_t m_max, int32_t words_live, float* ring, int64_t* written, int32_t* word_ring, int64_t* n_words, int32_t B, int32_t R,
+                      int32_t A, int32_t W, void* stream);
+/* tg_pool_stage for 1 <= B <= 128: row b with active[b] != 0 gets the inputs of ITS window win[b] (win, active: int32 [B], device memory); the
+ * out_audio / out_text rows of the other rows are not written.  Envelope: tg_pool_stage's with 1 <= B <= 128. */
+int tg_wide_pool_stage(const float* ring, const int64_t* written, const int32_t* word_ring, const int64_t* n_words, const int32_t* win,
+                       const int32_t* active, int32_t B, int32_t R, int32_t S, int32_t A, int32_t W, int32_t T, float* out_audio, int64_t* out_text,
+                       void* stream);
+/* tg_pool_handover for 1 <= B <= 128, both seed layouts (0: pre_seq [B][T][D + 1], 1: pre [B][n_pre][D]).  Envelope: tg_pool_handover's with
+ * 1 <= B <= 128. */
+int tg_wide_pool_handover(const float* res, float* out, float* tail, float* seed, int32_t seed_layout, int32_t* win, const int32_t* active,
+                          int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream);
+
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over
  * T-2 frames, sums[2] = sum |out - target|.  (joint_mae = sums[0]/(B*(T-n_pre)*30), accel = sums[1]/(B*(T-2)*30), l1 = sums[2]/(B*T*27).) */
