@@ -7,6 +7,7 @@
 //   tg_pool_handover  the tail of a window in one launch, per active row: out = res, cross-faded with the row's tail where win[b] > 0
 //                     (tg_window_blend's expression, operand for operand), tail = the last n_pre frames, the next window's seed
 //                     (tg_make_pre_seq's layout [T][D + 1], or the plain [n_pre][D]), and -- behind a barrier -- win[b] += 1.
+// tg_wide_pool_stage / tg_wide_pool_handover (synthesize.WideStreamPool, up to 128 rows) are the same two kernels behind the same checks.
 // One workgroup (push, handover) or one grid column (stage) per row; nothing waits on another workgroup, nothing needs an atomic, and the
 // results do not depend on the order in which the workgroups run.  The row bodies of push and stage are stream_rows.hpp's, shared with
 // stream.hip (whose kernels serve every stream that shares a clock), and so are the bounds: here a row brings its own chunk length and
@@ -82,31 +83,57 @@ extern "C" int tg_pool_push(const float* chunk, int64_t chunk_stride, int32_t n0
     return check_launch("tg_pool_push");
 }
 
+// The launchers of the stage and the hand-over: tg_pool_* (synthesize.StreamPool, rows <= ST_MAX_ROWS) and tg_wide_pool_* (WideStreamPool, rows <=
+// ST_MAX_WIDE_ROWS) are the same kernels behind the same checks; an entry brings its name and its row limit.
+static int launch_pool_stage(const char* who, int max_rows, const float* ring, const int64_t* written, const int32_t* word_ring, const int64_t* n_words,
+                             const int32_t* win, const int32_t* active, int32_t B, int32_t R, int32_t S, int32_t A, int32_t W, int32_t T,
+                             float* out_audio, int64_t* out_text, void* stream) {
+    TG_REQUIRE(win && active && (out_audio || out_text), "%s: null pointer", who);
+    TG_REQUIRE(!out_audio || (ring && written), "%s: audio output without the ring or its counter", who);
+    TG_REQUIRE(!out_text || (word_ring && n_words), "%s: text output without the word ring or its counter", who);
+    TG_REQUIRE(B >= 1 && B <= max_rows && S >= 1 && A >= 1 && A <= ST_MAX_WINDOW && R > A && R <= ST_MAX_RING && W >= 1 && W <= ST_MAX_WORDS && T >= 1 &&
+                   T <= ST_MAX_FRAMES,
+               "%s: outside the envelope 1 <= B <= %d, S >= 1, 1 <= A <= 2^25, A + 1 <= R <= 2^30, 1 <= W <= %d, 1 <= T <= %d (B=%d R=%d S=%d A=%d W=%d "
+               "T=%d)",
+               who, max_rows, ST_MAX_WORDS, ST_MAX_FRAMES, B, R, S, A, W, T);
+    hipLaunchKernelGGL(pool_stage_kernel, dim3(B, out_audio ? cdiv(A, 1024) + 1 : 1), dim3(256), 0, (hipStream_t)stream, ring, written, word_ring,
+                       n_words, win, active, R, S, A, W, T, out_audio, out_text);
+    return check_launch(who);
+}
+
+static int launch_pool_handover(const char* who, int max_rows, const float* res, float* out, float* tail, float* seed, int32_t seed_layout,
+                                int32_t* win, const int32_t* active, int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream) {
+    TG_REQUIRE(B >= 1 && B <= max_rows && n_pre >= 1 && n_pre <= PL_MAX_PRE && D >= 1 && D <= PL_MAX_DIM && T <= ST_MAX_FRAMES && n_pre < T &&
+                   (seed_layout == 0 || seed_layout == 1),
+               "%s: outside the envelope 1 <= B <= %d, 1 <= n_pre <= %d, 1 <= D <= %d, n_pre < T <= %d, seed_layout 0 (pre_seq [T][D + 1]) or 1 (pre "
+               "[n_pre][D]) (B=%d n_pre=%d D=%d T=%d seed_layout=%d)",
+               who, max_rows, PL_MAX_PRE, PL_MAX_DIM, ST_MAX_FRAMES, B, n_pre, D, T, seed_layout);
+    TG_REQUIRE(res && out && tail && seed && win && active, "%s: null pointer", who);
+    hipLaunchKernelGGL(pool_handover_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, res, out, tail, seed, seed_layout == 0 ? 1 : 0, win, active, T,
+                       D, n_pre);
+    return check_launch(who);
+}
+
+#define POOL_STAGE_ARGS ring, written, word_ring, n_words, win, active, B, R, S, A, W, T, out_audio, out_text, stream
 extern "C" int tg_pool_stage(const float* ring, const int64_t* written, const int32_t* word_ring, const int64_t* n_words, const int32_t* win,
                              const int32_t* active, int32_t B, int32_t R, int32_t S, int32_t A, int32_t W, int32_t T, float* out_audio,
                              int64_t* out_text, void* stream) {
-    TG_REQUIRE(win && active && (out_audio || out_text), "tg_pool_stage: null pointer");
-    TG_REQUIRE(!out_audio || (ring && written), "tg_pool_stage: audio output without the ring or its counter");
-    TG_REQUIRE(!out_text || (word_ring && n_words), "tg_pool_stage: text output without the word ring or its counter");
-    TG_REQUIRE(B >= 1 && B <= ST_MAX_ROWS && S >= 1 && A >= 1 && A <= ST_MAX_WINDOW && R > A && R <= ST_MAX_RING && W >= 1 && W <= ST_MAX_WORDS &&
-                   T >= 1 && T <= ST_MAX_FRAMES,
-               "tg_pool_stage: outside the envelope 1 <= B <= %d, S >= 1, 1 <= A <= 2^25, A + 1 <= R <= 2^30, 1 <= W <= %d, 1 <= T <= %d (B=%d R=%d S=%d "
-               "A=%d W=%d T=%d)",
-               ST_MAX_ROWS, ST_MAX_WORDS, ST_MAX_FRAMES, B, R, S, A, W, T);
-    hipLaunchKernelGGL(pool_stage_kernel, dim3(B, out_audio ? cdiv(A, 1024) + 1 : 1), dim3(256), 0, (hipStream_t)stream, ring, written, word_ring,
-                       n_words, win, active, R, S, A, W, T, out_audio, out_text);
-    return check_launch("tg_pool_stage");
+    return launch_pool_stage("tg_pool_stage", ST_MAX_ROWS, POOL_STAGE_ARGS);
 }
 
+extern "C" int tg_wide_pool_stage(const float* ring, const int64_t* written, const int32_t* word_ring, const int64_t* n_words, const int32_t* win,
+                                  const int32_t* active, int32_t B, int32_t R, int32_t S, int32_t A, int32_t W, int32_t T, float* out_audio,
+                                  int64_t* out_text, void* stream) {
+    return launch_pool_stage("tg_wide_pool_stage", ST_MAX_WIDE_ROWS, POOL_STAGE_ARGS);
+}
+
+#define POOL_HANDOVER_ARGS res, out, tail, seed, seed_layout, win, active, B, T, D, n_pre, stream
 extern "C" int tg_pool_handover(const float* res, float* out, float* tail, float* seed, int32_t seed_layout, int32_t* win, const int32_t* active,
                                 int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream) {
-    TG_REQUIRE(B >= 1 && B <= ST_MAX_ROWS && n_pre >= 1 && n_pre <= PL_MAX_PRE && D >= 1 && D <= PL_MAX_DIM && T <= ST_MAX_FRAMES && n_pre < T &&
-                   (seed_layout == 0 || seed_layout == 1),
-               "tg_pool_handover: outside the envelope 1 <= B <= %d, 1 <= n_pre <= %d, 1 <= D <= %d, n_pre < T <= %d, seed_layout 0 (pre_seq "
-               "[T][D + 1]) or 1 (pre [n_pre][D]) (B=%d n_pre=%d D=%d T=%d seed_layout=%d)",
-               ST_MAX_ROWS, PL_MAX_PRE, PL_MAX_DIM, ST_MAX_FRAMES, B, n_pre, D, T, seed_layout);
-    TG_REQUIRE(res && out && tail && seed && win && active, "tg_pool_handover: null pointer");
-    hipLaunchKernelGGL(pool_handover_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, res, out, tail, seed, seed_layout == 0 ? 1 : 0, win, active, T,
-                       D, n_pre);
-    return check_launch("tg_pool_handover");
+    return launch_pool_handover("tg_pool_handover", ST_MAX_ROWS, POOL_HANDOVER_ARGS);
+}
+
+extern "C" int tg_wide_pool_handover(const float* res, float* out, float* tail, float* seed, int32_t seed_layout, int32_t* win, const int32_t* active,
+                                     int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream) {
+    return launch_pool_handover("tg_wide_pool_handover", ST_MAX_WIDE_ROWS, POOL_HANDOVER_ARGS);
 }

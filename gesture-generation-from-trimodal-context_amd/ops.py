@@ -2025,31 +2025,8 @@ def _stream_check(st):
     assert st["ring"].numel() >= B * R, "the ring is smaller than (B, R)"
 
 
-def stream_push(st, chunk, recs=None, m_max=0, words_live=0):
-    """Appends chunk (B, n) fp32 (device; unit inner stride) to the ring of the stream state st and advances `written`.  recs (B, >= 1 + 3 m_max)
-    int32 on the device: per row a count and that many (window, frame, word id) triples, appended to the word ring.  words_live: ring slots from
-    the oldest record a window still needs to the newest (the host's count).  A call outside the envelope (1 <= B <= 4, n >= 1, R >= A + n,
-    words_live + m_max <= W) is refused by the library (RuntimeError naming the envelope); nothing is launched."""
-    _stream_check(st)
-    _f32(chunk, "chunk")
-    if chunk.dim() != 2 or chunk.shape[0] != st["B"] or (chunk.shape[1] > 1 and chunk.stride(1) != 1):
-        raise ValueError(f"chunk: expected ({st['B']}, n) with unit inner stride, got {tuple(chunk.shape)} strides {chunk.stride()}")
-    n, cs = chunk.shape[1], chunk.stride(0) if chunk.shape[0] > 1 else max(chunk.shape[1], 1)
-    if n > 0 and (cs < n or (st["B"] - 1) * cs + n > _room(chunk)):
-        raise ValueError("chunk: rows overlap or exceed the tensor")
-    rs = 0
-    if m_max > 0:
-        if not (isinstance(recs, torch.Tensor) and recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 2 and recs.is_contiguous() and recs.shape[0] == st["B"]):
-            raise TypeError(f"recs: expected a contiguous CUDA int32 tensor ({st['B']}, >= 1 + 3 m_max)")
-        rs = recs.shape[1]
-    call("tg_stream_push", _p(chunk), cs, n, _p(recs if m_max > 0 else None), rs, int(m_max), int(words_live), _p(st["ring"]), _p(st["written"]),
-         _p(st["words"]), _p(st["n_words"]), st["B"], st["R"], st["A"], st["W"], _stream())
-
-
-def stream_stage(st, text_out=None, audio_out=None):
-    """The inputs of the window whose index is st['win'][0]: audio_out (B, A) fp32 = the window's samples from the ring, zeros where none have been
-    pushed yet; text_out (B, T) int64 = per frame the id of the last pushed record of that window, else 0.  Device buffers written in place."""
-    _stream_check(st)
+def _stage_outputs(st, text_out, audio_out):
+    """The output buffers of stream_stage / pool_stage, each or None: audio_out (B, A) fp32, text_out (B, T) int64, contiguous."""
     if audio_out is not None:
         _flat(audio_out, "audio_out")
         if tuple(audio_out.shape) != (st["B"], st["A"]):
@@ -2058,6 +2035,43 @@ def stream_stage(st, text_out=None, audio_out=None):
         _i64(text_out, "text_out")
         if tuple(text_out.shape) != (st["B"], st["T"]) or not text_out.is_contiguous():
             raise ValueError(f"text_out is {tuple(text_out.shape)}, a window's text is {(st['B'], st['T'])}, contiguous")
+
+
+def _push_operands(st, chunk, n_max, want, recs, m_max):
+    """The chunk (B, >= n_max) and the records table of stream_push / pool_push, checked (want: the chunk's shape as the refusal words it);
+    returns their row strides."""
+    B = st["B"]
+    if chunk.dim() != 2 or chunk.shape[0] != B or chunk.shape[1] < n_max or (chunk.shape[1] > 1 and chunk.stride(1) != 1):
+        raise ValueError(f"chunk: expected ({B}, {want}) with unit inner stride, got {tuple(chunk.shape)} strides {chunk.stride()}")
+    cs = chunk.stride(0) if B > 1 else max(chunk.shape[1], 1)
+    if n_max > 0 and (cs < n_max or (B - 1) * cs + n_max > _room(chunk)):
+        raise ValueError("chunk: rows overlap or exceed the tensor")
+    rs = 0
+    if m_max > 0:
+        if not (isinstance(recs, torch.Tensor) and recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 2 and recs.is_contiguous() and recs.shape[0] == B):
+            raise TypeError(f"recs: expected a contiguous CUDA int32 tensor ({B}, >= 1 + 3 m_max)")
+        rs = recs.shape[1]
+    return cs, rs
+
+
+def stream_push(st, chunk, recs=None, m_max=0, words_live=0):
+    """Appends chunk (B, n) fp32 (device; unit inner stride) to the ring of the stream state st and advances `written`.  recs (B, >= 1 + 3 m_max)
+    int32 on the device: per row a count and that many (window, frame, word id) triples, appended to the word ring.  words_live: ring slots from
+    the oldest record a window still needs to the newest (the host's count).  A call outside the envelope (1 <= B <= 4, n >= 1, R >= A + n,
+    words_live + m_max <= W) is refused by the library (RuntimeError naming the envelope); nothing is launched."""
+    _stream_check(st)
+    _f32(chunk, "chunk")
+    n = chunk.shape[1] if chunk.dim() == 2 else 0
+    cs, rs = _push_operands(st, chunk, n, "n", recs, m_max)
+    call("tg_stream_push", _p(chunk), cs, n, _p(recs if m_max > 0 else None), rs, int(m_max), int(words_live), _p(st["ring"]), _p(st["written"]),
+         _p(st["words"]), _p(st["n_words"]), st["B"], st["R"], st["A"], st["W"], _stream())
+
+
+def stream_stage(st, text_out=None, audio_out=None):
+    """The inputs of the window whose index is st['win'][0]: audio_out (B, A) fp32 = the window's samples from the ring, zeros where none have been
+    pushed yet; text_out (B, T) int64 = per frame the id of the last pushed record of that window, else 0.  Device buffers written in place."""
+    _stream_check(st)
+    _stage_outputs(st, text_out, audio_out)
     call("tg_stream_stage", _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(st["win"]), st["B"], st["R"], st["S"], st["A"],
          st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
 
@@ -2087,16 +2101,7 @@ def pool_push(st, chunk, n, recs=None, m_max=0, words_live=0):
     B, n_max = st["B"], max(n, default=0)
     if len(n) != B:
         raise ValueError(f"n: {len(n)} chunk lengths for {B} rows")
-    if chunk.dim() != 2 or chunk.shape[0] != B or chunk.shape[1] < n_max or (chunk.shape[1] > 1 and chunk.stride(1) != 1):
-        raise ValueError(f"chunk: expected ({B}, >= {n_max}) with unit inner stride, got {tuple(chunk.shape)} strides {chunk.stride()}")
-    cs = chunk.stride(0) if B > 1 else max(chunk.shape[1], 1)
-    if n_max > 0 and (cs < n_max or (B - 1) * cs + n_max > _room(chunk)):
-        raise ValueError("chunk: rows overlap or exceed the tensor")
-    rs = 0
-    if m_max > 0:
-        if not (isinstance(recs, torch.Tensor) and recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 2 and recs.is_contiguous() and recs.shape[0] == B):
-            raise TypeError(f"recs: expected a contiguous CUDA int32 tensor ({B}, >= 1 + 3 m_max)")
-        rs = recs.shape[1]
+    cs, rs = _push_operands(st, chunk, n_max, f">= {n_max}", recs, m_max)
     call("tg_pool_push", _p(chunk), cs, *(n + [0] * 4)[:4], _p(recs if m_max > 0 else None), rs, int(m_max), int(words_live), _p(st["ring"]),
          _p(st["written"]), _p(st["words"]), _p(st["n_words"]), B, st["R"], st["A"], st["W"], _stream())      # (B > 4: refused by the library)
 
@@ -2106,36 +2111,29 @@ def pool_stage(st, win, active, text_out=None, audio_out=None, entry="tg_pool_st
     audio_out / text_out that belong to the other rows are left as they are."""
     _stream_check(st)
     _dev_int(win, torch.int32, st["B"], "win"); _dev_int(active, torch.int32, st["B"], "active")
-    if audio_out is not None:
-        _flat(audio_out, "audio_out")
-        if tuple(audio_out.shape) != (st["B"], st["A"]):
-            raise ValueError(f"audio_out is {tuple(audio_out.shape)}, a window is {(st['B'], st['A'])}")
-    if text_out is not None:
-        _i64(text_out, "text_out")
-        if tuple(text_out.shape) != (st["B"], st["T"]) or not text_out.is_contiguous():
-            raise ValueError(f"text_out is {tuple(text_out.shape)}, a window's text is {(st['B'], st['T'])}, contiguous")
+    _stage_outputs(st, text_out, audio_out)
     call(entry, _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(win), _p(active), st["B"], st["R"], st["S"], st["A"],
          st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
+
+
+def _four_3d(**tensors):
+    """The four tensors of a hand-over (pool_handover, pool_handover_smooth, queue_handover), by name: flat fp32 on the device, three dimensions."""
+    for name, t in tensors.items():
+        _flat(t, name)
+        if t.dim() != 3:
+            raise ValueError(f"{name}: expected three dimensions, got {tuple(t.shape)}")
 
 
 def pool_handover(res, out, tail, seed, win, active, entry="tg_pool_handover"):
     """The tail of a window for the rows with active[b] != 0, one launch: out = res (B, T, D), cross-faded with tail (B, n_pre, D) where win[b] > 0
     (window_blend's arithmetic), tail = out's last n_pre frames, seed = the next window's seed -- (B, T, D + 1): make_pre_seq's layout, (B, n_pre,
     D): the frames themselves -- and win[b] += 1.  Nothing of an inactive row is written."""
-    for t, name in ((res, "res"), (out, "out"), (tail, "tail"), (seed, "seed")):
-        _flat(t, name)
-        if t.dim() != 3:
-            raise ValueError(f"{name}: expected three dimensions, got {tuple(t.shape)}")
+    _four_3d(res=res, out=out, tail=tail, seed=seed)
     B, T, D = out.shape
     n_pre = tail.shape[1]
     if tuple(res.shape) != (B, T, D) or tail.shape[0] != B or tail.shape[2] != D:
         raise ValueError(f"res {tuple(res.shape)} / tail {tuple(tail.shape)} do not belong to out {tuple(out.shape)}")
-    if tuple(seed.shape) == (B, T, D + 1):
-        layout = 0
-    elif tuple(seed.shape) == (B, n_pre, D):
-        layout = 1
-    else:
-        raise ValueError(f"seed is {tuple(seed.shape)}: expected {(B, T, D + 1)} (pre_seq) or {(B, n_pre, D)} (pre)")
+    layout = _seed_layout(seed, B, T, D, n_pre)
     _dev_int(win, torch.int32, B, "win"); _dev_int(active, torch.int32, B, "active")
     call(entry, _p(res), _p(out), _p(tail), _p(seed), layout, _p(win), _p(active), B, T, D, n_pre, _stream())
 
@@ -2188,10 +2186,7 @@ def pool_handover_smooth(res, out, tail, seed, win, active, proj):
     out = res, cross-faded with tail where win[b] > 0, frames [0, 3 n_pre) of out replaced by their cubic fit (proj: the fp64 tables of
     synthesize.projection_tables(n_pre); utterance_finish(smooth)'s bits on that window), tail = seed = out's last n_pre frames, win[b] += 1.
     Nothing of an inactive row is written.  3 n_pre > T - n_pre is refused by the library (RuntimeError naming the envelope), nothing is launched."""
-    for t, name in ((res, "res"), (out, "out"), (tail, "tail"), (seed, "seed")):
-        _flat(t, name)
-        if t.dim() != 3:
-            raise ValueError(f"{name}: expected three dimensions, got {tuple(t.shape)}")
+    _four_3d(res=res, out=out, tail=tail, seed=seed)
     B, T, D = out.shape
     n_pre = tail.shape[1]
     if tuple(res.shape) != (B, T, D) or tuple(tail.shape) != (B, n_pre, D) or tuple(seed.shape) != (B, n_pre, D):
@@ -2274,10 +2269,7 @@ def queue_handover(res, total, tail, seed, plan, q):
     window's seed ((R, T, D + 1): make_pre_seq's layout, (R, n_pre, D): the frames themselves); every row's rnd[b] += 1.  total: (N, F, D) with
     room for every window of every utterance.  Nothing else of an idle row is written."""
     rounds, R, N = _queue_check(q, plan)
-    for t, name in ((res, "res"), (total, "total"), (tail, "tail"), (seed, "seed")):
-        _flat(t, name)
-        if t.dim() != 3:
-            raise ValueError(f"{name}: expected three dimensions, got {tuple(t.shape)}")
+    _four_3d(res=res, total=total, tail=tail, seed=seed)
     _, T, D = res.shape
     n_pre = tail.shape[1]
     if res.shape[0] != R or tuple(tail.shape) != (R, n_pre, D) or total.shape[0] != N or total.shape[2] != D:

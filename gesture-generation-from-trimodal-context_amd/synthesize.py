@@ -57,7 +57,8 @@ csrc/queue.hip's two row-local kernels around one captured graph of the forward 
 
 Structure: the three window decoders are subclasses of _WindowDecoderBase (buffers, the eager / capture-once / replay skeleton, the pooled
 window, check_kept; _capture is the one place a graph is captured); the streams and the pool are subclasses of _StreamCore (constructor checks,
-a row's word records, the closing window); the five offline loops stay separate and share _seed_rows, _host_window_batch and _rows_result.
+a row's word records, the closing window); the offline models share one lock-step loop, _lock_step: a model brings
+its window(i) -- staging, forward, hand-over -- and the one rule that differs, write_idle.
 
 Audio that is not 16 kHz (input_sr= on every entry point above; resample_audio on its own): resampled on the device by csrc/resample.hip, the
 counterpart of the script's librosa.load(..., sr=16000) -- offline by one launch per batch, in the streams chunk by chunk with a carry and two
@@ -173,6 +174,56 @@ def _rows_result(total, n_win, stride, n_pre):
     return [res[b, :n * stride + n_pre] for b, n in enumerate(n_win)]
 
 
+def _n_windows(args, audios, audio_sr):
+    """The reference's window count of every utterance (synthesize.py:57-63)."""
+    return [num_windows(len(a) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate) for a in audios]
+
+
+def _lock_step(args, audios, audio_sr, dev, D, window, ub, device_opts, write_idle=False):
+    """The offline loop of every model: the utterances run in lock-step, step i is window min(i, n_win[b] - 1) of utterance b -- a finished
+    utterance idles on its last window.  window(i) stages step i's inputs (on the host, or from ub), runs the model with its hand-over and
+    returns the (B, T, D) device result; here it is written at frame i * stride of the stacked result (its first n_pre frames overwrite the
+    previous window's last n_pre with the cross-faded values, synthesize.py:145-153).  write_idle=False: an idling utterance's frames are not
+    written; True: every row is written on every step.  ub / device_opts (fade_out, joints, return_device): the on_device path's UtteranceBatch,
+    which sizes the result for its finish and makes the return value (_device_result); else one read-back (_rows_result)."""
+    T, n_pre = args.n_poses, args.n_pre_poses
+    stride, n_win = T - n_pre, _n_windows(args, audios, audio_sr)
+    total = torch.zeros(len(audios), max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), D, device=dev)
+    for i in range(max(n_win)):
+        out = window(i)
+        if write_idle:
+            total[:, i * stride:i * stride + T, :].copy_(out)
+        else:
+            for b, n in enumerate(n_win):
+                if i < n:
+                    total[b, i * stride:i * stride + T, :].copy_(out[b])
+    if ub is not None:
+        return _device_result(ub, total, *device_opts)
+    return _rows_result(total, n_win, stride, n_pre)
+
+
+class _FreshSeed:
+    """Seed and hand-over of the three models whose windows are fresh tensors (seq2seq, joint_embedding without a window decoder,
+    speech2gesture): self.pre (B, n_pre, D) is the next window's seed -- zeros or the seed poses on the first (synthesize.py:46-50) --, and
+    handover(i, out) cross-fades window i > 0 with the kept tail (:145-153), keeps its last n_pre frames and makes them the seed (:122-126).
+    seq2seq: that model also runs at n_pre == 0, with one zero row as `pre` and no blend and no tail."""
+
+    def __init__(self, B, T, n_pre, D, dev, seed_seqs, seq2seq=False):
+        self.T, self.n_pre, self.on = T, n_pre, n_pre > 0 or not seq2seq
+        self.pre = torch.zeros(B, max(n_pre, 1) if seq2seq else n_pre, D, device=dev)
+        if seed_seqs is not None and self.on:
+            self.pre[:, :n_pre].copy_(torch.as_tensor(_seed_rows(seed_seqs, n_pre), dtype=torch.float32))
+        self.tail = torch.zeros(B, n_pre, D, device=dev)
+
+    def handover(self, i, out):
+        if self.on:
+            if i > 0:
+                ops.window_blend(self.tail, out)
+            self.tail.copy_(out[:, self.T - self.n_pre:, :])
+            self.pre = self.tail.clone()
+        return out
+
+
 def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, device_opts=None):
     """The seq2seq branch for several utterances in lock-step; returns the stacked windows BEFORE seq2seq_smooth, one array per utterance.
     device_opts (fade_out, joints, return_device): the on_device path -- texts staged from the UtteranceBatch's plan, smoothing and fade-out in
@@ -181,15 +232,11 @@ def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
     B, T, n_pre, fps = len(audios), args.n_poses, args.n_pre_poses, args.motion_resampling_framerate
     if T != pose_decoder.n_frames or n_pre != pose_decoder.n_pre_poses:
         raise ValueError(f"seq2seq synthesis: args (n_poses, n_pre_poses) = {(T, n_pre)} but the model decodes {(pose_decoder.n_frames, pose_decoder.n_pre_poses)}")
-    stride, D = T - n_pre, pose_decoder.decoder.output_size
-    n_win = [num_windows(len(a) / audio_sr, T, n_pre, fps) for a in audios]
-    pre = torch.zeros(B, max(n_pre, 1), D, device=dev)
-    if seed_seqs is not None and n_pre > 0:                                      # synthesize.py:46-50
-        pre[:, :n_pre].copy_(torch.as_tensor(_seed_rows(seed_seqs, n_pre), dtype=torch.float32))
-    tail = torch.zeros(B, n_pre, D, device=dev)
+    D, n_win = pose_decoder.decoder.output_size, _n_windows(args, audios, audio_sr)
+    seed = _FreshSeed(B, T, n_pre, D, dev, seed_seqs, seq2seq=True)
     ub = None if device_opts is None else UtteranceBatch(args, lang_model, audios, words_list, dev, audio_sr)
-    total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), D, device=dev)
-    for i in range(max(n_win)):
+
+    def window(i):
         if ub is not None:
             lens = ub.seq_lens(i)
             text_dev = ub.text_buffer(max(lens))
@@ -201,18 +248,10 @@ def _seq2seq_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
             for b, t in enumerate(texts):
                 in_text[b, :len(t)] = t
             text_dev = torch.from_numpy(in_text).to(dev)
-        out = pose_decoder.synthesize(text_dev, lens, pre).contiguous()     # (B, T, D), synthesize.py:135-136
-        if i > 0 and n_pre > 0:
-            ops.window_blend(tail, out)                                          # :145-153
-        if n_pre > 0:
-            tail.copy_(out[:, T - n_pre:, :])
-            pre = tail.clone()                                                   # :122-126
-        for b in range(B):
-            if i < n_win[b]:                                                     # an idling utterance's frames are not written
-                total[b, i * stride:i * stride + T, :].copy_(out[b])
-    if ub is not None:
-        return _device_result(ub, total, *device_opts)
-    return _rows_result(total, n_win, stride, n_pre), n_win
+        return seed.handover(i, pose_decoder.synthesize(text_dev, lens, seed.pre).contiguous())     # (B, T, D), synthesize.py:135-136
+
+    res = _lock_step(args, audios, audio_sr, dev, D, window, ub, device_opts)
+    return res if ub is not None else (res, n_win)
 
 
 def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, device_opts=None):
@@ -226,33 +265,22 @@ def _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_li
                          f"from {dec.pre_pose_net[0].in_features // dec.pose_dim} seed poses")
     if pose_decoder.training:
         raise RuntimeError("joint_embedding synthesis: the model must be in eval mode (joint_embed.load_checkpoint_and_model leaves it so)")
-    stride, D = T - n_pre, dec.pose_dim
-    n_win = [num_windows(len(a) / audio_sr, T, n_pre, args.motion_resampling_framerate) for a in audios]
-    pre = torch.zeros(B, n_pre, D, device=dev)
-    if seed_seqs is not None:                                                   # synthesize.py:46-50
-        pre.copy_(torch.as_tensor(_seed_rows(seed_seqs, n_pre), dtype=torch.float32))
-    tail = torch.zeros(B, n_pre, D, device=dev)
+    n_win = _n_windows(args, audios, audio_sr)
+    seed = _FreshSeed(B, T, n_pre, dec.pose_dim, dev, seed_seqs)
     ub = None if device_opts is None else UtteranceBatch(args, lang_model, audios, words_list, dev, audio_sr)
-    total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), D, device=dev)
     if ub is not None:                                                          # device_opts: the on_device path (see _seq2seq_gestures_batch)
         text_dev, audio_dev = torch.zeros(B, T, dtype=torch.int64, device=dev), torch.zeros(B, ub.L, device=dev)
-    for i in range(max(n_win)):
+
+    def window(i):
         if ub is not None:
             ub.stage(i, text_dev, audio_dev)
+            text, audio = text_dev, audio_dev
         else:
-            text_dev, audio_dev = (t.to(dev) for t in _host_window_batch(args, lang_model, audios, words_list, n_win, i, audio_sr))
+            text, audio = (t.to(dev) for t in _host_window_batch(args, lang_model, audios, words_list, n_win, i, audio_sr))
         inject = None if eps_list is None else {"c.eps": torch.as_tensor(eps_list[i], dtype=torch.float32, device=dev)}
-        out = pose_decoder.synthesize(text_dev, audio_dev, pre, inject=inject).contiguous()                # (B, T, D), synthesize.py:133
-        if i > 0:
-            ops.window_blend(tail, out)                                          # :145-153
-        tail.copy_(out[:, T - n_pre:, :])
-        pre = tail.clone()                                                       # :122-126
-        for b in range(B):
-            if i < n_win[b]:                                                     # an idling utterance's frames are not written
-                total[b, i * stride:i * stride + T, :].copy_(out[b])
-    if ub is not None:
-        return _device_result(ub, total, *device_opts)
-    return _rows_result(total, n_win, stride, n_pre)
+        return seed.handover(i, pose_decoder.synthesize(text, audio, seed.pre, inject=inject).contiguous())     # (B, T, D), synthesize.py:133
+
+    return _lock_step(args, audios, audio_sr, dev, dec.pose_dim, window, ub, device_opts)
 
 
 def _capture(fn, state):
@@ -273,8 +301,8 @@ def _capture(fn, state):
 class _WindowDecoderBase:
     """What the window decoders share: the static buffers (text, audio, seed, tail, out and -- replay_draws -- draw), the window skeleton
     (_window: eager on the first window or without a graph, else captured once and replayed), the pooled window of a stream pool, and the
-    check a kept decoder passes before a stream or a synthesis call may use it.  A subclass gives its window() (the copies of ITS inputs into
-    the static buffers, then _window), _model_forward() -- the model on the static buffers, returning the (B, T, D) result or None if it
+    check a kept decoder passes before a stream or a synthesis call may use it.  A subclass gives its window() (ITS inputs, handed to _window
+    by the name of their static buffer), _model_forward() -- the model on the static buffers, returning the (B, T, D) result or None if it
     wrote self.out itself -- and, where the seed is not the plain `pre` (B, n_pre, D), seed() and _reseed().
     self.model is the network (self.gen and self.net: the names the decoders had for it)."""
 
@@ -329,7 +357,11 @@ class _WindowDecoderBase:
         handover = ops.pool_handover if self.B <= 4 else ops.wide_pool_handover           # (more than four rows: WideStreamPool)
         handover(self._model_forward().view(self.B, self.T, self.D), self.out, self.tail, self.pre, self.win, self.active)
 
-    def _window(self, first):
+    def _window(self, first, **inputs):
+        """inputs: the subclass's window() arguments by the name of their static buffer; each that is not None is copied into it first."""
+        for name, val in inputs.items():
+            if val is not None:
+                getattr(self, name).copy_(val, non_blocking=True)
         with torch.no_grad(), self.frozen:
             if first or not self.use_graph:
                 self._forward(first)
@@ -338,6 +370,18 @@ class _WindowDecoderBase:
                     self.graph = _capture(lambda: self._forward(False), (self.pre, self.tail, self.out))
                 self.graph.replay()
         return self.out
+
+    def _run_captured(self, name, fn, state, warm):
+        """fn() under the rule of the pooled, the queued and the previewed window: without a graph it runs eagerly; else it is ONE captured
+        graph, kept in the attribute `name`, from the first call on.  There is no eager first window in front of these, so the one eager
+        pass a capture needs (the weight-only operands of layers.FrozenWeights and the kernels' workspaces are made on first use and must stay
+        OUT of the graph) is warm(): fn's launches arranged by the caller so that they write nothing that counts.  state: _capture's."""
+        if not self.use_graph:
+            return fn()
+        if getattr(self, name) is None:
+            warm()
+            setattr(self, name, _capture(fn, state))
+        getattr(self, name).replay()
 
     def pool_buffers(self):
         """(active, win): the static (B,) int32 device buffers window_pooled reads -- the mask of the rows to run and every row's window index."""
@@ -360,20 +404,13 @@ class _WindowDecoderBase:
             w_buf.copy_(torch.as_tensor(win, dtype=torch.int32), non_blocking=True)
         if draw is not None:
             self.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
+        def warm():                                              # a pass with no row active: the hand-over then writes nothing
+            mask = a_buf.clone()
+            a_buf.zero_()
+            self._forward_pooled()
+            a_buf.copy_(mask)
         with torch.no_grad(), self.frozen:
-            if self.use_graph and self.graph_pooled is None:
-                # There is no eager first window here, so the one eager pass a capture needs in front of it (the weight-only operands of
-                # layers.FrozenWeights and the kernels' workspaces are made on first use and must stay OUT of the graph) runs with no row
-                # active: the hand-over then writes nothing
-                mask = a_buf.clone()
-                a_buf.zero_()
-                self._forward_pooled()
-                a_buf.copy_(mask)
-                self.graph_pooled = _capture(self._forward_pooled, (self.pre, self.tail, self.out, w_buf))
-            if self.use_graph:
-                self.graph_pooled.replay()
-            else:
-                self._forward_pooled()
+            self._run_captured("graph_pooled", self._forward_pooled, (self.pre, self.tail, self.out, w_buf), warm)
         return self.out
 
     # -------------------------------------------------------------------------------------------------------------- queue
@@ -406,13 +443,7 @@ class _WindowDecoderBase:
         self.queue_buffers()
         self._queue_stage(q)
         with torch.no_grad(), self.frozen:
-            if self.use_graph:
-                if self.graph_queue is None:
-                    self._forward_queue()                        # the eager pass a capture needs in front of it (see window_pooled); it writes self.res only
-                    self.graph_queue = _capture(self._forward_queue, (self.res,))
-                self.graph_queue.replay()
-            else:
-                self._forward_queue()
+            self._run_captured("graph_queue", self._forward_queue, (self.res,), self._forward_queue)     # (the warm-up pass writes self.res only)
         ops.queue_handover(self.res, q.total, self.tail, self.pre, q.plan, q.dev)
 
     # -------------------------------------------------------------------------------------------------------------- preview
@@ -476,13 +507,8 @@ class _WindowDecoderBase:
                     for n, t in zip(self._seed_names, real[0]):
                         setattr(self, n, t)
                     self.tail = real[1]
-            elif self.use_graph:
-                if self.graph_preview is None:
-                    self._forward_preview()                      # the eager pass a capture needs in front of it (see window_pooled); it writes what a preview may
-                    self.graph_preview = _capture(self._forward_preview, ())
-                self.graph_preview.replay()
             else:
-                self._forward_preview()
+                self._run_captured("graph_preview", self._forward_preview, (), self._forward_preview)     # (the warm-up pass writes what a preview may)
         return pv["out"]
 
     def preview(self, win=None, draw=None, after=None):
@@ -544,15 +570,7 @@ class WindowDecoder(_WindowDecoderBase):
     def window(self, in_text, in_audio, vid, first, draw=None):
         """One window for the whole batch.  Inputs may be CPU or GPU tensors, or None: self.text / self.audio were filled in place
         (UtteranceBatch.stage); returns the (B, T, D) output buffer (device, overwritten by the next call)."""
-        if in_text is not None:
-            self.text.copy_(in_text, non_blocking=True)
-        if in_audio is not None:
-            self.audio.copy_(in_audio, non_blocking=True)
-        if vid is not None:
-            self.vid.copy_(vid, non_blocking=True)
-        if draw is not None:
-            self.draw.copy_(draw, non_blocking=True)
-        return self._window(first)
+        return self._window(first, text=in_text, audio=in_audio, vid=vid, draw=draw)
 
 
 class JointEmbedWindowDecoder(_WindowDecoderBase):
@@ -592,13 +610,7 @@ class JointEmbedWindowDecoder(_WindowDecoderBase):
     def window(self, in_text, in_audio, first, draw=None):
         """One window for the whole batch.  Inputs may be CPU or GPU tensors, or None: self.text / self.audio were filled in place
         (UtteranceBatch.stage); returns the (B, T, D) output buffer (device, overwritten by the next call)."""
-        if in_text is not None:
-            self.text.copy_(in_text, non_blocking=True)
-        if in_audio is not None:
-            self.audio.copy_(in_audio, non_blocking=True)
-        if draw is not None:
-            self.draw.copy_(torch.as_tensor(draw, dtype=torch.float32), non_blocking=True)
-        return self._window(first)
+        return self._window(first, text=in_text, audio=in_audio, draw=None if draw is None else torch.as_tensor(draw, dtype=torch.float32))
 
 
 class Seq2SeqWindowDecoder(_WindowDecoderBase):
@@ -682,11 +694,7 @@ class Seq2SeqWindowDecoder(_WindowDecoderBase):
     def window(self, in_text=None, in_len=None, first=False):
         """One window for the whole batch.  in_text (B, Te) / in_len (B,) int64, CPU or GPU tensors, or None: self.text / self.len were
         filled in place (ops.stream_stage_text); returns the (B, T, D) output buffer (device, overwritten by the next call)."""
-        if in_text is not None:
-            self.text.copy_(in_text, non_blocking=True)
-        if in_len is not None:
-            self.len.copy_(in_len, non_blocking=True)
-        return self._window(first)
+        return self._window(first, text=in_text, len=in_len)
 
 
 def _kept_decoder(who, kind, d, model, batch, T, n_pre, rows="row(s)", **built_for):
@@ -696,6 +704,19 @@ def _kept_decoder(who, kind, d, model, batch, T, n_pre, rows="row(s)", **built_f
         raise ValueError(f"{who}: window_decoder must be a {kind.__name__} built for this model, {batch} {rows}, (n_poses, n_pre_poses) = {(T, n_pre)}"
                          + "".join(f", {k} = {v}" for k, v in built_for.items()))
     return d
+
+
+def _decoder_stage(dec, ub, args, lang_model, audios, words_list, audio_sr):
+    """stage(i) -> the (text, audio) arguments of dec.window for lock-step step i: the on_device path (ub) writes the decoder's static buffers
+    in place and hands over (None, None); the host path makes the CPU tensors of _host_window_batch."""
+    n_win = _n_windows(args, audios, audio_sr)
+
+    def stage(i):
+        if ub is None:
+            return _host_window_batch(args, lang_model, audios, words_list, n_win, i, audio_sr)
+        ub.stage(i, dec.text, dec.audio)
+        return None, None
+    return stage
 
 
 def _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, window_decoder,
@@ -713,23 +734,10 @@ def _joint_embed_window_gestures_batch(args, pose_decoder, lang_model, audios, w
         dec = JointEmbedWindowDecoder(args, pose_decoder, B, next(pose_decoder.parameters()).device, graph=False, replay_draws=eps_list is not None,
                                       audio_sr=audio_sr)
     dec.seed(_seed_rows(seed_seqs, n_pre))
-    stride = T - n_pre
-    n_win = [num_windows(len(a) / audio_sr, T, n_pre, args.motion_resampling_framerate) for a in audios]
     ub = None if device_opts is None else UtteranceBatch(args, lang_model, audios, words_list, dec.dev, audio_sr)
-    total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), dec.D, device=dec.dev)
-    for i in range(max(n_win)):
-        if ub is not None:                                                       # the on_device path: straight into the decoder's static buffers
-            ub.stage(i, dec.text, dec.audio)
-            t_in = a_in = None
-        else:
-            t_in, a_in = _host_window_batch(args, lang_model, audios, words_list, n_win, i, audio_sr)
-        out = dec.window(t_in, a_in, first=(i == 0), draw=None if eps_list is None else eps_list[i])
-        for b in range(B):
-            if i < n_win[b]:                                                     # an idling utterance's frames are not written
-                total[b, i * stride:i * stride + T, :].copy_(out[b])
-    if ub is not None:
-        return _device_result(ub, total, *device_opts)
-    return _rows_result(total, n_win, stride, n_pre)
+    stage = _decoder_stage(dec, ub, args, lang_model, audios, words_list, audio_sr)
+    window = lambda i: dec.window(*stage(i), first=(i == 0), draw=None if eps_list is None else eps_list[i])
+    return _lock_step(args, audios, audio_sr, dec.dev, dec.D, window, ub, device_opts)
 
 
 def spec_slice_length(n_poses=34, fps=15, sr=16000):
@@ -945,8 +953,7 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
         raise ValueError(f"speech2gesture synthesis: audio_sr = {audio_sr}; the spectrogram is defined for {melspec.SR} Hz audio")
     dev = next(pose_decoder.parameters()).device
     B, T, n_pre, fps = len(audios), args.n_poses, args.n_pre_poses, args.motion_resampling_framerate
-    stride, width, need = T - n_pre, spec_slice_length(T, fps), spectrogram_length(T, fps)
-    n_win = [num_windows(len(a) / audio_sr, T, n_pre, fps) for a in audios]
+    width, need, n_win = spec_slice_length(T, fps), spectrogram_length(T, fps), _n_windows(args, audios, audio_sr)
     starts = [[spec_window_start(i, len(a) / audio_sr, melspec.N_MELS, T, n_pre, fps) for i in range(n)] for a, n in zip(audios, n_win)]
     for a, st in zip(audios, starts):
         got = min(width, melspec.n_frames(len(a)) - st[-1])
@@ -959,44 +966,34 @@ def _s2g_gestures_batch(args, pose_decoder, audios, seed_seqs, audio_sr, spec_pa
     specs = [melspec.extract_melspectrogram(a if isinstance(a, torch.Tensor) else np.asarray(a, dtype=np.float32), melspec.SR, pad_mode=spec_pad_mode,
                                             device=dev) for a in audios]               # (a device tensor: audio resampled on the device)
     D = pose_decoder.final_out.out_channels
-    pre = torch.zeros(B, n_pre, D, device=dev)
-    if seed_seqs is not None:                                                   # synthesize.py:46-50
-        pre.copy_(torch.as_tensor(_seed_rows(seed_seqs, n_pre), dtype=torch.float32))
-    tail = torch.zeros(B, n_pre, D, device=dev)
+    seed = _FreshSeed(B, T, n_pre, D, dev, seed_seqs)
     ub = None
     if device_opts is not None:                                                 # the on_device path: slices cut by ops.spec_stage from the packed spectrograms
         ub = UtteranceBatch(args, None, audios, None, dev, audio_sr)
         ub.set_spectrograms(specs)
         spec_dev = torch.zeros(B, melspec.N_MELS, width, device=dev, dtype=specs[0].dtype)
-    total = torch.zeros(B, max(n_win) * stride + n_pre if ub is None else ub.frames(device_opts[0]), D, device=dev)
+
+    def window(i):
+        if ub is not None:
+            ub.stage_spec(i, spec_dev)
+            widths = ub.spec_widths(i, width)
+            pieces = [spec_dev[b, :, :widths[b]] for b in range(B)]
+        else:
+            a0 = [st[min(i, len(st) - 1)] for st in starts]                 # finished utterances idle on their last window
+            pieces = [specs[b][:, a0[b]:a0[b] + width] for b in range(B)]   # :90-92 (a slice at the spectrogram's end is one frame short)
+        out = torch.empty(B, T, D, device=dev)
+        for w in sorted({p.shape[1] for p in pieces}):
+            idx = [b for b in range(B) if pieces[b].shape[1] == w]
+            out[idx] = pose_decoder(torch.stack([pieces[b] for b in idx]), seed.pre[idx])     # (b, T, D), synthesize.py:138
+        return seed.handover(i, out)
+
     was_training = pose_decoder.training
     pose_decoder.eval()
     try:
         with torch.no_grad():
-            for i in range(max(n_win)):
-                if ub is not None:
-                    ub.stage_spec(i, spec_dev)
-                    widths = ub.spec_widths(i, width)
-                    pieces = [spec_dev[b, :, :widths[b]] for b in range(B)]
-                else:
-                    a0 = [st[min(i, len(st) - 1)] for st in starts]                 # finished utterances idle on their last window
-                    pieces = [specs[b][:, a0[b]:a0[b] + width] for b in range(B)]   # :90-92 (a slice at the spectrogram's end is one frame short)
-                out = torch.empty(B, T, D, device=dev)
-                for w in sorted({p.shape[1] for p in pieces}):
-                    idx = [b for b in range(B) if pieces[b].shape[1] == w]
-                    out[idx] = pose_decoder(torch.stack([pieces[b] for b in idx]), pre[idx])     # (b, T, D), synthesize.py:138
-                if i > 0:
-                    ops.window_blend(tail, out)                                 # :145-153
-                tail.copy_(out[:, T - n_pre:, :])
-                pre = tail.clone()                                              # :122-126
-                for b in range(B):
-                    if i < n_win[b]:                                            # an idling utterance's frames are not written
-                        total[b, i * stride:i * stride + T, :].copy_(out[b])
+            return _lock_step(args, audios, audio_sr, dev, D, window, ub, device_opts)
     finally:
         pose_decoder.train(was_training)
-    if ub is not None:
-        return _device_result(ub, total, *device_opts)
-    return _rows_result(total, n_win, stride, n_pre)
 
 
 def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, vids=None, seed_seqs=None, audio_sr=16000,
@@ -1052,7 +1049,6 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
         return _joint_embed_gestures_batch(args, pose_decoder, lang_model, audios, words_list, seed_seqs, audio_sr, eps_list, dopts)
     dev = next(pose_decoder.parameters()).device
     B = len(audios)
-    n_win = [num_windows(len(a) / audio_sr, args.n_poses, args.n_pre_poses, args.motion_resampling_framerate) for a in audios]
     dec = WindowDecoder(args, pose_decoder, B, dev, graph=graph, replay_draws=_draws is not None)
     dec.seed(_seed_rows(seed_seqs, args.n_pre_poses))
     vid = None
@@ -1062,22 +1058,12 @@ def generate_gestures_batch(args, pose_decoder, lang_model, audios, words_list, 
             if not vids[b]:
                 vids[b] = random.randrange(pose_decoder.z_obj.n_words)
         vid = torch.as_tensor(vids, dtype=torch.int64)
-    stride = args.n_poses - args.n_pre_poses
     ub = UtteranceBatch(args, lang_model, audios, words_list, dev, audio_sr) if on_device else None
-    total = torch.zeros(B, max(n_win) * stride + args.n_pre_poses if ub is None else ub.frames(fade_out), dec.D, device=dev)
-    for i in range(max(n_win)):
-        if ub is not None:                                         # straight into the decoder's static buffers; the speaker ids go up once
-            ub.stage(i, dec.text, dec.audio)
-            out = dec.window(None, None, vid if i == 0 else None, first=(i == 0), draw=None if _draws is None else _draws[i])
-        else:
-            out = dec.window(*_host_window_batch(args, lang_model, audios, words_list, n_win, i, audio_sr), vid, first=(i == 0),
-                             draw=None if _draws is None else _draws[i])
-        # out_list[-1][:-n_pre] + blended window == write the whole window at frame i*stride (its first n_pre frames overwrite
-        # the previous window's last n_pre frames with the cross-faded values)
-        total[:, i * stride:i * stride + args.n_poses, :].copy_(out)
-    if ub is not None:
-        return _device_result(ub, total, *dopts)
-    return _rows_result(total, n_win, stride, args.n_pre_poses)
+    stage = _decoder_stage(dec, ub, args, lang_model, audios, words_list, audio_sr)
+    # (on_device: the speaker ids go up once)
+    window = lambda i: dec.window(*stage(i), vid if ub is None or i == 0 else None, first=(i == 0), draw=None if _draws is None else _draws[i])
+    # write_idle=True: an idling row overwrites its utterance's last n_pre frames with its re-run window's cross-faded ones
+    return _lock_step(args, audios, audio_sr, dev, dec.D, window, ub, dopts, write_idle=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------ queue
@@ -2014,15 +2000,20 @@ class StreamPool(_StreamCore):
         """The active rows' inputs of their own windows, straight into the decoder's static buffers."""
         ops.pool_stage(self.state, self.win, self.active, self.dec.text, self.dec.audio)
 
-    def _round(self, mask):
-        """One window for the rows of `mask`: the mask (and the rows' draws) go up by a small copy, then stage -> window_pooled."""
+    def _send_round(self, mask):
+        """The mask goes up by a small copy; returns the rows' replayed draws for window_pooled to send up (behind the staging), or None."""
         if self._draw_host is not None:
             for b, a in enumerate(mask):
                 if a:
                     self._draw_host[b] = torch.as_tensor(self._draws[b][self.next_window[b]], dtype=torch.float32).reshape(-1)
         self.active.copy_(torch.tensor(mask, dtype=torch.int32), non_blocking=True)
+        return None if self._draw_host is None else self._draw_host.clone()
+
+    def _round(self, mask):
+        """One window for the rows of `mask`: the mask and the rows' draws go up (_send_round), then stage -> window_pooled."""
+        draw = self._send_round(mask)
         self._stage()
-        out = self.dec.window_pooled(draw=None if self._draw_host is None else self._draw_host.clone())
+        out = self.dec.window_pooled(draw=draw)
         for b, a in enumerate(mask):
             if a:
                 self.next_window[b] += 1
@@ -2055,31 +2046,35 @@ class StreamPool(_StreamCore):
         One upload, one ops.pool_push, then the rounds of pool_rounds.  Returns {slot: frames} for the pushed slots: the (k * stride, D) device
         view of the frames that became final (k windows of that slot completed; k = 0: an empty result); numpy=True reads them back;
         joints=True gives (frames, fp64 joint positions (k * stride, 10, 3))."""
-        B = self.B
         rows, words = self._take(chunks)
         recs, late = self._records(words)                                   # (may refuse; nothing has changed yet)
-        n = [len(rows[b]) if b in rows else 0 for b in range(B)]
-        host = np.zeros((B, max(n)), np.float32)
+        n = [len(rows[b]) if b in rows else 0 for b in range(self.B)]
+        fullest = max((self._live_slots(b) + len(r) for b, r in enumerate(recs) if r), default=0)      # slots of the fullest word ring after the push
+        n = self._send(rows, n, recs, fullest)
+        for b in range(self.B):
+            self.pushed[b] += n[b]
+            self.late_words[b] += late[b]
+        return {b: self._result(*fr, numpy) for b, fr in self._emit(list(rows), joints).items()}
+
+    def _send(self, rows, n, recs, fullest):
+        """The chunks {row: samples} (n: their lengths per row) and the records recs go up -- one dense (B, max n) upload and the records'
+        table -- and are appended to the rows' rings; the records are noted.  Returns the 16 kHz samples every row got."""
+        host = np.zeros((self.B, max(n)), np.float32)
         for b, c in rows.items():
             host[b, :n[b]] = c
         dst = (self.chunk_buf if self.rs is None else self.rs["stage"])[:, :max(n)]
         dst.copy_(torch.from_numpy(host), non_blocking=True)
-        fullest = max((self._live_slots(b) + len(r) for b, r in enumerate(recs) if r), default=0)      # slots of the fullest word ring after the push
         table, m_max = self._commit_records(recs)
         if self.rs is not None:                                             # input_sr samples -> every row's new 16 kHz samples, in chunk_buf
             n, dst = self._resample(dst, n), self.chunk_buf
         self._feed(dst, n, table, m_max, max(0, fullest - m_max))
-        for b in range(B):
-            self.late_words[b] += late[b]
-        return {b: self._result(*fr, numpy) for b, fr in self._emit(list(rows), joints).items()}
+        return n
 
     def _feed(self, chunk, n, table, m_max, words_live):
         """n[b] 16 kHz samples of chunk row b and the push's records go to row b's rings (nothing to do if a resampled push made no sample
         final and brought no records)."""
         if max(n) > 0 or m_max > 0:
             ops.pool_push(self.state, chunk, n, table, m_max, words_live)
-        for b in range(self.B):
-            self.pushed[b] += n[b]
 
     def _emit(self, slots, joints):
         """Runs the rounds of the windows that have become complete; {slot: (frames (k * stride, D), joint positions or None)} for `slots`:
@@ -2115,6 +2110,7 @@ class StreamPool(_StreamCore):
             # and the windows they complete run like a push's -- the other rows have none pending -- in front of the closing frames
             n = self._resample(None, [0] * self.B, flush=(b,))
             self._feed(self.chunk_buf, n, None, 0, 0)
+            self.pushed[b] += n[b]                                  # (only the flushed row got samples)
             self._head[b] = self._emit([b], joints)[b]
         n_win, k = self._windows_left(f"{type(self).__name__}.close: slot {b}", self.pushed[b], self.next_window[b])
         if k:
@@ -2322,8 +2318,8 @@ class WideStreamPool(StreamPool):
     def _stage(self):
         ops.wide_pool_stage(self.state, self.win, self.active, self.dec.text, self.dec.audio)
 
-    def _round(self, mask):
-        """One window for the rows of `mask`: the mask and the active rows' draws go up as ONE small copy, then stage -> window_pooled."""
+    def _send_round(self, mask):
+        """The mask and the active rows' draws go up as ONE small copy, into the decoder's round_buf."""
         B, dec = self.B, self.dec
         i = self._slot_to_fill("round")
         host = self._round_host[i].numpy()
@@ -2335,21 +2331,11 @@ class WideStreamPool(StreamPool):
         host[host.size - B:].view(np.int32)[:] = mask
         dec.round_buf.copy_(self._round_host[i], non_blocking=True)
         self._sent("round", i)
-        self._stage()
-        out = dec.window_pooled()
-        for b, a in enumerate(mask):
-            if a:
-                self.next_window[b] += 1
-                self._ran(b, self.next_window[b])
-        return out
 
-    def push(self, chunks, numpy=False, joints=False):
-        """StreamPool.push's arguments and result.  The header, the chunks and the records of every pushed row are packed into a pinned slot
-        (numpy copies), go up as one copy, and ops.wide_pool_push appends all rows in one launch; then the rounds of pool_rounds."""
-        B = self.B
-        rows, words = self._take(chunks)
-        recs, late = self._records(words)                                   # (may refuse; nothing has changed yet)
-        n, m = [len(rows[b]) if b in rows else 0 for b in range(B)], [len(r) for r in recs]
+    def _send(self, rows, n, recs, fullest):
+        """StreamPool._send for a wide pool: the header, the chunks and the records of every pushed row are packed into a pinned slot (numpy
+        copies), go up as one copy, and ops.wide_pool_push appends all rows in one launch."""
+        B, m = self.B, [len(r) for r in recs]
         lay = wide_push_layout(n, m)
         i = self._slot_to_fill("push")
         host = self._push_host[i].numpy()
@@ -2364,10 +2350,6 @@ class WideStreamPool(StreamPool):
                 table[3 * lay["record_off"][b]:3 * (lay["record_off"][b] + m[b])] = np.asarray(r, dtype=np.int32).reshape(-1)
         self._push_dev[i][:lay["total"]].copy_(self._push_host[i][:lay["total"]], non_blocking=True)
         self._sent("push", i)
-        fullest = max((self._live_slots(b) + len(r) for b, r in enumerate(recs) if r), default=0)      # slots of the fullest word ring after the push
         self._note_records(recs)
         ops.wide_pool_push(self.state, self._push_dev[i], lay, max(0, fullest - lay["m_max"]))
-        for b in range(B):
-            self.pushed[b] += n[b]
-            self.late_words[b] += late[b]
-        return {b: self._result(*fr, numpy) for b, fr in self._emit(list(rows), joints).items()}
+        return n

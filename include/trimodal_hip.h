@@ -855,7 +855,8 @@ int tg_queue_stage(const int32_t* sched, const int32_t* rnd, int32_t rounds, int
 int tg_queue_handover(const float* res, float* total, int64_t F, float* tail, float* seed, int32_t seed_layout, const int32_t* sched, int32_t* rnd,
                       int32_t rounds, const int32_t* win_off, int32_t R, int32_t N, int32_t T, int32_t D, int32_t n_pre, void* stream);
 
-/* Wide stream pool (csrc/stream_pool_wide.hip; synthesize.WideStreamPool; added under ABI 11 -- new symbols only): the stream pool's three
+/* Wide stream pool (csrc/stream_pool_wide.hip: the push; csrc/stream_pool.hip: stage and hand-over, tg_pool_*'s kernels and launchers with
+ * another row limit; synthesize.WideStreamPool; added under ABI 11 -- new symbols only): the stream pool's three
  * launches for 1 <= B <= 128 rows, with everything per row in device memory.  The state, the row bodies and every other bound are
  * tg_pool_*'s; for B <= 4 each entry writes what its tg_pool_* counterpart writes, bit for bit.  One workgroup (or grid column) per row, plain
  * loads and stores, no atomics, nothing waits on another workgroup; a row that is not selected leaves before any store and before any
