@@ -45,6 +45,20 @@ __device__ __forceinline__ void ring_push_row_from(int b, int n, int m, long wr,
     }
 }
 
+// The records' half of a push on its own, by a workgroup of THREADS threads: m records trip[0 .. 3 m) to row b's word ring at cnt mod W.  For
+// stream_pool_wide_rs.hip, whose workgroup is the resampler's (256 threads) and whose samples do not come from a chunk; it moves no counter.
+// (ring_push_row_from strides by 1024 and keeps its loop as it is: the kernels built from it are unchanged.)
+template <int THREADS>
+__device__ __forceinline__ void word_ring_append_row(int b, int m, long cnt, const int32_t* __restrict__ trip, int32_t* __restrict__ word_ring,
+                                                     int W) {
+    const int s0 = (int)(cnt % W);
+    for (int t = threadIdx.x; t < 3 * m; t += THREADS) {
+        int slot = s0 + t / 3;                                        // m <= W
+        if (slot >= W) slot -= W;
+        word_ring[((long)b * W + slot) * 3 + t % 3] = trip[t];
+    }
+}
+
 __device__ __forceinline__ void ring_push_row(int b, int n, int m, long wr, long cnt, const float* __restrict__ chunk, long chunk_stride,
                                               const int32_t* __restrict__ recs, int rec_stride, float* __restrict__ ring, int64_t* written,
                                               int32_t* __restrict__ word_ring, int64_t* n_words, int R, int W) {

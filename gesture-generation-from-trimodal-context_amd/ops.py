@@ -2307,15 +2307,16 @@ def resample(x, lengths, taps, L, M, K):
     return y, out_lengths
 
 
-def resample_state(B, taps, L, M, K, max_chunk, device):
+def resample_state(B, taps, L, M, K, max_chunk, device, stage=True):
     """The device-resident state of a streaming resampler of B rows: per row the carry of the last K - 1 input samples (zeros: the signal has
     not begun) and the int64 counters `consumed` (input samples) and `produced` (output samples); `stage` (B, max_chunk): where a host chunk
-    is uploaded.  out_stride: the most output samples one call can write per row -- ceil(max_chunk L / M) + 1, or what a flush adds."""
+    is uploaded -- None with stage=False (wide_pool_push_resampled reads its chunks from the packed push: 128 rows need no dense buffer).
+    out_stride: the most output samples one call can write per row -- ceil(max_chunk L / M) + 1, or what a flush adds."""
     _taps_check(taps, L, M, K)
     out_stride = max((int(max_chunk) * L + M - 1) // M, ((K // 2) * L + M - 1) // M) + 1
     return dict(B=int(B), L=int(L), M=int(M), K=int(K), taps=taps, max_chunk=int(max_chunk), out_stride=out_stride,
                 carry=torch.zeros(B, K - 1, device=device), consumed=torch.zeros(B, dtype=torch.int64, device=device),
-                produced=torch.zeros(B, dtype=torch.int64, device=device), stage=torch.zeros(B, int(max_chunk), device=device))
+                produced=torch.zeros(B, dtype=torch.int64, device=device), stage=torch.zeros(B, int(max_chunk), device=device) if stage else None)
 
 
 def resample_stream(rs, chunk, n, out, flush=()):
@@ -2349,6 +2350,36 @@ def resample_stream(rs, chunk, n, out, flush=()):
     assert rs["carry"].numel() == B * (rs["K"] - 1)
     call("tg_resample_stream", _p(chunk if n_max > 0 else None), cs, *(n + [0] * 4)[:4], mask, _p(rs["taps"]), rs["L"], rs["M"], rs["K"], _p(rs["carry"]),
          _p(rs["consumed"]), _p(rs["produced"]), _p(out), out.shape[1], B, _stream())      # (B > 4: refused by the library)
+
+
+# ------------------------------------------------------------------------------------------------- wide pool at any rate (csrc/stream_pool_wide_rs.hip)
+def wide_pool_push_resampled(st, rs, packed, lay, words_live=0, flush_row=None):
+    """resample_stream and wide_pool_push as ONE launch for up to 128 rows: packed / lay as for wide_pool_push, the chunks holding samples at
+    the input rate of the resampler state rs (as many rows as st; at most rs['max_chunk'] per row).  Row b resamples its chunk -- flush_row:
+    the one row whose input has ended, which also produces what is left, zeros past the end; None: no row -- and appends the 16 kHz samples
+    that became final, and its records, to its rings.  How many samples a row got is the host's to compute (synthesize.resampled_ready /
+    resampled_length on its own counts); a row with no samples and no records that is not flushed keeps every bit.  Outside the envelope
+    (1 <= B <= 128, a row with samples, records or the flush, R >= A + ceil((longest chunk + K/2 on a flush) L / M) + 1) the library refuses
+    (RuntimeError naming the envelope); nothing is launched."""
+    _stream_check(st)
+    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 1 and packed.is_contiguous()):
+        raise TypeError("packed: expected a flat contiguous CUDA uint8 tensor")
+    B = st["B"]
+    if lay["B"] != B or packed.numel() < lay["total"] or packed.data_ptr() % 16:
+        raise ValueError(f"packed: {packed.numel()} bytes for a layout of {lay['B']} rows and {lay['total']} bytes on a state of {B} rows")
+    if rs["B"] != B or lay["n_max"] > rs["max_chunk"]:
+        raise ValueError(f"rs: a resampler of {rs['B']} row(s) of at most {rs['max_chunk']} samples for {B} rows whose longest chunk has {lay['n_max']}")
+    flush = -1 if flush_row is None else int(flush_row)
+    if not -1 <= flush < B:
+        raise ValueError(f"flush_row: row {flush_row} of {B}")
+    _taps_check(rs["taps"], rs["L"], rs["M"], rs["K"])
+    _flat(rs["carry"], "carry"); _dev_int(rs["consumed"], torch.int64, B, "consumed"); _dev_int(rs["produced"], torch.int64, B, "produced")
+    assert rs["carry"].numel() == B * (rs["K"] - 1)
+    base = packed.data_ptr()
+    n_s, n_r = lay["n_samples"], lay["n_records"]
+    call("tg_wide_pool_push_resampled", base + lay["hdr"], base + lay["samples"] if n_s else None, n_s, base + lay["records"] if n_r else None, n_r,
+         lay["n_max"], lay["m_max"], int(words_live), flush, _p(rs["taps"]), rs["L"], rs["M"], rs["K"], _p(rs["carry"]), _p(rs["consumed"]),
+         _p(rs["produced"]), _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), B, st["R"], st["A"], st["W"], _stream())
 
 
 # ------------------------------------------------------------------------------------------------- stream preview (csrc/stream_preview.hip)

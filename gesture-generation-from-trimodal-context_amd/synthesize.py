@@ -1450,7 +1450,9 @@ class _StreamCore:
         self.state = ops.stream_state(self.B, R, self.S, self.A, word_ring, T, dev)
         self.chunk_buf = torch.zeros(self.B, chunk16 if self._dense_chunks else 0, device=dev)
         # the streaming resampler: device state (carry, counters) and the host's mirror of both counters per row, plain integers
-        self.rs = None if self.input_sr is None else ops.resample_state(self.B, *resample.device_taps(self.input_sr, dev), self.max_chunk, dev)
+        # (a stream without dense chunks reads its input from the packed push: no staging buffer either)
+        self.rs = None if self.input_sr is None else ops.resample_state(self.B, *resample.device_taps(self.input_sr, dev), self.max_chunk, dev,
+                                                                        stage=self._dense_chunks)
         self._rs_in, self._rs_out = [0] * self.B, [0] * self.B
         self._live, self._n_rec = [[] for _ in range(self.B)], [0] * self.B
         self._ones = torch.ones(self.B, dtype=torch.int32, device=dev)
@@ -1499,6 +1501,11 @@ class _StreamCore:
         has ended -- writes its new 16 kHz samples to chunk_buf[b].  Returns their counts per row, from the host's own counters by the
         integer expressions the kernel evaluates on the device's (resampled_ready / resampled_length); nothing is read back."""
         ops.resample_stream(self.rs, chunk, n, self.chunk_buf, flush)
+        return self._resampled(n, flush)
+
+    def _resampled(self, n, flush=()):
+        """The host's mirror of one resampling launch: row b took n[b] input samples (flush: the rows whose input has ended); advances
+        _rs_in / _rs_out and returns the 16 kHz samples every row got."""
         got = [0] * self.B
         for b in range(self.B):
             if n[b] or b in flush:
@@ -2076,6 +2083,12 @@ class StreamPool(_StreamCore):
         if max(n) > 0 or m_max > 0:
             ops.pool_push(self.state, chunk, n, table, m_max, words_live)
 
+    def _flush(self, b):
+        """Row b's input has ended: the resampler's remaining outputs of that row go to its ring.  Returns the 16 kHz samples every row got."""
+        n = self._resample(None, [0] * self.B, flush=(b,))
+        self._feed(self.chunk_buf, n, None, 0, 0)
+        return n
+
     def _emit(self, slots, joints):
         """Runs the rounds of the windows that have become complete; {slot: (frames (k * stride, D), joint positions or None)} for `slots`:
         device views of what became final."""
@@ -2108,8 +2121,7 @@ class StreamPool(_StreamCore):
         if self.rs is not None and self._head[b] is None:
             # the session's input has ended: the resampler's remaining outputs of this row (zeros past the end) go to its ring like a push,
             # and the windows they complete run like a push's -- the other rows have none pending -- in front of the closing frames
-            n = self._resample(None, [0] * self.B, flush=(b,))
-            self._feed(self.chunk_buf, n, None, 0, 0)
+            n = self._flush(b)
             self.pushed[b] += n[b]                                  # (only the flushed row got samples)
             self._head[b] = self._emit([b], joints)[b]
         n_win, k = self._windows_left(f"{type(self).__name__}.close: slot {b}", self.pushed[b], self.next_window[b])
@@ -2269,10 +2281,11 @@ class WideStreamPool(StreamPool):
     small copy into the decoder's round_buf.  push() never reads from the device.  A refused call (ValueError) leaves the pool as it was.
 
     args.model 'multimodal_context' only, 16 kHz input only and no preview(): the other models' window decoders, the stream resampler and the
-    preview chain are built for four rows (each refusal says so)."""
+    preview chain are built for four rows (each refusal says so).  WideResampledStreamPool is this pool for audio at another rate."""
     _max_rows = 128
     _models = ("multimodal_context",)
     _dense_chunks = False
+    _resamples = False                               # whether input_sr is served (WideResampledStreamPool: by the fused resample-and-push)
 
     def _refusal(self, model):
         few = "its window decoder holds four rows: use {} (1 to 4 slots)"
@@ -2281,10 +2294,11 @@ class WideStreamPool(StreamPool):
 
     def __init__(self, args, pose_decoder, lang_model, slots=128, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, ring=None,
                  window_decoder=None, _replay_draws=False, input_sr=None):
-        if input_sr is not None and int(input_sr) != resample.TARGET_SR:
+        if not self._resamples and input_sr is not None and int(input_sr) != resample.TARGET_SR:
             raise ValueError(f"WideStreamPool: input_sr = {input_sr}: the stream resampler takes its chunk lengths by value for four rows -- push "
-                             f"{resample.TARGET_SR} Hz audio (resample_audio converts whole signals)")
-        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, graph, word_ring, ring, window_decoder, _replay_draws, input_sr=None)
+                             f"{resample.TARGET_SR} Hz audio (resample_audio converts whole signals), or use WideResampledStreamPool")
+        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, graph, word_ring, ring, window_decoder, _replay_draws,
+                         input_sr=input_sr if self._resamples else None)
         B, pin = self.B, self.dev.type == "cuda"
         host = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, pin_memory=pin)
         # a push: two pinned slots of the worst-case size (every row a full chunk and a full word ring) and a device buffer behind each
@@ -2312,8 +2326,8 @@ class WideStreamPool(StreamPool):
             self._copied[kind][i] = ev
 
     def preview(self, slot, fade_out=False, joints=False, numpy=False):
-        raise ValueError("WideStreamPool.preview: a wide pool has no preview -- the preview chain's kernels take their lengths by value for four "
-                         "rows (StreamPool.preview)")
+        raise ValueError(f"{type(self).__name__}.preview: a wide pool has no preview -- the preview chain's kernels take their lengths by value for "
+                         "four rows (StreamPool.preview)")
 
     def _stage(self):
         ops.wide_pool_stage(self.state, self.win, self.active, self.dec.text, self.dec.audio)
@@ -2335,6 +2349,13 @@ class WideStreamPool(StreamPool):
     def _send(self, rows, n, recs, fullest):
         """StreamPool._send for a wide pool: the header, the chunks and the records of every pushed row are packed into a pinned slot (numpy
         copies), go up as one copy, and ops.wide_pool_push appends all rows in one launch."""
+        i, lay = self._upload(rows, n, recs)
+        ops.wide_pool_push(self.state, self._push_dev[i], lay, max(0, fullest - lay["m_max"]))
+        return n
+
+    def _upload(self, rows, n, recs):
+        """One tick on its way up: packs it into the pinned slot whose turn it is, starts the one copy and notes the records.  Returns
+        (the slot, the layout)."""
         B, m = self.B, [len(r) for r in recs]
         lay = wide_push_layout(n, m)
         i = self._slot_to_fill("push")
@@ -2351,5 +2372,42 @@ class WideStreamPool(StreamPool):
         self._push_dev[i][:lay["total"]].copy_(self._push_host[i][:lay["total"]], non_blocking=True)
         self._sent("push", i)
         self._note_records(recs)
-        ops.wide_pool_push(self.state, self._push_dev[i], lay, max(0, fullest - lay["m_max"]))
-        return n
+        return i, lay
+
+
+class WideResampledStreamPool(WideStreamPool):
+    """WideStreamPool for audio at any rate the resampler serves: the same interface, limits and refusals (multimodal_context only, 1 to 128
+    slots, open / push / close, late_words, window_decoder=, _replay_draws, no preview) with a required input_sr, as StreamPool(input_sr=...)
+    sits beside StreamPool.  max_chunk counts INPUT samples and the ring is sized from the 16 kHz count.  Everything push() and close()
+    returned for the session in slot b, concatenated, is row b of generate_gestures_batch(on_device=True, input_sr=input_sr) on a batch of
+    `slots` utterances with that session's input-rate audio in row b and the same draws, bit for bit, whatever the other rows hold or do,
+    for lengths where stream_matches_offline holds on the resampled length.
+
+    A tick is still one upload and one launch (csrc/stream_pool_wide_rs.hip): the packed push holds input-rate chunks, and
+    ops.wide_pool_push_resampled resamples every row and appends what became final to its ring -- per slot a resampler row (carry and two
+    counters, reset by open()).  pushed[b] advances by the 16 kHz count of the host's integer mirror; a push that makes no sample final still
+    advances the carry.  close(slot) sends a flush-only tick -- the header alone, flush_row = slot --, and the windows the flush completes
+    run like a push's, in front of the closing frames (StreamPool.close).  Nothing is read from the device.
+    input_sr None or 16000 is WideStreamPool itself: its launches, its bits, no resampler state."""
+    _resamples = True
+
+    def __init__(self, args, pose_decoder, lang_model, input_sr, slots=128, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, ring=None,
+                 window_decoder=None, _replay_draws=False):
+        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, graph, word_ring, ring, window_decoder, _replay_draws,
+                         input_sr=input_sr)
+
+    def _tick(self, rows, n, recs, words_live, flush=()):
+        i, lay = self._upload(rows, n, recs)
+        ops.wide_pool_push_resampled(self.state, self.rs, self._push_dev[i], lay, words_live, flush_row=flush[0] if flush else None)
+        return self._resampled(n, flush)
+
+    def _send(self, rows, n, recs, fullest):
+        """WideStreamPool._send with input-rate chunks: one packed upload, one fused resample-and-push.  Returns the 16 kHz samples every row
+        got, from the host's mirror."""
+        if self.rs is None:
+            return super()._send(rows, n, recs, fullest)
+        return self._tick(rows, n, recs, max(0, fullest - max(len(r) for r in recs)))
+
+    def _flush(self, b):
+        """StreamPool._flush as a tick of its own: the header alone, no samples and no records, with flush_row = b."""
+        return self._tick({}, [0] * self.B, [[] for _ in range(self.B)], 0, flush=(b,))

@@ -881,6 +881,24 @@ int tg_wide_pool_stage(const float* ring, const int64_t* written, const int32_t*
  * 1 <= B <= 128. */
 int tg_wide_pool_handover(const float* res, float* out, float* tail, float* seed, int32_t seed_layout, int32_t* win, const int32_t* active,
                           int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream);
+/* Wide stream pool at any sample rate (csrc/stream_pool_wide_rs.hip; synthesize.WideResampledStreamPool; added under ABI 11 -- new symbols
+ * only): tg_resample_stream and tg_wide_pool_push as ONE launch for 1 <= B <= 128 rows, one workgroup per row.  hdr, samples and recs are
+ * tg_wide_pool_push's packed pieces, with n_b counting INPUT-rate samples; taps [L][K], carry [B][K - 1], consumed [B] and produced [B] are
+ * tg_resample_stream's, ring, written, word_ring and n_words tg_pool_push's.  Row b takes samples[off_b .. off_b + n_b) into its resampler
+ * row; the outputs that became final -- n_new = ((consumed - K/2) L - 1) div M + 1 - produced, or, for the one row b == flush_row whose input
+ * has ended, ceil(consumed L / M) - produced with zeros past the end -- go to its ring at (written[b] + r) mod R, bit for bit the samples
+ * tg_resample gives for the whole signal; the carry is rewritten, the row's m_b records are appended to its word ring, and consumed,
+ * produced, written (+ n_new) and n_words (+ m_b) advance.  A row with n_b == 0, m_b == 0 that is not flush_row is not touched; a row with
+ * records only keeps its resampler row.  flush_row: -1, or the row to flush.  The host mirrors every counter with the same integer
+ * expressions; nothing is read back.  For B <= 4 the call writes what tg_resample_stream followed by tg_pool_push write.  The kernel clamps
+ * the header as tg_wide_pool_push's does and n_new to [0, ceil((n_max + (K/2 on a flush)) L / M) + 1].
+ * Envelope: 1 <= B <= 128, -1 <= flush_row < B, tg_resample's L, M, K, n_max >= 0, m_max >= 0, n_max >= 1 or m_max >= 1 or flush_row >= 0,
+ * A >= 1, A + ceil((n_max + (K/2 on a flush)) L / M) + 1 <= R <= 2^30, 1 <= W <= 1024, words_live + m_max <= W, n_max <= samples_len <=
+ * B n_max, m_max <= recs_len <= B m_max; samples (recs) may be null if n_max (m_max) is 0; refused otherwise, nothing is launched. */
+int tg_wide_pool_push_resampled(const int32_t* hdr, const float* samples, int64_t samples_len, const int32_t* recs, int64_t recs_len, int32_t n_max,
+                                int32_t m_max, int32_t words_live, int32_t flush_row, const float* taps, int32_t L, int32_t M, int32_t K,
+                                float* carry, int64_t* consumed, int64_t* produced, float* ring, int64_t* written, int32_t* word_ring,
+                                int64_t* n_words, int32_t B, int32_t R, int32_t A, int32_t W, void* stream);
 
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over

@@ -2,6 +2,7 @@
 of four (synthesize.StreamPool), full-size multimodal model, 160-sample pushes (10 ms of audio).
 
     python tools/wide_pool_bench.py [--sessions 4 32 128] [--strides 2] [--reps 3] [--out profiles/wide_pool.txt]
+    python tools/wide_pool_bench.py --input-sr 44100 [...] [--out profiles/wide_pool_rs.txt]
 
 S sessions are open; session i joins at tick (i * ticks per stride) // S, so the sessions' windows complete at phases spread over a stride
 (200 ticks) and a tick completes windows of few sessions or of none.  A tick pushes 160 samples to every open session, two ways:
@@ -13,7 +14,13 @@ Every tick is timed on the host: t_call = the push calls have returned, t_done =
   push with windows   median t_done of the ticks that complete at least one window
   per window          sum of t_done over those ticks / windows they emitted
   memory              torch.cuda.memory_allocated delta around construction, S opens, one tick and one closing window, per session
-Medians over all passes; the spread is the range of the per-pass medians.  No words are pushed (the word path is a few integers per tick)."""
+Medians over all passes; the spread is the range of the per-pass medians.  No words are pushed (the word path is a few integers per tick).
+
+--input-sr SR (a multiple of 100) runs the pool for audio at another rate instead (synthesize.WideResampledStreamPool,
+csrc/stream_pool_wide_rs.hip): a tick is still 10 ms, SR / 100 input samples per session, and three drivers alternate:
+  wide_rs  one WideResampledStreamPool(SR) of S slots: one packed upload, one fused resample-and-push launch, then the rounds
+  fours_rs S / 4 StreamPool(input_sr=SR) of four slots: per pool an upload, a resample launch and a push launch
+  wide16   one WideStreamPool on the same ticks' audio resampled beforehand (160 samples): what the resampler itself costs"""
 import argparse
 import importlib
 import os
@@ -40,10 +47,13 @@ class Lang:
 
 
 class Wide:
-    """S sessions on one WideStreamPool."""
+    """S sessions on one WideStreamPool -- or, input_sr: on one WideResampledStreamPool, `chunk` input samples per push."""
 
-    def __init__(self, args, net, n):
-        self.pool = syn.WideStreamPool(args, net, Lang(), slots=n, max_chunk=CHUNK)
+    def __init__(self, args, net, n, input_sr=None, chunk=CHUNK):
+        if input_sr is None:
+            self.pool = syn.WideStreamPool(args, net, Lang(), slots=n, max_chunk=chunk)
+        else:
+            self.pool = syn.WideResampledStreamPool(args, net, Lang(), input_sr, slots=n, max_chunk=chunk)
         self.n, self.open = n, []
 
     def join(self):
@@ -62,8 +72,8 @@ class Wide:
 class Fours:
     """S sessions on S / 4 StreamPools of four."""
 
-    def __init__(self, args, net, n):
-        self.pools = [syn.StreamPool(args, net, Lang(), slots=4, max_chunk=CHUNK) for _ in range(n // 4)]
+    def __init__(self, args, net, n, input_sr=None, chunk=CHUNK):
+        self.pools = [syn.StreamPool(args, net, Lang(), slots=4, max_chunk=chunk, input_sr=input_sr) for _ in range(n // 4)]
         self.n, self.open = n, []
 
     def join(self):
@@ -86,7 +96,7 @@ class Fours:
 
 def run_ticks(drv, block, ticks, join_at=()):
     """`ticks` ticks -> per tick (t_call us, t_done us, windows emitted)."""
-    out = []
+    out, block = [], getattr(drv, "block", block)                        # (--input-sr: every driver brings the block of its own rate)
     for t in range(ticks):
         for _ in range(join_at.count(t) if join_at else 0):
             drv.join()
@@ -115,7 +125,10 @@ def main():
     ap.add_argument("--strides", type=int, default=2)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--input-sr", type=int, default=None)
     a = ap.parse_args()
+    if a.input_sr is not None and (a.input_sr % 100 or a.input_sr == SR):
+        raise SystemExit("--input-sr: a multiple of 100 other than 16000")
     if not torch.cuda.is_available():
         raise SystemExit("wide_pool_bench needs a GPU")
     if any(n % 4 or not 4 <= n <= 128 for n in a.sessions):
@@ -128,26 +141,41 @@ def main():
     G = pkg.PoseGenerator(args, 27, V, 300, None, pkg.Vocab.speakers(1371)).to(dev).eval()
     S, A = syn.stream_geometry(args)
     per_stride = S // CHUNK
-    lines = [f"tools/wide_pool_bench.py --sessions {' '.join(map(str, a.sessions))} --strides {a.strides} --reps {a.reps}: {CHUNK}-sample pushes to every open "
-             f"session per tick, {per_stride} ticks per stride, phases spread over a stride; wide and fours passes alternate; host clock, us"]
+    chunk_in = CHUNK if a.input_sr is None else a.input_sr // 100
+    lines = [f"tools/wide_pool_bench.py --sessions {' '.join(map(str, a.sessions))} --strides {a.strides} --reps {a.reps}"
+             f"{'' if a.input_sr is None else f' --input-sr {a.input_sr}'}: {chunk_in}-sample pushes to every open "
+             f"session per tick, {per_stride} ticks per stride, phases spread over a stride; the drivers' passes alternate; host clock, us"]
+    # (key, name, driver class, input_sr): the drivers of a run, the first against the others
+    if a.input_sr is None:
+        kinds = [("wide", "one WideStreamPool({n})", Wide, None), ("fours", "{q} StreamPool(4)", Fours, None)]
+    else:
+        kinds = [("wide_rs", "one WideResampledStreamPool({n})", Wide, a.input_sr), ("fours_rs", "{q} StreamPool(4, input_sr)", Fours, a.input_sr),
+                 ("wide16", "one WideStreamPool({n}), 16 kHz", Wide, None)]
     rng = lambda v: f"{min(v):.0f} .. {max(v):.0f}"
     for n in a.sessions:
-        block = (0.1 * np.random.default_rng(n).standard_normal((n, CHUNK))).astype(np.float32)
+        block = (0.1 * np.random.default_rng(n).standard_normal((n, chunk_in))).astype(np.float32)
+        block16 = block if a.input_sr is None else np.stack(syn.resample_audio(list(block), a.input_sr))        # (SR / 100 samples -> 160)
 
-        def made(kind):
-            drv = kind(args, G, n)
+        def new(kind, sr):
+            drv = kind(args, G, n) if a.input_sr is None else kind(args, G, n, sr, chunk_in if sr else CHUNK)
+            drv.block = block if sr or a.input_sr is None else block16
+            return drv
+
+        def made(kind, sr):
+            drv = new(kind, sr)
             for _ in range(n):
                 drv.join()
-            drv.tick(block)
+            drv.tick(drv.block)
             drv.first_window()
             return drv
 
-        made(Wide); made(Fours)                                          # process-wide workspaces are made on first use: charged to neither
+        for _, _, kind, sr in kinds:                                     # process-wide workspaces are made on first use: charged to nobody
+            made(kind, sr)
         mem = {}
-        for kind in (Wide, Fours):
-            mem[kind.__name__], keep = allocated(lambda: made(kind))
+        for key, _, kind, sr in kinds:
+            mem[key], keep = allocated(lambda: made(kind, sr))
             del keep
-        drivers = {"wide": Wide(args, G, n), "fours": Fours(args, G, n)}
+        drivers = {key: new(kind, sr) for key, _, kind, sr in kinds}
         join_at = [(i * per_stride) // n for i in range(n)]
         for drv in drivers.values():                                     # the join phase, the first (eager, captured) windows, one more stride
             run_ticks(drv, block, -(-A // CHUNK) + 2 * per_stride, join_at)
@@ -162,16 +190,18 @@ def main():
                 st["per_win"].append(sum(t[1] for t in busy) / sum(t[2] for t in busy))
                 st["shape"] = (len(idle), len(busy), sum(t[2] for t in busy))
         lines.append(f"S = {n} sessions:")
-        for key, name in (("wide", f"one WideStreamPool({n})"), ("fours", f"{n // 4} StreamPool(4)")):
-            st = stat[key]
-            lines.append(f"  {name:24s} push, no window {med(st['all_call']):8.1f} us (per pass {rng(st['call'])});  push with windows, to completion "
+        for key, name, _, _ in kinds:
+            st, name = stat[key], name.format(n=n, q=n // 4)
+            lines.append(f"  {name:{24 if a.input_sr is None else 36}s} push, no window {med(st['all_call']):8.1f} us (per pass {rng(st['call'])});  push with windows, to completion "
                          f"{med(st['all_done']):8.1f} us ({rng(st['done'])});  per emitted window {med(st['per_win']):8.1f} us ({rng(st['per_win'])});  "
-                         f"memory {mem['Wide' if key == 'wide' else 'Fours']:8.2f} MiB = {mem['Wide' if key == 'wide' else 'Fours'] / n:6.2f} per session;  "
+                         f"memory {mem[key]:8.2f} MiB = {mem[key] / n:6.2f} per session;  "
                          f"per pass {st['shape'][0]} ticks without and {st['shape'][1]} with windows, {st['shape'][2]} windows")
-        w, f = stat["wide"], stat["fours"]
-        lines.append(f"  wide / fours: push, no window {med(w['all_call']) / med(f['all_call']):.3f};  push with windows {med(w['all_done']) / med(f['all_done']):.3f};  "
-                     f"per emitted window {med(w['per_win']) / med(f['per_win']):.3f}")
-        print("\n".join(lines[-4:]), flush=True)
+        w = stat[kinds[0][0]]
+        for key, _, _, _ in kinds[1:]:
+            f = stat[key]
+            lines.append(f"  {kinds[0][0]} / {key}: push, no window {med(w['all_call']) / med(f['all_call']):.3f};  push with windows "
+                         f"{med(w['all_done']) / med(f['all_done']):.3f};  per emitted window {med(w['per_win']) / med(f['per_win']):.3f}")
+        print("\n".join(lines[-2 * len(kinds):]), flush=True)
         del drivers
         torch.cuda.empty_cache()
     if a.out:
