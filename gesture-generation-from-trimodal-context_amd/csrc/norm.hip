@@ -1,24 +1,41 @@
 // BatchNorm1d (train + eval), channel-last [rows][C].  HBM-bound streaming kernels: coalesced 16-byte accesses,
 // per-thread fp64 partial sums, one LDS reduction per workgroup, one fp64 atomic per (workgroup, channel).
 // Statistics of "groups" stacked reference forward calls are kept apart (each call normalises with its own batch).
-#include "common.hpp"
+// The arithmetic -- moments, element formulas, the 16-byte loops, the LDS fold -- is csrc/bn_math.hpp; this file is the kernels' data movement.
+#include "bn_math.hpp"
 
 namespace tg {
 
-// ws layout: [groups][2][C] doubles = (sum, sum of squares)
-__global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__ x, int rows_per_group, int C, double* __restrict__ ws) {
+// ---- the streaming chain: zero | reduce | finalize | apply forward, zero | reduce | apply backward.
+// Sums of statistics group blockIdx.y into ws [groups][2][C] doubles.  BWD false: (sum x, sum x^2); true: (sum dz, sum dz xhat) with
+// dz = dy act'(z) and the group's statistics at mean / rstd + g C (tg_bn_backward: one group)
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy, int rows_per_group, int C,
+                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                        const float* __restrict__ gamma, const float* __restrict__ beta, float slope,
+                                                        double* __restrict__ ws) {
     __shared__ double sh[2][256];
     const int g = blockIdx.y;
     const int rpi = 256 / C;                 // rows per iteration of this workgroup (C <= 256)
     const int c = threadIdx.x % C, rsub = threadIdx.x / C;
-    const float* xg = x + (long)g * rows_per_group * C;
+    const long base = (long)g * rows_per_group * C;
     double s = 0.0, ss = 0.0;
-    if (rsub < rpi)
+    if (rsub < rpi) {
+        float mu = 0.f, rs = 0.f, ga = 0.f, be = 0.f;
+        if constexpr (BWD) { mu = mean[g * C + c]; rs = rstd[g * C + c]; ga = gamma[c]; be = beta[c]; }
         for (long r = (long)blockIdx.x * rpi + rsub; r < rows_per_group; r += (long)gridDim.x * rpi) {
-            const float v = xg[r * C + c];
-            s += v;
-            ss += (double)v * v;
+            const float v = x[base + r * C + c];
+            if constexpr (BWD) {
+                float xh, dz;
+                bn_bwd_element(v, dy[base + r * C + c], mu, rs, ga, be, slope, xh, dz);
+                s += dz;
+                ss += (double)dz * xh;
+            } else {
+                s += v;
+                ss += (double)v * v;
+            }
         }
+    }
     sh[0][threadIdx.x] = s;
     sh[1][threadIdx.x] = ss;
     __syncthreads();
@@ -30,27 +47,24 @@ __global__ __launch_bounds__(256) void bn_stats_kernel(const float* __restrict__
     }
 }
 
-// 16-byte version (C % 4 == 0, C divides 1024): a thread's four channels never change (its element index advances by a multiple of C), so
-// the partial sums are eight fp64 registers and four independent 16-byte loads are in flight per thread -- the scalar kernel above had one
+// 16-byte version (C % 4 == 0, C divides 1024): four independent 16-byte loads in flight per thread -- the scalar kernel above has one
 // 4-byte load in flight per thread and ran the audio encoder's 21 MB BatchNorm at 0.75 TB/s.
-__global__ __launch_bounds__(256) void bn_stats_vec_kernel(const float* __restrict__ x, long rows_per_group, int C, double* __restrict__ ws) {
+template <bool BWD>
+__global__ __launch_bounds__(256) void bn_reduce_vec_kernel(const float* __restrict__ x, const float* __restrict__ dy, long rows_per_group, int C,
+                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta, float slope,
+                                                            double* __restrict__ ws) {
     __shared__ double sh[2][256];
     const int g = blockIdx.y;
-    const f32x4* xg = reinterpret_cast<const f32x4*>(x + (long)g * rows_per_group * C);
     const long total4 = rows_per_group * C / 4;
     const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
     const int c0 = (int)((i0 * 4) % C);
-    if ((int)threadIdx.x < C) { sh[0][threadIdx.x] = 0.0; sh[1][threadIdx.x] = 0.0; }
-    __syncthreads();
-    double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (long i = i0; i < total4; i += step) {
-        const f32x4 v = xg[i];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { s[q] += v[q]; ss[q] += (double)v[q] * v[q]; }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { atomicAdd(&sh[0][c0 + q], s[q]); atomicAdd(&sh[1][c0 + q], ss[q]); }
+    bn_lds_zero(sh[0], sh[1], C);
+    BnCh ch = {};
+    if constexpr (BWD) ch = bn_channels(mean + g * C, rstd + g * C, gamma, beta, c0);
+    double s[4], ss[4];
+    bn_accumulate<BWD>(reinterpret_cast<const f32x4*>(x) + g * total4, BWD ? reinterpret_cast<const f32x4*>(dy) + g * total4 : nullptr, ch, slope, i0, step, total4, s, ss);
+    bn_lds_fold(s, ss, sh[0], sh[1], c0);
     __syncthreads();
     if ((int)threadIdx.x < C) {
         atomicAdd(&ws[((long)g * 2 + 0) * C + threadIdx.x], sh[0][threadIdx.x]);
@@ -63,19 +77,12 @@ __global__ void bn_finalize_kernel(const double* __restrict__ ws, int rows_per_g
                                    int64_t* __restrict__ nbt, float eps, float momentum, int repeats) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < C) {
-        const double n = (double)rows_per_group;
         float rm = rmean ? rmean[c] : 0.f, rv = rvar ? rvar[c] : 0.f;
         for (int g = 0; g < groups; ++g) {
-            const double m = ws[((long)g * 2 + 0) * C + c] / n;
-            double var = ws[((long)g * 2 + 1) * C + c] / n - m * m;
-            if (var < 0.0) var = 0.0;
-            mean[g * C + c] = (float)m;
-            rstd[g * C + c] = (float)(1.0 / sqrt(var + (double)eps));
-            const double unbiased = rows_per_group > 1 ? var * n / (n - 1.0) : var;
-            for (int q = 0; q < repeats; ++q) {   // the same batch normalised by `repeats` identical forward calls
-                rm = (1.f - momentum) * rm + momentum * (float)m;
-                rv = (1.f - momentum) * rv + momentum * (float)unbiased;
-            }
+            const BnMoments st = bn_moments(ws[((long)g * 2 + 0) * C + c], ws[((long)g * 2 + 1) * C + c], (double)rows_per_group, eps);
+            mean[g * C + c] = st.mf;
+            rstd[g * C + c] = st.rs;
+            bn_running(rm, rv, st, momentum, repeats);
         }
         if (rmean) rmean[c] = rm;
         if (rvar) rvar[c] = rv;
@@ -92,7 +99,8 @@ __global__ void bn_eval_stats_kernel(const float* __restrict__ rmean, const floa
     }
 }
 
-// y = act((x - mean) * rstd * gamma + beta); four channels per thread (C % 4 == 0 on this path), scalar otherwise
+// y = act((x - mean) * rstd * gamma + beta); four channels per thread (C % 4 == 0 is all this path asks, so the channel is recomputed per
+// element), scalar otherwise
 template <bool VEC>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, float* __restrict__ y, long rows, int C,
                                                        int rows_per_group, const float* __restrict__ mean,
@@ -109,171 +117,54 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
             const f32x4 xv = *reinterpret_cast<const f32x4*>(x + e);
             f32x4 o;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float xh = (xv[q] - mean[g * C + c + q]) * rstd[g * C + c + q];
-                o[q] = act_fn(xh * gamma[c + q] + beta[c + q], slope);
-            }
+            for (int q = 0; q < 4; ++q) o[q] = bn_fwd_element(xv[q], mean[g * C + c + q], rstd[g * C + c + q], gamma[c + q], beta[c + q], slope);
             *reinterpret_cast<f32x4*>(y + e) = o;
         } else {
-            const float xh = (x[e] - mean[g * C + c]) * rstd[g * C + c];
-            y[e] = act_fn(xh * gamma[c] + beta[c], slope);
+            y[e] = bn_fwd_element(x[e], mean[g * C + c], rstd[g * C + c], gamma[c], beta[c], slope);
         }
     }
 }
 
-// ws: [2][C] doubles = (sum dz, sum dz * xhat), dz = dy * act'(z)
-__global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ x, int rows, int C,
-                                                            const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                            float slope, double* __restrict__ ws) {
-    __shared__ double sh[2][256];
-    const int rpi = 256 / C;
-    const int c = threadIdx.x % C, rsub = threadIdx.x / C;
-    double s = 0.0, sx = 0.0;
-    if (rsub < rpi) {
-        const float mu = mean[c], rs = rstd[c], ga = gamma[c], be = beta[c];
-        for (long r = (long)blockIdx.x * rpi + rsub; r < rows; r += (long)gridDim.x * rpi) {
-            const float xh = (x[r * C + c] - mu) * rs;
-            const float z = xh * ga + be;
-            const float dz = dy[r * C + c] * (z > 0.f ? 1.f : slope);
-            s += dz;
-            sx += (double)dz * xh;
-        }
-    }
-    sh[0][threadIdx.x] = s;
-    sh[1][threadIdx.x] = sx;
-    __syncthreads();
-    if (threadIdx.x < C) {
-        double a = 0.0, b = 0.0;
-        for (int q = 0; q < rpi; ++q) { a += sh[0][q * C + c]; b += sh[1][q * C + c]; }
-        atomicAdd(&ws[c], a);
-        atomicAdd(&ws[C + c], b);
-    }
-}
-
+// ws: [2][C] doubles = (sum dz, sum dz * xhat) of bn_reduce_kernel<true>
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ dx,
                                                            long rows, int C, const float* __restrict__ mean,
                                                            const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float slope,
                                                            const double* __restrict__ ws, float* __restrict__ dgamma,
                                                            float* __restrict__ dbeta) {
-    if (blockIdx.x == 0 && (int)threadIdx.x < C) {
-        const int c = threadIdx.x;
-        if (dbeta) dbeta[c] += (float)ws[c];
-        if (dgamma) dgamma[c] += (float)ws[C + c];
-    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < C) bn_param_grads(dgamma, dbeta, threadIdx.x, ws[threadIdx.x], ws[C + threadIdx.x]);
     const long total = rows * C;
     const double inv_n = 1.0 / (double)rows;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int c = (int)(e % C);
         const float rs = rstd[c], ga = gamma[c];
-        const float xh = (x[e] - mean[c]) * rs;
-        const float z = xh * ga + beta[c];
-        const float dz = dy[e] * (z > 0.f ? 1.f : slope);
-        // the two batch means are subtracted in fp64: rounding them to fp32 first would shift every element of the
-        // channel by the same amount, and the next layer's weight-gradient sum over ~1e6 rows amplifies that coherently
-        const double m1 = ws[c] * inv_n, m2 = ws[C + c] * inv_n;
-        dx[e] = (float)((double)(ga * rs) * ((double)dz - m1 - (double)xh * m2));
+        float xh, dz;
+        bn_bwd_element(x[e], dy[e], mean[c], rs, ga, beta[c], slope, xh, dz);
+        dx[e] = bn_dx_element(xh, dz, ga, rs, ws[c] * inv_n, ws[C + c] * inv_n);
     }
 }
 
-// 16-byte versions of the two backward kernels (same conditions as bn_stats_vec_kernel)
-__global__ __launch_bounds__(256) void bn_bwd_reduce_vec_kernel(const float* __restrict__ dy, const float* __restrict__ x, long rows, int C,
-                                                                const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                                const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                                float slope, double* __restrict__ ws) {
-    __shared__ double sh[2][256];
-    const long total4 = rows * C / 4;
-    const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
-    const int c0 = (int)((i0 * 4) % C);
-    if ((int)threadIdx.x < C) { sh[0][threadIdx.x] = 0.0; sh[1][threadIdx.x] = 0.0; }
-    __syncthreads();
-    float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { mu[q] = mean[c0 + q]; rs[q] = rstd[c0 + q]; ga[q] = gamma[c0 + q]; be[q] = beta[c0 + q]; }
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-    const f32x4* dy4 = reinterpret_cast<const f32x4*>(dy);
-    double s[4] = {0.0, 0.0, 0.0, 0.0}, sx[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (long i = i0; i < total4; i += step) {
-        const f32x4 xv = x4[i], dv = dy4[i];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float xh = (xv[q] - mu[q]) * rs[q];
-            const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
-            s[q] += dz;
-            sx[q] += (double)dz * xh;
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { atomicAdd(&sh[0][c0 + q], s[q]); atomicAdd(&sh[1][c0 + q], sx[q]); }
-    __syncthreads();
-    if ((int)threadIdx.x < C) {
-        atomicAdd(&ws[threadIdx.x], sh[0][threadIdx.x]);
-        atomicAdd(&ws[C + threadIdx.x], sh[1][threadIdx.x]);
-    }
-}
-
+// 16-byte version (same conditions as bn_reduce_vec_kernel)
 __global__ __launch_bounds__(256) void bn_bwd_apply_vec_kernel(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ dx,
                                                                long rows, int C, const float* __restrict__ mean,
                                                                const float* __restrict__ rstd, const float* __restrict__ gamma,
                                                                const float* __restrict__ beta, float slope,
                                                                const double* __restrict__ ws, float* __restrict__ dgamma,
                                                                float* __restrict__ dbeta) {
-    if (blockIdx.x == 0 && (int)threadIdx.x < C) {
-        const int c = threadIdx.x;
-        if (dbeta) dbeta[c] += (float)ws[c];
-        if (dgamma) dgamma[c] += (float)ws[C + c];
-    }
+    if (blockIdx.x == 0 && (int)threadIdx.x < C) bn_param_grads(dgamma, dbeta, threadIdx.x, ws[threadIdx.x], ws[C + threadIdx.x]);
     const long total4 = rows * C / 4;
     const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
     const int c0 = (int)((i0 * 4) % C);
-    const double inv_n = 1.0 / (double)rows;
-    float mu[4], rs[4], ga[4], be[4];
-    double m1[4], m2[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        mu[q] = mean[c0 + q]; rs[q] = rstd[c0 + q]; ga[q] = gamma[c0 + q]; be[q] = beta[c0 + q];
-        m1[q] = ws[c0 + q] * inv_n; m2[q] = ws[C + c0 + q] * inv_n;
-    }
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
-    const f32x4* dy4 = reinterpret_cast<const f32x4*>(dy);
-    f32x4* dx4 = reinterpret_cast<f32x4*>(dx);
-#pragma unroll 2
-    for (long i = i0; i < total4; i += step) {
-        const f32x4 xv = x4[i], dv = dy4[i];
-        f32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float xh = (xv[q] - mu[q]) * rs[q];
-            const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
-            o[q] = (float)((double)(ga[q] * rs[q]) * ((double)dz - m1[q] - (double)xh * m2[q]));     // fp64 means: see bn_bwd_apply_kernel
-        }
-        dx4[i] = o;
-    }
+    bn_dx_loop<2>(reinterpret_cast<const f32x4*>(x), reinterpret_cast<const f32x4*>(dy), reinterpret_cast<f32x4*>(dx),
+                  bn_channels(mean, rstd, gamma, beta, c0), bn_dx_means(ws, ws + C, c0, 1.0 / (double)rows), slope, i0, step, total4);
 }
 
 // ---- small tensors (the discriminator's and the autoencoder's BatchNorms: a few thousand rows): ONE workgroup does statistics,
 // running-stat update and normalisation in one launch -- the multi-kernel path costs four launches of ~5 us for microseconds of work.
 // 16-byte accesses throughout: with C a multiple of 4 that divides 4096, thread t always sees the same four channels (its element
-// index advances by 4096 per iteration), so the per-thread partial sums are eight fp64 registers and the loads of successive
-// iterations are independent requests in flight together.
+// index advances by 4096 per iteration).  LDS fp64 atomics of the fold: 1024 / (C / 4) adders per channel, once per pass.
 constexpr int BN_SMALL_THREADS = 1024;
 constexpr long BN_SMALL_MAX = 1L << 19;          // elements (2 MB): stays in L2 between the two passes
-
-// per-channel totals of the four per-thread partial pairs: threads with equal (t * 4) % C hold the same channels
-__device__ __forceinline__ void bn_small_reduce(const double (&a)[4], const double (&b)[4], double* sh_a, double* sh_b, int C) {
-    // sh_a / sh_b: [C] accumulators in LDS, zeroed by the caller
-    const int c0 = (threadIdx.x * 4) % C;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        atomicAdd(&sh_a[c0 + q], a[q]);          // LDS fp64 atomics: 1024 / (C / 4) adders per channel, once per pass
-        atomicAdd(&sh_b[c0 + q], b[q]);
-    }
-    __syncthreads();
-}
 
 __global__ __launch_bounds__(BN_SMALL_THREADS) void bn_small_train_kernel(
     const float* __restrict__ x, float* __restrict__ y, int rows_per_group, int C, int groups, float* __restrict__ mean, float* __restrict__ rstd,
@@ -286,47 +177,21 @@ __global__ __launch_bounds__(BN_SMALL_THREADS) void bn_small_train_kernel(
     if ((int)threadIdx.x < C) { rm = rmean ? rmean[threadIdx.x] : 0.f; rv = rvar ? rvar[threadIdx.x] : 0.f; }
     const long total4 = (long)rows_per_group * C / 4;
     for (int g = 0; g < groups; ++g) {
-        const f32x4* xg = reinterpret_cast<const f32x4*>(x + (long)g * rows_per_group * C);
-        if ((int)threadIdx.x < C) { sh_a[threadIdx.x] = 0.0; sh_b[threadIdx.x] = 0.0; }
+        const f32x4* xg = reinterpret_cast<const f32x4*>(x) + g * total4;
+        bn_lds_zero(sh_a, sh_b, C);
+        double s[4], ss[4];
+        bn_accumulate<false>(xg, nullptr, BnCh{}, 1.f, threadIdx.x, BN_SMALL_THREADS, total4, s, ss);
+        bn_lds_fold(s, ss, sh_a, sh_b, c0);
         __syncthreads();
-        double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-        for (long i = threadIdx.x; i < total4; i += BN_SMALL_THREADS) {
-            const f32x4 v = xg[i];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { s[q] += v[q]; ss[q] += (double)v[q] * v[q]; }
-        }
-        bn_small_reduce(s, ss, sh_a, sh_b, C);
         if ((int)threadIdx.x < C) {
             const int c = threadIdx.x;
-            const double n = (double)rows_per_group;
-            const double m = sh_a[c] / n;
-            double var = sh_b[c] / n - m * m;
-            if (var < 0.0) var = 0.0;
-            const float mf = (float)m, rs = (float)(1.0 / sqrt(var + (double)eps));
-            mean[g * C + c] = mf; rstd[g * C + c] = rs;
-            s_mean[c] = mf; s_rstd[c] = rs;
-            const double unbiased = rows_per_group > 1 ? var * n / (n - 1.0) : var;
-            for (int q = 0; q < repeats; ++q) {
-                rm = (1.f - momentum) * rm + momentum * mf;
-                rv = (1.f - momentum) * rv + momentum * (float)unbiased;
-            }
+            const BnMoments st = bn_moments(sh_a[c], sh_b[c], (double)rows_per_group, eps);
+            mean[g * C + c] = st.mf; rstd[g * C + c] = st.rs;
+            s_mean[c] = st.mf; s_rstd[c] = st.rs;
+            bn_running(rm, rv, st, momentum, repeats);
         }
         __syncthreads();
-        if (y) {
-            f32x4* yg = reinterpret_cast<f32x4*>(y + (long)g * rows_per_group * C);
-            float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { mu[q] = s_mean[c0 + q]; rs[q] = s_rstd[c0 + q]; ga[q] = gamma[c0 + q]; be[q] = beta[c0 + q]; }
-#pragma unroll 4
-            for (long i = threadIdx.x; i < total4; i += BN_SMALL_THREADS) {
-                const f32x4 v = xg[i];
-                f32x4 o;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) o[q] = act_fn((v[q] - mu[q]) * rs[q] * ga[q] + be[q], slope);   // association of bn_apply_kernel
-                yg[i] = o;
-            }
-        }
+        if (y) bn_y_loop<4>(xg, reinterpret_cast<f32x4*>(y) + g * total4, bn_channels(s_mean, s_rstd, gamma, beta, c0), slope, threadIdx.x, BN_SMALL_THREADS, total4);
         __syncthreads();
     }
     if ((int)threadIdx.x < C) {
@@ -342,49 +207,17 @@ __global__ __launch_bounds__(BN_SMALL_THREADS) void bn_small_bwd_kernel(
     float* __restrict__ dgamma, float* __restrict__ dbeta) {
     __shared__ double sh_a[256], sh_b[256];
     const int c0 = (threadIdx.x * 4) % C;
-    if ((int)threadIdx.x < C) { sh_a[threadIdx.x] = 0.0; sh_b[threadIdx.x] = 0.0; }
-    __syncthreads();
-    float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { mu[q] = mean[c0 + q]; rs[q] = rstd[c0 + q]; ga[q] = gamma[c0 + q]; be[q] = beta[c0 + q]; }
+    bn_lds_zero(sh_a, sh_b, C);
+    const BnCh ch = bn_channels(mean, rstd, gamma, beta, c0);
     const long total4 = (long)rows * C / 4;
     const f32x4* x4 = reinterpret_cast<const f32x4*>(x);
     const f32x4* dy4 = reinterpret_cast<const f32x4*>(dy);
-    double s[4] = {0.0, 0.0, 0.0, 0.0}, sx[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-    for (long i = threadIdx.x; i < total4; i += BN_SMALL_THREADS) {
-        const f32x4 xv = x4[i], dv = dy4[i];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float xh = (xv[q] - mu[q]) * rs[q];
-            const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
-            s[q] += dz;
-            sx[q] += (double)dz * xh;
-        }
-    }
-    bn_small_reduce(s, sx, sh_a, sh_b, C);
-    if ((int)threadIdx.x < C) {
-        if (dbeta) dbeta[threadIdx.x] += (float)sh_a[threadIdx.x];
-        if (dgamma) dgamma[threadIdx.x] += (float)sh_b[threadIdx.x];
-    }
-    double m1[4], m2[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { m1[q] = sh_a[c0 + q] / (double)rows; m2[q] = sh_b[c0 + q] / (double)rows; }
-    f32x4* dx4 = reinterpret_cast<f32x4*>(dx);
-#pragma unroll 4
-    for (long i = threadIdx.x; i < total4; i += BN_SMALL_THREADS) {
-        const f32x4 xv = x4[i], dv = dy4[i];
-        f32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float xh = (xv[q] - mu[q]) * rs[q];
-            const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
-            o[q] = (float)((double)(ga[q] * rs[q]) * ((double)dz - m1[q] - (double)xh * m2[q]));
-        }
-        dx4[i] = o;
-    }
+    double s[4], sx[4];
+    bn_accumulate<true>(x4, dy4, ch, slope, threadIdx.x, BN_SMALL_THREADS, total4, s, sx);
+    bn_lds_fold(s, sx, sh_a, sh_b, c0);
+    __syncthreads();
+    if ((int)threadIdx.x < C) bn_param_grads(dgamma, dbeta, threadIdx.x, sh_a[threadIdx.x], sh_b[threadIdx.x]);
+    bn_dx_loop<4>(x4, dy4, reinterpret_cast<f32x4*>(dx), ch, bn_dx_means(sh_a, sh_b, c0, 1.0 / (double)rows), slope, threadIdx.x, BN_SMALL_THREADS, total4);
 }
 
 // ---- two-launch BatchNorm (train forward: partial sums | finalize + apply; backward: partial sums | finalize + apply) --------------------
@@ -403,38 +236,16 @@ __global__ __launch_bounds__(256) void bn2_partial_kernel(const float* __restric
     __shared__ double sh_det[256][8];
     const int g = blockIdx.y, P = gridDim.x;
     const long total4 = rows_per_group * C / 4;
-    const long base4 = (long)g * total4;
     const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)P * 256;
     const int c0 = (int)((i0 * 4) % C);
-    if ((int)threadIdx.x < C) { sh[0][threadIdx.x] = 0.0; sh[1][threadIdx.x] = 0.0; }
-    __syncthreads();
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x) + base4;
-    double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
-    if (dy == nullptr) {
-#pragma unroll 4
-        for (long i = i0; i < total4; i += step) {
-            const f32x4 v = x4[i];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { s[q] += v[q]; ss[q] += (double)v[q] * v[q]; }
-        }
-    } else {
-        const f32x4* dy4 = reinterpret_cast<const f32x4*>(dy) + base4;
-        float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { mu[q] = mean[g * C + c0 + q]; rs[q] = rstd[g * C + c0 + q]; ga[q] = gamma[c0 + q]; be[q] = beta[c0 + q]; }
-#pragma unroll 4
-        for (long i = i0; i < total4; i += step) {
-            const f32x4 xv = x4[i], dv = dy4[i];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float xh = (xv[q] - mu[q]) * rs[q];
-                const float z = xh * ga[q] + be[q];
-                const float dz = dv[q] * (z > 0.f ? 1.f : slope);
-                s[q] += dz;
-                ss[q] += (double)dz * xh;
-            }
-        }
-    }
+    bn_lds_zero(sh[0], sh[1], C);
+    const f32x4* x4 = reinterpret_cast<const f32x4*>(x) + g * total4;
+    double s[4], ss[4];
+    if (dy == nullptr)
+        bn_accumulate<false>(x4, nullptr, BnCh{}, slope, i0, step, total4, s, ss);
+    else
+        bn_accumulate<true>(x4, reinterpret_cast<const f32x4*>(dy) + g * total4, bn_channels(mean + g * C, rstd + g * C, gamma, beta, c0), slope, i0, step,
+                            total4, s, ss);
     if (det) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) { sh_det[threadIdx.x][q] = s[q]; sh_det[threadIdx.x][4 + q] = ss[q]; }
@@ -446,8 +257,7 @@ __global__ __launch_bounds__(256) void bn2_partial_kernel(const float* __restric
             sh[0][c] = a; sh[1][c] = b;
         }
     } else {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { atomicAdd(&sh[0][c0 + q], s[q]); atomicAdd(&sh[1][c0 + q], ss[q]); }
+        bn_lds_fold(s, ss, sh[0], sh[1], c0);
     }
     __syncthreads();
     if ((int)threadIdx.x < C) {
@@ -507,17 +317,7 @@ __global__ __launch_bounds__(256) void bn2_fwd_apply_kernel(const float* __restr
         if ((int)threadIdx.x < C) { rm = rmean ? rmean[threadIdx.x] : 0.f; rv = rvar ? rvar[threadIdx.x] : 0.f; }
         for (int gg = 0; gg < groups; ++gg) {
             bn2_totals(part, gg, P, C, tot, sl);
-            if ((int)threadIdx.x < C) {
-                const int c = threadIdx.x;
-                const double m = tot[0][c] / n;
-                double var = tot[1][c] / n - m * m;
-                if (var < 0.0) var = 0.0;
-                const double unbiased = rows_per_group > 1 ? var * n / (n - 1.0) : var;
-                for (int q = 0; q < repeats; ++q) {
-                    rm = (1.f - momentum) * rm + momentum * (float)m;
-                    rv = (1.f - momentum) * rv + momentum * (float)unbiased;
-                }
-            }
+            if ((int)threadIdx.x < C) bn_running(rm, rv, bn_moments(tot[0][threadIdx.x], tot[1][threadIdx.x], n, eps), momentum, repeats);
             __syncthreads();
         }
         if ((int)threadIdx.x < C) {
@@ -529,31 +329,17 @@ __global__ __launch_bounds__(256) void bn2_fwd_apply_kernel(const float* __restr
     bn2_totals(part, g, P, C, tot, sl);
     if ((int)threadIdx.x < C) {
         const int c = threadIdx.x;
-        const double m = tot[0][c] / n;
-        double var = tot[1][c] / n - m * m;
-        if (var < 0.0) var = 0.0;
-        const float mf = (float)m, rs = (float)(1.0 / sqrt(var + (double)eps));
-        s_mean[c] = mf; s_rstd[c] = rs;
-        if (blockIdx.x == 0) { mean[g * C + c] = mf; rstd[g * C + c] = rs; }
+        const BnMoments st = bn_moments(tot[0][c], tot[1][c], n, eps);
+        s_mean[c] = st.mf; s_rstd[c] = st.rs;
+        if (blockIdx.x == 0) { mean[g * C + c] = st.mf; rstd[g * C + c] = st.rs; }
     }
     __syncthreads();
     if (y == nullptr) return;
     const long total4 = rows_per_group * C / 4;
     const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
     const int c0 = (int)((i0 * 4) % C);
-    float mu[4], rs[4], ga[4], be[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) { mu[q] = s_mean[c0 + q]; rs[q] = s_rstd[c0 + q]; ga[q] = gamma[c0 + q]; be[q] = beta[c0 + q]; }
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x) + (long)g * total4;
-    f32x4* y4 = reinterpret_cast<f32x4*>(y) + (long)g * total4;
-#pragma unroll 4
-    for (long i = i0; i < total4; i += step) {
-        const f32x4 v = x4[i];
-        f32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) o[q] = act_fn((v[q] - mu[q]) * rs[q] * ga[q] + be[q], slope);          // association of bn_apply_kernel
-        y4[i] = o;
-    }
+    bn_y_loop<4>(reinterpret_cast<const f32x4*>(x) + g * total4, reinterpret_cast<f32x4*>(y) + g * total4, bn_channels(s_mean, s_rstd, gamma, beta, c0), slope,
+                 i0, step, total4);
 }
 
 __global__ __launch_bounds__(256) void bn2_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x, float* __restrict__ dx,
@@ -570,43 +356,25 @@ __global__ __launch_bounds__(256) void bn2_bwd_apply_kernel(const float* __restr
             if ((int)threadIdx.x < C) { a += tot[0][threadIdx.x]; b += tot[1][threadIdx.x]; }
             __syncthreads();
         }
-        if ((int)threadIdx.x < C) {
-            if (dbeta) dbeta[threadIdx.x] += (float)a;
-            if (dgamma) dgamma[threadIdx.x] += (float)b;
-        }
+        if ((int)threadIdx.x < C) bn_param_grads(dgamma, dbeta, threadIdx.x, a, b);
     }
     bn2_totals(part, g, P, C, tot, sl);
     const long total4 = rows_per_group * C / 4;
     const long i0 = (long)blockIdx.x * 256 + threadIdx.x, step = (long)gridDim.x * 256;
     const int c0 = (int)((i0 * 4) % C);
-    const double inv_n = 1.0 / (double)rows_per_group;
-    float mu[4], rs[4], ga[4], be[4];
-    double m1[4], m2[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        mu[q] = mean[g * C + c0 + q]; rs[q] = rstd[g * C + c0 + q]; ga[q] = gamma[c0 + q]; be[q] = beta[c0 + q];
-        m1[q] = tot[0][c0 + q] * inv_n; m2[q] = tot[1][c0 + q] * inv_n;
-    }
-    const f32x4* x4 = reinterpret_cast<const f32x4*>(x) + (long)g * total4;
-    const f32x4* dy4 = reinterpret_cast<const f32x4*>(dy) + (long)g * total4;
-    f32x4* dx4 = reinterpret_cast<f32x4*>(dx) + (long)g * total4;
-#pragma unroll 2
-    for (long i = i0; i < total4; i += step) {
-        const f32x4 xv = x4[i], dv = dy4[i];
-        f32x4 o;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float xh = (xv[q] - mu[q]) * rs[q];
-            const float z = xh * ga[q] + be[q];
-            const float dz = dv[q] * (z > 0.f ? 1.f : slope);
-            o[q] = (float)((double)(ga[q] * rs[q]) * ((double)dz - m1[q] - (double)xh * m2[q]));     // fp64 means: see bn_bwd_apply_kernel
-        }
-        dx4[i] = o;
-    }
+    bn_dx_loop<2>(reinterpret_cast<const f32x4*>(x) + g * total4, reinterpret_cast<const f32x4*>(dy) + g * total4, reinterpret_cast<f32x4*>(dx) + g * total4,
+                  bn_channels(mean + g * C, rstd + g * C, gamma, beta, c0), bn_dx_means(tot[0], tot[1], c0, 1.0 / (double)rows_per_group), slope, i0, step,
+                  total4);
 }
 
 // 16-byte kernels: a thread keeps the same four channels across its grid-stride loop
 inline bool bn_vec_ok(int C, long elems) { return C >= 4 && C <= 256 && C % 4 == 0 && 1024 % C == 0 && elems % 4 == 0; }
+// grids of the streaming reduce kernels: eight 16-byte elements per thread; sixteen rows per thread of the scalar form, at most 1024 workgroups
+inline int bn_vec_grid(long total4) { return ew_grid(total4, 256, 8); }
+inline int bn_scalar_grid(int rows, int C) {
+    const int blocks = cdiv(rows, (256 / C) * 16);
+    return blocks < 1 ? 1 : (blocks > 1024 ? 1024 : blocks);
+}
 
 }  // namespace tg
 
@@ -637,18 +405,11 @@ extern "C" int tg_bn_train_stats(const float* x, int32_t rows, int32_t C, int32_
     hipStream_t s = (hipStream_t)stream;
     if (zero_async(ws, sizeof(double) * 2 * (size_t)groups * C, s)) return 1;
     const int rpg = rows / groups;
-    const int rpi = 256 / C;
-    int blocks = cdiv(rpg, rpi * 16);
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
-    if (bn_vec_ok(C, (long)rpg * C) && aligned16(x)) {
-        const long total4 = (long)rpg * C / 4;
-        int vb = (int)((total4 + 256 * 8 - 1) / (256 * 8));
-        if (vb > 2048) vb = 2048;
-        if (vb < 1) vb = 1;
-        hipLaunchKernelGGL(bn_stats_vec_kernel, dim3(vb, groups), dim3(256), 0, s, x, (long)rpg, C, ws);
-    } else
-        hipLaunchKernelGGL(bn_stats_kernel, dim3(blocks, groups), dim3(256), 0, s, x, rpg, C, ws);
+    const float* none = nullptr;
+    if (bn_vec_ok(C, (long)rpg * C) && aligned16(x))
+        hipLaunchKernelGGL(bn_reduce_vec_kernel<false>, dim3(bn_vec_grid((long)rpg * C / 4), groups), dim3(256), 0, s, x, none, (long)rpg, C, none, none, none, none, 1.f, ws);
+    else
+        hipLaunchKernelGGL(bn_reduce_kernel<false>, dim3(bn_scalar_grid(rpg, C), groups), dim3(256), 0, s, x, none, rpg, C, none, none, none, none, 1.f, ws);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(cdiv(C, 64)), dim3(64), 0, s, ws, rpg, C, groups, mean, rstd, running_mean, running_var,
                        num_batches_tracked, eps, momentum, repeats);
     return check_launch("tg_bn_train_stats");
@@ -684,21 +445,14 @@ extern "C" int tg_bn_backward(const float* dy, const float* x, float* dx, int32_
         return check_launch("tg_bn_backward(small)");
     }
     if (zero_async(ws, sizeof(double) * 2 * (size_t)C, s)) return 1;
-    const int rpi = 256 / C;
-    int blocks = cdiv(rows, rpi * 16);
-    if (blocks > 1024) blocks = 1024;
-    if (blocks < 1) blocks = 1;
     if (bn_vec_ok(C, (long)rows * C) && aligned16(dy) && aligned16(x) && aligned16(dx)) {
-        const long total4 = (long)rows * C / 4;
-        int vb = (int)((total4 + 256 * 8 - 1) / (256 * 8));
-        if (vb > 2048) vb = 2048;
-        if (vb < 1) vb = 1;
-        hipLaunchKernelGGL(bn_bwd_reduce_vec_kernel, dim3(vb), dim3(256), 0, s, dy, x, (long)rows, C, mean, rstd, gamma, beta, act_slope, ws);
+        const int vb = bn_vec_grid((long)rows * C / 4);
+        hipLaunchKernelGGL(bn_reduce_vec_kernel<true>, dim3(vb), dim3(256), 0, s, x, dy, (long)rows, C, mean, rstd, gamma, beta, act_slope, ws);
         hipLaunchKernelGGL(bn_bwd_apply_vec_kernel, dim3(vb), dim3(256), 0, s, dy, x, dx, (long)rows, C, mean, rstd, gamma, beta, act_slope, ws,
                            dgamma, dbeta);
         return check_launch("tg_bn_backward(vec)");
     }
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(blocks), dim3(256), 0, s, dy, x, rows, C, mean, rstd, gamma, beta, act_slope, ws);
+    hipLaunchKernelGGL(bn_reduce_kernel<true>, dim3(bn_scalar_grid(rows, C)), dim3(256), 0, s, x, dy, rows, C, mean, rstd, gamma, beta, act_slope, ws);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid((long)rows * C, 256, 4)), dim3(256), 0, s, dy, x, dx, (long)rows, C, mean, rstd,
                        gamma, beta, act_slope, ws, dgamma, dbeta);
     return check_launch("tg_bn_backward");

@@ -9,7 +9,7 @@ st.rstd are fp64 values rounded once (2^-22 relative), eval rstd is formed in fp
 |rm0| + |mean| and |rv0| + var.  y and dx are NaN-filled views into the middle of a larger buffer whose 256 floats either side must come
 back bit-identical.  tests/test_bn_reference_cpu.py measures a plain fp32 restatement at least 4 x under every one of these gates.
 
-The three 16-byte streaming kernels (bn_stats_vec_kernel, bn_bwd_reduce_vec_kernel, bn_bwd_apply_vec_kernel) are reached by the C ABI
+The three 16-byte streaming kernels (bn_reduce_vec_kernel<false>, bn_reduce_vec_kernel<true>, bn_bwd_apply_vec_kernel) are reached by the C ABI
 alone (tg_bn_train_stats / tg_bn_backward, here through ops): every C they take is also taken by the bn2 and the fused kernels, which
 layers.bn_fwd / bn_bwd prefer at every size.  The stream_vec cases call them directly.
 
