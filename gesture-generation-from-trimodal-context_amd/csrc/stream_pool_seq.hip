@@ -11,6 +11,8 @@
 // segment touches -- so the tail and the seed are copied from frames the fit does not write, and no second barrier is needed.
 // One workgroup per row, no atomics, nothing waits on another workgroup and the results do not depend on the order in which the workgroups
 // run.  A row with active[b] == 0 leaves before any barrier: no text, length, output, tail, seed or counter of it is written.
+// tg_wide_pool_stage_text / tg_wide_pool_handover_smooth (synthesize.WideSeq2SeqStreamPool, up to 128 rows) are the same two kernels behind the
+// same checks; that pool's push is stream_pool_wide_seq.hip.
 #include "stream_rows.hpp"
 #include "window_rows.hpp"
 
@@ -57,25 +59,49 @@ __global__ __launch_bounds__(256) void pool_handover_smooth_kernel(const float* 
 
 using namespace tg;
 
-extern "C" int tg_pool_stage_text(const int32_t* word_ring, const int64_t* n_words, const int32_t* win, const int32_t* active, int32_t B, int32_t W,
-                                  int32_t Te, int64_t sos, int64_t eos, int64_t* out_text, int64_t* out_len, void* stream) {
-    TG_REQUIRE(word_ring && n_words && win && active && out_text && out_len, "tg_pool_stage_text: null pointer");
-    TG_REQUIRE(B >= 1 && B <= ST_MAX_ROWS && W >= 1 && W <= ST_MAX_WORDS && Te >= 2 && Te <= SQ_MAX_TE,
-               "tg_pool_stage_text: outside the envelope 1 <= B <= %d, 1 <= W <= %d, 2 <= Te <= %d (B=%d W=%d Te=%d)", ST_MAX_ROWS, ST_MAX_WORDS,
-               SQ_MAX_TE, B, W, Te);
+// The launchers: tg_pool_* (synthesize.Seq2SeqStreamPool, rows <= ST_MAX_ROWS) and tg_wide_pool_* (WideSeq2SeqStreamPool, rows <= ST_MAX_WIDE_ROWS)
+// are the same kernels behind the same checks; an entry brings its name and its row limit (as stream_pool.hip's do).
+static int launch_pool_stage_text(const char* who, int max_rows, const int32_t* word_ring, const int64_t* n_words, const int32_t* win,
+                                  const int32_t* active, int32_t B, int32_t W, int32_t Te, int64_t sos, int64_t eos, int64_t* out_text, int64_t* out_len,
+                                  void* stream) {
+    TG_REQUIRE(word_ring && n_words && win && active && out_text && out_len, "%s: null pointer", who);
+    TG_REQUIRE(B >= 1 && B <= max_rows && W >= 1 && W <= ST_MAX_WORDS && Te >= 2 && Te <= SQ_MAX_TE,
+               "%s: outside the envelope 1 <= B <= %d, 1 <= W <= %d, 2 <= Te <= %d (B=%d W=%d Te=%d)", who, max_rows, ST_MAX_WORDS, SQ_MAX_TE, B, W, Te);
     hipLaunchKernelGGL(pool_stage_text_kernel, dim3(B), dim3(SQ_THREADS), 0, (hipStream_t)stream, word_ring, n_words, win, active, W, Te,
                        (long long)sos, (long long)eos, (long long*)out_text, (long long*)out_len);
-    return check_launch("tg_pool_stage_text");
+    return check_launch(who);
 }
 
+static int launch_pool_handover_smooth(const char* who, int max_rows, const float* res, float* out, float* tail, float* seed, int32_t* win,
+                                       const int32_t* active, const double* proj, int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream) {
+    TG_REQUIRE(B >= 1 && B <= max_rows && n_pre >= 1 && n_pre <= PL_MAX_PRE && D >= 1 && D <= PL_MAX_DIM && T <= ST_MAX_FRAMES &&
+                   (int64_t)3 * n_pre <= (int64_t)T - n_pre,
+               "%s: outside the envelope 1 <= B <= %d, 1 <= n_pre <= %d, 1 <= D <= %d, 3 n_pre <= T - n_pre (the smoothing "
+               "segment inside the window's first T - n_pre frames), T <= %d (B=%d n_pre=%d D=%d T=%d)",
+               who, max_rows, PL_MAX_PRE, PL_MAX_DIM, ST_MAX_FRAMES, B, n_pre, D, T);
+    TG_REQUIRE(res && out && tail && seed && win && active && proj, "%s: null pointer", who);
+    hipLaunchKernelGGL(pool_handover_smooth_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, res, out, tail, seed, win, active, proj, T, D, n_pre);
+    return check_launch(who);
+}
+
+#define POOL_STAGE_TEXT_ARGS word_ring, n_words, win, active, B, W, Te, sos, eos, out_text, out_len, stream
+extern "C" int tg_pool_stage_text(const int32_t* word_ring, const int64_t* n_words, const int32_t* win, const int32_t* active, int32_t B, int32_t W,
+                                  int32_t Te, int64_t sos, int64_t eos, int64_t* out_text, int64_t* out_len, void* stream) {
+    return launch_pool_stage_text("tg_pool_stage_text", ST_MAX_ROWS, POOL_STAGE_TEXT_ARGS);
+}
+
+extern "C" int tg_wide_pool_stage_text(const int32_t* word_ring, const int64_t* n_words, const int32_t* win, const int32_t* active, int32_t B,
+                                       int32_t W, int32_t Te, int64_t sos, int64_t eos, int64_t* out_text, int64_t* out_len, void* stream) {
+    return launch_pool_stage_text("tg_wide_pool_stage_text", ST_MAX_WIDE_ROWS, POOL_STAGE_TEXT_ARGS);
+}
+
+#define POOL_HANDOVER_SMOOTH_ARGS res, out, tail, seed, win, active, proj, B, T, D, n_pre, stream
 extern "C" int tg_pool_handover_smooth(const float* res, float* out, float* tail, float* seed, int32_t* win, const int32_t* active, const double* proj,
                                        int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream) {
-    TG_REQUIRE(B >= 1 && B <= ST_MAX_ROWS && n_pre >= 1 && n_pre <= PL_MAX_PRE && D >= 1 && D <= PL_MAX_DIM && T <= ST_MAX_FRAMES &&
-                   (int64_t)3 * n_pre <= (int64_t)T - n_pre,
-               "tg_pool_handover_smooth: outside the envelope 1 <= B <= %d, 1 <= n_pre <= %d, 1 <= D <= %d, 3 n_pre <= T - n_pre (the smoothing "
-               "segment inside the window's first T - n_pre frames), T <= %d (B=%d n_pre=%d D=%d T=%d)",
-               ST_MAX_ROWS, PL_MAX_PRE, PL_MAX_DIM, ST_MAX_FRAMES, B, n_pre, D, T);
-    TG_REQUIRE(res && out && tail && seed && win && active && proj, "tg_pool_handover_smooth: null pointer");
-    hipLaunchKernelGGL(pool_handover_smooth_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, res, out, tail, seed, win, active, proj, T, D, n_pre);
-    return check_launch("tg_pool_handover_smooth");
+    return launch_pool_handover_smooth("tg_pool_handover_smooth", ST_MAX_ROWS, POOL_HANDOVER_SMOOTH_ARGS);
+}
+
+extern "C" int tg_wide_pool_handover_smooth(const float* res, float* out, float* tail, float* seed, int32_t* win, const int32_t* active,
+                                            const double* proj, int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream) {
+    return launch_pool_handover_smooth("tg_wide_pool_handover_smooth", ST_MAX_WIDE_ROWS, POOL_HANDOVER_SMOOTH_ARGS);
 }

@@ -2,6 +2,7 @@
 // n_words -- does in a push and in the staging of a window.  stream.hip runs them for rows that share a clock (one chunk length, one window
 // index), stream_pool.hip for rows with clocks of their own (a length and a window index per row, idle rows skipped); stream_seq.hip and
 // stream_pool_seq.hip stage the Seq2Seq model's word list from the same word ring, in the same two ways.  The bounds are the files' bounds.
+// stream_pool_wide.hip, stream_pool_wide_rs.hip and stream_pool_wide_seq.hip push rows whose lengths come from a packed header.
 // As in utterance.hip the device sees integers only and samples and ids move as bits: plain loads and stores.
 #pragma once
 #include "common.hpp"
@@ -14,6 +15,20 @@ constexpr int ST_MAX_WORDS = 1024;      // largest word ring per row: 12 KB of L
 constexpr int ST_MAX_FRAMES = 1024;     // frames of a window: one thread each
 constexpr int ST_MAX_RING = 1 << 30;    // samples of a row's ring: positions and their sums stay inside an int
 constexpr int ST_MAX_WINDOW = 1 << 25;  // samples of a window: the stage kernels' grid
+
+// The records' half of a push, by a workgroup of THREADS threads: m records trip[0 .. 3 m) to row b's word ring at cnt mod W; it moves no counter.
+// Every push body appends its records through it: ring_push_row_from below (1024 threads), stream_pool_wide_rs.hip (the resampler's workgroup, 256,
+// whose samples do not come from a chunk) and stream_pool_wide_seq.hip (256, a push without samples).
+template <int THREADS>
+__device__ __forceinline__ void word_ring_append_row(int b, int m, long cnt, const int32_t* __restrict__ trip, int32_t* __restrict__ word_ring,
+                                                     int W) {
+    const int s0 = (int)(cnt % W);
+    for (int t = threadIdx.x; t < 3 * m; t += THREADS) {
+        int slot = s0 + t / 3;                                        // m <= W
+        if (slot >= W) slot -= W;
+        word_ring[((long)b * W + slot) * 3 + t % 3] = trip[t];
+    }
+}
 
 // Row b of a push, by a workgroup of 1024 threads: n samples of chunk row b go to the ring at wr mod R (the chunk may straddle the wrap point),
 // m records of recs row b (behind its count) to the word ring at cnt mod W, then thread 0 advances both counters.  wr = written[b] and
@@ -33,29 +48,10 @@ __device__ __forceinline__ void ring_push_row_from(int b, int n, int m, long wr,
         if (p >= R) p -= R;
         row[p] = src[k];
     }
-    const int s0 = (int)(cnt % W);
-    for (int t = threadIdx.x; t < 3 * m; t += 1024) {
-        int slot = s0 + t / 3;                                        // m <= W
-        if (slot >= W) slot -= W;
-        word_ring[((long)b * W + slot) * 3 + t % 3] = trip[t];
-    }
+    word_ring_append_row<1024>(b, m, cnt, trip, word_ring, W);
     if (threadIdx.x == 0) {
         written[b] = wr + n;
         n_words[b] = cnt + m;
-    }
-}
-
-// The records' half of a push on its own, by a workgroup of THREADS threads: m records trip[0 .. 3 m) to row b's word ring at cnt mod W.  For
-// stream_pool_wide_rs.hip, whose workgroup is the resampler's (256 threads) and whose samples do not come from a chunk; it moves no counter.
-// (ring_push_row_from strides by 1024 and keeps its loop as it is: the kernels built from it are unchanged.)
-template <int THREADS>
-__device__ __forceinline__ void word_ring_append_row(int b, int m, long cnt, const int32_t* __restrict__ trip, int32_t* __restrict__ word_ring,
-                                                     int W) {
-    const int s0 = (int)(cnt % W);
-    for (int t = threadIdx.x; t < 3 * m; t += THREADS) {
-        int slot = s0 + t / 3;                                        // m <= W
-        if (slot >= W) slot -= W;
-        word_ring[((long)b * W + slot) * 3 + t % 3] = trip[t];
     }
 }
 

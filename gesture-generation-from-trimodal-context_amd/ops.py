@@ -2168,7 +2168,7 @@ def wide_pool_handover(res, out, tail, seed, win, active):
 
 
 # ------------------------------------------------------------------------------------------------- seq2seq stream pool (csrc/stream_pool_seq.hip)
-def pool_stage_text(st, win, active, sos, eos, text_out, len_out):
+def pool_stage_text(st, win, active, sos, eos, text_out, len_out, entry="tg_pool_stage_text"):
     """stream_stage_text per row: row b with active[b] != 0 gets the Seq2Seq text of its own window win[b] (win, active: (B,) int32 on the device)
     in text_out[b] (B, Te) int64 and its length in len_out[b] (B,) int64; the other rows of both buffers are left as they are."""
     _stream_check(st)
@@ -2177,11 +2177,11 @@ def pool_stage_text(st, win, active, sos, eos, text_out, len_out):
     if text_out.dim() != 2 or text_out.shape[0] != st["B"] or not text_out.is_contiguous():
         raise ValueError(f"text_out is {tuple(text_out.shape)}, expected ({st['B']}, Te), contiguous")
     _dev_int(len_out, torch.int64, st["B"], "len_out")
-    call("tg_pool_stage_text", _p(st["words"]), _p(st["n_words"]), _p(win), _p(active), st["B"], st["W"], int(text_out.shape[1]), int(sos), int(eos),
-         _p(text_out), _p(len_out), _stream())
+    call(entry, _p(st["words"]), _p(st["n_words"]), _p(win), _p(active), st["B"], st["W"], int(text_out.shape[1]), int(sos), int(eos), _p(text_out),
+         _p(len_out), _stream())
 
 
-def pool_handover_smooth(res, out, tail, seed, win, active, proj):
+def pool_handover_smooth(res, out, tail, seed, win, active, proj, entry="tg_pool_handover_smooth"):
     """pool_handover for the plain seed (B, n_pre, D) with the Seq2Seq model's smoothing of the window it hands over: per row with active[b] != 0
     out = res, cross-faded with tail where win[b] > 0, frames [0, 3 n_pre) of out replaced by their cubic fit (proj: the fp64 tables of
     synthesize.projection_tables(n_pre); utterance_finish(smooth)'s bits on that window), tail = seed = out's last n_pre frames, win[b] += 1.
@@ -2193,7 +2193,44 @@ def pool_handover_smooth(res, out, tail, seed, win, active, proj):
         raise ValueError(f"res {tuple(res.shape)} / tail {tuple(tail.shape)} / seed {tuple(seed.shape)} do not belong to out {tuple(out.shape)}")
     _dev_int(win, torch.int32, B, "win"); _dev_int(active, torch.int32, B, "active")
     assert proj.is_cuda and proj.dtype == torch.float64 and proj.is_contiguous() and proj.numel() >= 9 * n_pre * n_pre
-    call("tg_pool_handover_smooth", _p(res), _p(out), _p(tail), _p(seed), _p(win), _p(active), _p(proj), B, T, D, n_pre, _stream())
+    call(entry, _p(res), _p(out), _p(tail), _p(seed), _p(win), _p(active), _p(proj), B, T, D, n_pre, _stream())
+
+
+# ------------------------------------------------------------------------------------------------- wide seq2seq stream pool (csrc/stream_pool_wide_seq.hip)
+def words_state(B, S, A, W, T, device):
+    """stream_state without a sample ring, for a model that reads no sample (synthesize.WideSeq2SeqStreamPool): the word ring (B, W, 3) int32,
+    zeroed, its counter `n_words` and the sample counter `written` (B,) int64; R = 0 and an empty `ring`."""
+    return stream_state(B, 0, S, A, W, T, device)
+
+
+def wide_pool_push_words(st, packed, lay, words_live=0):
+    """The tick of a wide pool whose model reads no sample, for up to 128 rows from ONE packed device buffer: packed (flat uint8, device) holds,
+    at the byte offsets of lay (synthesize.wide_words_layout), the header (B, 4) int32 = per row (n samples, 0, record count, record offset) and
+    the rows' (window, frame, word id) records concatenated.  Row b appends its records to its word ring and adds n to written[b]; a row with
+    n == 0 and no records keeps every bit.  No sample travels and no sample ring is touched (st may be words_state's).  words_live + the
+    largest record count: the slot count of the fullest word ring after the push.  Outside the envelope (1 <= B <= 128, words_live + m_max <=
+    W <= 1024, m_max <= the records' count <= B m_max) the library refuses (RuntimeError naming the envelope); nothing is launched."""
+    B, W = st["B"], st["W"]
+    _dev_int(st["words"], torch.int32, B * W * 3, "word ring")
+    _dev_int(st["written"], torch.int64, B, "written"); _dev_int(st["n_words"], torch.int64, B, "n_words")
+    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 1 and packed.is_contiguous()):
+        raise TypeError("packed: expected a flat contiguous CUDA uint8 tensor")
+    if lay["B"] != B or packed.numel() < lay["total"] or packed.data_ptr() % 16:
+        raise ValueError(f"packed: {packed.numel()} bytes for a layout of {lay['B']} rows and {lay['total']} bytes on a state of {B} rows")
+    base = packed.data_ptr()
+    n_r = lay["n_records"]
+    call("tg_wide_pool_push_words", base + lay["hdr"], base + lay["records"] if n_r else None, n_r, lay["m_max"], int(words_live), _p(st["written"]),
+         _p(st["words"]), _p(st["n_words"]), B, W, _stream())
+
+
+def wide_pool_stage_text(st, win, active, sos, eos, text_out, len_out):
+    """pool_stage_text for up to 128 rows (the same row body: for B <= 4 the same bits)."""
+    pool_stage_text(st, win, active, sos, eos, text_out, len_out, entry="tg_wide_pool_stage_text")
+
+
+def wide_pool_handover_smooth(res, out, tail, seed, win, active, proj):
+    """pool_handover_smooth for up to 128 rows (the same row body: for B <= 4 the same bits)."""
+    pool_handover_smooth(res, out, tail, seed, win, active, proj, entry="tg_wide_pool_handover_smooth")
 
 
 # ------------------------------------------------------------------------------------------------- synthesis queue (csrc/queue.hip)

@@ -635,6 +635,7 @@ class Seq2SeqWindowDecoder(_WindowDecoderBase):
     later windows, an eager pass with no row active in front of the capture; window() and its graph are not touched.  Every row of self.text /
     self.len must hold a valid list at all times (idle rows: [SOS, EOS], length 2): the forward runs on all B rows.
     Host-side validation raises ValueError before anything touches the GPU."""
+    _max_rows = 4                                    # the rows of a stream and of the narrow pool (WideSeq2SeqWindowDecoder: 128)
 
     def __init__(self, args, net, batch, device, graph=True, max_words=32, row_local_encoder=True, audio_sr=16000):
         if getattr(args, "model", "multimodal_context") != "seq2seq":
@@ -651,8 +652,8 @@ class Seq2SeqWindowDecoder(_WindowDecoderBase):
             raise ValueError(f"Seq2SeqWindowDecoder: args (n_poses, n_pre_poses) = {(T, n_pre)} but the model decodes {(net.n_frames, net.n_pre_poses)}")
         if not 1 <= n_pre < T:
             raise ValueError(f"Seq2SeqWindowDecoder: 1 <= n_pre_poses < n_poses, got {(n_pre, T)}")
-        if not 1 <= batch <= 4:
-            raise ValueError(f"Seq2SeqWindowDecoder: 1 to 4 utterances in lock-step (the rows of a stream), got {batch}")
+        if not 1 <= batch <= self._max_rows:
+            raise ValueError(f"{type(self).__name__}: 1 to {self._max_rows} utterances in lock-step (the rows of a stream), got {batch}")
         if not 0 <= max_words <= 126:
             raise ValueError(f"Seq2SeqWindowDecoder: 0 <= max_words <= 126 (the kernels take lists of at most 128 entries), got {max_words}")
         self.max_words, self.Te, self.row_local = int(max_words), int(max_words) + 2, bool(row_local_encoder)
@@ -675,7 +676,8 @@ class Seq2SeqWindowDecoder(_WindowDecoderBase):
 
     def _forward_pooled(self):
         self._model_forward(self.res)
-        ops.pool_handover_smooth(self.res, self.out, self.tail, self.pre, self.win, self.active, self.proj)
+        handover = ops.pool_handover_smooth if self.B <= 4 else ops.wide_pool_handover_smooth      # (more than four rows: WideSeq2SeqWindowDecoder)
+        handover(self.res, self.out, self.tail, self.pre, self.win, self.active, self.proj)
 
     def _model_forward(self, out=None):
         from .rnn import _EmbedFn, _SumHalvesFn
@@ -695,6 +697,14 @@ class Seq2SeqWindowDecoder(_WindowDecoderBase):
         """One window for the whole batch.  in_text (B, Te) / in_len (B,) int64, CPU or GPU tensors, or None: self.text / self.len were
         filled in place (ops.stream_stage_text); returns the (B, T, D) output buffer (device, overwritten by the next call)."""
         return self._window(first, text=in_text, len=in_len)
+
+
+class WideSeq2SeqWindowDecoder(Seq2SeqWindowDecoder):
+    """Seq2SeqWindowDecoder for 1 to 128 rows (WideSeq2SeqStreamPool, generate_gestures_queue(rows > 4)): everything is the parent's.  The
+    kernels of a window are row-local -- the encoder one workgroup per (row, direction), the decoder loop one workgroup per row, a row's bits
+    independent of the row count -- and with more than four rows the pooled window hands over through ops.wide_pool_handover_smooth, the
+    narrow entry's kernel behind another row limit.  One captured graph per use (graph, graph_pooled, graph_queue), as in the parent."""
+    _max_rows = 128
 
 
 def _kept_decoder(who, kind, d, model, batch, T, n_pre, rows="row(s)", **built_for):
@@ -1143,7 +1153,8 @@ def generate_gestures_queue(args, pose_decoder, lang_model, audios, words_list, 
     rounds = the fullest row's load, against lock-step's max(n_win) per group of `rows`.  Then UtteranceBatch.finish as in lock-step (seq2seq's
     smoothing, fade_out, joints, return_device).
     args.model: 'multimodal_context' -- 1 <= rows <= 128, the caller picks the row count and with it the recurrence kernels every window
-    runs on --; 'joint_embedding' and 'seq2seq' -- rows <= 4, their window decoders' limit (N is not limited); 'speech2gesture' is refused.
+    runs on --; 'joint_embedding' and 'seq2seq' -- rows <= 4, their window decoders' limit (N is not limited; 'seq2seq' on a kept
+    WideSeq2SeqWindowDecoder built for `rows` rows: rows <= 128) --; 'speech2gesture' is refused.
     vids, seed_seqs: one entry per utterance; a seed_seqs entry may be None (that utterance starts from zeros, without the constraint bit).
     window_decoder: a kept WindowDecoder / JointEmbedWindowDecoder / Seq2SeqWindowDecoder built for this model and `rows` rows (and, with
     replayed draws, replay_draws=True; seq2seq: this max_words), whose graph_queue is captured once and replayed by later calls; None builds
@@ -1162,6 +1173,8 @@ def generate_gestures_queue(args, pose_decoder, lang_model, audios, words_list, 
         raise ValueError(f"{who}: args.model is {model!r}")
     kind = {"multimodal_context": WindowDecoder, "joint_embedding": JointEmbedWindowDecoder, "seq2seq": Seq2SeqWindowDecoder}[model]
     limit = QUEUE_MAX_ROWS if model == "multimodal_context" else 4
+    if model == "seq2seq" and isinstance(window_decoder, WideSeq2SeqWindowDecoder):      # the width comes with the kept wide decoder, and only with it
+        kind, limit = WideSeq2SeqWindowDecoder, QUEUE_MAX_ROWS
     if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= limit:
         raise ValueError(f"{who}: 1 <= rows <= {limit} for the {model} model" + ("" if limit == QUEUE_MAX_ROWS else " (its window decoder's rows)")
                          + f", got {rows!r}")
@@ -1406,6 +1419,8 @@ class _StreamCore:
     _max_rows = 4                                    # the few-row decoders' and the by-value kernels' limit (WideStreamPool: 128)
     _dense_chunks = True                             # whether a push goes through the dense (B, max_chunk) device buffer chunk_buf
     _smooth_closing = False                          # whether close() smooths the window it ran (Seq2SeqGestureStream)
+    _decoder_kind = None                             # the window decoder's class where it is not the model's of _STREAM_DECODERS
+    _sample_ring = True                              # whether the state holds the rows' samples (WideSeq2SeqStreamPool: the counters alone)
 
     def _refusal(self, model):
         return {"seq2seq": "the seq2seq model cannot stream: its smoothing rewrites frames of a window after the next window has run -- in the "
@@ -1439,7 +1454,7 @@ class _StreamCore:
         if R < self.A + chunk16:
             raise ValueError(f"{who}: a ring of {R} samples; window + max_chunk = {self.A + chunk16} (at 16 kHz) are needed")
         dev = self.dev = next(pose_decoder.parameters()).device
-        kind = _STREAM_DECODERS[model]
+        kind = self._decoder_kind or _STREAM_DECODERS[model]
         if window_decoder is not None:
             self.dec = _kept_decoder(who, kind, window_decoder, pose_decoder, self.B, T, n_pre, **built_for)
         else:
@@ -1447,17 +1462,20 @@ class _StreamCore:
         if self.dec.audio_len != self.A:
             raise ValueError(f"{who}: the window decoder takes {self.dec.audio_len} samples, the stream's window is {self.A} (audio_sr = {audio_sr})")
         self.D = self.dec.D
-        self.state = ops.stream_state(self.B, R, self.S, self.A, word_ring, T, dev)
+        self.state = ops.stream_state(self.B, R, self.S, self.A, word_ring, T, dev) if self._sample_ring else ops.words_state(self.B, self.S, self.A,
+                                                                                                                              word_ring, T, dev)
         self.chunk_buf = torch.zeros(self.B, chunk16 if self._dense_chunks else 0, device=dev)
         # the streaming resampler: device state (carry, counters) and the host's mirror of both counters per row, plain integers
         # (a stream without dense chunks reads its input from the packed push: no staging buffer either)
-        self.rs = None if self.input_sr is None else ops.resample_state(self.B, *resample.device_taps(self.input_sr, dev), self.max_chunk, dev,
-                                                                        stage=self._dense_chunks)
+        self.rs = None if self.input_sr is None else self._resampler_state()
         self._rs_in, self._rs_out = [0] * self.B, [0] * self.B
         self._live, self._n_rec = [[] for _ in range(self.B)], [0] * self.B
         self._ones = torch.ones(self.B, dtype=torch.int32, device=dev)
         self._mean = self._tables = None                 # the fp64 mean and the projection tables on the device: made once, on first use
         self._extra = None                               # preview(): where the resampler's flush is peeked at, made on first use
+
+    def _resampler_state(self):
+        return ops.resample_state(self.B, *resample.device_taps(self.input_sr, self.dev), self.max_chunk, self.dev, stage=self._dense_chunks)
 
     # -------------------------------------------------------------------------------------------------------------- host bookkeeping (integers)
     def _row_records(self, words, next_window):
@@ -1973,7 +1991,7 @@ class StreamPool(_StreamCore):
         for t in (self.state["written"], self.state["n_words"], self.win, dec.tail, dec.pre):
             t[b:b + 1].zero_()
         if self.rs is not None:                                                 # the resampler's row: its carry and both counters, nothing else
-            for t in (self.rs["carry"], self.rs["consumed"], self.rs["produced"]):
+            for t in (self.rs[k] for k in ("carry", "consumed", "produced") if k in self.rs):      # (a host-only resampler has no device row)
                 t[b:b + 1].zero_()
             self._rs_in[b] = self._rs_out[b] = 0
             self._head[b] = None
@@ -2047,6 +2065,8 @@ class StreamPool(_StreamCore):
             rows[b], words[b] = c, w
         return rows, words
 
+    _n_of = staticmethod(len)                        # the sample count of what _take keeps of a chunk
+
     def push(self, chunks, numpy=False, joints=False):
         """chunks: {slot: chunk} or {slot: (chunk, words)} for any non-empty subset of the open slots; chunk: 1-D float32 (numpy or a host
         tensor), 1 <= len <= max_chunk, the lengths need not agree; words: a list of (word, start, end), absolute seconds of that session.
@@ -2055,7 +2075,7 @@ class StreamPool(_StreamCore):
         joints=True gives (frames, fp64 joint positions (k * stride, 10, 3))."""
         rows, words = self._take(chunks)
         recs, late = self._records(words)                                   # (may refuse; nothing has changed yet)
-        n = [len(rows[b]) if b in rows else 0 for b in range(self.B)]
+        n = [self._n_of(rows[b]) if b in rows else 0 for b in range(self.B)]
         fullest = max((self._live_slots(b) + len(r) for b, r in enumerate(recs) if r), default=0)      # slots of the fullest word ring after the push
         n = self._send(rows, n, recs, fullest)
         for b in range(self.B):
@@ -2190,9 +2210,9 @@ class Seq2SeqStreamPool(StreamPool):
                  window_decoder=None, max_words=32, row_local_encoder=True, input_sr=None):
         n_pre, stride = args.n_pre_poses, args.n_poses - args.n_pre_poses
         if not 1 <= n_pre <= 8:
-            raise ValueError(f"Seq2SeqStreamPool: 1 <= n_pre_poses <= 8 (the smoothing kernel's tables), got {n_pre}")
+            raise ValueError(f"{type(self).__name__}: 1 <= n_pre_poses <= 8 (the smoothing kernel's tables), got {n_pre}")
         if 3 * n_pre > stride:
-            raise ValueError(f"Seq2SeqStreamPool: a window's smoothing segment of 3 n_pre = {3 * n_pre} frames must lie inside its first "
+            raise ValueError(f"{type(self).__name__}: a window's smoothing segment of 3 n_pre = {3 * n_pre} frames must lie inside its first "
                              f"n_poses - n_pre_poses = {stride} frames, else it would rewrite frames the next window has handed out")
         super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, graph, word_ring, ring, window_decoder,
                          _built_for=dict(max_words=max_words, row_local_encoder=bool(row_local_encoder)), input_sr=input_sr)
@@ -2203,7 +2223,7 @@ class Seq2SeqStreamPool(StreamPool):
             self._idle_text(b)
 
     def preview(self, slot, fade_out=False, joints=False, numpy=False):
-        raise ValueError("Seq2SeqStreamPool.preview: the seq2seq model has no preview -- its closing path smooths the window it ran and "
+        raise ValueError(f"{type(self).__name__}.preview: the seq2seq model has no preview -- its closing path smooths the window it ran and "
                          "stages a word list, which the preview chain does not do")
 
     def _idle_text(self, b):
@@ -2232,14 +2252,14 @@ class Seq2SeqStreamPool(StreamPool):
             for win, c in cnt.items():
                 have = self._win_words[b].get(win, 0)
                 if have + c > self.max_words:
-                    raise ValueError(f"Seq2SeqStreamPool.push: slot {b}: window {win} would hold {have + c} words, max_words is {self.max_words}")
+                    raise ValueError(f"{type(self).__name__}.push: slot {b}: window {win} would hold {have + c} words, max_words is {self.max_words}")
         return rows, late
 
-    def _commit_records(self, rows):
+    def _note_records(self, rows):
         for b, r in enumerate(rows):                                     # (the push can no longer be refused)
             for rec in r:
                 self._win_words[b][rec[0]] = self._win_words[b].get(rec[0], 0) + 1
-        return super()._commit_records(rows)
+        super()._note_records(rows)
 
     def _ran(self, b, next_window):
         super()._ran(b, next_window)
@@ -2268,7 +2288,51 @@ def wide_push_layout(n, m):
                 sample_off=[sum(n[:b]) for b in range(B)], record_off=[sum(m[:b]) for b in range(B)], n_max=max(n), m_max=max(m))
 
 
-class WideStreamPool(StreamPool):
+class _PinnedTicks:
+    """How a wide pool's ticks and rounds travel (WideStreamPool, WideSeq2SeqStreamPool): a push is packed into one of two pinned host slots
+    and goes up by one copy into the device buffer behind it; a round's [draws | active mask] goes up by one small copy into the decoder's
+    round_buf.  A slot is reused only after the event recorded behind its last copy."""
+
+    def _pinned(self, push_bytes):
+        """Two pinned slots of push_bytes (a push of the worst-case size) with a device buffer behind each, and round_buf's two pinned twins."""
+        pin = self.dev.type == "cuda"
+        host = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, pin_memory=pin)
+        self._push_host = [host(push_bytes) for _ in range(2)]
+        self._push_dev = [torch.zeros(push_bytes, dtype=torch.uint8, device=self.dev) for _ in range(2)]
+        self._round_host = [host(4 * self.dec.round_buf.numel()).view(torch.float32) for _ in range(2)]
+        self._copied = {"push": [None, None], "round": [None, None]}            # per slot: the event behind its last host -> device copy
+        self._turn = {"push": 0, "round": 0}
+
+    def _slot_to_fill(self, kind):
+        """The pinned slot of `kind` whose turn it is, safe to overwrite: its previous copy has finished."""
+        i = self._turn[kind]
+        self._turn[kind] = i ^ 1
+        if self._copied[kind][i] is not None:
+            self._copied[kind][i].synchronize()
+        return i
+
+    def _sent(self, kind, i):
+        if self.dev.type == "cuda":
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.dev))
+            self._copied[kind][i] = ev
+
+    def _send_round(self, mask):
+        """The mask and the active rows' draws go up as ONE small copy, into the decoder's round_buf."""
+        B, dec = self.B, self.dec
+        i = self._slot_to_fill("round")
+        host = self._round_host[i].numpy()
+        if dec.draw is not None:
+            draws = host[:dec.draw.numel()].reshape(tuple(dec.draw.shape))
+            for b, a in enumerate(mask):
+                if a:
+                    draws[b] = np.asarray(self._draws[b][self.next_window[b]], dtype=np.float32).reshape(-1)
+        host[host.size - B:].view(np.int32)[:] = mask
+        dec.round_buf.copy_(self._round_host[i], non_blocking=True)
+        self._sent("round", i)
+
+
+class WideStreamPool(_PinnedTicks, StreamPool):
     """StreamPool for up to 128 sessions: `slots` (1 to 128) rows on ONE multimodal WindowDecoder, the same interface -- open(vid, seed_seq),
     push({slot: chunk or (chunk, words)}), close(slot, fade_out, joints, numpy), late_words, window_decoder= -- and the same contract:
     everything push() and close() returned for the session in slot b, concatenated, is row b of generate_gestures_batch(on_device=True) on a
@@ -2299,31 +2363,9 @@ class WideStreamPool(StreamPool):
                              f"{resample.TARGET_SR} Hz audio (resample_audio converts whole signals), or use WideResampledStreamPool")
         super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, graph, word_ring, ring, window_decoder, _replay_draws,
                          input_sr=input_sr if self._resamples else None)
-        B, pin = self.B, self.dev.type == "cuda"
-        host = lambda nbytes: torch.zeros(nbytes, dtype=torch.uint8, pin_memory=pin)
-        # a push: two pinned slots of the worst-case size (every row a full chunk and a full word ring) and a device buffer behind each
-        size = wide_push_layout([self.max_chunk] * B, [self.state["W"]] * B)["total"]
-        self._push_host = [host(size) for _ in range(2)]
-        self._push_dev = [torch.zeros(size, dtype=torch.uint8, device=self.dev) for _ in range(2)]
-        # a round: the decoder's round_buf = [draws | active mask], two pinned twins
-        self._round_host = [host(4 * self.dec.round_buf.numel()).view(torch.float32) for _ in range(2)]
-        self._copied = {"push": [None, None], "round": [None, None]}            # per slot: the event behind its last host -> device copy
-        self._turn = {"push": 0, "round": 0}
+        # a push of the worst-case size: every row a full chunk and a full word ring
+        self._pinned(wide_push_layout([self.max_chunk] * self.B, [self.state["W"]] * self.B)["total"])
         self._draw_host = None                                                  # (StreamPool's staging of the draws: the round slots replace it)
-
-    def _slot_to_fill(self, kind):
-        """The pinned slot of `kind` whose turn it is, safe to overwrite: its previous copy has finished."""
-        i = self._turn[kind]
-        self._turn[kind] = i ^ 1
-        if self._copied[kind][i] is not None:
-            self._copied[kind][i].synchronize()
-        return i
-
-    def _sent(self, kind, i):
-        if self.dev.type == "cuda":
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(self.dev))
-            self._copied[kind][i] = ev
 
     def preview(self, slot, fade_out=False, joints=False, numpy=False):
         raise ValueError(f"{type(self).__name__}.preview: a wide pool has no preview -- the preview chain's kernels take their lengths by value for "
@@ -2331,20 +2373,6 @@ class WideStreamPool(StreamPool):
 
     def _stage(self):
         ops.wide_pool_stage(self.state, self.win, self.active, self.dec.text, self.dec.audio)
-
-    def _send_round(self, mask):
-        """The mask and the active rows' draws go up as ONE small copy, into the decoder's round_buf."""
-        B, dec = self.B, self.dec
-        i = self._slot_to_fill("round")
-        host = self._round_host[i].numpy()
-        if dec.draw is not None:
-            draws = host[:dec.draw.numel()].reshape(tuple(dec.draw.shape))
-            for b, a in enumerate(mask):
-                if a:
-                    draws[b] = np.asarray(self._draws[b][self.next_window[b]], dtype=np.float32).reshape(-1)
-        host[host.size - B:].view(np.int32)[:] = mask
-        dec.round_buf.copy_(self._round_host[i], non_blocking=True)
-        self._sent("round", i)
 
     def _send(self, rows, n, recs, fullest):
         """StreamPool._send for a wide pool: the header, the chunks and the records of every pushed row are packed into a pinned slot (numpy
@@ -2411,3 +2439,115 @@ class WideResampledStreamPool(WideStreamPool):
     def _flush(self, b):
         """StreamPool._flush as a tick of its own: the header alone, no samples and no records, with flush_row = b."""
         return self._tick({}, [0] * self.B, [[] for _ in range(self.B)], 0, flush=(b,))
+
+
+# ------------------------------------------------------------------------------------------------------------------ wide seq2seq stream pool (DESIGN.md section 38)
+def wide_words_layout(n, m):
+    """Where the pieces of one tick of a WideSeq2SeqStreamPool lie in its packed buffer, integers only -- wide_push_layout without the samples.
+    n, m: per row the samples the tick stands for and the number of word records (>= 0; a row may have neither, or records without samples).
+    The pieces -- the header (B, 4) int32 = per row (n, 0, m, record offset) and the records concatenated ((window, frame, id) int32) -- start
+    on 256-byte boundaries.  Returns a dict: the byte offsets hdr, records and the byte size total; record_off: per row the first record of
+    its slice, in records; n_records: the slices' sum; n_max, m_max; B."""
+    n, m = [int(v) for v in n], [int(v) for v in m]
+    if len(n) != len(m) or not n or min(n) < 0 or min(m) < 0:
+        raise ValueError(f"wide_words_layout: {len(n)} sample counts and {len(m)} record counts; expected one of each per row, none negative")
+    up = lambda v: (v + 255) // 256 * 256
+    B, n_records = len(n), sum(m)
+    records = up(16 * B)
+    return dict(B=B, hdr=0, records=records, total=records + up(12 * n_records), n_records=n_records,
+                record_off=[sum(m[:b]) for b in range(B)], n_max=max(n), m_max=max(m))
+
+
+class WideSeq2SeqStreamPool(_PinnedTicks, Seq2SeqStreamPool):
+    """Seq2SeqStreamPool for up to 128 sessions: `slots` (1 to 128) rows on ONE WideSeq2SeqWindowDecoder, the same interface -- open(seed_seq),
+    push, close(slot, fade_out, joints, numpy), late_words, max_words, window_decoder= (a WideSeq2SeqWindowDecoder built for `slots` rows), no
+    preview -- and the same contract: everything push() and close() returned for the session in slot b, concatenated, is row b of
+    generate_gestures_batch(on_device=True, fade_out=...) on a batch of `slots` utterances with that session's utterance in row b, bit for
+    bit, whatever the other rows hold or do, for lengths where stream_matches_offline holds.  The forward always runs `slots` rows.
+
+    What differs is how a tick travels (csrc/stream_pool_wide_seq.hip).  The model never reads a sample -- a chunk only drives its row's clock --
+    so no sample is uploaded and no sample ring exists: push({slot: n_samples | chunk | (n_samples or chunk, words)}) takes of a chunk its
+    length alone and an integer in its place.  A tick is one packed pinned buffer of integers (wide_words_layout: the header and the word
+    records; two slots, a slot is reused only after the event behind its copy), one copy and one launch, ops.wide_pool_push_words; a round is
+    one small copy of the mask, ops.wide_pool_stage_text and the decoder's pooled graph.  Idle rows hold [SOS, EOS], length 2.  push() never
+    reads from the device.  A refused call (ValueError) leaves the pool as it was.
+    input_sr: the rate the pushed counts are in -- max_chunk and every n_samples then count INPUT samples.  It is honoured on the host alone:
+    a row's clock advances by the samples the streaming resampler would have made final (resampled_ready; a close adds the flush's,
+    resampled_length), the integers every resampled stream mirrors on the host; no resample launch is issued, since no sample is read."""
+    _max_rows = 128
+    _dense_chunks = False
+    _sample_ring = False
+    _decoder_kind = WideSeq2SeqWindowDecoder
+    _n_of = staticmethod(int)
+
+    def __init__(self, args, pose_decoder, lang_model, slots=128, audio_sr=16000, max_chunk=16000, graph=True, word_ring=256, window_decoder=None,
+                 max_words=32, row_local_encoder=True, input_sr=None):
+        super().__init__(args, pose_decoder, lang_model, slots, audio_sr, max_chunk, graph, word_ring, None, window_decoder, max_words,
+                         row_local_encoder, input_sr)
+        # a tick of the worst-case size: every row a full word ring
+        self._pinned(wide_words_layout([0] * self.B, [self.state["W"]] * self.B)["total"])
+
+    def _resampler_state(self):
+        """The rate's integers: what the host's mirror of the resampler's counters needs (_made).  No taps, no carry, no device row."""
+        L_, M_, K_, _ = resample.geometry(self.input_sr)
+        return dict(L=L_, M=M_, K=K_)
+
+    def _take(self, chunks):
+        """push()'s argument, checked: ({row: sample count}, {row: word list or None}).  An integer stands for a chunk of that many samples; a
+        chunk goes through StreamPool's checks and leaves its length.  Nothing is changed here."""
+        who = type(self).__name__
+        if not isinstance(chunks, dict) or not chunks:
+            raise ValueError(f"{who}.push: expected a non-empty {{slot: n_samples or chunk}} dict")
+        counts, arrays = {}, {}
+        for slot, c in chunks.items():
+            n = c[0] if isinstance(c, tuple) else c
+            if isinstance(n, (int, np.integer)) and not isinstance(n, bool):
+                counts[slot] = c
+            else:
+                arrays[slot] = c
+        rows, words = super()._take(arrays) if arrays else ({}, {})
+        rows = {b: len(c) for b, c in rows.items()}
+        for slot, c in counts.items():
+            b = self._slot(slot, "push")
+            n, w = c if isinstance(c, tuple) else (c, None)
+            if not 1 <= n <= self.max_chunk:
+                raise ValueError(f"{who}.push: slot {b}: n_samples = {n}; expected 1 <= n_samples <= max_chunk = {self.max_chunk}")
+            rows[b], words[b] = int(n), w
+        return rows, words
+
+    def _stage(self):
+        ops.wide_pool_stage_text(self.state, self.win, self.active, self._sos, self._eos, self.dec.text, self.dec.len)
+
+    def _send(self, rows, n, recs, fullest):
+        """The tick: the counts n (input_sr: turned into the 16 kHz samples that became final, on the host) and the records go up as one packed
+        copy and are appended by one launch.  Returns the 16 kHz samples every row got."""
+        if self.rs is not None:
+            n = self._resampled(n)
+        self._tick(n, recs, max(0, fullest - max(len(r) for r in recs)))
+        return n
+
+    def _flush(self, b):
+        """Row b's input has ended: the samples the resampler's flush would still append advance its clock, as a tick of counts alone."""
+        n = self._resampled([0] * self.B, flush=(b,))
+        self._tick(n, [[] for _ in range(self.B)], 0)
+        return n
+
+    def _tick(self, n, recs, words_live):
+        """Packs the header and the records into the pinned slot whose turn it is, starts the one copy, notes the records and launches the
+        push (nothing to do if a resampled tick made no sample final and brought no records)."""
+        B, m = self.B, [len(r) for r in recs]
+        if max(n) == 0 and max(m) == 0:
+            return
+        lay = wide_words_layout(n, m)
+        i = self._slot_to_fill("push")
+        host = self._push_host[i].numpy()
+        hdr = host[lay["hdr"]:lay["hdr"] + 16 * B].view(np.int32).reshape(B, 4)
+        hdr[:, 0], hdr[:, 1], hdr[:, 2], hdr[:, 3] = n, 0, m, lay["record_off"]
+        table = host[lay["records"]:lay["records"] + 12 * lay["n_records"]].view(np.int32)
+        for b, r in enumerate(recs):
+            if r:
+                table[3 * lay["record_off"][b]:3 * (lay["record_off"][b] + m[b])] = np.asarray(r, dtype=np.int32).reshape(-1)
+        self._push_dev[i][:lay["total"]].copy_(self._push_host[i][:lay["total"]], non_blocking=True)
+        self._sent("push", i)
+        self._note_records(recs)
+        ops.wide_pool_push_words(self.state, self._push_dev[i], lay, words_live)

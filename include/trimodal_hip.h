@@ -900,6 +900,27 @@ int tg_wide_pool_push_resampled(const int32_t* hdr, const float* samples, int64_
                                 float* carry, int64_t* consumed, int64_t* produced, float* ring, int64_t* written, int32_t* word_ring,
                                 int64_t* n_words, int32_t B, int32_t R, int32_t A, int32_t W, void* stream);
 
+/* Wide stream pool of the Seq2Seq model (csrc/stream_pool_wide_seq.hip: the push; csrc/stream_pool_seq.hip: text staging and hand-over,
+ * tg_pool_stage_text's and tg_pool_handover_smooth's kernels and launchers with another row limit; synthesize.WideSeq2SeqStreamPool; added under
+ * ABI 11 -- new symbols only): the Seq2Seq stream pool's three launches for 1 <= B <= 128 rows.  One workgroup per row, plain loads and
+ * stores, no atomics, nothing waits on another workgroup; a row that is not selected leaves before any store and before any barrier and
+ * keeps every bit it owns.  For B <= 4 the stage and the hand-over write what their tg_pool_* counterparts write, bit for bit.
+ * tg_wide_pool_push_words: the tick of a model that reads no sample.  hdr [B][4] int32 = per row (n samples, unused, record count, record
+ * offset) -- tg_wide_pool_push's header --; recs [recs_len][3] int32 = the rows' records (window, frame, word id) concatenated.  Row b appends
+ * recs[roff_b .. roff_b + m_b) to its word ring exactly as tg_wide_pool_push's row does and adds n_b to written[b] (n_words[b] += m_b); there
+ * is no sample ring and no sample is copied.  A row with n_b == 0 and m_b == 0 is skipped.  The kernel clamps n_b to >= 0, m_b to [0, m_max]
+ * and the slice into recs, so that no index leaves it.  words_live as for tg_pool_push.
+ * Envelope: 1 <= B <= 128, m_max >= 0, 1 <= W <= 1024, words_live >= 0, words_live + m_max <= W, m_max <= recs_len <= B m_max; recs may be null
+ * if m_max is 0; refused otherwise, nothing is launched. */
+int tg_wide_pool_push_words(const int32_t* hdr, const int32_t* recs, int64_t recs_len, int32_t m_max, int32_t words_live, int64_t* written,
+                            int32_t* word_ring, int64_t* n_words, int32_t B, int32_t W, void* stream);
+/* tg_pool_stage_text for 1 <= B <= 128.  Envelope: tg_pool_stage_text's with 1 <= B <= 128. */
+int tg_wide_pool_stage_text(const int32_t* word_ring, const int64_t* n_words, const int32_t* win, const int32_t* active, int32_t B, int32_t W,
+                            int32_t Te, int64_t sos, int64_t eos, int64_t* out_text, int64_t* out_len, void* stream);
+/* tg_pool_handover_smooth for 1 <= B <= 128.  Envelope: tg_pool_handover_smooth's with 1 <= B <= 128. */
+int tg_wide_pool_handover_smooth(const float* res, float* out, float* tail, float* seed, int32_t* win, const int32_t* active, const double* proj,
+                                 int32_t B, int32_t T, int32_t D, int32_t n_pre, void* stream);
+
 /* evaluate_testset metrics of one batch (train.py:282-310; utils/data_utils.py:77-98): out/target direction vectors [B][T][27],
  * mean_dir_vec [27].  sums[0] = sum |joint error| over frames >= n_pre and 10x3 joints, sums[1] = sum |second-difference error| over
  * T-2 frames, sums[2] = sum |out - target|.  (joint_mae = sums[0]/(B*(T-n_pre)*30), accel = sums[1]/(B*(T-2)*30), l1 = sums[2]/(B*T*27).) */
