@@ -4,7 +4,7 @@
 //   tg_wide_pool_push      the push of ONE packed device buffer: a header hdr [B][4] int32 = (n samples, sample offset, record count, record
 //                          offset) per row, the rows' chunks concatenated without padding, the rows' records concatenated.  Row b appends
 //                          samples[off .. off + n) and its records; a row with n == 0 and no records is skipped.  The header is the host's (it is
-//                          validated before the upload); the kernel clamps every count and offset so that no index leaves the two slices.
+//                          validated before the upload); packed_row (stream_rows.hpp) clamps every count and offset so that no index leaves the two slices.
 // (tg_wide_pool_stage and tg_wide_pool_handover are stream_pool.hip's kernels and launchers with the row limit ST_MAX_WIDE_ROWS: they live there.)
 // One workgroup per row, plain loads and stores, no atomics, nothing waits on another workgroup; a row that is not selected leaves before any store
 // and before any barrier: an idle row costs a workgroup that reads four integers and ends, so a launch over 128 rows of which one is busy takes
@@ -18,14 +18,7 @@ __global__ __launch_bounds__(1024) void wide_pool_push_kernel(const int32_t* __r
                                                               float* __restrict__ ring, int64_t* __restrict__ written, int32_t* __restrict__ word_ring,
                                                               int64_t* __restrict__ n_words, int R, int W) {
     const int b = blockIdx.x;
-    long n = hdr[4 * b], off = hdr[4 * b + 1], m = hdr[4 * b + 2], roff = hdr[4 * b + 3];
-    // the slices [off, off + n) of samples [samples_len] and [roff, roff + m) of recs [recs_len][3]: inside them whatever the header says
-    n = n < 0 ? 0 : (n > n_max ? n_max : n);
-    off = off < 0 ? 0 : (off > samples_len ? samples_len : off);
-    n = n > samples_len - off ? samples_len - off : n;
-    m = m < 0 ? 0 : (m > m_max ? m_max : m);
-    roff = roff < 0 ? 0 : (roff > recs_len ? recs_len : roff);
-    m = m > recs_len - roff ? recs_len - roff : m;
+    const auto [n, off, m, roff] = packed_row(hdr, b, n_max, samples_len, m_max, recs_len);
     if (n == 0 && m == 0) return;                                     // (the whole workgroup, before any barrier: the row keeps its counters and rings)
     const long wr = written[b], cnt = n_words[b];
     ring_push_row_from(b, (int)n, (int)m, wr, cnt, samples + off, recs + 3 * roff, ring, written, word_ring, n_words, R, W);

@@ -11,8 +11,8 @@
 // writes a contiguous tile, so a tile is staged in LDS and copied to the ring from there, each sample to its own position: a tile may straddle
 // the ring's wrap point.
 // One workgroup of RS_THREADS threads per row, plain loads and stores, no atomics, nothing waits on another workgroup; a row with no samples,
-// no records and no flush leaves before any store and before any barrier.  The header is the host's; the kernel clamps every count and offset
-// as wide_pool_push_kernel does, and the new output count to what the launcher checked the ring for, so that no index leaves a slice or a row.
+// no records and no flush leaves before any store and before any barrier.  The header is the host's; packed_row (stream_rows.hpp) clamps every
+// count and offset, and the kernel the new output count to what the launcher checked the ring for, so that no index leaves a slice or a row.
 // LDS: the tile body's two arrays (50 KB) and one tile of outputs (1 KB); three workgroups per CU fit.
 #include "resample_tile.hpp"
 #include "stream_rows.hpp"
@@ -31,14 +31,7 @@ __global__ __launch_bounds__(RS_THREADS) void wide_pool_push_resampled_kernel(co
     __shared__ float s_t[RS_TAP_FLOATS];
     __shared__ float s_y[RS_THREADS];                                 // one tile of outputs (TN <= RS_THREADS)
     const int b = blockIdx.x, tid = threadIdx.x;
-    long n = hdr[4 * b], off = hdr[4 * b + 1], m = hdr[4 * b + 2], roff = hdr[4 * b + 3];
-    // the slices [off, off + n) of samples [samples_len] and [roff, roff + m) of recs [recs_len][3]: inside them whatever the header says
-    n = n < 0 ? 0 : (n > n_max ? n_max : n);
-    off = off < 0 ? 0 : (off > samples_len ? samples_len : off);
-    n = n > samples_len - off ? samples_len - off : n;
-    m = m < 0 ? 0 : (m > m_max ? m_max : m);
-    roff = roff < 0 ? 0 : (roff > recs_len ? recs_len : roff);
-    m = m > recs_len - roff ? recs_len - roff : m;
+    const auto [n, off, m, roff] = packed_row(hdr, b, n_max, samples_len, m_max, recs_len);
     const bool flush = b == flush_row;
     if (n == 0 && m == 0 && !flush) return;                           // (the whole workgroup, before any barrier: the row keeps every bit)
     const bool resampling = n > 0 || flush;                           // a row with records only: its resampler row keeps every bit

@@ -4,8 +4,8 @@
 //   tg_wide_pool_push_words   the push of ONE packed device buffer: a header hdr [B][4] int32 = (n samples, 0, record count, record offset) per
 //                             row -- tg_wide_pool_push's header; the second entry is not read -- and the rows' records concatenated.  Row b appends
 //                             its records to its word ring and adds n to written[b]; a row with n == 0 and no records is skipped.  The header is
-//                             the host's (it is validated before the upload); the kernel clamps the counts and the offset so that no index leaves
-//                             the record slice.
+//                             the host's (it is validated before the upload); packed_row<false> (stream_rows.hpp) clamps the counts and the
+//                             records' offset so that no index leaves the record slice.
 // (tg_wide_pool_stage_text and tg_wide_pool_handover_smooth are stream_pool_seq.hip's kernels and launchers with the row limit ST_MAX_WIDE_ROWS:
 // they live there.)
 // One workgroup per row, plain loads and stores, no atomics, nothing waits on another workgroup; a row that is not selected leaves before any
@@ -21,12 +21,7 @@ __global__ __launch_bounds__(PW_THREADS) void wide_pool_push_words_kernel(const 
                                                                           long recs_len, int m_max, int64_t* written, int32_t* __restrict__ word_ring,
                                                                           int64_t* n_words, int W) {
     const int b = blockIdx.x;
-    long n = hdr[4 * b], m = hdr[4 * b + 2], roff = hdr[4 * b + 3];
-    // the slice [roff, roff + m) of recs [recs_len][3]: inside it whatever the header says (wide_pool_push_kernel's clamps)
-    n = n < 0 ? 0 : n;
-    m = m < 0 ? 0 : (m > m_max ? m_max : m);
-    roff = roff < 0 ? 0 : (roff > recs_len ? recs_len : roff);
-    m = m > recs_len - roff ? recs_len - roff : m;
+    const auto [n, off, m, roff] = packed_row<false>(hdr, b, 0, 0, m_max, recs_len);     // (no sample piece: the second entry is not loaded, off is 0)
     if (n == 0 && m == 0) return;                                     // (the whole workgroup, before any barrier: the row keeps its counters and ring)
     const long wr = written[b], cnt = n_words[b];
     __syncthreads();                                                  // every thread has the counters before thread 0 moves them

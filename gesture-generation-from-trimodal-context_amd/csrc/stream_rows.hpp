@@ -2,7 +2,8 @@
 // n_words -- does in a push and in the staging of a window.  stream.hip runs them for rows that share a clock (one chunk length, one window
 // index), stream_pool.hip for rows with clocks of their own (a length and a window index per row, idle rows skipped); stream_seq.hip and
 // stream_pool_seq.hip stage the Seq2Seq model's word list from the same word ring, in the same two ways.  The bounds are the files' bounds.
-// stream_pool_wide.hip, stream_pool_wide_rs.hip and stream_pool_wide_seq.hip push rows whose lengths come from a packed header.
+// stream_pool_wide.hip, stream_pool_wide_rs.hip and stream_pool_wide_seq.hip push rows whose lengths come from a packed header, which
+// packed_row reads and clamps for all three.
 // As in utterance.hip the device sees integers only and samples and ids move as bits: plain loads and stores.
 #pragma once
 #include "common.hpp"
@@ -15,6 +16,24 @@ constexpr int ST_MAX_WORDS = 1024;      // largest word ring per row: 12 KB of L
 constexpr int ST_MAX_FRAMES = 1024;     // frames of a window: one thread each
 constexpr int ST_MAX_RING = 1 << 30;    // samples of a row's ring: positions and their sums stay inside an int
 constexpr int ST_MAX_WINDOW = 1 << 25;  // samples of a window: the stage kernels' grid
+
+// Row b of a packed tick's header hdr [B][4] int32 = (n samples, sample offset, record count, record offset), clamped so that the slices
+// [off, off + n) of samples [samples_len] and [roff, roff + m) of recs [recs_len][3] lie inside them whatever the header says.  SAMPLES = false
+// (a tick without a sample piece, stream_pool_wide_seq.hip): n is a count that only has to be >= 0, and the second entry is not loaded.
+struct PackedRow { long n, off, m, roff; };
+template <bool SAMPLES = true>
+__device__ __forceinline__ PackedRow packed_row(const int32_t* __restrict__ hdr, int b, int n_max, long samples_len, int m_max, long recs_len) {
+    long n = hdr[4 * b], off = SAMPLES ? hdr[4 * b + 1] : 0, m = hdr[4 * b + 2], roff = hdr[4 * b + 3];
+    n = n < 0 ? 0 : (SAMPLES && n > n_max ? n_max : n);
+    if constexpr (SAMPLES) {
+        off = off < 0 ? 0 : (off > samples_len ? samples_len : off);
+        n = n > samples_len - off ? samples_len - off : n;
+    }
+    m = m < 0 ? 0 : (m > m_max ? m_max : m);
+    roff = roff < 0 ? 0 : (roff > recs_len ? recs_len : roff);
+    m = m > recs_len - roff ? recs_len - roff : m;
+    return {n, off, m, roff};
+}
 
 // The records' half of a push, by a workgroup of THREADS threads: m records trip[0 .. 3 m) to row b's word ring at cnt mod W; it moves no counter.
 // Every push body appends its records through it: ring_push_row_from below (1024 threads), stream_pool_wide_rs.hip (the resampler's workgroup, 256,

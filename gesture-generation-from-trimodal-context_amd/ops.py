@@ -2037,15 +2037,43 @@ def _stage_outputs(st, text_out, audio_out):
             raise ValueError(f"text_out is {tuple(text_out.shape)}, a window's text is {(st['B'], st['T'])}, contiguous")
 
 
-def _push_operands(st, chunk, n_max, want, recs, m_max):
-    """The chunk (B, >= n_max) and the records table of stream_push / pool_push, checked (want: the chunk's shape as the refusal words it);
-    returns their row strides."""
-    B = st["B"]
+def _text_outputs(st, text_out, len_out):
+    """The output buffers of stream_stage_text / pool_stage_text: text_out (B, Te) int64, contiguous, and len_out (B,) int64."""
+    _i64(text_out, "text_out")
+    if text_out.dim() != 2 or text_out.shape[0] != st["B"] or not text_out.is_contiguous():
+        raise ValueError(f"text_out is {tuple(text_out.shape)}, expected ({st['B']}, Te), contiguous")
+    _dev_int(len_out, torch.int64, st["B"], "len_out")
+
+
+def _win_active(win, active, B):
+    """The rows' selectors of a pooled launch: win and active, (B,) int32 on the device."""
+    _dev_int(win, torch.int32, B, "win"); _dev_int(active, torch.int32, B, "active")
+
+
+def _selectors(win, active, B):
+    """The selectors of a preview launch: win (B,) int32 on the device or one host integer for every row, active (B,) int32 on the device or
+    None (every row).  Returns (win or None, the host integer or 0, active)."""
+    win, w_value = (_dev_int(win, torch.int32, B, "win"), 0) if isinstance(win, torch.Tensor) else (None, int(win))
+    if active is not None:
+        _dev_int(active, torch.int32, B, "active")
+    return win, w_value, active
+
+
+def _chunk_stride(B, chunk, n_max, want):
+    """The chunk (B, >= n_max) of a push or of resample_stream, checked (want: its shape as the refusal words it); returns its row stride."""
     if chunk.dim() != 2 or chunk.shape[0] != B or chunk.shape[1] < n_max or (chunk.shape[1] > 1 and chunk.stride(1) != 1):
         raise ValueError(f"chunk: expected ({B}, {want}) with unit inner stride, got {tuple(chunk.shape)} strides {chunk.stride()}")
     cs = chunk.stride(0) if B > 1 else max(chunk.shape[1], 1)
     if n_max > 0 and (cs < n_max or (B - 1) * cs + n_max > _room(chunk)):
         raise ValueError("chunk: rows overlap or exceed the tensor")
+    return cs
+
+
+def _push_operands(st, chunk, n_max, want, recs, m_max):
+    """The chunk (B, >= n_max) and the records table of stream_push / pool_push, checked (want: the chunk's shape as the refusal words it);
+    returns their row strides."""
+    B = st["B"]
+    cs = _chunk_stride(B, chunk, n_max, want)
     rs = 0
     if m_max > 0:
         if not (isinstance(recs, torch.Tensor) and recs.is_cuda and recs.dtype == torch.int32 and recs.dim() == 2 and recs.is_contiguous() and recs.shape[0] == B):
@@ -2081,10 +2109,7 @@ def stream_stage_text(st, sos, eos, text_out, len_out):
     record of that window in push order, eos, 0 ...], len_out (B,) int64 = count + 2.  Device buffers written in place; the host refuses
     a window with more than Te - 2 records before it is pushed (the kernel clamps)."""
     _stream_check(st)
-    _i64(text_out, "text_out")
-    if text_out.dim() != 2 or text_out.shape[0] != st["B"] or not text_out.is_contiguous():
-        raise ValueError(f"text_out is {tuple(text_out.shape)}, expected ({st['B']}, Te), contiguous")
-    _dev_int(len_out, torch.int64, st["B"], "len_out")
+    _text_outputs(st, text_out, len_out)
     call("tg_stream_stage_text", _p(st["words"]), _p(st["n_words"]), _p(st["win"]), st["B"], st["W"], int(text_out.shape[1]), int(sos), int(eos),
          _p(text_out), _p(len_out), _stream())
 
@@ -2110,14 +2135,15 @@ def pool_stage(st, win, active, text_out=None, audio_out=None, entry="tg_pool_st
     """stream_stage per row: row b with active[b] != 0 gets the inputs of its own window win[b] (win, active: (B,) int32 on the device); the rows of
     audio_out / text_out that belong to the other rows are left as they are."""
     _stream_check(st)
-    _dev_int(win, torch.int32, st["B"], "win"); _dev_int(active, torch.int32, st["B"], "active")
+    _win_active(win, active, st["B"])
     _stage_outputs(st, text_out, audio_out)
     call(entry, _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(win), _p(active), st["B"], st["R"], st["S"], st["A"],
          st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
 
 
 def _four_3d(**tensors):
-    """The four tensors of a hand-over (pool_handover, pool_handover_smooth, queue_handover), by name: flat fp32 on the device, three dimensions."""
+    """The tensors of a hand-over (pool_handover, pool_handover_smooth, queue_handover: four; preview_handover: three), by name: flat fp32 on the
+    device, three dimensions."""
     for name, t in tensors.items():
         _flat(t, name)
         if t.dim() != 3:
@@ -2134,11 +2160,22 @@ def pool_handover(res, out, tail, seed, win, active, entry="tg_pool_handover"):
     if tuple(res.shape) != (B, T, D) or tail.shape[0] != B or tail.shape[2] != D:
         raise ValueError(f"res {tuple(res.shape)} / tail {tuple(tail.shape)} do not belong to out {tuple(out.shape)}")
     layout = _seed_layout(seed, B, T, D, n_pre)
-    _dev_int(win, torch.int32, B, "win"); _dev_int(active, torch.int32, B, "active")
+    _win_active(win, active, B)
     call(entry, _p(res), _p(out), _p(tail), _p(seed), layout, _p(win), _p(active), B, T, D, n_pre, _stream())
 
 
 # ------------------------------------------------------------------------------------------------- wide stream pool (csrc/stream_pool_wide.hip)
+def _packed_pieces(st, packed, lay):
+    """The packed buffer of a wide push, checked against its layout lay and the state's rows.  Returns the device addresses of its pieces:
+    (the header, the samples or None, the records or None) -- None for a piece the layout does not have or that is empty."""
+    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 1 and packed.is_contiguous()):
+        raise TypeError("packed: expected a flat contiguous CUDA uint8 tensor")
+    if lay["B"] != st["B"] or packed.numel() < lay["total"] or packed.data_ptr() % 16:
+        raise ValueError(f"packed: {packed.numel()} bytes for a layout of {lay['B']} rows and {lay['total']} bytes on a state of {st['B']} rows")
+    base = packed.data_ptr()
+    return base + lay["hdr"], base + lay["samples"] if lay.get("n_samples") else None, base + lay["records"] if lay["n_records"] else None
+
+
 def wide_pool_push(st, packed, lay, words_live=0):
     """pool_push for up to 128 rows from ONE packed device buffer: packed (flat uint8, device) holds, at the byte offsets of lay
     (synthesize.wide_push_layout), the header (B, 4) int32 = per row (n samples, sample offset, record count, record offset), the rows' chunks
@@ -2146,15 +2183,9 @@ def wide_pool_push(st, packed, lay, words_live=0):
     words_live + the largest record count: the slot count of the fullest word ring after the push.  Outside the envelope (1 <= B <= 128, a row
     with samples or records, R >= A + the longest chunk) the library refuses (RuntimeError naming the envelope); nothing is launched."""
     _stream_check(st)
-    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 1 and packed.is_contiguous()):
-        raise TypeError("packed: expected a flat contiguous CUDA uint8 tensor")
-    if lay["B"] != st["B"] or packed.numel() < lay["total"] or packed.data_ptr() % 16:
-        raise ValueError(f"packed: {packed.numel()} bytes for a layout of {lay['B']} rows and {lay['total']} bytes on a state of {st['B']} rows")
-    base = packed.data_ptr()
-    n_s, n_r = lay["n_samples"], lay["n_records"]
-    call("tg_wide_pool_push", base + lay["hdr"], base + lay["samples"] if n_s else None, n_s, base + lay["records"] if n_r else None, n_r,
-         lay["n_max"], lay["m_max"], int(words_live), _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), st["B"], st["R"], st["A"],
-         st["W"], _stream())
+    hdr, samples, records = _packed_pieces(st, packed, lay)
+    call("tg_wide_pool_push", hdr, samples, lay["n_samples"], records, lay["n_records"], lay["n_max"], lay["m_max"], int(words_live), _p(st["ring"]),
+         _p(st["written"]), _p(st["words"]), _p(st["n_words"]), st["B"], st["R"], st["A"], st["W"], _stream())
 
 
 def wide_pool_stage(st, win, active, text_out=None, audio_out=None):
@@ -2172,11 +2203,8 @@ def pool_stage_text(st, win, active, sos, eos, text_out, len_out, entry="tg_pool
     """stream_stage_text per row: row b with active[b] != 0 gets the Seq2Seq text of its own window win[b] (win, active: (B,) int32 on the device)
     in text_out[b] (B, Te) int64 and its length in len_out[b] (B,) int64; the other rows of both buffers are left as they are."""
     _stream_check(st)
-    _dev_int(win, torch.int32, st["B"], "win"); _dev_int(active, torch.int32, st["B"], "active")
-    _i64(text_out, "text_out")
-    if text_out.dim() != 2 or text_out.shape[0] != st["B"] or not text_out.is_contiguous():
-        raise ValueError(f"text_out is {tuple(text_out.shape)}, expected ({st['B']}, Te), contiguous")
-    _dev_int(len_out, torch.int64, st["B"], "len_out")
+    _win_active(win, active, st["B"])
+    _text_outputs(st, text_out, len_out)
     call(entry, _p(st["words"]), _p(st["n_words"]), _p(win), _p(active), st["B"], st["W"], int(text_out.shape[1]), int(sos), int(eos), _p(text_out),
          _p(len_out), _stream())
 
@@ -2191,7 +2219,7 @@ def pool_handover_smooth(res, out, tail, seed, win, active, proj, entry="tg_pool
     n_pre = tail.shape[1]
     if tuple(res.shape) != (B, T, D) or tuple(tail.shape) != (B, n_pre, D) or tuple(seed.shape) != (B, n_pre, D):
         raise ValueError(f"res {tuple(res.shape)} / tail {tuple(tail.shape)} / seed {tuple(seed.shape)} do not belong to out {tuple(out.shape)}")
-    _dev_int(win, torch.int32, B, "win"); _dev_int(active, torch.int32, B, "active")
+    _win_active(win, active, B)
     assert proj.is_cuda and proj.dtype == torch.float64 and proj.is_contiguous() and proj.numel() >= 9 * n_pre * n_pre
     call(entry, _p(res), _p(out), _p(tail), _p(seed), _p(win), _p(active), _p(proj), B, T, D, n_pre, _stream())
 
@@ -2213,13 +2241,8 @@ def wide_pool_push_words(st, packed, lay, words_live=0):
     B, W = st["B"], st["W"]
     _dev_int(st["words"], torch.int32, B * W * 3, "word ring")
     _dev_int(st["written"], torch.int64, B, "written"); _dev_int(st["n_words"], torch.int64, B, "n_words")
-    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 1 and packed.is_contiguous()):
-        raise TypeError("packed: expected a flat contiguous CUDA uint8 tensor")
-    if lay["B"] != B or packed.numel() < lay["total"] or packed.data_ptr() % 16:
-        raise ValueError(f"packed: {packed.numel()} bytes for a layout of {lay['B']} rows and {lay['total']} bytes on a state of {B} rows")
-    base = packed.data_ptr()
-    n_r = lay["n_records"]
-    call("tg_wide_pool_push_words", base + lay["hdr"], base + lay["records"] if n_r else None, n_r, lay["m_max"], int(words_live), _p(st["written"]),
+    hdr, _, records = _packed_pieces(st, packed, lay)
+    call("tg_wide_pool_push_words", hdr, records, lay["n_records"], lay["m_max"], int(words_live), _p(st["written"]),
          _p(st["words"]), _p(st["n_words"]), B, W, _stream())
 
 
@@ -2356,6 +2379,13 @@ def resample_state(B, taps, L, M, K, max_chunk, device, stage=True):
                 produced=torch.zeros(B, dtype=torch.int64, device=device), stage=torch.zeros(B, int(max_chunk), device=device) if stage else None)
 
 
+def _resampler_rows(rs):
+    """The rows of a resampler state on the device: the carry (B, K - 1) fp32 and the int64 counters consumed and produced."""
+    B = rs["B"]
+    _flat(rs["carry"], "carry"); _dev_int(rs["consumed"], torch.int64, B, "consumed"); _dev_int(rs["produced"], torch.int64, B, "produced")
+    assert rs["carry"].numel() == B * (rs["K"] - 1)
+
+
 def resample_stream(rs, chunk, n, out, flush=()):
     """Row b of the resampler state rs takes chunk[b, :n[b]] (chunk (B, >= max n) fp32, device, unit inner stride; None if every n[b] is 0; n: B
     host integers in [0, max_chunk]) and writes the output samples that became final to out[b, 0:...] (out (B, >= rs['out_stride']) fp32, device,
@@ -2375,16 +2405,11 @@ def resample_stream(rs, chunk, n, out, flush=()):
     cs = 0
     if n_max > 0:
         _f32(chunk, "chunk")
-        if chunk.dim() != 2 or chunk.shape[0] != B or chunk.shape[1] < n_max or (chunk.shape[1] > 1 and chunk.stride(1) != 1):
-            raise ValueError(f"chunk: expected ({B}, >= {n_max}) with unit inner stride, got {tuple(chunk.shape)} strides {chunk.stride()}")
-        cs = chunk.stride(0) if B > 1 else max(chunk.shape[1], 1)
-        if cs < n_max or (B - 1) * cs + n_max > _room(chunk):
-            raise ValueError("chunk: rows overlap or exceed the tensor")
+        cs = _chunk_stride(B, chunk, n_max, f">= {n_max}")
     _flat(out, "out")
     if out.dim() != 2 or out.shape[0] != B or out.shape[1] < rs["out_stride"]:
         raise ValueError(f"out: expected a contiguous ({B}, >= {rs['out_stride']}) tensor, got {tuple(out.shape)}")
-    _flat(rs["carry"], "carry"); _dev_int(rs["consumed"], torch.int64, B, "consumed"); _dev_int(rs["produced"], torch.int64, B, "produced")
-    assert rs["carry"].numel() == B * (rs["K"] - 1)
+    _resampler_rows(rs)
     call("tg_resample_stream", _p(chunk if n_max > 0 else None), cs, *(n + [0] * 4)[:4], mask, _p(rs["taps"]), rs["L"], rs["M"], rs["K"], _p(rs["carry"]),
          _p(rs["consumed"]), _p(rs["produced"]), _p(out), out.shape[1], B, _stream())      # (B > 4: refused by the library)
 
@@ -2399,24 +2424,18 @@ def wide_pool_push_resampled(st, rs, packed, lay, words_live=0, flush_row=None):
     (1 <= B <= 128, a row with samples, records or the flush, R >= A + ceil((longest chunk + K/2 on a flush) L / M) + 1) the library refuses
     (RuntimeError naming the envelope); nothing is launched."""
     _stream_check(st)
-    if not (isinstance(packed, torch.Tensor) and packed.is_cuda and packed.dtype == torch.uint8 and packed.dim() == 1 and packed.is_contiguous()):
-        raise TypeError("packed: expected a flat contiguous CUDA uint8 tensor")
+    hdr, samples, records = _packed_pieces(st, packed, lay)
     B = st["B"]
-    if lay["B"] != B or packed.numel() < lay["total"] or packed.data_ptr() % 16:
-        raise ValueError(f"packed: {packed.numel()} bytes for a layout of {lay['B']} rows and {lay['total']} bytes on a state of {B} rows")
     if rs["B"] != B or lay["n_max"] > rs["max_chunk"]:
         raise ValueError(f"rs: a resampler of {rs['B']} row(s) of at most {rs['max_chunk']} samples for {B} rows whose longest chunk has {lay['n_max']}")
     flush = -1 if flush_row is None else int(flush_row)
     if not -1 <= flush < B:
         raise ValueError(f"flush_row: row {flush_row} of {B}")
     _taps_check(rs["taps"], rs["L"], rs["M"], rs["K"])
-    _flat(rs["carry"], "carry"); _dev_int(rs["consumed"], torch.int64, B, "consumed"); _dev_int(rs["produced"], torch.int64, B, "produced")
-    assert rs["carry"].numel() == B * (rs["K"] - 1)
-    base = packed.data_ptr()
-    n_s, n_r = lay["n_samples"], lay["n_records"]
-    call("tg_wide_pool_push_resampled", base + lay["hdr"], base + lay["samples"] if n_s else None, n_s, base + lay["records"] if n_r else None, n_r,
-         lay["n_max"], lay["m_max"], int(words_live), flush, _p(rs["taps"]), rs["L"], rs["M"], rs["K"], _p(rs["carry"]), _p(rs["consumed"]),
-         _p(rs["produced"]), _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), B, st["R"], st["A"], st["W"], _stream())
+    _resampler_rows(rs)
+    call("tg_wide_pool_push_resampled", hdr, samples, lay["n_samples"], records, lay["n_records"], lay["n_max"], lay["m_max"], int(words_live), flush,
+         _p(rs["taps"]), rs["L"], rs["M"], rs["K"], _p(rs["carry"]), _p(rs["consumed"]), _p(rs["produced"]), _p(st["ring"]), _p(st["written"]),
+         _p(st["words"]), _p(st["n_words"]), B, st["R"], st["A"], st["W"], _stream())
 
 
 # ------------------------------------------------------------------------------------------------- stream preview (csrc/stream_preview.hip)
@@ -2433,8 +2452,7 @@ def resample_stream_peek(rs, extra, rows):
     _flat(extra, "extra")
     if extra.dim() != 2 or extra.shape[0] != B:
         raise ValueError(f"extra: expected a contiguous ({B}, n) tensor, got {tuple(extra.shape)}")
-    _flat(rs["carry"], "carry"); _dev_int(rs["consumed"], torch.int64, B, "consumed"); _dev_int(rs["produced"], torch.int64, B, "produced")
-    assert rs["carry"].numel() == B * (rs["K"] - 1)
+    _resampler_rows(rs)
     call("tg_resample_stream_peek", mask, _p(rs["taps"]), rs["L"], rs["M"], rs["K"], _p(rs["carry"]), _p(rs["consumed"]), _p(rs["produced"]),
          _p(extra), extra.shape[1], B, _stream())
 
@@ -2455,21 +2473,8 @@ def stream_stage_preview(st, win, active, extra, extra_n, text_out=None, audio_o
         if extra.dim() != 2 or extra.shape[0] != B or extra.shape[1] < max(extra_n):
             raise ValueError(f"extra: expected a contiguous ({B}, >= {max(extra_n)}) tensor, got {tuple(extra.shape)}")
         es = extra.shape[1]
-    w_value = 0
-    if not isinstance(win, torch.Tensor):
-        win, w_value = None, int(win)
-    else:
-        _dev_int(win, torch.int32, B, "win")
-    if active is not None:
-        _dev_int(active, torch.int32, B, "active")
-    if audio_out is not None:
-        _flat(audio_out, "audio_out")
-        if tuple(audio_out.shape) != (B, st["A"]):
-            raise ValueError(f"audio_out is {tuple(audio_out.shape)}, a window is {(B, st['A'])}")
-    if text_out is not None:
-        _i64(text_out, "text_out")
-        if tuple(text_out.shape) != (B, st["T"]) or not text_out.is_contiguous():
-            raise ValueError(f"text_out is {tuple(text_out.shape)}, a window's text is {(B, st['T'])}, contiguous")
+    win, w_value, active = _selectors(win, active, B)
+    _stage_outputs(st, text_out, audio_out)
     call("tg_stream_stage_preview", _p(st["ring"]), _p(st["written"]), _p(st["words"]), _p(st["n_words"]), _p(win), w_value, _p(active),
          _p(extra if es else None), es, *(extra_n + [0] * 4)[:4], B, st["R"], st["S"], st["A"], st["W"], st["T"], _p(audio_out), _p(text_out), _stream())
 
@@ -2478,21 +2483,12 @@ def preview_handover(res, tail, win, active, preview_out):
     """pool_handover's first half and nothing else: for the rows with active[b] != 0 (active None: every row) preview_out = res (B, T, D),
     cross-faded with tail (B, n_pre, D) where the row's window index -- win[b], (B,) int32 on the device, or one host integer for every row --
     is > 0 (window_blend's arithmetic).  tail, the seeds and win are only read."""
-    for t, name in ((res, "res"), (tail, "tail"), (preview_out, "preview_out")):
-        _flat(t, name)
-        if t.dim() != 3:
-            raise ValueError(f"{name}: expected three dimensions, got {tuple(t.shape)}")
+    _four_3d(res=res, tail=tail, preview_out=preview_out)
     B, T, D = preview_out.shape
     n_pre = tail.shape[1]
     if tuple(res.shape) != (B, T, D) or tail.shape[0] != B or tail.shape[2] != D:
         raise ValueError(f"res {tuple(res.shape)} / tail {tuple(tail.shape)} do not belong to preview_out {tuple(preview_out.shape)}")
-    w_value = 0
-    if not isinstance(win, torch.Tensor):
-        win, w_value = None, int(win)
-    else:
-        _dev_int(win, torch.int32, B, "win")
-    if active is not None:
-        _dev_int(active, torch.int32, B, "active")
+    win, w_value, active = _selectors(win, active, B)
     call("tg_preview_handover", _p(res), _p(tail), _p(win), w_value, _p(active), B, T, D, n_pre, _p(preview_out), _stream())
 
 

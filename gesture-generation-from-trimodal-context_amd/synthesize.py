@@ -2077,15 +2077,16 @@ class StreamPool(_StreamCore):
         recs, late = self._records(words)                                   # (may refuse; nothing has changed yet)
         n = [self._n_of(rows[b]) if b in rows else 0 for b in range(self.B)]
         fullest = max((self._live_slots(b) + len(r) for b, r in enumerate(recs) if r), default=0)      # slots of the fullest word ring after the push
-        n = self._send(rows, n, recs, fullest)
+        n = self._send(rows, n, recs, max(0, fullest - max(map(len, recs))))
         for b in range(self.B):
             self.pushed[b] += n[b]
             self.late_words[b] += late[b]
         return {b: self._result(*fr, numpy) for b, fr in self._emit(list(rows), joints).items()}
 
-    def _send(self, rows, n, recs, fullest):
+    def _send(self, rows, n, recs, words_live):
         """The chunks {row: samples} (n: their lengths per row) and the records recs go up -- one dense (B, max n) upload and the records'
-        table -- and are appended to the rows' rings; the records are noted.  Returns the 16 kHz samples every row got."""
+        table -- and are appended to the rows' rings; the records are noted.  words_live: the fullest word ring's slots without the push's
+        largest record count (ops.pool_push).  Returns the 16 kHz samples every row got."""
         host = np.zeros((self.B, max(n)), np.float32)
         for b, c in rows.items():
             host[b, :n[b]] = c
@@ -2094,7 +2095,7 @@ class StreamPool(_StreamCore):
         table, m_max = self._commit_records(recs)
         if self.rs is not None:                                             # input_sr samples -> every row's new 16 kHz samples, in chunk_buf
             n, dst = self._resample(dst, n), self.chunk_buf
-        self._feed(dst, n, table, m_max, max(0, fullest - m_max))
+        self._feed(dst, n, table, m_max, words_live)
         return n
 
     def _feed(self, chunk, n, table, m_max, words_live):
@@ -2277,15 +2278,22 @@ def wide_push_layout(n, m):
     start on 256-byte boundaries, like data.packed_like's.  Returns a dict: the byte offsets hdr, samples, records and the byte size total;
     sample_off / record_off: per row the first sample / record of its slice, in samples / records; n_samples, n_records: the slices' sums;
     n_max, m_max; B."""
+    return _packed_layout("wide_push_layout", "chunk lengths", n, m, True)
+
+
+def _packed_layout(who, what, n, m, samples):
+    """wide_push_layout (samples) and wide_words_layout (no sample piece: the records follow the header, and no key speaks of samples)."""
     n, m = [int(v) for v in n], [int(v) for v in m]
     if len(n) != len(m) or not n or min(n) < 0 or min(m) < 0:
-        raise ValueError(f"wide_push_layout: {len(n)} chunk lengths and {len(m)} record counts; expected one of each per row, none negative")
+        raise ValueError(f"{who}: {len(n)} {what} and {len(m)} record counts; expected one of each per row, none negative")
     up = lambda v: (v + 255) // 256 * 256
-    B, n_samples, n_records = len(n), sum(n), sum(m)
-    samples = up(16 * B)
-    records = samples + up(4 * n_samples)
-    return dict(B=B, hdr=0, samples=samples, records=records, total=records + up(12 * n_records), n_samples=n_samples, n_records=n_records,
-                sample_off=[sum(n[:b]) for b in range(B)], record_off=[sum(m[:b]) for b in range(B)], n_max=max(n), m_max=max(m))
+    B, n_samples, n_records = len(n), sum(n) if samples else 0, sum(m)
+    records = up(16 * B) + up(4 * n_samples)
+    lay = dict(B=B, hdr=0, records=records, total=records + up(12 * n_records), n_records=n_records, record_off=[sum(m[:b]) for b in range(B)],
+               n_max=max(n), m_max=max(m))
+    if samples:
+        lay.update(samples=up(16 * B), n_samples=n_samples, sample_off=[sum(n[:b]) for b in range(B)])
+    return lay
 
 
 class _PinnedTicks:
@@ -2316,6 +2324,29 @@ class _PinnedTicks:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(self.dev))
             self._copied[kind][i] = ev
+
+    def _pack(self, layout, n, recs, rows=None):
+        """One tick on its way up: packs it into the pinned slot whose turn it is -- the header of layout(n, record counts), the chunks rows
+        ({row: samples}; None: a tick without a sample piece, whose header has zeros for the sample offsets) and the records --, starts the
+        one copy and notes the records.  Returns (the slot, the layout)."""
+        B, m = self.B, [len(r) for r in recs]
+        lay = layout(n, m)
+        i = self._slot_to_fill("push")
+        host = self._push_host[i].numpy()
+        hdr = host[lay["hdr"]:lay["hdr"] + 16 * B].view(np.int32).reshape(B, 4)
+        hdr[:, 0], hdr[:, 1], hdr[:, 2], hdr[:, 3] = n, lay.get("sample_off", 0), m, lay["record_off"]
+        if rows is not None:
+            samples = host[lay["samples"]:lay["samples"] + 4 * lay["n_samples"]].view(np.float32)
+            for b, c in rows.items():
+                samples[lay["sample_off"][b]:lay["sample_off"][b] + n[b]] = c
+        table = host[lay["records"]:lay["records"] + 12 * lay["n_records"]].view(np.int32)
+        for b, r in enumerate(recs):
+            if r:
+                table[3 * lay["record_off"][b]:3 * (lay["record_off"][b] + m[b])] = np.asarray(r, dtype=np.int32).reshape(-1)
+        self._push_dev[i][:lay["total"]].copy_(self._push_host[i][:lay["total"]], non_blocking=True)
+        self._sent("push", i)
+        self._note_records(recs)
+        return i, lay
 
     def _send_round(self, mask):
         """The mask and the active rows' draws go up as ONE small copy, into the decoder's round_buf."""
@@ -2374,33 +2405,12 @@ class WideStreamPool(_PinnedTicks, StreamPool):
     def _stage(self):
         ops.wide_pool_stage(self.state, self.win, self.active, self.dec.text, self.dec.audio)
 
-    def _send(self, rows, n, recs, fullest):
+    def _send(self, rows, n, recs, words_live):
         """StreamPool._send for a wide pool: the header, the chunks and the records of every pushed row are packed into a pinned slot (numpy
-        copies), go up as one copy, and ops.wide_pool_push appends all rows in one launch."""
-        i, lay = self._upload(rows, n, recs)
-        ops.wide_pool_push(self.state, self._push_dev[i], lay, max(0, fullest - lay["m_max"]))
+        copies), go up as one copy (_PinnedTicks._pack), and ops.wide_pool_push appends all rows in one launch."""
+        i, lay = self._pack(wide_push_layout, n, recs, rows)
+        ops.wide_pool_push(self.state, self._push_dev[i], lay, words_live)
         return n
-
-    def _upload(self, rows, n, recs):
-        """One tick on its way up: packs it into the pinned slot whose turn it is, starts the one copy and notes the records.  Returns
-        (the slot, the layout)."""
-        B, m = self.B, [len(r) for r in recs]
-        lay = wide_push_layout(n, m)
-        i = self._slot_to_fill("push")
-        host = self._push_host[i].numpy()
-        hdr = host[lay["hdr"]:lay["hdr"] + 16 * B].view(np.int32).reshape(B, 4)
-        hdr[:, 0], hdr[:, 1], hdr[:, 2], hdr[:, 3] = n, lay["sample_off"], m, lay["record_off"]
-        samples = host[lay["samples"]:lay["samples"] + 4 * lay["n_samples"]].view(np.float32)
-        for b, c in rows.items():
-            samples[lay["sample_off"][b]:lay["sample_off"][b] + n[b]] = c
-        table = host[lay["records"]:lay["records"] + 12 * lay["n_records"]].view(np.int32)
-        for b, r in enumerate(recs):
-            if r:
-                table[3 * lay["record_off"][b]:3 * (lay["record_off"][b] + m[b])] = np.asarray(r, dtype=np.int32).reshape(-1)
-        self._push_dev[i][:lay["total"]].copy_(self._push_host[i][:lay["total"]], non_blocking=True)
-        self._sent("push", i)
-        self._note_records(recs)
-        return i, lay
 
 
 class WideResampledStreamPool(WideStreamPool):
@@ -2425,16 +2435,16 @@ class WideResampledStreamPool(WideStreamPool):
                          input_sr=input_sr)
 
     def _tick(self, rows, n, recs, words_live, flush=()):
-        i, lay = self._upload(rows, n, recs)
+        i, lay = self._pack(wide_push_layout, n, recs, rows)
         ops.wide_pool_push_resampled(self.state, self.rs, self._push_dev[i], lay, words_live, flush_row=flush[0] if flush else None)
         return self._resampled(n, flush)
 
-    def _send(self, rows, n, recs, fullest):
+    def _send(self, rows, n, recs, words_live):
         """WideStreamPool._send with input-rate chunks: one packed upload, one fused resample-and-push.  Returns the 16 kHz samples every row
         got, from the host's mirror."""
         if self.rs is None:
-            return super()._send(rows, n, recs, fullest)
-        return self._tick(rows, n, recs, max(0, fullest - max(len(r) for r in recs)))
+            return super()._send(rows, n, recs, words_live)
+        return self._tick(rows, n, recs, words_live)
 
     def _flush(self, b):
         """StreamPool._flush as a tick of its own: the header alone, no samples and no records, with flush_row = b."""
@@ -2448,14 +2458,7 @@ def wide_words_layout(n, m):
     The pieces -- the header (B, 4) int32 = per row (n, 0, m, record offset) and the records concatenated ((window, frame, id) int32) -- start
     on 256-byte boundaries.  Returns a dict: the byte offsets hdr, records and the byte size total; record_off: per row the first record of
     its slice, in records; n_records: the slices' sum; n_max, m_max; B."""
-    n, m = [int(v) for v in n], [int(v) for v in m]
-    if len(n) != len(m) or not n or min(n) < 0 or min(m) < 0:
-        raise ValueError(f"wide_words_layout: {len(n)} sample counts and {len(m)} record counts; expected one of each per row, none negative")
-    up = lambda v: (v + 255) // 256 * 256
-    B, n_records = len(n), sum(m)
-    records = up(16 * B)
-    return dict(B=B, hdr=0, records=records, total=records + up(12 * n_records), n_records=n_records,
-                record_off=[sum(m[:b]) for b in range(B)], n_max=max(n), m_max=max(m))
+    return _packed_layout("wide_words_layout", "sample counts", n, m, False)
 
 
 class WideSeq2SeqStreamPool(_PinnedTicks, Seq2SeqStreamPool):
@@ -2518,12 +2521,12 @@ class WideSeq2SeqStreamPool(_PinnedTicks, Seq2SeqStreamPool):
     def _stage(self):
         ops.wide_pool_stage_text(self.state, self.win, self.active, self._sos, self._eos, self.dec.text, self.dec.len)
 
-    def _send(self, rows, n, recs, fullest):
+    def _send(self, rows, n, recs, words_live):
         """The tick: the counts n (input_sr: turned into the 16 kHz samples that became final, on the host) and the records go up as one packed
         copy and are appended by one launch.  Returns the 16 kHz samples every row got."""
         if self.rs is not None:
             n = self._resampled(n)
-        self._tick(n, recs, max(0, fullest - max(len(r) for r in recs)))
+        self._tick(n, recs, words_live)
         return n
 
     def _flush(self, b):
@@ -2535,19 +2538,7 @@ class WideSeq2SeqStreamPool(_PinnedTicks, Seq2SeqStreamPool):
     def _tick(self, n, recs, words_live):
         """Packs the header and the records into the pinned slot whose turn it is, starts the one copy, notes the records and launches the
         push (nothing to do if a resampled tick made no sample final and brought no records)."""
-        B, m = self.B, [len(r) for r in recs]
-        if max(n) == 0 and max(m) == 0:
+        if max(n) == 0 and not any(recs):
             return
-        lay = wide_words_layout(n, m)
-        i = self._slot_to_fill("push")
-        host = self._push_host[i].numpy()
-        hdr = host[lay["hdr"]:lay["hdr"] + 16 * B].view(np.int32).reshape(B, 4)
-        hdr[:, 0], hdr[:, 1], hdr[:, 2], hdr[:, 3] = n, 0, m, lay["record_off"]
-        table = host[lay["records"]:lay["records"] + 12 * lay["n_records"]].view(np.int32)
-        for b, r in enumerate(recs):
-            if r:
-                table[3 * lay["record_off"][b]:3 * (lay["record_off"][b] + m[b])] = np.asarray(r, dtype=np.int32).reshape(-1)
-        self._push_dev[i][:lay["total"]].copy_(self._push_host[i][:lay["total"]], non_blocking=True)
-        self._sent("push", i)
-        self._note_records(recs)
+        i, lay = self._pack(wide_words_layout, n, recs)
         ops.wide_pool_push_words(self.state, self._push_dev[i], lay, words_live)

@@ -116,6 +116,32 @@ def test_a_refused_push_leaves_the_pool_as_it_was(syn):
         host_pool(syn, _replay_draws=True).open()
 
 
+def test_a_push_packs_the_bytes_of_the_reference_packing(pkg, syn, monkeypatch):
+    """The packer this pool shares with the Seq2Seq one, against the packing written for the GPU tests: after a push with ragged chunks, and
+    records on some rows only, the pinned slot holds pack()'s bytes.  The slot starts out filled with pack()'s 0xEE, so every byte of the
+    tick is compared: the packer writes the three pieces and nothing between them."""
+    pool = host_pool(syn, slots=6, max_chunk=100, word_ring=12)
+    seen = []
+    monkeypatch.setattr(pkg.ops, "wide_pool_push", lambda st, packed, lay, live=0: seen.append(("wide_pool_push", (st, packed, lay, live))))
+    monkeypatch.setattr(pkg.ops, "call", lambda name, *a: seen.append((name, a)))
+    assert [pool.open() for _ in range(6)] == list(range(6))
+    for h in pool._push_host:
+        h.fill_(0xEE)
+    rng = np.random.default_rng(39)
+    n = [10, 0, 33, 100, 0, 1]
+    chunks = [rng.standard_normal(k).astype(np.float32) for k in n]
+    words = [["a", 0.10, 0.12], ["bb", 0.13, 0.20]]
+    res = pool.push({0: chunks[0], 2: (chunks[2], words), 5: chunks[5], 3: (chunks[3], words[:1])})
+    assert sorted(res) == [0, 2, 3, 5] and pool.pushed == n and pool._n_rec == [0, 0, 2, 1, 0, 0]
+    recs = [[], [], syn.word_records(pool.args, pool.lang, words), syn.word_records(pool.args, pool.lang, words[:1]), [], []]
+    lay = syn.wide_push_layout(n, [len(r) for r in recs])
+    assert bytes(pool._push_host[0].numpy()[:lay["total"]]) == bytes(WR.pack(lay, chunks, recs))
+    assert [name for name, _ in seen] == ["wide_pool_push"]
+    st, packed, sent_lay, live = seen[0][1]
+    assert st is pool.state and packed is pool._push_dev[0] and sent_lay == lay and live == 0
+    assert bytes(packed.numpy()[:lay["total"]]) == bytes(pool._push_host[0].numpy()[:lay["total"]])      # (one copy of the whole tick)
+
+
 def test_a_wide_decoder_hands_over_through_the_wide_entry_and_a_narrow_one_as_before(pkg, syn, monkeypatch):
     """window_pooled's hand-over by row count: up to four rows ops.pool_handover, as before; above, ops.wide_pool_handover."""
     import torch
